@@ -2,6 +2,7 @@
 cell-updates/s (GCUPS) and % of the roofline at 1/2/4/8 GPUs).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload weak|strong262k|bit64k|byte16k]
+                    [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 With --gpus N > 1 and no WORLD_SIZE in the environment, bench.py starts its N ranks itself
@@ -20,7 +21,25 @@ its halo exchange and the fused AliveCellsCount):
            k = 32 turns per launch of the byte pipeline; replicas for N > 1.
 
 Inputs are synthetic (splitmix64 Bernoulli(1/2) cells, generated on the GPU) and resident in
-HBM before timing.  Rank 0 prints one JSON line.  (GOL_BENCH_STACKS_AFTER_S=N: every thread's
+HBM before timing: the same cells in every run with the same arguments.  Rank 0 prints one JSON
+line.
+
+A plain run does only what its headline figure needs: it builds the board, runs the settle and
+warmup steps, times the --steps steps, writes --dump-outputs / --snapshot if asked, and prints the
+line (metric, value, unit, higher_is_better, dtype, ms_per_step and the run's config).  --full adds
+everything else the line can carry: `config.parity` (every alive count of the run against the
+reference series under tests/golden/, exit 1 on a mismatch), `roofline` (the step kernel against
+its VALU / HBM roof, from the PMC profile of the current kernel sources), `cpu_baseline` (the CPU
+port on config 1; --no-cpu-baseline leaves it out) and, with N > 1 ranks, `config.rank_stats`
+(per-rank step and halo-exchange times; the exchanges are timed during the warmup steps).  The
+timed region is the same with and without --full.
+
+--dump-outputs DIR writes, after the timed steps, what the last timed step handed back:
+DIR/alive_counts.npy (float64: the alive count after every timed step, the last one being the last
+step's) and DIR/board_rows.npy (float32, 0 / 255 as Engine.store_rows returns them: a fixed, seeded
+sample of whole rows of the board after the last timed step, at most 48 MB) with
+DIR/board_rows_index.npy (float64: the rows' numbers).  With N > 1 ranks rank 0 writes its own
+shard's sample.  (GOL_BENCH_STACKS_AFTER_S=N: every thread's
 Python stack to stderr every N seconds, for a run that seems stuck.)
 """
 from __future__ import annotations
@@ -76,7 +95,15 @@ def parse(argv=None):
                     help="cells per lane of the bit kernels (0 = library default: 128 on the band layout)")
     ap.add_argument("--rows-per-gpu", type=int, default=1 << 17)
     ap.add_argument("--width", type=int, default=1 << 20)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also check and measure what the headline figure does not need: config.parity (the "
+                         "run's alive counts against the reference series), roofline, cpu_baseline and, for "
+                         "N > 1, config.rank_stats; off by default")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave cpu_baseline out")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what the last timed step computed as DIR/<name>.npy: "
+                         "alive_counts (float64, every timed step's count), board_rows (float32, a fixed seeded "
+                         "sample of rows of the final board) and board_rows_index (float64)")
     ap.add_argument("--settle-s", type=float, default=0.6,
                     help="before the warmup steps, untimed steps of the same workload for about this many "
                          "seconds of GPU work (a fixed count per workload from a nominal rate): the shader clock "
@@ -407,12 +434,12 @@ def run_bits(args, ranks):
     several = sharded and world > 1
     x = {"exchanges": 0, "mean_ms": 0.0, "wait_ms": 0.0, "transfer_ms": 0.0}
     if args.warmup:
-        # several ranks: the halo exchanges are timed during the warmup steps (the same work), so
+        # --full, several ranks: the halo exchanges are timed during the warmup steps (the same work), so
         # that their events stay out of the timed region
-        if several:
+        if several and args.full:
             e.set_timing(True, exchanges=True)
         run_n(args.warmup)
-        if several:
+        if several and args.full:
             x = e.exchange_timing()
             e.set_timing(False)
     ranks.barrier()
@@ -424,9 +451,9 @@ def run_bits(args, ranks):
     t = e.timing()
     e.set_timing(False)
     series.extend(counts.tolist())
-    per_rank = rank_stats(ranks, dt, t, x, topo)
+    per_rank = rank_stats(ranks, dt, t, x, topo) if args.full else None
     dt = ranks.max(dt)
-    par = parity(ranks, f"{H}x{W}", k, series)
+    par = parity(ranks, f"{H}x{W}", k, series) if args.full else None
     alive = int(counts[-1]) if len(counts) else None
     if not sharded and world > 1:
         cells_total = ranks.sum(H * W)  # independent replicas
@@ -442,12 +469,16 @@ def run_bits(args, ranks):
         sdt = ranks.max(time.perf_counter() - s0)
         snap = {"path": args.snapshot, "bytes": H * W, "GB_per_s": round(H * W / sdt / 1e9, 3),
                 "note": "device unpack + D2H + pwrite of every rank's rows (PCIe and disk inclusive)"}
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, ranks, e, counts)
     layout = {0: "bytes", 1: "standard", 2: "band"}[2 if info["layout"] == "band" else 1]
     key = f"{args.workload}:{args.rows_per_gpu if args.workload == 'weak' else H}x{W}:k{k}:{layout}"
     if info["cells_per_lane"] != 128:
         key += f":cpl{info['cells_per_lane']}"
-    pmc, note = load_pmc(key)
-    roof = roofline("bits", t["mean_ms"], t["mean_cell_updates"], pmc, note)
+    roof = None
+    if args.full:
+        pmc, note = load_pmc(key)
+        roof = roofline("bits", t["mean_ms"], t["mean_cell_updates"], pmc, note)
     rpg = args.rows_per_gpu
     rows_name = f"2^{rpg.bit_length() - 1}" if rpg & (rpg - 1) == 0 else str(rpg)
     wname = f"2^{W.bit_length() - 1}" if W & (W - 1) == 0 else str(W)
@@ -458,8 +489,10 @@ def run_bits(args, ranks):
            "transport": topo["transport"], "turns_per_step": k, "layout": layout,
            "cells_per_lane": info["cells_per_lane"], "strip_rows": args.strip or "auto",
            "alive_count_every_step": True, "alive_final": alive, "turns_done": (settle + args.warmup + args.steps) * k,
-           "settle_steps": settle, "timed_launches": t["launches"], "parity": par}
-    if world > 1:
+           "settle_steps": settle, "timed_launches": t["launches"]}
+    if par:
+        cfg["parity"] = par
+    if per_rank and world > 1:
         cfg["rank_stats"] = per_rank
     if snap:
         cfg["snapshot"] = snap
@@ -494,6 +527,31 @@ def rank_stats(ranks, wall_s, timing, xtiming, topo):
                      "stream) = exchange_wait_ms (waiting for the ring neighbours to reach the exchange: IPC READY "
                      "polls; RCCL a one-word send/recv with each neighbour issued first while timed) + "
                      "exchange_transfer_ms (the halo rows); max / min over ranks"}
+
+
+DUMP_ROWS_BYTES = 48 << 20  # of board_rows.npy (float32 cells); every file of a dump together < 64 MB
+
+
+def dump_outputs(path, ranks, e, counts):
+    """--dump-outputs: what the last timed step handed back, for an output-for-output comparison of
+    two builds.  The step's call returns the alive counts (all timed steps', float64: exact below
+    2^53) and leaves the board, read back as Engine.store_rows gives it (0 / 255 per cell, float32):
+    whole rows drawn by a fixed seed from the rows this process holds, as many as fit
+    DUMP_ROWS_BYTES.  Every rank reads its sample (the readback converts the band layout back, and
+    the ranks' boards stay in one state); rank 0 writes the files."""
+    import numpy as np
+    lo = e.shard(0)["y0"]
+    hi = e.shard(e.topology()["shards"] - 1)["y1"]
+    n = int(max(1, min(hi - lo, DUMP_ROWS_BYTES // (e.W * 4))))
+    rows = np.sort(np.random.default_rng(20240229).choice(hi - lo, size=n, replace=False)) + lo
+    board = np.empty((n, e.W), dtype=np.float32)
+    for i, y in enumerate(rows.tolist()):
+        board[i] = e.store_rows(y, y + 1)[0]
+    if ranks.rank == 0:
+        os.makedirs(path, exist_ok=True)
+        np.save(os.path.join(path, "alive_counts.npy"), np.asarray(counts, dtype=np.float64))
+        np.save(os.path.join(path, "board_rows.npy"), board)
+        np.save(os.path.join(path, "board_rows_index.npy"), rows.astype(np.float64))
 
 
 def settle_steps(args, run_n, cell_updates_per_step, nominal_rate):
@@ -535,20 +593,26 @@ def run_bytes(args, ranks):
     ranks.barrier()
     t = e.timing()
     e.set_timing(False)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, ranks, e, counts)
     e.close()
     series.extend(counts.tolist())
-    par = parity(ranks, f"{H}x{W}", k, series)
+    par = parity(ranks, f"{H}x{W}", k, series) if args.full else None
     dt = ranks.max(dt)
     value = H * W * ranks.world * k * args.steps / dt
     alive = int(counts[-1]) if len(counts) else None
     if ranks.world > 1:
         alive = int(ranks.sum(alive))  # independent replicas
-    pmc, note = load_pmc(f"byte16k:{H}x{W}:k{k}:bytes")
-    roof = roofline("bytes", t["mean_ms"], t["mean_cell_updates"], pmc, note)
+    roof = None
+    if args.full:
+        pmc, note = load_pmc(f"byte16k:{H}x{W}:k{k}:bytes")
+        roof = roofline("bytes", t["mean_ms"], t["mean_cell_updates"], pmc, note)
     cfg = {"workload": "byte-16384x16384", "H": H, "W": W, "turns_per_step": k, "layout": "bytes",
            "parallelism": f"replicas{ranks.world}" if ranks.world > 1 else "1gpu",
            "alive_count_every_step": True, "alive_final": alive, "turns_done": (settle + args.warmup + args.steps) * k,
-           "settle_steps": settle, "parity": par}
+           "settle_steps": settle}
+    if par:
+        cfg["parity"] = par
     return value, dt, cfg, roof, "u8 (byte per cell)"
 
 
@@ -573,17 +637,16 @@ def main():
         fake_t = {"mean_ms": wall * 1e3 / max(args.steps, 1), "launches": args.steps}
         fake_x = {"mean_ms": 0.01 * (ranks.rank + 1), "exchanges": args.warmup if ranks.world > 1 else 0,
                   "wait_ms": 0.004 * (ranks.rank + 1), "transfer_ms": 0.006 * (ranks.rank + 1)}
-        per_rank = rank_stats(ranks, wall, fake_t, fake_x, {"nranks": ranks.world, "transport": "dry-run"})
         dt = ranks.max(wall)
         value, cfg, roof, dtype = 0.0, {"workload": "dry-run", "ranks": ranks.world}, None, None
-        if ranks.world > 1:
-            cfg["rank_stats"] = per_rank
+        if args.full and ranks.world > 1:
+            cfg["rank_stats"] = rank_stats(ranks, wall, fake_t, fake_x, {"nranks": ranks.world, "transport": "dry-run"})
     elif args.workload == "byte16k":
         value, dt, cfg, roof, dtype = run_bytes(args, ranks)
     else:
         value, dt, cfg, roof, dtype = run_bits(args, ranks)
     cpu = None
-    if ranks.rank == 0 and ranks.world == 1 and not args.no_cpu_baseline and not args.dry_run:
+    if args.full and ranks.rank == 0 and ranks.world == 1 and not args.no_cpu_baseline and not args.dry_run:
         cpu = cpu_baseline(args)
     if ranks.rank == 0:
         line = {"metric": METRIC, "value": round(value / 1e9, 2), "unit": "GCUPS", "n_gpus": ranks.world,
@@ -595,7 +658,7 @@ def main():
         print(json.dumps(line), flush=True)
     ranks.close()
     if cfg.get("parity", {}).get("status") == "FAIL":
-        sys.exit(1)  # a board that differs from the reference is not a measurement
+        sys.exit(1)  # (--full) a board that differs from the reference is not a measurement
 
 
 if __name__ == "__main__":

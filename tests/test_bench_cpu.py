@@ -14,7 +14,7 @@ import bench  # noqa: E402
 
 def test_self_launch_two_ranks_dry_run():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    p = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--dry-run", "--steps", "4"], cwd=ROOT, env=env,
+    p = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--dry-run", "--full", "--steps", "4"], cwd=ROOT, env=env,
                        capture_output=True, text=True, timeout=120)
     assert p.returncode == 0, p.stderr[-2000:]
     # rank 0's stdout is the one JSON line and nothing else (gloo's "[Gloo] Rank 0 is connected"

@@ -219,7 +219,7 @@ def test_bench_share_gpu_shards_over_ipc(G):
         lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
         assert len(lines) == 1, p.stdout[-2000:]
         return json.loads(lines[0])
-    common = ["--width", "65536", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--settle-s", "0"]
+    common = ["--width", "65536", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--settle-s", "0"]
     two = line(["--gpus", "2", "--share-gpu", "--rows-per-gpu", "2048"] + common)
     one = line(["--rows-per-gpu", "4096"] + common)
     assert two["n_gpus"] == 2 and two["config"]["parallelism"] == "rows2" and two["config"]["transport"] == "ipc"
@@ -257,7 +257,7 @@ def test_bench_share_gpu_weak_board_parity(G):
     """The weak workload as the driver's N = 2 run sizes it (2 x 2^17 rows x 2^20, the default
     settle steps), 2 rank processes on this GPU over IPC: every alive count of the run equals one
     GPU's series of the same 2^18 x 2^20 torus (tests/golden/bench_counts.json)."""
-    rc, d, err = _bench(["--gpus", "2", "--share-gpu", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"])
+    rc, d, err = _bench(["--gpus", "2", "--share-gpu", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"])
     assert rc == 0 and d, err
     assert d["config"]["H"] == 1 << 18 and d["config"]["parallelism"] == "rows2"
     par = d["config"]["parity"]
@@ -270,7 +270,7 @@ def test_bench_share_gpu_ring_parity(G, n):
     4096 x 65536 split into N shares of 4096 / N rows -- the same torus as the N = 2 and the one-GPU
     runs -- every count of the run against its one-GPU series."""
     rc, d, err = _bench(["--gpus", str(n), "--share-gpu", "--rows-per-gpu", str(4096 // n), "--width", "65536",
-                         "--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--settle-s", "0"])
+                         "--steps", "6", "--warmup", "2", "--full", "--no-cpu-baseline", "--settle-s", "0"])
     assert rc == 0 and d, err
     par = d["config"]["parity"]
     assert d["config"]["parallelism"] == f"rows{n}" and par["status"] == "ok" and par["ranks"] == ["ok"] * n, par
@@ -285,7 +285,7 @@ def test_bench_mispaired_halo_fails_the_line(G):
     if not os.path.exists(lib):
         pytest.skip("libgolhip_mispair.so not built (make -C gol-distributed-final_amd/csrc mispair)")
     rc, d, err = _bench(["--gpus", "2", "--share-gpu", "--rows-per-gpu", "2048", "--width", "65536", "--steps", "3",
-                         "--warmup", "1", "--no-cpu-baseline", "--settle-s", "0", "--library", lib])
+                         "--warmup", "1", "--full", "--no-cpu-baseline", "--settle-s", "0", "--library", lib])
     assert rc == 1 and d, err
     par = d["config"]["parity"]
     assert par["status"] == "FAIL" and par["turn"] == 12 and par["got"] != par["want"], par

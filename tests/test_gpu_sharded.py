@@ -156,7 +156,7 @@ def test_bench_self_launch_two_replicas():
     import torch
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
-    common = ["--workload", "bit64k", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--settle-s", "0"]
+    common = ["--workload", "bit64k", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--settle-s", "0"]
     two = _bench_line(["--gpus", "2", "--share-gpu"] + common)
     one = _bench_line(common)
     assert two["n_gpus"] == 2 and one["n_gpus"] == 1
@@ -182,3 +182,39 @@ def test_bench_settle_steps_reported():
     assert cfg["settle_steps"] == int(0.2 * 145e12 / (65536 * 65536 * k) + 0.5)
     assert cfg["turns_done"] == (cfg["settle_steps"] + 1 + 4) * k
     assert cfg["timed_launches"] == 4 and line["steps"] == 4 and line["warmup"] == 1
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain bench run (no --full) carries the headline and the run's config only, and
+    --dump-outputs writes what its last timed step returned: the alive count after every timed
+    step and the final board (600 x 8192: the whole board fits the sample, so every row is
+    drawn), float64 / float32 .npy files below 64 MB, equal from run to run and equal to the
+    oracle's run of the same load_random(1) board."""
+    import torch
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    H, W, steps, warm = 600, 8192, 3, 2
+    args = ["--rows-per-gpu", str(H), "--width", str(W), "--steps", str(steps), "--warmup", str(warm), "--settle-s", "0"]
+    a, b = tmp_path / "a", tmp_path / "b"
+    line = _bench_line(args + ["--dump-outputs", str(a)])
+    _bench_line(args + ["--dump-outputs", str(b)])
+    assert line["roofline"] is None and line["cpu_baseline"] is None
+    assert "parity" not in line["config"] and "rank_stats" not in line["config"]
+    assert line["steps"] == steps and line["config"]["timed_launches"] == steps and line["ms_per_step"] > 0
+    assert abs(line["value"] - H * W * line["config"]["turns_per_step"] / (line["ms_per_step"] * 1e-3) / 1e9) \
+        <= 0.01 * line["value"] + 0.01
+    names = ["alive_counts.npy", "board_rows.npy", "board_rows_index.npy"]
+    assert sorted(os.listdir(a)) == names == sorted(os.listdir(b))
+    assert sum(os.path.getsize(a / n) for n in names) <= 64 << 20
+    out = {n: np.load(a / n) for n in names}
+    for n in names:
+        assert np.array_equal(out[n], np.load(b / n)), n
+    k = line["config"]["turns_per_step"]
+    turns = (warm + steps) * k
+    ref, rc = O.bits_run(O.random_words(1, 0, H, W // 64), turns, with_counts=True)
+    counts, rows, idx = (out[n] for n in names)
+    assert counts.dtype == np.float64 and rows.dtype == np.float32 and idx.dtype == np.float64
+    assert counts.tolist() == [float(rc[(warm + i + 1) * k - 1]) for i in range(steps)]
+    assert counts[-1] == line["config"]["alive_final"]
+    assert idx.tolist() == list(range(H))
+    assert np.array_equal(rows, O.unpack(ref).astype(np.float32))

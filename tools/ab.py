@@ -37,7 +37,7 @@ def main():
         for lib in libs:
             path = lib if lib == "lib" else os.path.join(ROOT, lib)
             code = CHILD % (ROOT, os.path.join(ROOT, "gol-distributed-final_amd"), lib, path,
-                            shlex.split(a.bench) + ["--no-cpu-baseline"])
+                            shlex.split(a.bench) + ["--full", "--no-cpu-baseline"])
             p = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300, cwd=ROOT)
             lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
             # (exit 1 with a line: bench.py's parity check failed -- a diagnostic build that computes

@@ -5,7 +5,7 @@
 #   tools/gpu.sh suite [pytest -k expr]     GPU tests (-m gpu) + smoke + the default bench line
 #   tools/gpu.sh tests [pytest args...]     GPU tests only (default: the whole -m gpu suite)
 #   tools/gpu.sh smoke                      __graft_entry__.smoke()
-#   tools/gpu.sh bench [workloads...]       one default bench line per workload (weak bit64k strong262k byte16k)
+#   tools/gpu.sh bench [workloads...]       one default --full bench line per workload (weak bit64k strong262k byte16k)
 #   tools/gpu.sh profile TAG [workloads...] per workload: rocprofv3 trace + one --pmc pass per counter set
 #                                           (summarise here with tools/pmc_summary.py TAG_<workload> <key>)
 #   tools/gpu.sh clock [workloads...]       in-kernel shader clock (needs tools/variants/libclock.so:
@@ -19,6 +19,8 @@
 set -o pipefail
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd "$R" && mkdir -p gpurun_out
+OUT=${GOL_BENCH_OUT:-$R/bench_out}  # the --full bench lines of bench / share / share_parity
+mkdir -p "$OUT"
 WORKLOADS="weak bit64k strong262k byte16k"
 PYT="python -u -m pytest -x --timeout 300 --timeout-method thread"
 
@@ -36,8 +38,8 @@ bench_default() {
 }
 bench() {
   for w in ${@:-$WORKLOADS}; do
-    timeout -k 10 300 python bench.py --workload $w $BENCH_EXTRA > gpurun_out/bench_$w.json 2> gpurun_out/bench_$w.err || { tail -20 gpurun_out/bench_$w.err; exit 5; }
-    python -c "import json; d=json.load(open('gpurun_out/bench_$w.json')); r=d['roofline']; print('$w', d['value'], d['ms_per_step'], r['launch_ms'], r.get('frac'), d['config']['alive_final'], (d.get('cpu_baseline') or {}).get('value'))"
+    timeout -k 10 300 python bench.py --full --workload $w $BENCH_EXTRA > $OUT/bench_$w.json 2> $OUT/bench_$w.err || { tail -20 $OUT/bench_$w.err; exit 5; }
+    python -c "import json; d=json.load(open('$OUT/bench_$w.json')); r=d['roofline']; print('$w', d['value'], d['ms_per_step'], r['launch_ms'], r.get('frac'), d['config']['alive_final'], (d.get('cpu_baseline') or {}).get('value'))"
   done
 }
 profile_one() {  # tag, bench args...: rocprofv3 --kernel-trace --stats of the bench command, then PMC passes
@@ -81,16 +83,16 @@ share() {
   export GOL_IPC_TIMEOUT_MS=60000
   for a in "--workload strong262k --gpus 4" "--workload strong262k --gpus 2" "--workload weak --gpus 2" "--workload weak --gpus 4 --rows-per-gpu 65536"; do
     echo "$a"
-    timeout -k 10 240 python3 -u bench.py $a --share-gpu --no-cpu-baseline --steps 10 --warmup 3 >> gpurun_out/share.jsonl 2>> gpurun_out/share.err || { tail -5 gpurun_out/share.err; exit 8; }
+    timeout -k 10 240 python3 -u bench.py $a --share-gpu --full --no-cpu-baseline --steps 10 --warmup 3 >> $OUT/share.jsonl 2>> $OUT/share.err || { tail -5 $OUT/share.err; exit 8; }
   done
-  tail -4 gpurun_out/share.jsonl
+  tail -4 $OUT/share.jsonl
 }
 
 share_parity() {  # the weak board as the driver's N = 2 and 4 runs size it, rank processes on this GPU (IPC)
   export GOL_IPC_TIMEOUT_MS=60000
   for n in 2 4; do
-    timeout -k 10 300 python3 -u bench.py --gpus $n --share-gpu --no-cpu-baseline --steps 10 --warmup 3 > gpurun_out/share_parity_$n.json 2> gpurun_out/share_parity_$n.err || { tail -5 gpurun_out/share_parity_$n.err; exit 8; }
-    python3 -c "import json; ls=open('gpurun_out/share_parity_$n.json').read().splitlines(); assert len(ls) == 1, ls; d=json.loads(ls[0]); c=d['config']; print($n, d['value'], c['H'], c['parity']['status'], c['parity']['turns_checked'], c['rank_stats']['exchange_ms'], c['rank_stats']['exchange_wait_ms'])"
+    timeout -k 10 300 python3 -u bench.py --gpus $n --share-gpu --full --no-cpu-baseline --steps 10 --warmup 3 > $OUT/share_parity_$n.json 2> $OUT/share_parity_$n.err || { tail -5 $OUT/share_parity_$n.err; exit 8; }
+    python3 -c "import json; ls=open('$OUT/share_parity_$n.json').read().splitlines(); assert len(ls) == 1, ls; d=json.loads(ls[0]); c=d['config']; print($n, d['value'], c['H'], c['parity']['status'], c['parity']['turns_checked'], c['rank_stats']['exchange_ms'], c['rank_stats']['exchange_wait_ms'])"
   done
 }
 
