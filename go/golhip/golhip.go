@@ -207,3 +207,27 @@ func (s *Broker) Quit() error { return check(C.gol_broker_quit(s.b)) }
 
 // SuperQuit is Operations.SuperQuit (broker.go:241-249).
 func (s *Broker) SuperQuit() error { return check(C.gol_broker_superquit(s.b)) }
+
+// View is a viewport frame of the broker's board (gol_broker_view; no reference counterpart, the
+// reference's live view is the controller's SDL window): outH rows of outW greyscale pixels, pixel
+// (i, j) the density ceil(255 n / scale^2) of the scale x scale box of cells at
+// (x0 + i*scale, y0 + j*scale) on the torus.  It is served between the chunks of a running Run
+// from the board as it is stepped, with work proportional to the viewport; turns is the number of
+// turns completed when it was taken, layout what was read (0 byte rows, 1 standard, 2 band bit
+// rows).  At turn 0 it shows the loaded board, unlike RetrieveCurrentData.
+func (s *Broker) View(x0, y0, scale, outW, outH int) (pixels [][]byte, turns int, layout int, err error) {
+	if outW < 1 || outH < 1 || outW*outH > 1<<26 {
+		return nil, 0, 0, fmt.Errorf("bad view size %d x %d pixels", outW, outH)
+	}
+	var pin runtime.Pinner
+	defer pin.Unpin()
+	flat := make([]byte, outW*outH)
+	pin.Pin(&flat[0])
+	var t C.int64_t
+	var lay C.int32_t
+	if err := check(C.gol_broker_view(s.b, C.int64_t(x0), C.int64_t(y0), C.int32_t(scale), C.int32_t(outW),
+		C.int32_t(outH), bytePtr(flat), C.int64_t(outW), &t, &lay)); err != nil {
+		return nil, 0, 0, err
+	}
+	return rows(flat, outH, outW), int(t), int(lay), nil
+}

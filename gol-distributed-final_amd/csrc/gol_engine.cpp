@@ -129,6 +129,9 @@ static void shard_release(gol_shard &s)
     if (s.host_word) (void)hipHostFree(s.host_word);
     if (s.staging) (void)hipFree(s.staging);
     if (s.host_staging) (void)hipHostFree(s.host_staging);
+    if (s.view_frame) (void)hipFree(s.view_frame);
+    if (s.view_pix) (void)hipFree(s.view_pix);
+    if (s.view_host) (void)hipHostFree(s.view_host);
     for (auto ev : s.tev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : {s.ev_start, s.ev_edge, s.ev_halo})
         if (ev) (void)hipEventDestroy(ev);
@@ -1617,6 +1620,151 @@ extern "C" int gol_engine_step_flips(gol_engine *e, int32_t *xy, int64_t cap, in
     gol_shard &s = e->sh[0];
     RCCHK(list_cells(e, s, false, s.bytes[e->bcur], s.bytes[1 - e->bcur], e->H, e->W, e->bstride, 0, xy, cap, &total));
     *n = total;
+    return GOL_OK;
+}
+
+// ------------------------------------------------------------------ viewport frames
+// (include/golhip.h, "viewport frames")  The board is read where it is and as it is: no layout
+// conversion, no change to cur / band / the halo state, rows [0, R) of the current buffer only
+// (never the ghost rows, which an exchange for the next step may be writing).
+static int ensure_view(gol_shard &s, int64_t n)
+{
+    if (s.view_cap >= n) return GOL_OK;
+    if (s.view_frame) (void)hipFree(s.view_frame);
+    if (s.view_pix) (void)hipFree(s.view_pix);
+    if (s.view_host) (void)hipHostFree(s.view_host);
+    s.view_frame = nullptr;
+    s.view_pix = nullptr;
+    s.view_host = nullptr;
+    s.view_cap = 0;
+    const int64_t cap = std::max<int64_t>((n + 3) / 4 * 4, 1 << 16);  // (golk_view_pixels: 4 pixels per lane)
+    HIPCHK(hipMalloc(&s.view_frame, cap * sizeof(uint32_t)));
+    HIPCHK(hipMalloc(&s.view_pix, cap));
+    HIPCHK(hipHostMalloc((void **)&s.view_host, cap * sizeof(uint32_t), hipHostMallocDefault));
+    s.view_cap = cap;
+    return GOL_OK;
+}
+
+static int view_check(gol_engine *e, int64_t x0, int64_t y0, int32_t scale, int32_t out_w, int32_t out_h, const void *out,
+                      int64_t stride)
+{
+    if (!e || !out) return gol_set_error(GOL_EINVAL, "bad view arguments (NULL)");
+    if (scale < 1 || scale > 4096 || out_w < 1 || out_h < 1 || (int64_t)out_w * scale > e->W ||
+        (int64_t)out_h * scale > e->H || x0 < 0 || x0 >= e->W || y0 < 0 || y0 >= e->H ||
+        (int64_t)out_w * out_h > (int64_t(1) << 26) || stride < out_w)
+        return gol_set_error(GOL_EINVAL,
+                             "bad view (x0 %lld, y0 %lld, scale %d, %d x %d pixels, stride %lld) of a %lld x %lld board: "
+                             "1 <= scale <= 4096, the viewport within one turn of the torus, at most 2^26 pixels",
+                             (long long)x0, (long long)y0, scale, out_w, out_h, (long long)stride, (long long)e->W,
+                             (long long)e->H);
+    return GOL_OK;
+}
+
+static int view_layout(const gol_engine *e) { return e->mode != GOL_MODE_BITS ? 0 : (e->band ? 2 : 1); }
+
+// Every local shard counts its runs of the viewport (gol_view_plan) into its own frame and copies
+// it to its pinned buffer: the counts, or with `pixels` (one shard holding every row) the pixels.
+// used[i]: shard i holds viewport rows.
+static int view_render(gol_engine *e, int64_t x0, int64_t y0, int32_t scale, int32_t out_w, int32_t out_h, bool pixels,
+                       std::vector<char> &used)
+{
+    const int64_t n = (int64_t)out_w * out_h, vrows = (int64_t)out_h * scale;
+    const int form = e->mode != GOL_MODE_BITS ? GOLK_VIEW_BYTES : (e->band ? GOLK_VIEW_BAND : GOLK_VIEW_STANDARD);
+    used.assign(e->sh.size(), 0);
+    for (size_t i = 0; i < e->sh.size(); ++i) {
+        gol_shard &s = e->sh[i];
+        gol_view_run runs[2];
+        int32_t nr = 0;
+        RCCHK(gol_view_plan(e->H, e->nranks, e->rank + (int32_t)i, y0, vrows, runs, 2, &nr));
+        if (nr == 0) continue;
+        used[i] = 1;
+        RCCHK(set_dev(s.device));
+        RCCHK(ensure_view(s, n));
+        // behind every launch of the last step: the compute stream's own, and (sync_all's waits)
+        // the edge stream's and the halo copies'
+        HIPCHK(hipStreamWaitEvent(s.stream, s.ev_edge, 0));
+        HIPCHK(hipStreamWaitEvent(s.stream, s.ev_halo, 0));
+        HIPCHK(hipMemsetAsync(s.view_frame, 0, (n + 3) / 4 * 4 * sizeof(uint32_t), s.stream));
+        const void *src = s.bits[e->cur];
+        int64_t pitch = e->pitch;
+        if (e->mode == GOL_MODE_BYTES) {
+            src = s.bytes[e->bcur];
+            pitch = e->bstride;
+        } else if (e->mode == GOL_MODE_EXACT) {
+            src = s.bytes[0] + e->bstride;  // (row 0 of bytes[0] is the halo row above)
+            pitch = e->bstride;
+        }
+        for (int32_t r = 0; r < nr; ++r)
+            HIPCHK(golk_view_counts(form, src, pitch, e->W, x0, scale, out_w, runs[r].row, runs[r].rows, runs[r].vrow,
+                                    s.view_frame, s.stream));
+        if (pixels) {
+            HIPCHK(golk_view_pixels(s.view_frame, n, scale, s.view_pix, s.stream));
+            HIPCHK(hipMemcpyAsync(s.view_host, s.view_pix, n, hipMemcpyDeviceToHost, s.stream));
+        } else {
+            HIPCHK(hipMemcpyAsync(s.view_host, s.view_frame, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s.stream));
+        }
+        HIPCHK(hipMemcpyAsync(s.host_word, s.err, sizeof(uint32_t), hipMemcpyDeviceToHost, s.stream));
+    }
+    uint32_t flags = 0;
+    for (size_t i = 0; i < e->sh.size(); ++i) {
+        if (!used[i]) continue;
+        gol_shard &s = e->sh[i];
+        RCCHK(set_dev(s.device));
+        HIPCHK(hipStreamSynchronize(s.stream));
+        flags |= s.host_word[0];
+    }
+    if (flags) return sync_all(e, false);  // a pending device fault: reported (and cleared) as by the other queries
+    return GOL_OK;
+}
+
+extern "C" int gol_engine_view_counts(gol_engine *e, int64_t x0, int64_t y0, int32_t scale, int32_t out_w, int32_t out_h,
+                                      uint32_t *counts, int64_t stride, int32_t *src_layout)
+{
+    RCCHK(view_check(e, x0, y0, scale, out_w, out_h, counts, stride));
+    std::vector<char> used;
+    RCCHK(view_render(e, x0, y0, scale, out_w, out_h, false, used));
+    for (int64_t j = 0; j < out_h; ++j) {
+        uint32_t *dst = counts + j * stride;
+        bool first = true;
+        for (size_t i = 0; i < e->sh.size(); ++i) {
+            if (!used[i]) continue;
+            const uint32_t *src = e->sh[i].view_host + j * out_w;
+            if (first) memcpy(dst, src, out_w * sizeof(uint32_t));
+            else
+                for (int32_t x = 0; x < out_w; ++x) dst[x] += src[x];
+            first = false;
+        }
+        if (first) memset(dst, 0, out_w * sizeof(uint32_t));  // none of this process's rows are in view
+    }
+    if (src_layout) *src_layout = view_layout(e);
+    return GOL_OK;
+}
+
+extern "C" int gol_engine_view(gol_engine *e, int64_t x0, int64_t y0, int32_t scale, int32_t out_w, int32_t out_h,
+                               uint8_t *pixels, int64_t stride, int32_t *src_layout)
+{
+    RCCHK(view_check(e, x0, y0, scale, out_w, out_h, pixels, stride));
+    if (e->sh.front().y0 != 0 || e->sh.back().y1 != e->H)
+        return gol_set_error(GOL_EINVAL, "view needs every row in this process (it holds rows [%lld, %lld)): add the "
+                                         "ranks' view_counts frames", (long long)e->sh.front().y0, (long long)e->sh.back().y1);
+    const bool one = e->sh.size() == 1;  // the pixels on the device; several shards: from the summed counts
+    std::vector<char> used;
+    RCCHK(view_render(e, x0, y0, scale, out_w, out_h, one, used));
+    const uint32_t s2 = (uint32_t)scale * (uint32_t)scale;
+    for (int64_t j = 0; j < out_h; ++j) {
+        uint8_t *dst = pixels + j * stride;
+        if (one) {
+            memcpy(dst, (const uint8_t *)e->sh[0].view_host + j * out_w, out_w);
+            continue;
+        }
+        for (int32_t x = 0; x < out_w; ++x) {
+            uint32_t c = 0;
+            for (size_t i = 0; i < e->sh.size(); ++i)
+                if (used[i]) c += e->sh[i].view_host[j * out_w + x];
+            dst[x] = (uint8_t)((255u * c + s2 - 1) / s2);
+        }
+    }
+    if (src_layout) *src_layout = view_layout(e);
     return GOL_OK;
 }
 

@@ -222,6 +222,18 @@ struct Operations {
         return rc;
     }
 
+    // No reference counterpart (its live view is the controller's SDL window): a viewport frame of
+    // the resident board, served between the chunks of a Run like RetrieveCurrentData.  It shows
+    // the engine's board as it is -- at turn 0 the loaded board, not Retrieve's all-zero cWorld.
+    int View(int64_t x0, int64_t y0, int32_t scale, int32_t out_w, int32_t out_h, uint8_t *pixels, int64_t stride,
+             int64_t *turns_completed, int32_t *src_layout)
+    {
+        Access acc(*this);
+        if (!have_world) return gol_set_error(GOL_ESTATE, "no board: Operations.Run has not been called");
+        if (turns_completed) *turns_completed = cTurn;
+        return gol_engine_view(eng, x0, y0, scale, out_w, out_h, pixels, stride, src_layout);
+    }
+
     int Pause()  // broker.go:251-254
     {
         Access acc(*this);
@@ -334,6 +346,13 @@ extern "C" int gol_broker_paused(gol_broker *b, int32_t *paused)
     Operations::Access acc(b->ops);
     *paused = b->ops.paused ? 1 : 0;
     return GOL_OK;
+}
+
+extern "C" int gol_broker_view(gol_broker *b, int64_t x0, int64_t y0, int32_t scale, int32_t out_w, int32_t out_h,
+                               uint8_t *pixels, int64_t stride, int64_t *turns_completed, int32_t *src_layout)
+{
+    if (!b) return gol_set_error(GOL_EINVAL, "NULL argument");
+    return b->ops.View(x0, y0, scale, out_w, out_h, pixels, stride, turns_completed, src_layout);
 }
 
 extern "C" int gol_worker_update(const gol_request *req, gol_response *res)

@@ -66,6 +66,11 @@ struct gol_shard {
     uint8_t *staging = nullptr;       // device byte rows for chunked copies
     uint8_t *host_staging = nullptr;  // pinned host rows
     int64_t stage_rows = 0;
+    // viewport frames (gol_engine_view): grown on demand, view_cap elements each
+    uint32_t *view_frame = nullptr;   // device counts of this shard's rows
+    uint8_t *view_pix = nullptr;      // device pixels (one shard: the whole frame)
+    uint32_t *view_host = nullptr;    // pinned host copy of either
+    int64_t view_cap = 0;
     ncclComm_t nccl = nullptr;
     // timing (gol_engine_set_timing): events on `stream` around the timed launches
     std::vector<hipEvent_t> tev;

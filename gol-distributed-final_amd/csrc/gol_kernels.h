@@ -79,6 +79,21 @@ hipError_t golk_row_counts(bool bits_mode, const void *board, const void *prev, 
 hipError_t golk_alive_list(bool bits_mode, const void *board, const void *prev, int64_t rows, int64_t width_units,
                            int64_t pitch, const int64_t *offs, int32_t *xy, int64_t cap, int64_t y0, hipStream_t s);
 
+// Viewport frames (gol_view.hip).  golk_view_counts adds to `frame` (out_w uint32 per pixel row,
+// dense) the alive cells of source rows [row, row + rows) of `src` (row 0 of a shard's rows), which
+// are viewport rows [vrow, vrow + rows): viewport cell (c, v) is board column (x0 + c) mod W and
+// belongs to pixel (c / scale, v / scale), 0 <= c < out_w * scale <= W.  form: byte rows (alive =
+// a byte != 0; pitch in bytes), standard bit rows (W % 32 == 0) or band bit rows (W % 1024 == 0),
+// pitch in words.  Reads only the words the viewport covers.  1 <= scale <= 4096.
+#define GOLK_VIEW_BYTES 0
+#define GOLK_VIEW_STANDARD 1
+#define GOLK_VIEW_BAND 2
+hipError_t golk_view_counts(int form, const void *src, int64_t pitch, int64_t W, int64_t x0, int32_t scale,
+                            int32_t out_w, int64_t row, int64_t rows, int64_t vrow, uint32_t *frame, hipStream_t s);
+// pixels[i] = ceil(255 * frame[i] / scale^2) for i < n; both buffers hold n rounded up to 4
+// elements, 16-byte aligned.
+hipError_t golk_view_pixels(const uint32_t *frame, int64_t n, int32_t scale, uint8_t *pixels, hipStream_t s);
+
 // IPC transport (gol_comm.h): set *flag = value with release ordering at system scope after the
 // stream's earlier work; wait (one wave on the stream) until every flags[i] (i < n <= 4, other
 // processes' flag words mapped through IPC) has reached `want` (wrap-safe sequence compare),

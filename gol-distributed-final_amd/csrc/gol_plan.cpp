@@ -65,3 +65,32 @@ extern "C" int gol_step_plan(int64_t R, int32_t k, int32_t kx, int32_t flags, go
     *n = m;
     return GOL_OK;
 }
+
+// The viewport rows a shard holds (include/golhip.h, "viewport frames"): viewport row v is global
+// row (y0 + v) mod H, so the viewport is rows [y0, min(y0 + vrows, H)) and, past the torus wrap,
+// rows [0, y0 + vrows - H); each part meets the shard's rows [a, b) in at most one run.
+extern "C" int gol_view_plan(int64_t H, int32_t nranks, int32_t rank, int64_t y0, int64_t vrows, gol_view_run *runs,
+                             int32_t cap, int32_t *n)
+{
+    if (!n || nranks < 1 || rank < 0 || rank >= nranks || H < nranks || y0 < 0 || y0 >= H || vrows < 1 || vrows > H ||
+        cap < 0 || (cap > 0 && !runs))
+        return gol_set_error(GOL_EINVAL, "bad view plan arguments (H %lld, rank %d of %d, y0 %lld, %lld rows)",
+                             (long long)H, rank, nranks, (long long)y0, (long long)vrows);
+    int64_t a = 0, b = 0;
+    int rc = gol_partition_rows(H, nranks, rank, &a, &b);
+    if (rc) return rc;
+    const int64_t wrapped = vrows - (H - y0);  // viewport rows past the torus wrap (no sum that could overflow)
+    const int64_t part[2][3] = {
+        {y0, wrapped > 0 ? H : y0 + vrows, 0},   // global rows [y0, ..) are viewport rows 0 ..
+        {0, wrapped > 0 ? wrapped : 0, H - y0},  // the wrapped rows [0, ..) are viewport rows H - y0 ..
+    };
+    int m = 0;
+    for (const auto &p : part) {
+        const int64_t lo = p[0] > a ? p[0] : a, hi = p[1] < b ? p[1] : b;
+        if (lo >= hi) continue;
+        if (m < cap) runs[m] = {lo - a, hi - lo, p[2] + (lo - p[0])};
+        ++m;
+    }
+    *n = m;
+    return GOL_OK;
+}

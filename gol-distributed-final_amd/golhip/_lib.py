@@ -39,6 +39,7 @@ GOL_STEP_SERIAL, GOL_STEP_EDGE_FIRST, GOL_STEP_OVERLAP = 2, 4, 8
 STEP_MODES = {"auto": 0, "serial": GOL_STEP_SERIAL, "edge_first": GOL_STEP_EDGE_FIRST, "overlap": GOL_STEP_OVERLAP}
 GOL_HALO_SEND, GOL_HALO_RECV = 0, 1
 GOL_LAUNCH_MAIN, GOL_LAUNCH_EDGE = 0, 1
+VIEW_LAYOUTS = {0: "bytes", 1: "standard", 2: "band"}  # *src_layout of the view calls
 
 _NAMES = {
     GOL_EINVAL: "EINVAL", GOL_EHIP: "EHIP", GOL_ENOMEM: "ENOMEM", GOL_EIO: "EIO",
@@ -87,6 +88,10 @@ class gol_launch(ctypes.Structure):
                 ("rows", ctypes.c_int64)]
 
 
+class gol_view_run(ctypes.Structure):
+    _fields_ = [("row", ctypes.c_int64), ("rows", ctypes.c_int64), ("vrow", ctypes.c_int64)]
+
+
 _i64 = ctypes.c_int64
 _i32 = ctypes.c_int32
 _u64 = ctypes.c_uint64
@@ -129,8 +134,11 @@ SIGNATURES = [
     ("gol_engine_timing", ctypes.c_int, [_vp, _P(_i64), _P(ctypes.c_double), _P(ctypes.c_double)]),
     ("gol_engine_exchange_timing", ctypes.c_int, [_vp, _P(_i64), _P(ctypes.c_double)]),
     ("gol_engine_exchange_split", ctypes.c_int, [_vp, _P(_i64), _P(ctypes.c_double), _P(ctypes.c_double)]),
+    ("gol_engine_view_counts", ctypes.c_int, [_vp, _i64, _i64, _i32, _i32, _i32, _vp, _i64, _P(_i32)]),
+    ("gol_engine_view", ctypes.c_int, [_vp, _i64, _i64, _i32, _i32, _i32, _vp, _i64, _P(_i32)]),
     ("gol_halo_plan", ctypes.c_int, [_i64, _i32, _i32, _i32, _P(gol_halo_op), _i32, _P(_i32)]),
     ("gol_step_plan", ctypes.c_int, [_i64, _i32, _i32, _i32, _P(gol_launch), _i32, _P(_i32)]),
+    ("gol_view_plan", ctypes.c_int, [_i64, _i32, _i32, _i64, _i64, _P(gol_view_run), _i32, _P(_i32)]),
     ("gol_dev_bits_step", ctypes.c_int,
      [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _vp, _vp]),
     ("gol_dev_random_fill", ctypes.c_int, [_vp, _i64, _i64, _i64, _i64, _u64, _vp]),
@@ -154,6 +162,7 @@ SIGNATURES = [
     ("gol_broker_quit", ctypes.c_int, [_vp]),
     ("gol_broker_superquit", ctypes.c_int, [_vp]),
     ("gol_broker_paused", ctypes.c_int, [_vp, _P(_i32)]),
+    ("gol_broker_view", ctypes.c_int, [_vp, _i64, _i64, _i32, _i32, _i32, _vp, _i64, _P(_i64), _P(_i32)]),
     ("gol_worker_update", ctypes.c_int, [_P(gol_request), _P(gol_response)]),
 ]
 
@@ -219,6 +228,16 @@ def step_plan(R: int, k: int, kx: int, mode: str = "overlap") -> list[tuple[str,
     check(lib().gol_step_plan(R, k, kx, STEP_MODES[mode], out, 3, ctypes.byref(n)))
     return [("edge" if L.stream == GOL_LAUNCH_EDGE else "main", bool(L.needs_halo), L.row0, L.rows)
             for L in out[:n.value]]
+
+
+def view_plan(H: int, nranks: int, rank: int, y0: int, vrows: int) -> list[tuple[int, int, int]]:
+    """gol_view_plan: the runs of viewport rows (viewport row v = global row (y0 + v) mod H, v < vrows)
+    that shard `rank` holds, as (first shard-local row, rows, first viewport row), in viewport order
+    (at most 2: the torus wrap).  Host code: no GPU needed."""
+    runs = (gol_view_run * 2)()
+    n = ctypes.c_int32()
+    check(lib().gol_view_plan(H, nranks, rank, y0, vrows, runs, 2, ctypes.byref(n)))
+    return [(r.row, r.rows, r.vrow) for r in runs[:n.value]]
 
 
 def device_count() -> int:

@@ -11,7 +11,8 @@ import ctypes
 
 import numpy as np
 
-from ._lib import LAYOUTS, TRANSPORTS, check, gol_config, gol_request, gol_response, lib
+from ._lib import (GOL_EINVAL, LAYOUTS, TRANSPORTS, VIEW_LAYOUTS, GolError, check, gol_config, gol_request,
+                   gol_response, lib)
 from .stubs import CellList, Request, Response
 
 
@@ -87,6 +88,20 @@ class Operations:
         """broker.go:256-277.  ``alive=False`` / ``world=False`` skip the list / board copy
         (the count is always returned)."""
         return self._call(lib().gol_broker_retrieve, req, alive=alive, world=world)
+
+    def view(self, x0: int, y0: int, scale: int, out_w: int, out_h: int, *, return_layout: bool = False):
+        """A viewport frame of the broker's board (gol_broker_view; no reference counterpart): the
+        (out_h, out_w) uint8 pixels of Engine.view and the turns completed when it was taken, served
+        between the chunks of a running Run.  It shows the board as it is: at turn 0 the loaded
+        board, not RetrieveCurrentData's all-zero one.  return_layout=True appends "bytes",
+        "standard" or "band"."""
+        if out_w < 1 or out_h < 1 or out_w * out_h > 1 << 26:
+            raise GolError(GOL_EINVAL, f"bad view size {out_w} x {out_h} pixels (at most 2^26)")
+        out = np.empty((out_h, out_w), dtype=np.uint8)
+        turns, lay = ctypes.c_int64(), ctypes.c_int32()
+        check(lib().gol_broker_view(self._h, x0, y0, scale, out_w, out_h, out.ctypes.data, out_w, ctypes.byref(turns),
+                                    ctypes.byref(lay)))
+        return (out, turns.value, VIEW_LAYOUTS[lay.value]) if return_layout else (out, turns.value)
 
     def Pause(self, req: Request | None = None) -> Response:  # broker.go:251-254
         check(lib().gol_broker_pause(self._h))

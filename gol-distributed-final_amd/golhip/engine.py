@@ -16,7 +16,8 @@ import ctypes
 import numpy as np
 
 from ._lib import (GOL_EINVAL, GOL_IPC_ID_BYTES, GOL_RCCL_ID_BYTES, GOL_SHARDS_SAME_DEVICE, GOL_TIMING_EXCHANGE,
-                   GOL_WRITE_FN, LAYOUTS, STEP_MODES, TRANSPORT_NAMES, TRANSPORTS, GolError, check, gol_config, lib)
+                   GOL_WRITE_FN, LAYOUTS, STEP_MODES, TRANSPORT_NAMES, TRANSPORTS, VIEW_LAYOUTS, GolError, check,
+                   gol_config, lib)
 
 
 def rccl_unique_id(library=None) -> bytes:
@@ -199,6 +200,27 @@ class Engine:
         n = ctypes.c_int64()
         self._check(self._L.gol_engine_step_flips(self._h, xy.ctypes.data, cap, ctypes.byref(n)))
         return xy[:min(n.value, cap)]
+
+    def _view(self, fn, dtype, x0, y0, scale, out_w, out_h, return_layout):
+        if out_w < 1 or out_h < 1 or out_w * out_h > 1 << 26:  # (before the frame is allocated here)
+            raise GolError(GOL_EINVAL, f"bad view size {out_w} x {out_h} pixels (at most 2^26)")
+        out = np.empty((out_h, out_w), dtype=dtype)
+        lay = ctypes.c_int32()
+        self._check(fn(self._h, x0, y0, scale, out_w, out_h, out.ctypes.data, out_w, ctypes.byref(lay)))
+        return (out, VIEW_LAYOUTS[lay.value]) if return_layout else out
+
+    def view_counts(self, x0: int, y0: int, scale: int, out_w: int, out_h: int, *, return_layout: bool = False):
+        """(out_h, out_w) uint32: the alive cells of every scale x scale box of the torus rectangle
+        at (x0, y0) (gol_engine_view_counts), counted on the GPU from the board as it is stepped (no
+        layout conversion; the work follows the viewport).  With ranks in several processes: the
+        cells of this rank's rows.  return_layout=True also returns what was read: "bytes",
+        "standard" or "band"."""
+        return self._view(self._L.gol_engine_view_counts, np.uint32, x0, y0, scale, out_w, out_h, return_layout)
+
+    def view(self, x0: int, y0: int, scale: int, out_w: int, out_h: int, *, return_layout: bool = False):
+        """(out_h, out_w) uint8 greyscale frame: ceil(255 n / scale^2) per box (gol_engine_view); at
+        scale 1 the board's 0/255 bytes.  Needs every row in this process."""
+        return self._view(self._L.gol_engine_view, np.uint8, x0, y0, scale, out_w, out_h, return_layout)
 
     def hash(self) -> int:
         h = ctypes.c_uint64()

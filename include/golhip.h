@@ -108,7 +108,8 @@ typedef struct gol_engine gol_engine;
  * 32s .. 32s+31.  BAND: word w holds, at bit b, cell b*(W/32) + w (32 column
  * bands), which makes a generation shift-free.  AUTO picks
  * BAND when W % 1024 == 0.  The layout is internal: every reader (store,
- * alive list, PGM, hash, device_bits) sees the standard layout.  BYTES keeps
+ * alive list, PGM, hash, device_bits) sees the standard layout, and converts
+ * the board to it; only the viewport frames read it as it is.  BYTES keeps
  * the board as the reference's one byte per cell (a W % 64 != 0 board always
  * does): one shard, 32 turns per launch on a 0/255 board with W % 32 == 0 (the
  * byte pipeline), the exact byte kernel otherwise; the
@@ -265,6 +266,44 @@ int gol_engine_exchange_timing(gol_engine *e, int64_t *exchanges, double *mean_m
  * processes (LOCAL, LOOPBACK) wait for nothing on the exchange's stream: 0. */
 int gol_engine_exchange_split(gol_engine *e, int64_t *exchanges, double *mean_wait_ms, double *mean_transfer_ms);
 
+/* ---------------------------------------------------------------- viewport frames
+ * (Added after ABI 6 without a version bump: GOL_ABI_VERSION stays 6, and a
+ * host that may meet an older library probes for gol_engine_view,
+ * gol_engine_view_counts, gol_view_plan and gol_broker_view by symbol.)
+ *
+ * A density-downsampled picture of a torus rectangle of the running board, for
+ * boards far larger than a screen (the reference's SDL view, sdl/, draws its
+ * 16^2-512^2 boards cell by cell).  A view is (x0, y0, scale, out_w, out_h):
+ * pixel (i, j) covers the scale x scale box of cells
+ *   x = (x0 + i*scale + dx) mod W,  y = (y0 + j*scale + dy) mod H,  0 <= dx, dy < scale
+ * and n(i, j) is the number of alive cells in it (set bits; bytes != 0 on a byte
+ * board and before the exact first turn: what gol_engine_alive_count counts, so
+ * a view that tiles the whole board sums to it).
+ *  - gol_engine_view_counts: counts[j*stride + i] = n(i, j), uint32.
+ *  - gol_engine_view: pixels[j*stride + i] = (255*n + scale^2 - 1) / scale^2
+ *    (integer division: ceil(255 n / scale^2)); at scale 1 the 0/255 bytes of
+ *    the PGM, at any scale non-zero for a box with one alive cell and 255 for a
+ *    full one.
+ * Valid: 1 <= scale <= 4096, out_w, out_h >= 1, out_w*scale <= W,
+ * out_h*scale <= H, 0 <= x0 < W, 0 <= y0 < H, out_w*out_h <= 2^26, stride >=
+ * out_w (in elements); anything else is GOL_EINVAL before any GPU work.
+ * The frame is computed on the GPU from the board in place, in whatever layout
+ * it is currently stepped in (no conversion to the standard layout, unlike the
+ * other readers; the next step pays nothing for the view), reading only the rows
+ * and words the viewport covers: the work follows the viewport, not the board.
+ * *src_layout (may be NULL) reports what was read: 0 byte rows, 1 standard bit
+ * rows, 2 band bit rows (gol_engine_info's bit_mode values, for the board's
+ * current state).  Blocking; ordered after the last step.  Several local shards
+ * each count their rows on their own GPU (gol_view_plan) and the frames are
+ * added.  view_counts is not collective: with ranks in several processes it
+ * returns the counts of the cells in this process's rows, and the caller adds
+ * the ranks' frames (as with gol_engine_alive_cells); view needs every row
+ * local (like gol_engine_store_bytes), else GOL_EINVAL. */
+int gol_engine_view_counts(gol_engine *e, int64_t x0, int64_t y0, int32_t scale, int32_t out_w, int32_t out_h,
+                           uint32_t *counts, int64_t stride, int32_t *src_layout);
+int gol_engine_view(gol_engine *e, int64_t x0, int64_t y0, int32_t scale, int32_t out_w, int32_t out_h,
+                    uint8_t *pixels, int64_t stride, int32_t *src_layout);
+
 /* ---------------------------------------------------------------- plans
  * The schedule of a sharded step as data (host functions, no GPU needed).  The
  * engine runs exactly these plans; golhip.sharded (the torch.distributed
@@ -314,6 +353,20 @@ typedef struct gol_launch {
     int64_t rows;
 } gol_launch;
 int gol_step_plan(int64_t R, int32_t k, int32_t kx, int32_t flags, gol_launch *out, int32_t cap, int32_t *n);
+/* gol_view_plan: the rows of a viewport that shard `rank` of gol_partition_rows(H,
+ * nranks, .) holds.  Viewport row v (0 <= v < vrows <= H) is global row
+ * (y0 + v) mod H; a run is `rows` consecutive rows from shard-local row `row`,
+ * which are viewport rows vrow .. vrow + rows - 1.  Runs come in increasing
+ * vrow order, at most 2 per shard (the second from the torus wrap); over all
+ * ranks they cover every viewport row once.  Writes min(*n, cap) runs.  The
+ * engine's view calls run exactly this plan. */
+typedef struct gol_view_run {
+    int64_t row;   /* first shard-local source row */
+    int64_t rows;
+    int64_t vrow;  /* first viewport row */
+} gol_view_run;
+int gol_view_plan(int64_t H, int32_t nranks, int32_t rank, int64_t y0, int64_t vrows, gol_view_run *runs, int32_t cap,
+                  int32_t *n);
 
 /* ---------------------------------------------------------------- device launchers
  * Asynchronous kernel launches on caller-owned device memory and a caller
@@ -427,6 +480,14 @@ int gol_broker_pause(gol_broker *b);                                            
 int gol_broker_quit(gol_broker *b);                                               /* Operations.Quit, broker.go:236-239 */
 int gol_broker_superquit(gol_broker *b);                                          /* Operations.SuperQuit, broker.go:241-249 */
 int gol_broker_paused(gol_broker *b, int32_t *paused);
+/* gol_engine_view of the broker's board, served between the chunks of a running
+ * Run like RetrieveCurrentData; *turns_completed = cTurn (may be NULL).
+ * GOL_ESTATE with no board.  No reference counterpart (the reference's live
+ * view is the controller's SDL window): it shows the engine's board as it is,
+ * so at turn 0 the loaded board -- deliberately not RetrieveCurrentData's
+ * all-zero cWorld of broker.go:67-70. */
+int gol_broker_view(gol_broker *b, int64_t x0, int64_t y0, int32_t scale, int32_t out_w, int32_t out_h,
+                    uint8_t *pixels, int64_t stride, int64_t *turns_completed, int32_t *src_layout);
 int gol_worker_update(const gol_request *req, gol_response *res);                 /* GameOfLifeOperations.Update, worker.go:77-80 */
 
 #ifdef __cplusplus
