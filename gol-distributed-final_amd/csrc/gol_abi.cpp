@@ -12,6 +12,7 @@
 #include "golhip.h"
 #include "gol_internal.h"
 #include "gol_kernels.h"
+#include "gol_rule.h"
 
 // ------------------------------------------------------------------ errors
 static thread_local std::string g_err;
@@ -127,6 +128,24 @@ extern "C" int gol_dev_band_step(const uint32_t *top, const uint32_t *mid, const
                           (hipStream_t)stream));
 }
 
+extern "C" int gol_dev_rule_step(const uint32_t *top, const uint32_t *mid, const uint32_t *bot, uint32_t *dst,
+                                 int64_t R, int64_t Wd, int64_t pitch, int64_t row0, int64_t rows, int32_t k,
+                                 int32_t layout, uint32_t birth, uint32_t survive, int32_t cells_per_lane,
+                                 int32_t strip_rows, uint64_t *count_slots, void *stream)
+{
+    const int dw = GOLK_RULE_DW;
+    if (!top || !mid || !bot || !dst || R <= 0 || Wd <= 0 || Wd % dw || pitch < Wd || pitch % dw || row0 < 0 ||
+        rows < 0 || row0 + rows > R || !(k == 1 || k == 2 || k == 4 || k == 8) || k > R ||
+        (layout != GOL_LAYOUT_STANDARD && layout != GOL_LAYOUT_BAND) || birth >= 512 || survive >= 512 ||
+        !(cells_per_lane <= 0 || cells_per_lane == 32 * dw) ||
+        (((uintptr_t)mid | (uintptr_t)top | (uintptr_t)bot | (uintptr_t)dst) & (4 * dw - 1)))
+        return gol_set_error(GOL_EINVAL,
+                             "bad rule_step arguments (R=%lld Wd=%lld pitch=%lld k=%d layout=%d B=0x%x S=0x%x cells_per_lane=%d)",
+                             (long long)R, (long long)Wd, (long long)pitch, k, layout, birth, survive, cells_per_lane);
+    LAUNCH(golk_rule_step(top, mid, bot, dst, R, Wd, pitch, row0, rows, k, layout == GOL_LAYOUT_BAND, birth, survive,
+                          strip_rows, count_slots, (hipStream_t)stream));
+}
+
 extern "C" int gol_band_max_k(int32_t cells_per_lane)
 {
     const int dw = cells_per_lane == 64 ? 2 : (cells_per_lane == 128 ? 4 : (cells_per_lane <= 0 ? GOL_BAND_DEFAULT_DW : 0));
@@ -220,5 +239,61 @@ extern "C" int gol_dev_error(int32_t device, uint32_t *flags)
     if (he != hipSuccess) return gol_set_error(GOL_EHIP, "error word: %s", hipGetErrorString(he));
     *flags = v;
     if (v) return gol_set_error(GOL_EHIP, "device fault in a launch on device %d (error flags 0x%x)", dev, v);
+    return GOL_OK;
+}
+
+// ------------------------------------------------------------------ rules (host only)
+extern "C" int gol_rule_parse(const char *text, uint32_t *birth, uint32_t *survive)
+{
+    if (!text || !birth || !survive) return gol_set_error(GOL_EINVAL, "bad rule_parse arguments (NULL)");
+    const char *p = text;
+    uint32_t m[2] = {0, 0};
+    for (int half = 0; half < 2; ++half) {
+        const char want = half == 0 ? 'B' : 'S';
+        if (*p != want && *p != want + ('a' - 'A'))
+            return gol_set_error(GOL_EINVAL, "rule \"%s\": expected B<digits>/S<digits>", text);
+        for (++p; *p >= '0' && *p <= '8'; ++p) {
+            const uint32_t bit = 1u << (*p - '0');
+            if (m[half] & bit) return gol_set_error(GOL_EINVAL, "rule \"%s\": digit %c repeated", text, *p);
+            m[half] |= bit;
+        }
+        if (half == 0 && *p++ != '/') return gol_set_error(GOL_EINVAL, "rule \"%s\": expected B<digits>/S<digits>, digits 0-8", text);
+    }
+    if (*p) return gol_set_error(GOL_EINVAL, "rule \"%s\": expected B<digits>/S<digits>, digits 0-8, nothing after", text);
+    *birth = m[0];
+    *survive = m[1];
+    return GOL_OK;
+}
+
+extern "C" int gol_rule_format(uint32_t birth, uint32_t survive, char *buf, int64_t len)
+{
+    if (!buf || birth >= 512 || survive >= 512) return gol_set_error(GOL_EINVAL, "bad rule_format arguments (masks are 9 bits)");
+    char out[24];
+    int n = 0;
+    out[n++] = 'B';
+    for (int d = 0; d <= 8; ++d)
+        if (birth >> d & 1u) out[n++] = (char)('0' + d);
+    out[n++] = '/';
+    out[n++] = 'S';
+    for (int d = 0; d <= 8; ++d)
+        if (survive >> d & 1u) out[n++] = (char)('0' + d);
+    out[n++] = 0;
+    if (len < n) return gol_set_error(GOL_EINVAL, "rule_format: the buffer holds %lld bytes, the text needs %d", (long long)len, n);
+    memcpy(buf, out, n);
+    return GOL_OK;
+}
+
+extern "C" int gol_rule_eval_host(uint32_t birth, uint32_t survive, const uint32_t nb[8], uint32_t centre, uint32_t *next)
+{
+    if (!nb || !next || birth >= 512 || survive >= 512) return gol_set_error(GOL_EINVAL, "bad rule_eval_host arguments");
+    // the kernels' count: the 3x3 block as three rows' horizontal sums, the centre in the middle one
+    const uint32_t in[3][3] = {{nb[0], nb[1], nb[2]}, {nb[3], centre, nb[4]}, {nb[5], nb[6], nb[7]}};
+    uint32_t h0[3], h1[3], t0, t1, t2, t3;
+    for (int r = 0; r < 3; ++r) {
+        h0[r] = gol_rule_xor3(in[r][0], in[r][1], in[r][2]);
+        h1[r] = gol_rule_maj(in[r][0], in[r][1], in[r][2]);
+    }
+    gol_rule_sum3(h0[0], h1[0], h0[1], h1[1], h0[2], h1[2], t0, t1, t2, t3);
+    *next = gol_rule_next(birth, survive, t0, t1, t2, t3, centre);
     return GOL_OK;
 }

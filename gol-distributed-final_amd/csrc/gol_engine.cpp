@@ -77,6 +77,25 @@ static int pick_k(int want, int64_t remaining, int64_t rows, int dw, bool band)
     return 1;
 }
 
+// The bit board's launches under the engine's rule: words per lane of the kernel that runs them
+// and their turns per launch.  The rule kernels run at most GOLK_RULE_MAX_K turns, so under them
+// pick_k never sees a want of 12 or 16; e->kx (the exchanged halo, from the Conway k) stays >= k.
+static int step_dw(const gol_engine *e, bool band) { return e->rule_generic ? GOLK_RULE_DW : (band ? e->band_dw : e->dw); }
+static int step_pick_k(const gol_engine *e, int64_t remaining, bool band)
+{
+    const int want = e->rule_generic ? std::min(e->k, GOLK_RULE_MAX_K) : e->k;
+    return pick_k(want, remaining, e->min_rows, step_dw(e, band), band);
+}
+// Stepping calls under a non-B3/S23 rule: the reference's byte semantics (exactly 0 / exactly
+// 255) are defined for B3/S23 only, so a board still holding loaded bytes other than 0/255 (its
+// exact first turn pending) cannot be stepped.
+static int rule_step_check(const gol_engine *e)
+{
+    if (e->rule_generic && e->mode == GOL_MODE_EXACT && (e->birth != 0x008 || e->survive != 0x00C))
+        return gol_set_error(GOL_ESTATE, "the board holds loaded bytes other than 0/255: their first turn is defined for B3/S23 only");
+    return GOL_OK;
+}
+
 // ------------------------------------------------------------------ allocation
 static int ensure_staging(gol_engine *e, gol_shard &s)
 {
@@ -752,7 +771,10 @@ static int step_launch(gol_engine *e, gol_shard &s, hipStream_t st, int k, int64
         bot = mid;
     }
     uint32_t *dst = s.bits[1 - e->cur];
-    if (e->band)
+    if (e->rule_generic)
+        HIPCHK(golk_rule_step(top, mid, bot, dst, s.R, e->Wd, e->pitch, row0, rows, k, e->band, e->birth, e->survive, e->strip,
+                              slots, st));
+    else if (e->band)
         HIPCHK(golk_band_step(top, mid, bot, dst, s.R, e->Wd, e->pitch, row0, rows, k, e->band_dw, e->strip, slots, s.err, st));
     else
         HIPCHK(golk_bits_step(top, mid, bot, dst, s.R, e->Wd, e->pitch, row0, rows, k, e->dw, e->strip, slots, st));
@@ -885,6 +907,7 @@ static int step_mode(gol_engine *e, const gol_shard &s, int k)
 {
     if (e->step_flags) return e->step_flags;
     if (local_wrap(e)) return GOL_STEP_SERIAL;  // nothing to exchange, nothing to overlap
+    if (e->rule_generic) return GOL_STEP_OVERLAP;  // the rule kernels: equal strips, launches of many rounds
     const double rounds = golk_step_rounds(e->band, s.R, e->Wd, e->pitch, k, e->band ? e->band_dw : e->dw, e->strip);
     return rounds > GOL_OVERLAP_ROUNDS ? GOL_STEP_OVERLAP : GOL_STEP_SERIAL;
 }
@@ -1064,7 +1087,7 @@ static int advance(gol_engine *e, int64_t n, int64_t ci)
             continue;
         }
         if (e->band_capable) RCCHK(convert(e, true));
-        const int k = pick_k(e->k, n, e->min_rows, e->band ? e->band_dw : e->dw, e->band);
+        const int k = step_pick_k(e, n, e->band);
         const bool last = n == k && ci >= 0;
         if (last) RCCHK(batch_begin(e, ci));
         RCCHK(launch_k(e, k, last ? ci : -1));
@@ -1092,6 +1115,7 @@ int gol_engine_step_async(gol_engine *e, int64_t turns) { return advance(e, turn
 extern "C" int gol_engine_step(gol_engine *e, int64_t turns)
 {
     if (!e || turns < 0) return gol_set_error(GOL_EINVAL, "bad step arguments");
+    RCCHK(rule_step_check(e));
     RCCHK(agree_step_state(e));
     RCCHK(timing_begin(e));
     int rc = advance(e, turns, -1);
@@ -1127,6 +1151,7 @@ extern "C" int gol_engine_step_counted(gol_engine *e, int64_t turns, int64_t eve
         return gol_set_error(GOL_EINVAL, "bad step_counted arguments (turns %lld, every %lld, cap %lld)", (long long)turns,
                              (long long)every, (long long)cap);
     const int64_t n = turns / every;
+    RCCHK(rule_step_check(e));
     for (auto &s : e->sh) {
         RCCHK(set_dev(s.device));
         RCCHK(ensure_counts(s, n));
@@ -1578,6 +1603,7 @@ extern "C" int gol_engine_alive_cells(gol_engine *e, int32_t *xy, int64_t cap, i
 extern "C" int gol_engine_step_flips(gol_engine *e, int32_t *xy, int64_t cap, int64_t *n)
 {
     if (!e || !n || cap < 0 || (cap > 0 && !xy)) return gol_set_error(GOL_EINVAL, "bad arguments");
+    RCCHK(rule_step_check(e));
     RCCHK(agree_step_state(e));
     RCCHK(ensure_standard(e));
     int64_t total = 0;
@@ -1944,20 +1970,49 @@ extern "C" int gol_engine_info(gol_engine *e, int32_t *k, int32_t *cells_per_lan
     if (!e) return gol_set_error(GOL_EINVAL, "engine is NULL");
     const bool bits = e->mode == GOL_MODE_BITS;
     const bool band = bits && e->band_capable;
-    const int dw = band ? e->band_dw : e->dw;
+    const int dw = bits ? step_dw(e, band) : e->dw;
     // the k of the next launch, as advance() picks it
     int kk = 1;  // the exact one-turn kernel: a board before its exact first turn, a byte board of W % 32 != 0 or non-0/255 bytes
-    if (bits) kk = pick_k(e->k, e->k, e->min_rows, dw, band);
+    if (bits) kk = step_pick_k(e, e->k, band);
     else if (e->mode == GOL_MODE_BYTES && e->bytes_binary && e->W % 32 == 0)
         kk = e->k >= 32 && e->H >= 32 ? 32 : pick_k(e->k, e->k, e->H, 1, false);
     if (k) *k = kk;
     if (cells_per_lane) *cells_per_lane = 32 * dw;
     if (strip_rows) {
-        const int64_t u = band ? golk_band_useful_words(kk, dw) : 62 * dw;
+        const int64_t u = bits && e->rule_generic ? golk_rule_useful_words(band, kk)
+                                                  : (band ? golk_band_useful_words(kk, dw) : 62 * dw);
         const int64_t ng = (e->Wd + u - 1) / u;
         *strip_rows = e->strip > 0 ? e->strip : golk_auto_strip(e->min_rows, ng, kk);
     }
     if (bit_mode) *bit_mode = bits ? (band ? 2 : 1) : 0;
+    return GOL_OK;
+}
+
+// ------------------------------------------------------------------ rules
+extern "C" int gol_engine_set_rule(gol_engine *e, uint32_t birth, uint32_t survive, int32_t flags)
+{
+    if (!e) return gol_set_error(GOL_EINVAL, "engine is NULL");
+    if (birth >= 512 || survive >= 512 || (flags & ~GOL_RULE_GENERIC))
+        return gol_set_error(GOL_EINVAL, "bad rule (B 0x%x, S 0x%x, flags 0x%x): 9-bit masks, flags GOL_RULE_GENERIC", birth,
+                             survive, flags);
+    const bool conway = birth == 0x008 && survive == 0x00C;
+    const bool generic = !conway || (flags & GOL_RULE_GENERIC);
+    if (generic && !e->bit_capable)
+        return gol_set_error(GOL_EINVAL, "rules other than B3/S23 (and GOL_RULE_GENERIC) need a bit board: W %% 64 == 0 (W = %lld), layout not BYTES",
+                             (long long)e->W);
+    // nothing else changes: the board, the turn and the halo (cells, whatever rule made them) stay
+    e->birth = birth;
+    e->survive = survive;
+    e->rule_generic = generic;
+    return GOL_OK;
+}
+
+extern "C" int gol_engine_rule(gol_engine *e, uint32_t *birth, uint32_t *survive, int32_t *generic)
+{
+    if (!e) return gol_set_error(GOL_EINVAL, "engine is NULL");
+    if (birth) *birth = e->birth;
+    if (survive) *survive = e->survive;
+    if (generic) *generic = e->rule_generic ? 1 : 0;
     return GOL_OK;
 }
 

@@ -47,6 +47,17 @@ int golk_band_useful_words(int k, int dw);
 // its one-round rank-weighted launch; other kernels: 1e9, i.e. many); for the engine's choice of
 // step plan.
 double golk_step_rounds(bool band, int64_t rows, int64_t Wd, int64_t pitch, int k, int dw, int strip);
+// Life-like rules (gol_rule.hip; birth / survive: 9-bit masks over the neighbour count, gol_rule.h):
+// k in {1, 2, 4, 8} turns of a standard or band bit board, GOLK_RULE_DW words per lane in both
+// layouts (Wd and pitch multiples of it, rows aligned to 4 bytes x GOLK_RULE_DW); row addressing,
+// strips and count slots as golk_bits_step / golk_band_step.  golk_rule_useful_words: output words
+// of a wave's column group.
+#define GOLK_RULE_DW 2
+#define GOLK_RULE_MAX_K 8
+hipError_t golk_rule_step(const uint32_t *top, const uint32_t *mid, const uint32_t *bot, uint32_t *dst, int64_t R,
+                          int64_t Wd, int64_t pitch, int64_t row0, int64_t rows, int k, bool band, uint32_t birth,
+                          uint32_t survive, int strip, uint64_t *slots, hipStream_t s);
+int golk_rule_useful_words(bool band, int k);
 // Standard <-> band rows (Wd % 32 == 0), out of place.
 hipError_t golk_band_convert(bool to_band, const uint32_t *src, uint32_t *dst, int64_t rows, int64_t Wd,
                              int64_t spitch, int64_t dpitch, hipStream_t s);

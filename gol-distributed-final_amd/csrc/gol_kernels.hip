@@ -1248,6 +1248,10 @@ hipError_t golk_band_pipe_launch(bool contig, bool count, unsigned nwg, const Bi
     else hipLaunchKernelGGL((band_pipe_kernel<KW, P, false, false>), g, blk, 0, s, a);
     return hipGetLastError();
 }
+#elif defined(GOL_TU_RULE)
+}  // namespace golk
+// gol_rule.hip: this file up to here (the helpers, the register pipeline's state and horizontal
+// sums, BitsArgs and the strip maps), then the rule kernels of its own.
 #else  // the rest of the kernels and the host side
 
 // 32 x 32 bit-matrix transpose in registers: afterwards x[i] bit b = (before) x[b] bit i.

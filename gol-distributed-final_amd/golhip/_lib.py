@@ -40,6 +40,7 @@ STEP_MODES = {"auto": 0, "serial": GOL_STEP_SERIAL, "edge_first": GOL_STEP_EDGE_
 GOL_HALO_SEND, GOL_HALO_RECV = 0, 1
 GOL_LAUNCH_MAIN, GOL_LAUNCH_EDGE = 0, 1
 VIEW_LAYOUTS = {0: "bytes", 1: "standard", 2: "band"}  # *src_layout of the view calls
+GOL_RULE_GENERIC = 1  # gol_engine_set_rule flag: B3/S23 on the rule kernels too
 
 _NAMES = {
     GOL_EINVAL: "EINVAL", GOL_EHIP: "EHIP", GOL_ENOMEM: "ENOMEM", GOL_EIO: "EIO",
@@ -136,6 +137,12 @@ SIGNATURES = [
     ("gol_engine_exchange_split", ctypes.c_int, [_vp, _P(_i64), _P(ctypes.c_double), _P(ctypes.c_double)]),
     ("gol_engine_view_counts", ctypes.c_int, [_vp, _i64, _i64, _i32, _i32, _i32, _vp, _i64, _P(_i32)]),
     ("gol_engine_view", ctypes.c_int, [_vp, _i64, _i64, _i32, _i32, _i32, _vp, _i64, _P(_i32)]),
+    ("gol_rule_parse", ctypes.c_int, [ctypes.c_char_p, _P(ctypes.c_uint32), _P(ctypes.c_uint32)]),
+    ("gol_rule_format", ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_char_p, _i64]),
+    ("gol_rule_eval_host", ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint32, _P(ctypes.c_uint32), ctypes.c_uint32,
+                                          _P(ctypes.c_uint32)]),
+    ("gol_engine_set_rule", ctypes.c_int, [_vp, ctypes.c_uint32, ctypes.c_uint32, _i32]),
+    ("gol_engine_rule", ctypes.c_int, [_vp, _P(ctypes.c_uint32), _P(ctypes.c_uint32), _P(_i32)]),
     ("gol_halo_plan", ctypes.c_int, [_i64, _i32, _i32, _i32, _P(gol_halo_op), _i32, _P(_i32)]),
     ("gol_step_plan", ctypes.c_int, [_i64, _i32, _i32, _i32, _P(gol_launch), _i32, _P(_i32)]),
     ("gol_view_plan", ctypes.c_int, [_i64, _i32, _i32, _i64, _i64, _P(gol_view_run), _i32, _P(_i32)]),
@@ -151,6 +158,9 @@ SIGNATURES = [
      [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _vp, _vp]),
     ("gol_dev_band_step", ctypes.c_int,
      [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _vp, _vp]),
+    ("gol_dev_rule_step", ctypes.c_int,
+     [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i32, _i32, ctypes.c_uint32, ctypes.c_uint32, _i32, _i32, _vp,
+      _vp]),
     ("gol_band_max_k", ctypes.c_int, [_i32]),
     ("gol_dev_band_convert", ctypes.c_int, [_i32, _vp, _vp, _i64, _i64, _i64, _i64, _vp]),
     ("gol_dev_error", ctypes.c_int, [_i32, _P(ctypes.c_uint32)]),
@@ -238,6 +248,30 @@ def view_plan(H: int, nranks: int, rank: int, y0: int, vrows: int) -> list[tuple
     n = ctypes.c_int32()
     check(lib().gol_view_plan(H, nranks, rank, y0, vrows, runs, 2, ctypes.byref(n)))
     return [(r.row, r.rows, r.vrow) for r in runs[:n.value]]
+
+
+def _lib_check(L, rc: int) -> None:
+    if rc != GOL_OK:
+        raise GolError(rc, L.gol_last_error().decode(errors="replace"))
+
+
+def parse_rule(text: str, library=None) -> tuple[int, int]:
+    """gol_rule_parse: "B36/S23" -> (birth, survive), two 9-bit masks over the neighbour count
+    (bit n: exactly n alive neighbours).  Host code: no GPU needed."""
+    L = library or lib()
+    b, s = ctypes.c_uint32(), ctypes.c_uint32()
+    _lib_check(L, L.gol_rule_parse(str(text).encode(), ctypes.byref(b), ctypes.byref(s)))
+    return b.value, s.value
+
+
+def format_rule(birth: int, survive: int, library=None) -> str:
+    """gol_rule_format: the canonical text of a rule (upper case, ascending digits)."""
+    L = library or lib()
+    if not (0 <= birth < 1 << 32 and 0 <= survive < 1 << 32):
+        raise GolError(GOL_EINVAL, f"rule masks out of range ({birth}, {survive})")
+    buf = ctypes.create_string_buffer(24)
+    _lib_check(L, L.gol_rule_format(birth, survive, buf, len(buf)))
+    return buf.value.decode()
 
 
 def device_count() -> int:

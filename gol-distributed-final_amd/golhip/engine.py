@@ -15,9 +15,9 @@ import ctypes
 
 import numpy as np
 
-from ._lib import (GOL_EINVAL, GOL_IPC_ID_BYTES, GOL_RCCL_ID_BYTES, GOL_SHARDS_SAME_DEVICE, GOL_TIMING_EXCHANGE,
-                   GOL_WRITE_FN, LAYOUTS, STEP_MODES, TRANSPORT_NAMES, TRANSPORTS, VIEW_LAYOUTS, GolError, check,
-                   gol_config, lib)
+from ._lib import (GOL_EINVAL, GOL_IPC_ID_BYTES, GOL_RCCL_ID_BYTES, GOL_RULE_GENERIC, GOL_SHARDS_SAME_DEVICE,
+                   GOL_TIMING_EXCHANGE, GOL_WRITE_FN, LAYOUTS, STEP_MODES, TRANSPORT_NAMES, TRANSPORTS, VIEW_LAYOUTS,
+                   GolError, check, format_rule, gol_config, lib, parse_rule)
 
 
 def rccl_unique_id(library=None) -> bytes:
@@ -49,7 +49,8 @@ def unique_id(transport: str = "rccl", library=None) -> bytes:
 class Engine:
     def __init__(self, height: int, width: int, *, turns_per_launch: int = 0, cells_per_lane: int = 0,
                  strip_rows: int = 0, device: int = -1, layout: str = "auto", shards: int = 1,
-                 transport: str = "auto", same_device: bool = False, step: str = "auto", library=None, _rank=None):
+                 transport: str = "auto", same_device: bool = False, step: str = "auto", rule=None, library=None,
+                 _rank=None):
         self.H, self.W = int(height), int(width)
         self._L = library or lib()
         cfg = gol_config(device=device, turns_per_launch=turns_per_launch, strip_rows=strip_rows,
@@ -71,6 +72,12 @@ class Engine:
             self._check(self._L.gol_engine_create_rank(self.H, self.W, nranks, rank, idbuf, ctypes.byref(cfg),
                                                        ctypes.byref(h)))
         self._h = h
+        if rule is not None:  # default: B3/S23 on the Conway kernels
+            try:
+                self.set_rule(rule)
+            except BaseException:
+                self.close()
+                raise
 
     @classmethod
     def rank(cls, height: int, width: int, nranks: int, rank: int, uid: bytes | None, **kw) -> "Engine":
@@ -159,6 +166,33 @@ class Engine:
         out = np.empty((max(y1 - y0, 0), self.W // 64), dtype=np.uint64)
         self._check(self._L.gol_engine_store_words(self._h, y0, y1, out.ctypes.data, self.W // 64))
         return out
+
+    # -- the rule
+    def set_rule(self, rule, generic: bool = False) -> None:
+        """The life-like rule of every later turn (gol_engine_set_rule): "B36/S23" or a (birth,
+        survive) pair of 9-bit masks.  The board and the turn counter stay.  Rules other than
+        B3/S23 run on the rule kernels (bit boards only); generic=True runs B3/S23 on them too.
+        With several ranks every rank sets the same rule before the next stepping call."""
+        birth, survive = parse_rule(rule, self._L) if isinstance(rule, str) else (int(rule[0]), int(rule[1]))
+        if not (0 <= birth < 1 << 32 and 0 <= survive < 1 << 32):
+            raise GolError(GOL_EINVAL, f"rule masks out of range ({birth}, {survive})")
+        self._check(self._L.gol_engine_set_rule(self._h, birth, survive, GOL_RULE_GENERIC if generic else 0))
+
+    def _rule(self):
+        b, s, g = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_int32()
+        self._check(self._L.gol_engine_rule(self._h, ctypes.byref(b), ctypes.byref(s), ctypes.byref(g)))
+        return b.value, s.value, bool(g.value)
+
+    @property
+    def rule(self) -> str:
+        """The current rule's canonical text, e.g. "B3/S23"."""
+        b, s, _ = self._rule()
+        return format_rule(b, s, self._L)
+
+    @property
+    def rule_generic(self) -> bool:
+        """The rule kernels step the board (any rule but plain B3/S23)."""
+        return self._rule()[2]
 
     # -- stepping and queries
     def step(self, turns: int) -> None:

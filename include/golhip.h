@@ -304,6 +304,52 @@ int gol_engine_view_counts(gol_engine *e, int64_t x0, int64_t y0, int32_t scale,
 int gol_engine_view(gol_engine *e, int64_t x0, int64_t y0, int32_t scale, int32_t out_w, int32_t out_h,
                     uint8_t *pixels, int64_t stride, int32_t *src_layout);
 
+/* ---------------------------------------------------------------- life-like rules
+ * (Added after ABI 6 without a version bump, like the viewport calls:
+ * GOL_ABI_VERSION stays 6; probe for gol_engine_set_rule, gol_engine_rule,
+ * gol_rule_parse, gol_rule_format, gol_rule_eval_host and gol_dev_rule_step by
+ * symbol.)
+ *
+ * A rule is two 9-bit masks over the number n of alive cells among a cell's 8
+ * neighbours: birth bit n (0 <= n <= 8) = a dead cell with exactly n alive
+ * neighbours becomes alive, survive bit n = an alive cell with exactly n stays
+ * alive; every other cell is dead next turn.  B3/S23 (the default, the
+ * reference's rule) is birth 0x008, survive 0x00C.  Bit 0 of birth (B0 rules)
+ * is legal: the board is a finite torus.
+ *
+ * gol_rule_parse / gol_rule_format / gol_rule_eval_host are host functions (no
+ * GPU needed).
+ *  - parse: "B<digits>/S<digits>", case-insensitive, digits 0-8 in any order,
+ *    either list may be empty ("B2/S").  GOL_EINVAL for a digit 9, a repeated
+ *    digit, a missing half or trailing text.
+ *  - format: the canonical text (upper case, ascending digits) into buf[len]
+ *    (at most 22 bytes with the NUL); GOL_EINVAL for masks >= 512 or a buffer
+ *    too small.
+ *  - eval_host: the circuit of the rule kernels (csrc/gol_rule.h: the bit-sliced
+ *    3x3 count and a mux tree over the masks) applied to 32 independent cells;
+ *    bit i of nb[j] is neighbour j of cell i, bit i of centre the cell itself. */
+int gol_rule_parse(const char *text, uint32_t *birth, uint32_t *survive);
+int gol_rule_format(uint32_t birth, uint32_t survive, char *buf, int64_t len);
+int gol_rule_eval_host(uint32_t birth, uint32_t survive, const uint32_t nb[8], uint32_t centre, uint32_t *next);
+/* gol_engine_set_rule: the rule of every later turn.  Valid between stepping
+ * calls at any turn; the board, the turn counter and the halo stay as they are.
+ * A rule other than B3/S23 -- or B3/S23 with GOL_RULE_GENERIC, for tests and A/B
+ * measurement -- is stepped by the rule kernels (masks as data, at most 8 turns
+ * per launch, 64 cells per lane, standard and band layout); B3/S23 with flags 0
+ * restores the B3/S23 kernels exactly.  GOL_EINVAL for masks >= 512, unknown
+ * flags, or the rule kernels on a board that is not a bit board (W % 64 != 0
+ * or GOL_LAYOUT_BYTES).  The reference's byte semantics (exactly 0 / exactly
+ * 255) are defined for B3/S23 only: while another rule is set and the board
+ * holds loaded bytes other than 0/255 (its exact first turn pending), stepping
+ * calls return GOL_ESTATE and change nothing.  With several ranks every rank
+ * must set the same rule before the next collective stepping call (the
+ * caller's duty, like H and W).
+ * gol_engine_rule: the current masks; *generic != 0 while the rule kernels are
+ * in use (any pointer may be NULL). */
+#define GOL_RULE_GENERIC 1
+int gol_engine_set_rule(gol_engine *e, uint32_t birth, uint32_t survive, int32_t flags);
+int gol_engine_rule(gol_engine *e, uint32_t *birth, uint32_t *survive, int32_t *generic);
+
 /* ---------------------------------------------------------------- plans
  * The schedule of a sharded step as data (host functions, no GPU needed).  The
  * engine runs exactly these plans; golhip.sharded (the torch.distributed
@@ -430,6 +476,15 @@ int gol_dev_bytes_step_k(const uint8_t *top, const uint8_t *mid, const uint8_t *
 int gol_dev_band_step(const uint32_t *top, const uint32_t *mid, const uint32_t *bot, uint32_t *dst,
                       int64_t R, int64_t Wd, int64_t pitch, int64_t row0, int64_t rows, int32_t k,
                       int32_t cells_per_lane, int32_t strip_rows, uint64_t *count_slots, void *stream);
+/* k turns (1, 2, 4 or 8) of a life-like rule (birth / survive: 9-bit masks, see
+ * "life-like rules") on a bit board in the standard (GOL_LAYOUT_STANDARD) or
+ * the band (GOL_LAYOUT_BAND) layout; row addressing and count_slots as
+ * gol_dev_bits_step.  cells_per_lane: 64 (0 = default, the same); Wd and pitch
+ * even, rows 8-byte aligned.  No version bump: probe by symbol. */
+int gol_dev_rule_step(const uint32_t *top, const uint32_t *mid, const uint32_t *bot, uint32_t *dst,
+                      int64_t R, int64_t Wd, int64_t pitch, int64_t row0, int64_t rows, int32_t k,
+                      int32_t layout, uint32_t birth, uint32_t survive, int32_t cells_per_lane,
+                      int32_t strip_rows, uint64_t *count_slots, void *stream);
 /* Largest k gol_dev_band_step accepts for this cells_per_lane (0 = default);
  * 0 if cells_per_lane is not supported. */
 int gol_band_max_k(int32_t cells_per_lane);
