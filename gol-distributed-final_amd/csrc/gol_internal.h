@@ -114,7 +114,7 @@ struct gol_engine {
     bool bytes_binary = false; // BYTES mode: the board holds only 0/255
     int cur = 0, bcur = 0;
     int64_t turn = 0;
-    // the rule (gol_engine_set_rule): 9-bit masks; rule_generic: the rule kernels (gol_rule.hip)
+    // the rule (gol_engine_set_rule): 9-bit masks; rule_generic: the rule kernels (golk_rule_step)
     // step the bit board, with at most GOLK_RULE_MAX_K turns per launch -- else B3/S23 on the Conway kernels
     uint32_t birth = 0x008, survive = 0x00C;
     bool rule_generic = false;

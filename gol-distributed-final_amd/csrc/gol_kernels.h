@@ -47,7 +47,7 @@ int golk_band_useful_words(int k, int dw);
 // its one-round rank-weighted launch; other kernels: 1e9, i.e. many); for the engine's choice of
 // step plan.
 double golk_step_rounds(bool band, int64_t rows, int64_t Wd, int64_t pitch, int k, int dw, int strip);
-// Life-like rules (gol_rule.hip; birth / survive: 9-bit masks over the neighbour count, gol_rule.h):
+// Life-like rules (the step kernels with TableRule; birth / survive: 9-bit masks over the neighbour count, gol_rule.h):
 // k in {1, 2, 4, 8} turns of a standard or band bit board, GOLK_RULE_DW words per lane in both
 // layouts (Wd and pitch multiples of it, rows aligned to 4 bytes x GOLK_RULE_DW); row addressing,
 // strips and count slots as golk_bits_step / golk_band_step.  golk_rule_useful_words: output words

@@ -28,6 +28,7 @@
 #include <utility>
 
 #include "gol_kernels.h"
+#include "gol_rule.h"
 
 // Polls of a pipeline flag before a wave gives up (sets GOLK_ERR_SPIN in the launch's error
 // word and leaves; the host turns that into GOL_EHIP).  A test build sets 0 to force the path.
@@ -325,11 +326,42 @@ __device__ __forceinline__ int work_dir(const StripMap &sm, int l, uint32_t *&ct
     return sm.dir[rank];
 }
 
+// ------------------------------------------------------------------ the rule of a step kernel
+// bits_step_kernel and band_step_kernel are generic over the rule (B3S23 and TableRule, below
+// the band stages).  Rule::Args is the kernel's argument block: BitsArgs, plus the rule's data if
+// it has any.  Rule::tab(args) is the rule's wave-uniform state, formed once per wave;
+// Rule::stage<K, DW, S, BAND>(tab, p, g, cur) is one stage (generation g+1) of one row step S, in
+// place on `cur`.
+struct B3S23;
+
+// The three rows of a block run through the K stages as a wavefront (row S is at stage w - S),
+// so every instruction has two independent neighbours to issue beside it and the DPP
+// read-after-write hazards are covered without s_nop.  (K, DW, Rule: template parameters where
+// it is expanded.)
+#define GOL_STAGE_BLOCK(BAND, tab, p, cur)                                                        \
+    _Pragma("unroll") for (int w = 0; w < K + 2; ++w) {                                           \
+        if (w < K) Rule::template stage<K, DW, 0, BAND>(tab, p, w, cur[0]);                       \
+        if (w >= 1 && w - 1 < K) Rule::template stage<K, DW, 1, BAND>(tab, p, w - 1, cur[1]);     \
+        if (w >= 2 && w - 2 < K) Rule::template stage<K, DW, 2, BAND>(tab, p, w - 2, cur[2]);     \
+    }
+// Where the wavefront is expanded is a matter of instruction scheduling only: as a function the
+// compiler unrolls and simplifies it on its own before it inlines it, in the kernel's body
+// together with the loads and stores around it, and the same operations come out in another
+// order.  Each rule keeps the form it was measured with (Rule::BLOCK_INLINE): B3/S23 in the
+// kernel's body (as a function e.g. bits_step_kernel<4, 2> has 1432 instructions instead of
+// 1014), the table rule as a function (in the body its k = 8 standard kernel has the same 2329
+// instructions in another order and ran 2.6 % slower).
+template <class Rule, bool BAND, int K, int DW>
+__device__ __forceinline__ void stage_block(const typename Rule::Tab &tab, Pipe<K, DW> &p, uint32_t (&cur)[3][DW])
+{
+    GOL_STAGE_BLOCK(BAND, tab, p, cur)
+}
+
 // ------------------------------------------------------------------ bit-board step, standard layout
 // grid.x: groups of 4 waves along the row; grid.y: strips of output rows.
 // Wave = one column group of 62*DW output words (+1 halo lane each side).
-template <int K, int DW>
-__global__ void __launch_bounds__(256) bits_step_kernel(BitsArgs a)
+template <int K, int DW, class Rule = B3S23>
+__global__ void __launch_bounds__(256) bits_step_kernel(typename Rule::Args a)
 {
     const int lane = threadIdx.x & 63;
     const int group = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -361,6 +393,7 @@ __global__ void __launch_bounds__(256) bits_step_kernel(BitsArgs a)
         return reinterpret_cast<const uint32_t *>(rb + lane_off);
     };
 
+    const typename Rule::Tab tab = Rule::tab(a);
     Pipe<K, DW> p;
     pipe_init(p);
 
@@ -375,20 +408,13 @@ __global__ void __launch_bounds__(256) bits_step_kernel(BitsArgs a)
 #pragma unroll
         for (int s = 0; s < 3; ++s) load_words<DW>(row_ptr(first_in + t0 + 3 + s), nxt[s]);
 
-        // The three rows of this block run through the K stages as a wavefront (row S is
-        // at stage w - S), so every instruction has two independent neighbours to issue
-        // beside it and the DPP read-after-write hazards are covered without s_nop.
         uint32_t cur[3][DW];
 #pragma unroll
         for (int s = 0; s < 3; ++s)
 #pragma unroll
             for (int j = 0; j < DW; ++j) cur[s][j] = buf[s][j];
-#pragma unroll
-        for (int w = 0; w < K + 2; ++w) {
-            if (w < K) sstage<K, DW, 0>(p, w, cur[0]);
-            if (w >= 1 && w - 1 < K) sstage<K, DW, 1>(p, w - 1, cur[1]);
-            if (w >= 2 && w - 2 < K) sstage<K, DW, 2>(p, w - 2, cur[2]);
-        }
+        if constexpr (Rule::BLOCK_INLINE) { GOL_STAGE_BLOCK(false, tab, p, cur) }
+        else stage_block<Rule, false>(tab, p, cur);
 #pragma unroll
         for (int S = 0; S < 3; ++S) {
             uint32_t (&out)[DW] = cur[S];
@@ -502,6 +528,64 @@ __device__ __forceinline__ void bstage_seq(Pipe<K, DW> &p, const int g, uint32_t
                       p.h1[g][S][j], p.cc[g][SM][j]);
 }
 
+// The same stage for a life-like rule as data (gol_rule.h): the full 4-bit count of the 3x3 block
+// and a mux tree over the rule's two tables instead of the hard-wired B3/S23 tail.  Per word and
+// generation: 2 ops of horizontal sums (band; the standard layout's shifted frame adds its 2
+// v_alignbit), 7 for the count, 19 for the rule.
+template <int K, int DW, int S, bool BAND>
+__device__ __forceinline__ void rstage(const gol_rule_tab &tab, Pipe<K, DW> &p, const int g, uint32_t (&cur)[DW])
+{
+    constexpr int SA = (S + 1) % 3, SM = (S + 2) % 3;
+    if constexpr (BAND) {
+#pragma unroll
+        for (int j = 0; j < DW; ++j) p.cc[g][S][j] = cur[j];
+        hsum_band<DW>(p.cc[g][S], p.h0[g][S], p.h1[g][S]);
+    } else {
+        hsum_left<DW>(cur, p.h0[g][S], p.h1[g][S], p.cc[g][S]);
+    }
+#pragma unroll
+    for (int j = 0; j < DW; ++j) {
+        uint32_t t0, t1, t2, t3;
+        gol_rule_sum3(p.h0[g][SA][j], p.h1[g][SA][j], p.h0[g][SM][j], p.h1[g][SM][j], p.h0[g][S][j], p.h1[g][S][j],
+                      t0, t1, t2, t3);
+        cur[j] = gol_rule_eval(tab, t0, t1, t2, t3, p.cc[g][SM][j]);
+    }
+}
+
+// The two rules of the step kernels (GOL_STAGE_BLOCK).  B3/S23 hard-wired: no data, so the kernel's
+// argument block is BitsArgs itself.
+struct B3S23 {
+    typedef BitsArgs Args;
+    static constexpr bool BLOCK_INLINE = true;
+    struct Tab {};
+    static __device__ __forceinline__ Tab tab(const Args &) { return {}; }
+    template <int K, int DW, int S, bool BAND>
+    static __device__ __forceinline__ void stage(const Tab &, Pipe<K, DW> &p, const int g, uint32_t (&cur)[DW])
+    {
+        if constexpr (BAND) bstage<K, DW, S>(p, g, cur);
+        else sstage<K, DW, S>(p, g, cur);
+    }
+};
+// Any life-like rule: the two 9-bit masks, expanded into the circuit's tables once per wave.
+struct TableRule {
+    struct Args : BitsArgs {
+        uint32_t birth, survive;
+    };
+    typedef gol_rule_tab Tab;
+    static constexpr bool BLOCK_INLINE = false;
+    static __device__ __forceinline__ Tab tab(const Args &a)
+    {
+        Tab t;
+        gol_rule_expand(a.birth, a.survive, t);
+        return t;
+    }
+    template <int K, int DW, int S, bool BAND>
+    static __device__ __forceinline__ void stage(const Tab &t, Pipe<K, DW> &p, const int g, uint32_t (&cur)[DW])
+    {
+        rstage<K, DW, S, BAND>(t, p, g, cur);
+    }
+};
+
 __host__ __device__ constexpr int band_halo_lanes(int k, int dw) { return (k + dw - 1) / dw; }
 __host__ __device__ constexpr int band_useful_words(int k, int dw) { return (64 - 2 * band_halo_lanes(k, dw)) * dw; }
 
@@ -510,8 +594,8 @@ __host__ __device__ constexpr int band_useful_words(int k, int dw) { return (64 
 // grid.y: strips of output rows.
 // CONTIG: top == mid - K*pitch and bot == mid + R*pitch (halo rows stored right above and
 // below the shard), so input row y is simply mid + y*pitch: no per-row segment select.
-template <int K, int DW, bool CONTIG>
-__global__ void __launch_bounds__(256) band_step_kernel(BitsArgs a)
+template <int K, int DW, bool CONTIG, class Rule = B3S23>
+__global__ void __launch_bounds__(256) band_step_kernel(typename Rule::Args a)
 {
     constexpr int HL = band_halo_lanes(K, DW);
     constexpr int U = band_useful_words(K, DW);
@@ -566,6 +650,7 @@ __global__ void __launch_bounds__(256) band_step_kernel(BitsArgs a)
         }
     };
 
+    const typename Rule::Tab tab = Rule::tab(a);
     Pipe<K, DW> p;
     pipe_init(p);
 
@@ -593,12 +678,8 @@ __global__ void __launch_bounds__(256) band_step_kernel(BitsArgs a)
             uint32_t (&cur)[3][DW] = ring[u];
 #pragma unroll
             for (int s = 0; s < 3; ++s) unwrap(cur[s]);
-#pragma unroll
-            for (int w = 0; w < K + 2; ++w) {
-                if (w < K) bstage<K, DW, 0>(p, w, cur[0]);
-                if (w >= 1 && w - 1 < K) bstage<K, DW, 1>(p, w - 1, cur[1]);
-                if (w >= 2 && w - 2 < K) bstage<K, DW, 2>(p, w - 2, cur[2]);
-            }
+            if constexpr (Rule::BLOCK_INLINE) { GOL_STAGE_BLOCK(true, tab, p, cur) }
+            else stage_block<Rule, true>(tab, p, cur);
 #pragma unroll
             for (int S = 0; S < 3; ++S) {
                 const int t = t0 + S;
@@ -617,6 +698,7 @@ __global__ void __launch_bounds__(256) band_step_kernel(BitsArgs a)
     }
     if (a.slots) slot_add(a.slots, alive);
 }
+#undef GOL_STAGE_BLOCK
 
 // ------------------------------------------------------------------ LDS helpers of the pipelines
 // LDS accesses of the pipelines are inline asm: the compiler treats a global_load_lds in
@@ -1248,10 +1330,6 @@ hipError_t golk_band_pipe_launch(bool contig, bool count, unsigned nwg, const Bi
     else hipLaunchKernelGGL((band_pipe_kernel<KW, P, false, false>), g, blk, 0, s, a);
     return hipGetLastError();
 }
-#elif defined(GOL_TU_RULE)
-}  // namespace golk
-// gol_rule.hip: this file up to here (the helpers, the register pipeline's state and horizontal
-// sums, BitsArgs and the strip maps), then the rule kernels of its own.
 #else  // the rest of the kernels and the host side
 
 // 32 x 32 bit-matrix transpose in registers: afterwards x[i] bit b = (before) x[b] bit i.
@@ -2392,20 +2470,30 @@ static int64_t round_tiled_strip(int64_t rows, int64_t ngroups, int64_t slots, i
     return std::min(rows, std::max(strip, min_rows));
 }
 
-hipError_t golk_bits_step(const uint32_t *top, const uint32_t *mid, const uint32_t *bot, uint32_t *dst,
-                          int64_t R, int64_t Wd, int64_t pitch, int64_t row0, int64_t rows, int k, int dw,
-                          int strip, uint64_t *slots, hipStream_t s)
+// Arguments of a step launch (golk_bits_step, golk_band_step, golk_rule_step): waves of U output
+// words, strips of `strip` rows (<= 0: golk_auto_strip), no strip map, error word or CU slots.
+static BitsArgs step_args(const uint32_t *top, const uint32_t *mid, const uint32_t *bot, uint32_t *dst, int64_t R,
+                          int64_t Wd, int64_t pitch, int64_t row0, int64_t rows, int U, int k, int strip,
+                          uint64_t *slots)
 {
     BitsArgs a;
     a.top = top; a.mid = mid; a.bot = bot; a.dst = dst;
     a.R = R; a.Wd = Wd; a.pitch = pitch; a.row0 = row0; a.rows = rows;
-    a.ngroups = (int)((Wd + 62 * dw - 1) / (62 * dw));
+    a.ngroups = (int)((Wd + U - 1) / U);
     a.strip = strip > 0 ? std::min(strip, GOL_MAX_STRIP) : golk_auto_strip(rows, a.ngroups, k);
     a.slots = slots;
     a.sm = StripMap{};
-    a.err = nullptr;  // no flag waits in this kernel
+    a.err = nullptr;  // no flag waits in the step kernels
     a.cu_slots = nullptr;
+    return a;
+}
+
+hipError_t golk_bits_step(const uint32_t *top, const uint32_t *mid, const uint32_t *bot, uint32_t *dst,
+                          int64_t R, int64_t Wd, int64_t pitch, int64_t row0, int64_t rows, int k, int dw,
+                          int strip, uint64_t *slots, hipStream_t s)
+{
     if (rows <= 0) return hipSuccess;
+    const BitsArgs a = step_args(top, mid, bot, dst, R, Wd, pitch, row0, rows, 62 * dw, k, strip, slots);
     switch (dw) {
     case 1: return launch_bits_k<1>(k, a, s);
     case 2: return launch_bits_k<2>(k, a, s);
@@ -2707,21 +2795,14 @@ hipError_t golk_band_step(const uint32_t *top, const uint32_t *mid, const uint32
                           uint64_t *slots, uint32_t *err, hipStream_t s)
 {
     if (rows <= 0) return hipSuccess;
-    BitsArgs a;
-    a.top = top; a.mid = mid; a.bot = bot; a.dst = dst;
-    a.R = R; a.Wd = Wd; a.pitch = pitch; a.row0 = row0; a.rows = rows;
-    a.slots = slots;
-    a.sm = StripMap{};
+    BitsArgs a = step_args(top, mid, bot, dst, R, Wd, pitch, row0, rows, band_useful_words(k, dw), k, strip, slots);
     a.err = err_or_default(err);
     if (!a.err) return hipErrorOutOfMemory;
-    a.cu_slots = nullptr;
     if (GOL_BAND_PLACE) {
         int dev = 0;
         if (hipGetDevice(&dev) == hipSuccess) a.cu_slots = golk_cu_slots(dev);
     }
     const bool contig = top + (int64_t)k * pitch == mid && bot == mid + R * pitch;
-    const int U = band_useful_words(k, dw);
-    a.ngroups = (int)((Wd + U - 1) / U);
     if (dw == 4 && k == GOL_BAND_KW * GOL_BAND_P) {
         // one workgroup per (column group, strip): strips up to 1024 rows (measured best at k = 12)
         // Boards with fewer than ~256 tiles of 8k rows are latency-bound (a launch lasts one
@@ -2740,7 +2821,6 @@ hipError_t golk_band_step(const uint32_t *top, const uint32_t *mid, const uint32
         a.strip = (int)std::max<int64_t>(1, std::min<int64_t>(a.strip, (int64_t(1) << 30) / (pitch * 4)));
         return launch_band_pipe(contig, a, s, strip <= 0 && !small);
     }
-    a.strip = strip > 0 ? std::min(strip, GOL_MAX_STRIP) : golk_auto_strip(rows, a.ngroups, k);
     dim3 grid((a.ngroups + 3) / 4, (int)((rows + a.strip - 1) / a.strip));
     if (dw == 2) return contig ? launch_band<2, true>(k, grid, a, s) : launch_band<2, false>(k, grid, a, s);
     if (dw == 4) return contig ? launch_band<4, true>(k, grid, a, s) : launch_band<4, false>(k, grid, a, s);
@@ -2748,6 +2828,37 @@ hipError_t golk_band_step(const uint32_t *top, const uint32_t *mid, const uint32
 }
 
 int golk_band_useful_words(int k, int dw) { return band_useful_words(k, dw); }
+
+// Life-like rules: the step kernels with the rule as data, general row addressing.
+template <int K>
+static hipError_t launch_rule(bool band, dim3 grid, const TableRule::Args &a, hipStream_t s)
+{
+    constexpr int DW = GOLK_RULE_DW;
+    if (band) hipLaunchKernelGGL((band_step_kernel<K, DW, false, TableRule>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((bits_step_kernel<K, DW, TableRule>), grid, dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+int golk_rule_useful_words(bool band, int k) { return band ? band_useful_words(k, GOLK_RULE_DW) : 62 * GOLK_RULE_DW; }
+
+hipError_t golk_rule_step(const uint32_t *top, const uint32_t *mid, const uint32_t *bot, uint32_t *dst, int64_t R,
+                          int64_t Wd, int64_t pitch, int64_t row0, int64_t rows, int k, bool band, uint32_t birth,
+                          uint32_t survive, int strip, uint64_t *slots, hipStream_t s)
+{
+    if (rows <= 0) return hipSuccess;
+    if (birth >= 512 || survive >= 512 || Wd % GOLK_RULE_DW || pitch % GOLK_RULE_DW) return hipErrorInvalidValue;
+    const TableRule::Args a{step_args(top, mid, bot, dst, R, Wd, pitch, row0, rows, golk_rule_useful_words(band, k), k,
+                                      strip, slots),
+                            birth, survive};
+    const dim3 grid((a.ngroups + 3) / 4, (unsigned)((rows + a.strip - 1) / a.strip));
+    switch (k) {
+    case 1: return launch_rule<1>(band, grid, a, s);
+    case 2: return launch_rule<2>(band, grid, a, s);
+    case 4: return launch_rule<4>(band, grid, a, s);
+    case 8: return launch_rule<8>(band, grid, a, s);
+    default: return hipErrorInvalidValue;
+    }
+}
 
 double golk_step_rounds(bool band, int64_t rows, int64_t Wd, int64_t pitch, int k, int dw, int strip)
 {

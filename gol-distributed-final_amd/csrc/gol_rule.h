@@ -1,5 +1,5 @@
 // gol_rule.h -- a life-like rule (B/S, radius 1, outer-totalistic) as data, and the one circuit
-// that evaluates it on bit-sliced words.  Shared by the rule kernels (gol_rule.hip) and the host
+// that evaluates it on bit-sliced words.  Shared by the rule kernels (gol_kernels.hip, TableRule) and the host
 // (gol_rule_eval_host, include/golhip.h), so the circuit the GPU runs is tested on the CPU.
 //
 // A rule is two 9-bit masks: birth bit n / survive bit n = a dead / an alive cell with exactly n

@@ -229,6 +229,39 @@ def test_valu_hazard_checker_catches_asm_hazards():
     assert not scan(fall.replace(".LBB0_1:", "\ts_branch .LBB0_2\n.LBB0_1:"))
 
 
+def test_isa_diff_compares_streams_not_text():
+    """tools/isa_diff.py on hand-made assembly: comments, directives and the numbering of local
+    labels do not count, an immediate operand is reported as such, another instruction or register
+    as a difference; the policy argument of a kernel's name is not part of its identity."""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import isa_diff as D
+    a = ("\ts_load_dwordx2 s[0:1], s[4:5], 0xd0 ; args\n\t.p2align 4\n.LBB3_1: ; %loop\n"
+         "\tv_bitop3_b32 v1, v2, v3, v4 bitop3:0x96\n\ts_waitcnt vmcnt(6)\n\tglobal_load_dword v5, v6, s[2:3] offset:16\n"
+         "\ts_cbranch_scc1 .LBB3_1\n\ts_endpgm\n")
+    sa = D.stream(a)
+    assert len(sa) == 7 and sa[1] == ".L0:" and sa[5] == "s_cbranch_scc1 .L0"
+    assert D.compare(sa, D.stream(a)) == ("equal", 0)
+    renamed = a.replace(".LBB3_1", ".LBB17_4").replace("; %loop", "").replace("\t.p2align 4\n", "")
+    assert D.compare(sa, D.stream(renamed)) == ("equal", 0)
+    assert D.compare(sa, D.stream(a.replace("0xd0", "0xd8").replace("offset:16", "offset:32"))) == ("immediates", 2)
+    for changed in (a.replace("bitop3:0x96", "bitop3:0xe8"), a.replace("vmcnt(6)", "vmcnt(3)"),
+                    a.replace("v1, v2", "v1, v7"), a.replace("\ts_waitcnt vmcnt(6)\n", "")):
+        kind, diff = D.compare(sa, D.stream(changed))
+        assert kind == "differs" and 1 <= len(diff) <= 3
+    assert D.short_name("void golk::band_step_kernel<8, 2, false, golk::B3S23>(golk::B3S23::Args)") == \
+        D.short_name("void golk::band_step_kernel<8, 2, false>(golk::BitsArgs)") == "golk::band_step_kernel<8, 2, false>"
+    assert D.short_name("golk::hash_kernel(unsigned int const*, long)") == "golk::hash_kernel"
+    # two kernels of one short name pair up with their equals; the rest is listed, not compared
+    old = {"k<1>": [("k<1>(A)", sa, (10, 20, 0, 0))], "gone": [("gone()", sa, (1, 2, 0, 0))]}
+    new = {"k<1>": [("k<1, T>(T)", D.stream(changed), (12, 20, 0, 0)), ("k<1, B>(B)", D.stream(renamed), (10, 20, 0, 0))]}
+    lines = []
+    counts = D.report(old, new, 4, lines.append)
+    assert counts == {"equal": 1, "immediates": 0, "differs": 0, "unmatched": 2}
+    assert lines[0] == "only at REV: gone()  7 instructions  [vgpr 1 sgpr 2 scratch 0 lds 0]"
+    assert lines[1] == "equal: k<1, B>(B)  [vgpr 10 sgpr 20 scratch 0 lds 0]"
+    assert lines[2].startswith("only in the tree: k<1, T>(T)  6 instructions  [vgpr 12 ")
+
+
 def test_go_shims_use_only_declared_c_symbols():
     """The cgo drop-ins under go/ (not compiled here: no Go toolchain) call only functions, types
     and constants golhip.h declares, and fill only fields of its structs."""

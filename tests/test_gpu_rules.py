@@ -1,4 +1,4 @@
-"""Life-like rules on the GPU (gol_engine_set_rule, csrc/gol_rule.hip) against the numpy torus
+"""Life-like rules on the GPU (gol_engine_set_rule, csrc/gol_kernels.hip: TableRule) against the numpy torus
 stepper of tests/rule_ref.py (itself checked against the oracle in test_rules_cpu.py).  Boards come
 from a seeded numpy RNG at densities 0.1, 0.5 and 0.9 and are loaded through load_bytes as 0/255.
 """

@@ -25,19 +25,24 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "gol-distributed-final_amd", "csrc")
 
 
-def compile_asm(out):
-    """The kernel translation units with the Makefile's flags (KFLAGS; the pipeline units also
-    BANDFLAGS / BYTEFLAGS, their schedulers), concatenated into one assembly file."""
+UNITS = ("gol_kernels.hip", "gol_band_pipe.hip", "gol_bytes_pipe.hip")
+UNIT_FLAGS = {"gol_band_pipe.hip": "BANDFLAGS", "gol_bytes_pipe.hip": "BYTEFLAGS"}  # the Makefile's UNITFLAGS_*
+
+
+def compile_asm(out, csrc=CSRC, include=os.path.join(ROOT, "include"), units=UNITS):
+    """The kernel translation units `units` of the source directory `csrc` with its Makefile's
+    flags (KFLAGS; the pipeline units also BANDFLAGS / BYTEFLAGS, their schedulers), concatenated
+    into one assembly file."""
     parts = []
-    mk = open(os.path.join(CSRC, "Makefile")).read()
+    mk = open(os.path.join(csrc, "Makefile")).read()
     flags = {v: re.search(r"^%s = (.*)$" % v, mk, re.M).group(1).split() for v in ("BANDFLAGS", "BYTEFLAGS")}
-    for src, extra in (("gol_kernels.hip", []), ("gol_band_pipe.hip", flags["BANDFLAGS"]),
-                       ("gol_bytes_pipe.hip", flags["BYTEFLAGS"])):
+    for src in units:
         part = out + "." + src + ".s"
         subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17",
-                        "-mllvm", "-amdgpu-atomic-optimizer-strategy=None"] + extra +  # as the Makefile
-                       ["-I" + os.path.join(ROOT, "include"), "-I" + CSRC, "--cuda-device-only", "-S",
-                        os.path.join(CSRC, src), "-o", part], check=True, stderr=subprocess.DEVNULL)
+                        "-mllvm", "-amdgpu-atomic-optimizer-strategy=None"] +  # as the Makefile
+                       flags.get(UNIT_FLAGS.get(src), []) +
+                       ["-I" + include, "-I" + csrc, "--cuda-device-only", "-S",
+                        os.path.join(csrc, src), "-o", part], check=True, stderr=subprocess.DEVNULL)
         parts.append(open(part).read())
     with open(out, "w") as f:
         f.write("\n".join(parts))

@@ -9,7 +9,8 @@
 #   tools/variant.sh rev REV NAME               every source (and golhip.h) of a git revision
 #   tools/variant.sh patch NAME FILE [FLAGS]    current sources with FILE (a patch of csrc/, -p1) applied
 #   tools/variant.sh kernels REV NAME           current sources with gol_kernels.hip of REV (the
-#                                               kernels of REV behind today's engine and ABI)
+#                                               kernels of REV behind today's engine and ABI; REV
+#                                               must have the rule launchers in that file)
 #   tools/variant.sh res ["-DFLAG ..."]         VGPRs / LDS / scratch / occupancy of the pipe kernels
 set -e
 R=$(cd "$(dirname "$0")/.." && pwd)
