@@ -151,6 +151,8 @@ static void shard_release(gol_shard &s)
     if (s.view_frame) (void)hipFree(s.view_frame);
     if (s.view_pix) (void)hipFree(s.view_pix);
     if (s.view_host) (void)hipHostFree(s.view_host);
+    if (s.edit_dev) (void)hipFree(s.edit_dev);
+    if (s.edit_host) (void)hipHostFree(s.edit_host);
     for (auto ev : s.tev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : {s.ev_start, s.ev_edge, s.ev_halo})
         if (ev) (void)hipEventDestroy(ev);
@@ -1791,6 +1793,105 @@ extern "C" int gol_engine_view(gol_engine *e, int64_t x0, int64_t y0, int32_t sc
         }
     }
     if (src_layout) *src_layout = view_layout(e);
+    return GOL_OK;
+}
+
+// ------------------------------------------------------------------ board edits
+// (include/golhip.h, "board edits")  The write-side twin of the views: the rectangle goes into rows
+// [0, R) of the current buffer where they are and as they are -- no layout conversion, no change to
+// cur / band / mode / the turn; only the halo becomes stale.
+static int ensure_edit(gol_shard &s, int64_t words)
+{
+    if (s.edit_cap >= words && s.edit_dev && s.edit_host) return GOL_OK;  // (both: one allocation may have failed)
+    if (s.edit_dev) (void)hipFree(s.edit_dev);
+    if (s.edit_host) (void)hipHostFree(s.edit_host);
+    s.edit_dev = nullptr;
+    s.edit_host = nullptr;
+    s.edit_cap = 0;
+    const int64_t cap = std::max<int64_t>(words, 1 << 12);
+    HIPCHK(hipMalloc(&s.edit_dev, (1 + cap) * sizeof(uint64_t)));
+    HIPCHK(hipHostMalloc((void **)&s.edit_host, (1 + cap) * sizeof(uint64_t), hipHostMallocDefault));
+    s.edit_cap = cap;
+    return GOL_OK;
+}
+
+// One shard's part of a paste, queued on its compute stream: its runs of the rectangle's rows
+// (gol_view_plan), then the readback of the counter and of the error word.
+static int paste_enqueue(gol_engine *e, gol_shard &s, const gol_view_run *runs, int32_t nr, int form, int64_t x0, int64_t w,
+                         const uint64_t *pattern, int64_t stride, int32_t op)
+{
+    const int64_t pw = (w + 63) / 64;  // the staged pattern rows are dense
+    RCCHK(set_dev(s.device));
+    int64_t rows = 0;
+    for (int32_t r = 0; r < nr; ++r) rows += runs[r].rows;
+    RCCHK(ensure_edit(s, pattern ? rows * pw : 0));
+    // behind every launch of the last step, as the views (invalidate_halo has queued the waits
+    // for an exchange in flight; these cover a step whose exchange was not issued)
+    HIPCHK(hipStreamWaitEvent(s.stream, s.ev_edge, 0));
+    HIPCHK(hipStreamWaitEvent(s.stream, s.ev_halo, 0));
+    HIPCHK(hipMemsetAsync(s.edit_dev, 0, sizeof(uint64_t), s.stream));
+    if (pattern) {
+        uint64_t *dst = s.edit_host + 1;
+        for (int32_t r = 0; r < nr; ++r)
+            for (int64_t j = 0; j < runs[r].rows; ++j, dst += pw)
+                memcpy(dst, pattern + (runs[r].vrow + j) * stride, pw * sizeof(uint64_t));
+        HIPCHK(hipMemcpyAsync(s.edit_dev + 1, s.edit_host + 1, rows * pw * sizeof(uint64_t), hipMemcpyHostToDevice, s.stream));
+    }
+    void *board = form == 0 ? (void *)s.bytes[e->bcur] : (void *)s.bits[e->cur];
+    int64_t staged = 0;
+    for (int32_t r = 0; r < nr; ++r) {
+        HIPCHK(golk_paste(form, board, form == 0 ? e->bstride : e->pitch, e->W, x0, w, runs[r].row, runs[r].rows, staged,
+                          pattern ? s.edit_dev + 1 : nullptr, pw, op, s.edit_dev, s.stream));
+        staged += runs[r].rows;
+    }
+    HIPCHK(hipMemcpyAsync(s.edit_host, s.edit_dev, sizeof(uint64_t), hipMemcpyDeviceToHost, s.stream));
+    HIPCHK(hipMemcpyAsync(s.host_word, s.err, sizeof(uint32_t), hipMemcpyDeviceToHost, s.stream));
+    return GOL_OK;
+}
+
+extern "C" int gol_engine_paste(gol_engine *e, int64_t x0, int64_t y0, int64_t w, int64_t h, const uint64_t *pattern,
+                                int64_t stride, int32_t op, int64_t *changed, int32_t *dst_layout)
+{
+    if (!e) return gol_set_error(GOL_EINVAL, "engine is NULL");
+    if (w < 1 || w > e->W || h < 1 || h > e->H || x0 < 0 || x0 >= e->W || y0 < 0 || y0 >= e->H ||
+        w > (int64_t(1) << 26) / h || (pattern && stride < (w + 63) / 64) || op < GOL_PASTE_COPY || op > GOL_PASTE_ANDNOT)
+        return gol_set_error(GOL_EINVAL,
+                             "bad paste (%lld x %lld cells at (%lld, %lld), stride %lld, op %d) into a %lld x %lld board: the "
+                             "rectangle within one turn of the torus, at most 2^26 cells, stride >= ceil(w / 64), op 0..3",
+                             (long long)w, (long long)h, (long long)x0, (long long)y0, (long long)stride, op, (long long)e->W,
+                             (long long)e->H);
+    if (e->mode == GOL_MODE_EXACT)
+        return gol_set_error(GOL_ESTATE, "the board holds loaded bytes other than 0/255 until turn 1: step once before editing it");
+    RCCHK(invalidate_halo(e));
+    const int form = view_layout(e);
+    std::vector<char> used(e->sh.size(), 0);
+    int rc = GOL_OK;
+    for (size_t i = 0; i < e->sh.size() && rc == GOL_OK; ++i) {
+        gol_view_run runs[2];
+        int32_t nr = 0;
+        rc = gol_view_plan(e->H, e->nranks, e->rank + (int32_t)i, y0, h, runs, 2, &nr);
+        if (rc != GOL_OK || nr == 0) continue;
+        used[i] = 1;
+        rc = paste_enqueue(e, e->sh[i], runs, nr, form, x0, w, pattern, stride, op);
+    }
+    if (rc != GOL_OK) {  // the copies already queued read the shards' pinned buffers: they end before the call does
+        for (size_t i = 0; i < e->sh.size(); ++i)
+            if (used[i] && hipSetDevice(e->sh[i].device) == hipSuccess) (void)hipStreamSynchronize(e->sh[i].stream);
+        return rc;
+    }
+    uint32_t flags = 0;
+    int64_t n = 0;
+    for (size_t i = 0; i < e->sh.size(); ++i) {
+        if (!used[i]) continue;
+        gol_shard &s = e->sh[i];
+        RCCHK(set_dev(s.device));
+        HIPCHK(hipStreamSynchronize(s.stream));
+        flags |= s.host_word[0];
+        n += (int64_t)s.edit_host[0];
+    }
+    if (flags) return sync_all(e, false);  // a pending device fault: reported (and cleared) as by the queries
+    if (changed) *changed = n;
+    if (dst_layout) *dst_layout = form;
     return GOL_OK;
 }
 

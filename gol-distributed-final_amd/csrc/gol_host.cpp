@@ -234,6 +234,17 @@ struct Operations {
         return gol_engine_view(eng, x0, y0, scale, out_w, out_h, pixels, stride, src_layout);
     }
 
+    // An edit of the resident board (gol_engine_paste), between the chunks of a Run like View: it
+    // lands after turn cTurn, and the next chunk steps the edited board.
+    int Paste(int64_t x0, int64_t y0, int64_t w, int64_t h, const uint64_t *pattern, int64_t stride, int32_t op,
+              int64_t *changed, int64_t *turns_completed)
+    {
+        Access acc(*this);
+        if (!have_world) return gol_set_error(GOL_ESTATE, "no board: Operations.Run has not been called");
+        if (turns_completed) *turns_completed = cTurn;
+        return gol_engine_paste(eng, x0, y0, w, h, pattern, stride, op, changed, nullptr);
+    }
+
     int Pause()  // broker.go:251-254
     {
         Access acc(*this);
@@ -353,6 +364,13 @@ extern "C" int gol_broker_view(gol_broker *b, int64_t x0, int64_t y0, int32_t sc
 {
     if (!b) return gol_set_error(GOL_EINVAL, "NULL argument");
     return b->ops.View(x0, y0, scale, out_w, out_h, pixels, stride, turns_completed, src_layout);
+}
+
+extern "C" int gol_broker_paste(gol_broker *b, int64_t x0, int64_t y0, int64_t w, int64_t h, const uint64_t *pattern,
+                                int64_t stride, int32_t op, int64_t *changed, int64_t *turns_completed)
+{
+    if (!b) return gol_set_error(GOL_EINVAL, "NULL argument");
+    return b->ops.Paste(x0, y0, w, h, pattern, stride, op, changed, turns_completed);
 }
 
 extern "C" int gol_worker_update(const gol_request *req, gol_response *res)

@@ -71,6 +71,10 @@ struct gol_shard {
     uint8_t *view_pix = nullptr;      // device pixels (one shard: the whole frame)
     uint32_t *view_host = nullptr;    // pinned host copy of either
     int64_t view_cap = 0;
+    // board edits (gol_engine_paste): word 0 the changed-cells counter, then edit_cap pattern words; grown on demand
+    uint64_t *edit_dev = nullptr;     // device
+    uint64_t *edit_host = nullptr;    // pinned host: the staged pattern rows, the counter's readback
+    int64_t edit_cap = 0;
     ncclComm_t nccl = nullptr;
     // timing (gol_engine_set_timing): events on `stream` around the timed launches
     std::vector<hipEvent_t> tev;

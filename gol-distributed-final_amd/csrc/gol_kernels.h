@@ -105,6 +105,16 @@ hipError_t golk_view_counts(int form, const void *src, int64_t pitch, int64_t W,
 // elements, 16-byte aligned.
 hipError_t golk_view_pixels(const uint32_t *frame, int64_t n, int32_t scale, uint8_t *pixels, hipStream_t s);
 
+// Board edits (gol_edit.hip).  golk_paste applies pattern rows [prow, prow + rows) (pstride uint64
+// words per row, bit c % 64 of word c / 64 = cell c; pattern NULL: all ones) to rows [row, row + rows)
+// of `dst` (row 0 of a shard's rows) at board columns (x0 + c) mod W, 0 <= c < w <= W, under op
+// (GOL_PASTE_*), in place; form as the views' (GOLK_VIEW_BYTES / _STANDARD / _BAND; pitch in bytes
+// or words).  Adds the number of cells whose state changed to *changed (a device counter).  Writes
+// only units the rectangle covers; one lane per unit and row (gol_edit.h).
+hipError_t golk_paste(int form, void *dst, int64_t pitch, int64_t W, int64_t x0, int64_t w, int64_t row, int64_t rows,
+                      int64_t prow, const uint64_t *pattern, int64_t pstride, int32_t op, uint64_t *changed,
+                      hipStream_t s);
+
 // IPC transport (gol_comm.h): set *flag = value with release ordering at system scope after the
 // stream's earlier work; wait (one wave on the stream) until every flags[i] (i < n <= 4, other
 // processes' flag words mapped through IPC) has reached `want` (wrap-safe sequence compare),

@@ -41,6 +41,8 @@ GOL_HALO_SEND, GOL_HALO_RECV = 0, 1
 GOL_LAUNCH_MAIN, GOL_LAUNCH_EDGE = 0, 1
 VIEW_LAYOUTS = {0: "bytes", 1: "standard", 2: "band"}  # *src_layout of the view calls
 GOL_RULE_GENERIC = 1  # gol_engine_set_rule flag: B3/S23 on the rule kernels too
+GOL_PASTE_COPY, GOL_PASTE_OR, GOL_PASTE_XOR, GOL_PASTE_ANDNOT = 0, 1, 2, 3
+PASTE_OPS = {"copy": GOL_PASTE_COPY, "or": GOL_PASTE_OR, "xor": GOL_PASTE_XOR, "andnot": GOL_PASTE_ANDNOT}
 
 _NAMES = {
     GOL_EINVAL: "EINVAL", GOL_EHIP: "EHIP", GOL_ENOMEM: "ENOMEM", GOL_EIO: "EIO",
@@ -143,6 +145,10 @@ SIGNATURES = [
                                           _P(ctypes.c_uint32)]),
     ("gol_engine_set_rule", ctypes.c_int, [_vp, ctypes.c_uint32, ctypes.c_uint32, _i32]),
     ("gol_engine_rule", ctypes.c_int, [_vp, _P(ctypes.c_uint32), _P(ctypes.c_uint32), _P(_i32)]),
+    ("gol_engine_paste", ctypes.c_int, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _i32, _P(_i64), _P(_i32)]),
+    ("gol_paste_host", ctypes.c_int, [_i32, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _i64, _i32, _P(_i64)]),
+    ("gol_rle_parse", ctypes.c_int, [ctypes.c_char_p, _i64, _P(_i64), _P(_i64), _vp, _i64, _i64, ctypes.c_char_p, _i64]),
+    ("gol_rle_format", ctypes.c_int, [_vp, _i64, _i64, _i64, ctypes.c_char_p, ctypes.c_char_p, _i64, _P(_i64)]),
     ("gol_halo_plan", ctypes.c_int, [_i64, _i32, _i32, _i32, _P(gol_halo_op), _i32, _P(_i32)]),
     ("gol_step_plan", ctypes.c_int, [_i64, _i32, _i32, _i32, _P(gol_launch), _i32, _P(_i32)]),
     ("gol_view_plan", ctypes.c_int, [_i64, _i32, _i32, _i64, _i64, _P(gol_view_run), _i32, _P(_i32)]),
@@ -173,6 +179,7 @@ SIGNATURES = [
     ("gol_broker_superquit", ctypes.c_int, [_vp]),
     ("gol_broker_paused", ctypes.c_int, [_vp, _P(_i32)]),
     ("gol_broker_view", ctypes.c_int, [_vp, _i64, _i64, _i32, _i32, _i32, _vp, _i64, _P(_i64), _P(_i32)]),
+    ("gol_broker_paste", ctypes.c_int, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _i32, _P(_i64), _P(_i64)]),
     ("gol_worker_update", ctypes.c_int, [_P(gol_request), _P(gol_response)]),
 ]
 
@@ -271,6 +278,58 @@ def format_rule(birth: int, survive: int, library=None) -> str:
         raise GolError(GOL_EINVAL, f"rule masks out of range ({birth}, {survive})")
     buf = ctypes.create_string_buffer(24)
     _lib_check(L, L.gol_rule_format(birth, survive, buf, len(buf)))
+    return buf.value.decode()
+
+
+def pack_pattern(cells) -> "np.ndarray":
+    """A 2-D array of cells (non-zero = alive) as the uint64 rows of the paste calls: bit c % 64 of
+    word c // 64 of a row = cell c (the bit order of load_words)."""
+    import numpy as np
+    a = np.asarray(cells)
+    if a.ndim != 2 or a.shape[0] < 1 or a.shape[1] < 1:
+        raise GolError(GOL_EINVAL, f"a pattern is a 2-D array of at least one cell, got shape {a.shape}")
+    h, w = a.shape
+    bits = np.zeros((h, (w + 63) // 64 * 64), dtype=np.uint8)
+    bits[:, :w] = a != 0
+    return np.ascontiguousarray(np.packbits(bits, axis=1, bitorder="little")).view("<u8")
+
+
+def unpack_pattern(words, w: int) -> "np.ndarray":
+    """The inverse of pack_pattern: (h, w) bool cells of uint64 pattern rows."""
+    import numpy as np
+    rows = np.ascontiguousarray(words, dtype="<u8")
+    return np.unpackbits(rows.view(np.uint8), axis=1, bitorder="little")[:, :w].astype(bool)
+
+
+def parse_rle(text, library=None):
+    """gol_rle_parse: RLE text ("x = 3, y = 3, rule = B3/S23\\nbob$2bo$3o!") -> ((h, w) bool array,
+    rule text, "" if the header names none).  Two-state patterns only; malformed text is
+    GolError EFORMAT with the offset.  Host code: no GPU needed."""
+    import numpy as np
+    L = library or lib()
+    raw = text if isinstance(text, (bytes, bytearray)) else str(text).encode()
+    w, h = ctypes.c_int64(), ctypes.c_int64()
+    rule = ctypes.create_string_buffer(max(len(raw), 1) + 1)
+    _lib_check(L, L.gol_rle_parse(raw, len(raw), ctypes.byref(w), ctypes.byref(h), None, 0, 0, rule, len(rule)))
+    words = np.zeros((h.value, (w.value + 63) // 64), dtype=np.uint64)
+    _lib_check(L, L.gol_rle_parse(raw, len(raw), ctypes.byref(w), ctypes.byref(h), words.ctypes.data, words.shape[1],
+                                  words.shape[0], None, 0))
+    return unpack_pattern(words, w.value), rule.value.decode(errors="replace")
+
+
+def format_rle(cells, rule=None, library=None) -> str:
+    """gol_rle_format: a 2-D array of cells (non-zero = alive) as RLE text, with `rule` in the
+    header when given; lines of at most 70 characters, ending in "!\\n"."""
+    import numpy as np
+    L = library or lib()
+    cells = np.asarray(cells)
+    words = pack_pattern(cells)
+    h, w = cells.shape
+    r = None if rule is None else str(rule).encode()
+    need = ctypes.c_int64()
+    _lib_check(L, L.gol_rle_format(words.ctypes.data, words.shape[1], w, h, r, None, 0, ctypes.byref(need)))
+    buf = ctypes.create_string_buffer(need.value)
+    _lib_check(L, L.gol_rle_format(words.ctypes.data, words.shape[1], w, h, r, buf, need.value, None))
     return buf.value.decode()
 
 

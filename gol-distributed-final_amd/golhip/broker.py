@@ -11,8 +11,8 @@ import ctypes
 
 import numpy as np
 
-from ._lib import (GOL_EINVAL, LAYOUTS, TRANSPORTS, VIEW_LAYOUTS, GolError, check, gol_config, gol_request,
-                   gol_response, lib)
+from ._lib import (GOL_EINVAL, LAYOUTS, PASTE_OPS, TRANSPORTS, VIEW_LAYOUTS, GolError, check, gol_config, gol_request,
+                   gol_response, lib, pack_pattern, parse_rle)
 from .stubs import CellList, Request, Response
 
 
@@ -102,6 +102,24 @@ class Operations:
         check(lib().gol_broker_view(self._h, x0, y0, scale, out_w, out_h, out.ctypes.data, out_w, ctypes.byref(turns),
                                     ctypes.byref(lay)))
         return (out, turns.value, VIEW_LAYOUTS[lay.value]) if return_layout else (out, turns.value)
+
+    def paste(self, pattern, x0: int, y0: int, op: str = "copy"):
+        """Engine.paste on the broker's board (gol_broker_paste; no reference counterpart), served
+        between the chunks of a running Run: `pattern` is a 2-D array, RLE text, or a (w, h) pair
+        for a rectangle of alive cells (Engine.fill).  Returns (cells changed, the turn the edit
+        landed after)."""
+        if op not in PASTE_OPS:
+            raise GolError(GOL_EINVAL, f"paste op {op!r}: one of {sorted(PASTE_OPS)}")
+        if isinstance(pattern, tuple):
+            (w, h), words, stride = pattern, None, 0
+        else:
+            cells = parse_rle(pattern)[0] if isinstance(pattern, (str, bytes)) else pattern
+            words = pack_pattern(cells)
+            (h, w), stride = np.shape(cells), words.shape[1]
+        n, turns = ctypes.c_int64(), ctypes.c_int64()
+        check(lib().gol_broker_paste(self._h, x0, y0, w, h, None if words is None else words.ctypes.data, stride,
+                                     PASTE_OPS[op], ctypes.byref(n), ctypes.byref(turns)))
+        return n.value, turns.value
 
     def Pause(self, req: Request | None = None) -> Response:  # broker.go:251-254
         check(lib().gol_broker_pause(self._h))

@@ -16,8 +16,8 @@ import ctypes
 import numpy as np
 
 from ._lib import (GOL_EINVAL, GOL_IPC_ID_BYTES, GOL_RCCL_ID_BYTES, GOL_RULE_GENERIC, GOL_SHARDS_SAME_DEVICE,
-                   GOL_TIMING_EXCHANGE, GOL_WRITE_FN, LAYOUTS, STEP_MODES, TRANSPORT_NAMES, TRANSPORTS, VIEW_LAYOUTS,
-                   GolError, check, format_rule, gol_config, lib, parse_rule)
+                   GOL_TIMING_EXCHANGE, GOL_WRITE_FN, LAYOUTS, PASTE_OPS, STEP_MODES, TRANSPORT_NAMES, TRANSPORTS,
+                   VIEW_LAYOUTS, GolError, check, format_rule, gol_config, lib, pack_pattern, parse_rle, parse_rule)
 
 
 def rccl_unique_id(library=None) -> bytes:
@@ -255,6 +255,39 @@ class Engine:
         """(out_h, out_w) uint8 greyscale frame: ceil(255 n / scale^2) per box (gol_engine_view); at
         scale 1 the board's 0/255 bytes.  Needs every row in this process."""
         return self._view(self._L.gol_engine_view, np.uint8, x0, y0, scale, out_w, out_h, return_layout)
+
+    # -- edits of the running board
+    def _paste(self, x0, y0, w, h, words, stride, op, return_layout):
+        if op not in PASTE_OPS:
+            raise GolError(GOL_EINVAL, f"paste op {op!r}: one of {sorted(PASTE_OPS)}")
+        n, lay = ctypes.c_int64(), ctypes.c_int32()
+        self._check(self._L.gol_engine_paste(self._h, x0, y0, w, h, None if words is None else words.ctypes.data, stride,
+                                             PASTE_OPS[op], ctypes.byref(n), ctypes.byref(lay)))
+        return (n.value, VIEW_LAYOUTS[lay.value]) if return_layout else n.value
+
+    def paste(self, pattern, x0: int, y0: int, op: str = "copy", *, return_layout: bool = False):
+        """Write a pattern into the running board in place (gol_engine_paste): a 2-D array (non-zero
+        = alive) or RLE text; pattern cell (c, r) lands on ((x0 + c) mod W, (y0 + r) mod H) under op
+        "copy" (the whole rectangle is overwritten), "or", "xor" or "andnot".  The board keeps its
+        layout and its turn counter; returns the number of cells (of this process's rows) whose
+        state changed, with return_layout=True also the layout written: "bytes", "standard" or "band"."""
+        cells = parse_rle(pattern, self._L)[0] if isinstance(pattern, (str, bytes)) else pattern
+        words = pack_pattern(cells)
+        h, w = np.shape(cells)
+        return self._paste(x0, y0, w, h, words, words.shape[1], op, return_layout)
+
+    def paste_words(self, words: np.ndarray, w: int, x0: int, y0: int, op: str = "copy", *, return_layout: bool = False):
+        """paste of a pattern that is already bit-packed: (h, >= ceil(w / 64)) uint64 rows, bit c % 64
+        of word c // 64 = cell c (as load_words packs them; bits at c >= w are ignored)."""
+        words = np.ascontiguousarray(words, dtype=np.uint64)
+        if words.ndim != 2 or words.shape[0] < 1 or words.shape[1] < (w + 63) // 64:
+            raise ValueError(f"expected (rows, >= {(w + 63) // 64}) uint64 words for {w} cells per row")
+        return self._paste(x0, y0, w, words.shape[0], words, words.shape[1], op, return_layout)
+
+    def fill(self, x0: int, y0: int, w: int, h: int, op: str = "copy", *, return_layout: bool = False):
+        """paste with every pattern cell alive: "copy" / "or" set the w x h rectangle at (x0, y0),
+        "andnot" clears it, "xor" inverts it.  Returns the number of cells that changed."""
+        return self._paste(x0, y0, w, h, None, 0, op, return_layout)
 
     def hash(self) -> int:
         h = ctypes.c_uint64()

@@ -109,7 +109,8 @@ typedef struct gol_engine gol_engine;
  * bands), which makes a generation shift-free.  AUTO picks
  * BAND when W % 1024 == 0.  The layout is internal: every reader (store,
  * alive list, PGM, hash, device_bits) sees the standard layout, and converts
- * the board to it; only the viewport frames read it as it is.  BYTES keeps
+ * the board to it; only the viewport frames read it, and gol_engine_paste
+ * writes it, as it is.  BYTES keeps
  * the board as the reference's one byte per cell (a W % 64 != 0 board always
  * does): one shard, 32 turns per launch on a 0/255 board with W % 32 == 0 (the
  * byte pipeline), the exact byte kernel otherwise; the
@@ -350,6 +351,80 @@ int gol_rule_eval_host(uint32_t birth, uint32_t survive, const uint32_t nb[8], u
 int gol_engine_set_rule(gol_engine *e, uint32_t birth, uint32_t survive, int32_t flags);
 int gol_engine_rule(gol_engine *e, uint32_t *birth, uint32_t *survive, int32_t *generic);
 
+/* ---------------------------------------------------------------- board edits
+ * (Added after ABI 6 without a version bump, like the viewport and rule calls:
+ * GOL_ABI_VERSION stays 6; probe for gol_engine_paste, gol_paste_host,
+ * gol_rle_parse, gol_rle_format and gol_broker_paste by symbol.)
+ *
+ * gol_engine_paste: a w x h rectangle of cells written into the running board
+ * where it is and as it is (the write-side twin of the viewport frames; the
+ * load calls replace whole rows or the whole board and restart the turn count).
+ * Pattern cell (c, r), 0 <= c < w, 0 <= r < h, is bit c % 64 of
+ * pattern[r*stride + c/64] (the bit order of load_words; bits at c >= w of a
+ * row's last word are ignored) and lands on board cell ((x0 + c) mod W,
+ * (y0 + r) mod H) under `op`.  pattern == NULL: every p = 1 and stride is
+ * ignored (COPY sets the rectangle, ANDNOT clears it, XOR inverts it).
+ * Valid: 1 <= w <= W, 1 <= h <= H, 0 <= x0 < W, 0 <= y0 < H, w*h <= 2^26,
+ * stride >= ceil(w/64), op 0..3; anything else is GOL_EINVAL before any GPU work.
+ * The board is written on the GPU in the layout it is currently stepped in
+ * (*dst_layout, may be NULL: 0 byte rows, 1 standard bit rows, 2 band bit rows,
+ * as the views' src_layout): no conversion, and the buffer, the layout and the
+ * turn counter stay as they are.  Only the words (bytes) and rows the rectangle
+ * covers are touched.  *changed (may be NULL) = the cells of this process's
+ * rows whose state changed.  Blocking; ordered after the last step and before
+ * the next one, whose halo exchange is made again.
+ *  - byte boards: a cell is alive if its byte is non-zero; written cells become
+ *    0 or 255, and under OR, XOR and ANDNOT only cells whose pattern bit is set
+ *    are written (other bytes, whatever their value, stay);
+ *  - a bit-capable board loaded with bytes other than 0/255, its exact first
+ *    turn pending: GOL_ESTATE, nothing changes;
+ *  - several local shards each apply their own rows (gol_view_plan) on their own
+ *    GPU; with ranks in several processes the call is not collective (like
+ *    view_counts): each process applies the rows it holds, a rank that holds
+ *    none may skip the call, and the next collective stepping call makes every
+ *    rank exchange its halo again. */
+#define GOL_PASTE_COPY   0  /* cell  = p  (the whole rectangle is overwritten) */
+#define GOL_PASTE_OR     1  /* cell |= p */
+#define GOL_PASTE_XOR    2  /* cell ^= p */
+#define GOL_PASTE_ANDNOT 3  /* cell &= ~p */
+int gol_engine_paste(gol_engine *e, int64_t x0, int64_t y0, int64_t w, int64_t h,
+                     const uint64_t *pattern, int64_t stride, int32_t op,
+                     int64_t *changed, int32_t *dst_layout);
+/* The per-word function of the paste kernels (csrc/gol_edit.h) applied to a
+ * host buffer (a host function, no GPU needed): pattern rows [prow, prow + rows)
+ * go to rows [row, row + rows) of `board`, a buffer of W-cell rows in `layout`
+ * (0 bytes, 1 standard, 2 band: W % 32 == 0 / W % 1024 == 0 for the bit
+ * layouts), row pitch `pitch` in uint32 words (bytes for layout 0); x0, w,
+ * pattern, stride, op and *changed (may be NULL) as above. */
+int gol_paste_host(int32_t layout, void *board, int64_t pitch, int64_t W,
+                   int64_t row, int64_t rows, int64_t prow, int64_t x0, int64_t w,
+                   const uint64_t *pattern, int64_t stride, int32_t op, int64_t *changed);
+/* RLE, the text form Life patterns are exchanged in ("x = 3, y = 3, rule =
+ * B3/S23\nbob$2bo$3o!"); host functions.
+ * gol_rle_parse reads text[0, len): lines that start with '#' are skipped; the
+ * header is "x = m, y = n[, rule = text]" (free blanks, either case); the body
+ * is [count]b (dead), [count]o (alive), [count]$ (end of row) and '!', with
+ * blanks and newlines between tokens; text after '!' is ignored.  *w = m, *h =
+ * n; with pattern != NULL the cells go to pattern[r*stride + c/64] bit c % 64
+ * (rows shorter than x are dead to the right); pattern == NULL returns the
+ * size only (the two-call form).  `rule` (may be NULL) receives the header's
+ * rule text verbatim, "" if there is none; it is not interpreted.
+ * GOL_EFORMAT, with a message naming the offset: no header, x or y < 1, x*y >
+ * 2^26, any other body character (multi-state RLE is refused), a count of 0
+ * or one that overflows, a run past x, rows past y (a '$' may close row y - 1),
+ * a missing '!'.  GOL_EINVAL: stride < ceil(m/64), cap_rows < n, a rule buffer
+ * too small.
+ * gol_rle_format writes the header (with the rule when rule != NULL), rows
+ * without their trailing dead cells, empty rows merged into n$, lines of at
+ * most 70 characters, and "!\n".  *need (may be NULL) = bytes with the NUL;
+ * buf == NULL returns it alone, a buffer too small is GOL_EINVAL with *need
+ * set. */
+int gol_rle_parse(const char *text, int64_t len, int64_t *w, int64_t *h,
+                  uint64_t *pattern, int64_t stride, int64_t cap_rows,
+                  char *rule, int64_t rule_len);
+int gol_rle_format(const uint64_t *pattern, int64_t stride, int64_t w, int64_t h,
+                   const char *rule, char *buf, int64_t len, int64_t *need);
+
 /* ---------------------------------------------------------------- plans
  * The schedule of a sharded step as data (host functions, no GPU needed).  The
  * engine runs exactly these plans; golhip.sharded (the torch.distributed
@@ -543,6 +618,12 @@ int gol_broker_paused(gol_broker *b, int32_t *paused);
  * all-zero cWorld of broker.go:67-70. */
 int gol_broker_view(gol_broker *b, int64_t x0, int64_t y0, int32_t scale, int32_t out_w, int32_t out_h,
                     uint8_t *pixels, int64_t stride, int64_t *turns_completed, int32_t *src_layout);
+/* gol_engine_paste on the broker's board, served between the chunks of a running
+ * Run like gol_broker_view; *turns_completed (may be NULL) = cTurn, the turn the
+ * edit landed after.  GOL_ESTATE with no board.  No reference counterpart. */
+int gol_broker_paste(gol_broker *b, int64_t x0, int64_t y0, int64_t w, int64_t h,
+                     const uint64_t *pattern, int64_t stride, int32_t op,
+                     int64_t *changed, int64_t *turns_completed);
 int gol_worker_update(const gol_request *req, gol_response *res);                 /* GameOfLifeOperations.Update, worker.go:77-80 */
 
 #ifdef __cplusplus
