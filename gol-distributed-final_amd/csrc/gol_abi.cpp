@@ -128,6 +128,39 @@ extern "C" int gol_dev_band_step(const uint32_t *top, const uint32_t *mid, const
                           (hipStream_t)stream));
 }
 
+static int pipe_on_check(bool band, bool contig, bool count, bool pipelined, int32_t cus, int32_t slots)
+{
+    if (!cus && !slots) return GOL_OK;
+    int dcus = 0;
+    int64_t dslots = 0;
+    if (!pipelined || cus <= 0 || slots <= 0 || cus % 8)
+        return gol_set_error(GOL_EINVAL, "a pretended device (%d CUs, %d resident workgroups) needs the pipelined k, cus %% 8 == 0 and both > 0", cus, slots);
+    if (!golk_pipe_limits(band, contig, count, &dcus, &dslots)) return gol_set_error(GOL_EHIP, "no device properties");
+    if (cus > dcus || slots > dslots)
+        return gol_set_error(GOL_EINVAL, "a pretended device of %d CUs and %d resident workgroups exceeds this one (%d, %lld)", cus,
+                             slots, dcus, (long long)dslots);
+    return GOL_OK;
+}
+
+extern "C" int gol_dev_band_step_on(const uint32_t *top, const uint32_t *mid, const uint32_t *bot, uint32_t *dst,
+                                    int64_t R, int64_t Wd, int64_t pitch, int64_t row0, int64_t rows, int32_t k,
+                                    int32_t cells_per_lane, int32_t strip_rows, uint64_t *count_slots, void *stream,
+                                    int32_t cus, int32_t slots)
+{
+    const int dw = cells_per_lane == 64 ? 2 : (cells_per_lane == 128 ? 4 : (cells_per_lane <= 0 ? GOL_BAND_DEFAULT_DW : 0));
+    if (!top || !mid || !bot || !dst || R <= 0 || Wd <= 0 || !dw || Wd % dw || pitch < Wd || pitch % dw ||
+        row0 < 0 || rows < 0 || row0 + rows > R ||
+        !(k == 1 || k == 2 || k == 4 || k == 8 || (k == 16 && dw == 2) || (k == 12 && dw == 4)) ||
+        k > R || (((uintptr_t)mid | (uintptr_t)top | (uintptr_t)bot | (uintptr_t)dst) & (4 * dw - 1)))
+        return gol_set_error(GOL_EINVAL, "bad band_step arguments (R=%lld Wd=%lld pitch=%lld k=%d cells_per_lane=%d)",
+                             (long long)R, (long long)Wd, (long long)pitch, k, cells_per_lane);
+    const bool contig = top + (int64_t)k * pitch == mid && bot == mid + R * pitch;
+    const int rc = pipe_on_check(true, contig, count_slots != nullptr, k == 12 && dw == 4, cus, slots);
+    if (rc) return rc;
+    LAUNCH(golk_band_step(top, mid, bot, dst, R, Wd, pitch, row0, rows, k, dw, strip_rows, count_slots, nullptr,
+                          (hipStream_t)stream, cus, slots));
+}
+
 extern "C" int gol_dev_rule_step(const uint32_t *top, const uint32_t *mid, const uint32_t *bot, uint32_t *dst,
                                  int64_t R, int64_t Wd, int64_t pitch, int64_t row0, int64_t rows, int32_t k,
                                  int32_t layout, uint32_t birth, uint32_t survive, int32_t cells_per_lane,
@@ -211,6 +244,35 @@ extern "C" int gol_dev_bytes_step_k(const uint8_t *top, const uint8_t *mid, cons
                              (long long)R, (long long)W, (long long)stride, k);
     LAUNCH(golk_bytes_blocked(top, mid, bot, dst, R, W, stride, row0, rows, k, strip_rows, count_slots, nullptr,
                               (hipStream_t)stream));
+}
+
+extern "C" int gol_dev_bytes_step_k_on(const uint8_t *top, const uint8_t *mid, const uint8_t *bot, uint8_t *dst,
+                                       int64_t R, int64_t W, int64_t stride, int64_t row0, int64_t rows, int32_t k,
+                                       int32_t strip_rows, uint64_t *count_slots, void *stream, int32_t cus,
+                                       int32_t slots)
+{
+    if (!top || !mid || !bot || !dst || R <= 0 || W <= 0 || W % 32 || stride < W || stride % 16 || row0 < 0 ||
+        rows < 0 || row0 + rows > R || !(k == 1 || k == 2 || k == 4 || k == 8 || k == 16 || k == 32) || k > R ||
+        (((uintptr_t)mid | (uintptr_t)top | (uintptr_t)bot | (uintptr_t)dst) & 15))
+        return gol_set_error(GOL_EINVAL, "bad bytes_step_k arguments (R=%lld W=%lld stride=%lld k=%d)",
+                             (long long)R, (long long)W, (long long)stride, k);
+    const int rc = pipe_on_check(false, false, count_slots != nullptr, k == 32, cus, slots);
+    if (rc) return rc;
+    LAUNCH(golk_bytes_blocked(top, mid, bot, dst, R, W, stride, row0, rows, k, strip_rows, count_slots, nullptr,
+                              (hipStream_t)stream, cus, slots));
+}
+
+extern "C" int gol_dev_pipe_limits(int32_t kernel, int32_t contiguous, int32_t counted, int32_t *cus, int32_t *slots)
+{
+    if (!cus || !slots || (kernel != GOL_STRIP_KERNEL_BAND && kernel != GOL_STRIP_KERNEL_BYTES))
+        return gol_set_error(GOL_EINVAL, "bad pipe_limits arguments (kernel %d)", kernel);
+    int c = 0;
+    int64_t n = 0;
+    if (!golk_pipe_limits(kernel == GOL_STRIP_KERNEL_BAND, contiguous != 0, counted != 0, &c, &n))
+        return gol_set_error(GOL_EHIP, "no device properties");
+    *cus = c;
+    *slots = (int32_t)n;
+    return GOL_OK;
 }
 
 extern "C" int gol_dev_bytes_step(const uint8_t *world, int64_t H, int64_t W, int64_t stride, int64_t y0,

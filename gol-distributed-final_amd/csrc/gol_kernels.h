@@ -36,12 +36,18 @@ hipError_t golk_bits_step(const uint32_t *top, const uint32_t *mid, const uint32
 // Band layout (bit b of word w = cell b*Wd + w): dw words per lane (2 or 4), k in {1, 2, 4, 8},
 // 16 for dw = 2, 12 for dw = 4 (the split pipeline); Wd % dw == 0, pitch % dw == 0, 4*dw-byte
 // aligned rows.  err: error word of the launch (NULL = the device's default word).
+// as_cus, as_slots (the pipelined k = 12 at dw = 4 only): schedule the launch as for a device of
+// as_cus CUs holding as_slots resident workgroups of the kernel (gol_strips.h band_strip_plan); 0,
+// 0: this device.  hipErrorInvalidValue unless as_cus % 8 == 0 and neither exceeds this device's.
 #ifndef GOL_BAND_DEFAULT_DW
 #define GOL_BAND_DEFAULT_DW 4
 #endif
 hipError_t golk_band_step(const uint32_t *top, const uint32_t *mid, const uint32_t *bot, uint32_t *dst, int64_t R,
                           int64_t Wd, int64_t pitch, int64_t row0, int64_t rows, int k, int dw, int strip,
-                          uint64_t *slots, uint32_t *err, hipStream_t s);
+                          uint64_t *slots, uint32_t *err, hipStream_t s, int as_cus = 0, int64_t as_slots = 0);
+// This device's CU count and resident workgroups of a pipeline kernel (band: band_pipe_kernel with
+// contiguous ghost rows or not; else bytes_pipe_kernel), with the fused count or not.
+bool golk_pipe_limits(bool band, bool contig, bool count, int *cus, int64_t *slots);
 int golk_band_useful_words(int k, int dw);
 // Rounds of resident workgroups a step launch over `rows` rows makes (the band pipeline: 1 for
 // its one-round rank-weighted launch; other kernels: 1e9, i.e. many); for the engine's choice of
@@ -65,7 +71,7 @@ hipError_t golk_bytes_step(const uint8_t *world, int64_t H, int64_t W, int64_t s
                            uint8_t *out, int64_t out_stride, hipStream_t s);
 hipError_t golk_bytes_blocked(const uint8_t *top, const uint8_t *mid, const uint8_t *bot, uint8_t *dst, int64_t R,
                               int64_t W, int64_t pitch, int64_t row0, int64_t rows, int k, int strip, uint64_t *slots,
-                              uint32_t *err, hipStream_t s);
+                              uint32_t *err, hipStream_t s, int as_cus = 0, int64_t as_slots = 0);  // (k = 32: as golk_band_step's)
 hipError_t golk_nonbinary(const uint8_t *bytes, int64_t rows, int64_t W, int64_t stride, uint32_t *flag, hipStream_t s);
 hipError_t golk_random_fill(uint32_t *dst, int64_t rows, int64_t grow0, int64_t W, int64_t pitch, uint64_t seed,
                             hipStream_t s);

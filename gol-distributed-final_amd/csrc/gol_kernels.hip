@@ -29,6 +29,7 @@
 
 #include "gol_kernels.h"
 #include "gol_rule.h"
+#include "gol_strips.h"
 
 // Polls of a pipeline flag before a wave gives up (sets GOLK_ERR_SPIN in the launch's error
 // word and leaves; the host turns that into GOL_EHIP).  A test build sets 0 to force the path.
@@ -244,30 +245,7 @@ __device__ __forceinline__ void sstage_waves3(Pipe<K, 1> &p, uint32_t (&c)[3], s
     (sstage_wave3<K, NSTG, W>(p, c), ...);
 }
 
-// Work items of the pipelined kernels (one workgroup = one column group x one strip of rows).
-// ranked = 0: equal strips of `strip` rows, workgroup l -> XCD-remapped item.  ranked = 1 (a
-// launch of exactly one round, cus x per_cu workgroups): the dispatcher deals workgroup l to CU
-// l % cus as the (l / cus)-th arrival there, and a SIMD issues to its oldest ready wave first,
-// so the CU's workgroups run at different speeds (one round of equal strips ended them at 247 /
-// 298 / 388 / 482 us, tools/timeline.py); each CU then takes one column group x `period` rows
-// and splits the rows by arrival rank: rank r gets len[r] rows at off[r].
-// Paired ranks (dir != 0): two workgroups of a CU share one row range [off, off + len) and
-// walk it from both ends (dir +1 down from its top, dir -1 up from its bottom), claiming input
-// blocks from a counter of the pair (claims: 16 words per (CU, pair slot): [0] blocks claimed,
-// [1] pipelines done; the second to finish zeroes both for the next launch).  3 * (claimed
-// blocks of both) = len + 4K exactly, so their outputs meet without overlap wherever the
-// faster one got to: no rank waits for a slower one at the end of the launch.
-// Tail (ranked = 0, launches of many rounds): workgroups l >= tail_l, the last dispatched,
-// take strips of tail_strip rows from row tail_row on, so the launch ends on short strips
-// instead of a partial round of full ones.
-struct StripMap {
-    int32_t ranked, cus, per_cu, period;
-    int32_t len[4], off[4];
-    int32_t dir[4], pslot[4];
-    uint32_t *claims;
-    int32_t chunk;  // blocks per claim
-    int32_t tail_l, tail_row, tail_strip;
-};
+// StripMap, work_item, work_dir, pair_extent: gol_strips.h (shared with the host)
 
 struct BitsArgs {
     const uint32_t *top, *mid, *bot;
@@ -279,52 +257,6 @@ struct BitsArgs {
     uint32_t *cu_slots;  // band pipeline: per-CU masks of the workgroup slots in use (GOL_CU_SLOT_WORDS)
     StripMap sm;
 };
-
-// Column group, strip [s0, s1) and a per-CU rotation index of workgroup l (1-D grid); false:
-// the workgroup has no rows.
-__device__ __forceinline__ bool work_item(const StripMap &sm, int ngroups, int64_t row0, int64_t rows, int strip, int l,
-                                          int &group, int &s0, int &s1, int &rot)
-{
-    const int end = (int)(row0 + rows);
-    if (!sm.ranked && sm.tail_l && l >= sm.tail_l) {
-        const int i = l - sm.tail_l;
-        group = i % ngroups;
-        const int t = i / ngroups;
-        s0 = (int)row0 + sm.tail_row + t * sm.tail_strip;
-        s1 = min(s0 + sm.tail_strip, end);
-        rot = group + t;
-    } else if (!sm.ranked) {
-        // XCD-aware order: workgroups are dispatched round-robin over the 8 XCDs (L2 per XCD), so
-        // consecutive ids are remapped to let each XCD walk its own contiguous run of column groups
-        // of a strip: the lateral halo columns two neighbouring groups both read then meet in one L2.
-        const int n = sm.tail_l ? sm.tail_l : (int)gridDim.x, per = n / 8;
-        const int m = l < per * 8 ? (l % 8) * per + l / 8 : l;
-        group = m % ngroups;
-        const int by = m / ngroups;
-        s0 = (int)row0 + by * strip;
-        s1 = min(s0 + strip, sm.tail_l ? (int)row0 + sm.tail_row : end);
-        rot = group + by;
-    } else {
-        const int rank = l / sm.cus, c = l % sm.cus;
-        const int c2 = (c % 8) * (sm.cus / 8) + c / 8;  // contiguous CUs per XCD (cus % 8 == 0)
-        group = c2 % ngroups;
-        const int t = c2 / ngroups;
-        s0 = (int)row0 + t * sm.period + sm.off[rank];
-        s1 = min(s0 + sm.len[rank], end);
-        rot = rank;
-    }
-    return s0 < s1;
-}
-// Direction and claim counter of workgroup l (0 / nullptr: a static strip).
-__device__ __forceinline__ int work_dir(const StripMap &sm, int l, uint32_t *&ctr)
-{
-    ctr = nullptr;
-    if (!sm.ranked) return 0;
-    const int rank = l / sm.cus, c = l % sm.cus;
-    if (!sm.dir[rank]) return 0;
-    ctr = sm.claims + ((int64_t)c * 2 + sm.pslot[rank]) * 16;
-    return sm.dir[rank];
-}
 
 // ------------------------------------------------------------------ the rule of a step kernel
 // bits_step_kernel and band_step_kernel are generic over the rule (B3S23 and TableRule, below
@@ -585,9 +517,6 @@ struct TableRule {
         rstage<K, DW, S, BAND>(t, p, g, cur);
     }
 };
-
-__host__ __device__ constexpr int band_halo_lanes(int k, int dw) { return (k + dw - 1) / dw; }
-__host__ __device__ constexpr int band_useful_words(int k, int dw) { return (64 - 2 * band_halo_lanes(k, dw)) * dw; }
 
 // One wave = all K stages (k = 1, 2, 4, 8; 16 with 2 words per lane).  Same row addressing,
 // strips and fused count as bits_step_kernel; grid.x: groups of 4 waves along the row,
@@ -920,14 +849,7 @@ __device__ __forceinline__ int claim_cu_slot(uint32_t *m)
 #ifndef GOL_BAND_LOAD_AUX
 #define GOL_BAND_LOAD_AUX 0
 #endif
-// Pipeline shape of k = 12: KW stages in each of P waves; blocks of GOL_BAND_RPB rows (one pair
-// step), rings of GOL_BAND_NS slots (the role loops are unrolled over the slots).
-#ifndef GOL_BAND_KW
-#define GOL_BAND_KW 3
-#endif
-#define GOL_BAND_P 4
-#define GOL_BAND_RPB 2
-#define GOL_BAND_NS 4
+// (Pipeline shape of k = 12, GOL_BAND_KW / _P / _RPB / _NS: gol_strips.h.)
 // The loader issues block b + GOL_BAND_PREFETCH at block b (its in_ring slot was read at the start
 // of block b + GOL_BAND_PREFETCH - NS, so up to NS) and waits for block b + 1 only.  Same box, 3
 // reps: 3 against 2 weak 163.6-164.1 vs 163.1-163.7 TCUPS, 262144^2 +0.6 %, 65536^2 +1.2 %; 4 as 3
@@ -957,7 +879,7 @@ band_pipe_kernel(BitsArgs a)
     const int lane = threadIdx.x & 63;
     const int litem = (int)blockIdx.x;
     int group, s0, s1, rotv;
-    const bool has_rows = work_item(a.sm, a.ngroups, a.row0, a.rows, a.strip, litem, group, s0, s1, rotv);
+    const bool has_rows = work_item(a.sm, a.ngroups, a.row0, a.rows, a.strip, litem, [] { return gridDim.x; }, group, s0, s1, rotv);
     uint32_t *ctr;
     const int dir = work_dir(a.sm, litem, ctr);  // 0: static strip, +1 / -1: paired (StripMap)
     // Pipeline position of this wave, rotated per workgroup (role placement below refines it)
@@ -977,11 +899,12 @@ band_pipe_kernel(BitsArgs a)
     // the stream: input row first_in + t at stream step t (walking up, dir -1: s1e + K - 1 - t);
     // output row first_in + t - K (s1e - 1 + 2K - t), valid from step 2K on
     const int nblk = ((s1 - s0) + 2 * K + RPB - 1) / RPB;
-    constexpr int TRIP = RPB * NS;  // rows per loop trip
     // a pair's range, stretched to s1e so that TRIP divides its len + 4K (whole loop trips); rows
-    // past s1 are read clamped and never stored
-    const int s1e = dir ? s0 + ((s1 - s0 + 4 * K + TRIP - 1) / TRIP) * TRIP - 4 * K : s1;
-    const int nclaim = (s1e - s0 + 4 * K) / RPB;  // blocks of the pair (a multiple of NS)
+    // past s1 are read clamped and never stored; nclaim: blocks of the pair, a multiple of NS
+    // (gol_strips.h: the expressions the host's pair_extent evaluates)
+    constexpr int TRIP = RPB * NS;  // rows per loop trip
+    const int s1e = GOL_PAIR_S1E(dir, s0, s1, K, TRIP);
+    const int nclaim = GOL_PAIR_NCLAIM(s0, s1e, K, RPB);
 
     const int pitch_b = (int)a.pitch * 4;
     const char *mid_b = reinterpret_cast<const char *>(a.mid);
@@ -1575,17 +1498,7 @@ __device__ __forceinline__ void spstage(PairState<1> &s, uint32_t &r0, uint32_t 
     s.cb[0] = l1;
 }
 
-#ifndef GOL_BYTES_PER_CU
-#define GOL_BYTES_PER_CU 3  // workgroups per CU of a one-round launch
-#endif
-// Ring slots of the byte pipeline: NS hand-off slots of 4 rows between the waves, NSI input slots
-// of the first wave (2 blocks in flight); the role loops are unrolled over NS (NSI divides it)
-#ifndef GOL_BYTES_NS
-#define GOL_BYTES_NS 3
-#endif
-#ifndef GOL_BYTES_NSI
-#define GOL_BYTES_NSI 3
-#endif
+// (Ring slots of the byte pipeline, GOL_BYTES_NS / _NSI, and GOL_BYTES_PER_CU: gol_strips.h.)
 // Cache policy bits of the byte pipeline's output stores (0: default)
 #ifndef GOL_BYTES_STORE_AUX
 #define GOL_BYTES_STORE_AUX 0
@@ -1595,7 +1508,8 @@ __global__ void __launch_bounds__(64 * P) __attribute__((amdgpu_waves_per_eu(6, 
 {
     constexpr int K = KW * P;
     static_assert(K <= 32, "one 32-cell halo word per side");
-    constexpr int RPB = 4;            // rows per block: two pair steps
+    constexpr int RPB = GOL_BYTES_RPB;  // rows per block: two pair steps
+    static_assert(RPB == 4, "a block is two pair steps");
     constexpr int NS = GOL_BYTES_NS;  // (the loops below are unrolled over the NS slots)
     constexpr int NSI = GOL_BYTES_NSI;
     static_assert(NS % NSI == 0 && NSI >= 3, "input slots: 2 blocks in flight, one being read");
@@ -1609,7 +1523,7 @@ __global__ void __launch_bounds__(64 * P) __attribute__((amdgpu_waves_per_eu(6, 
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     int group, s0, s1, rotv;
-    if (!work_item(a.sm, a.ngroups, a.row0, a.rows, a.strip, blockIdx.x, group, s0, s1, rotv)) return;
+    if (!work_item(a.sm, a.ngroups, a.row0, a.rows, a.strip, blockIdx.x, [] { return gridDim.x; }, group, s0, s1, rotv)) return;
     uint32_t *ctr;
     const int dir = work_dir(a.sm, blockIdx.x, ctr);  // 0: static strip, +1 / -1: paired
     const int64_t col_raw = (int64_t)group * 62 + (lane - 1);
@@ -1618,11 +1532,12 @@ __global__ void __launch_bounds__(64 * P) __attribute__((amdgpu_waves_per_eu(6, 
     const int R = (int)a.R;
     const int first_in = s0 - K, last_in = s1 + K - 1;
     const int nblk = ((s1 - s0) + 2 * K + RPB - 1) / RPB;
-    constexpr int TRIP = RPB * NS;  // rows per loop trip
     // a pair's range, stretched to s1e so that TRIP divides its len + 4K (rows past s1 are read
-    // clamped and never stored: they only feed outputs past s1)
-    const int s1e = dir ? s0 + ((s1 - s0 + 4 * K + TRIP - 1) / TRIP) * TRIP - 4 * K : s1;
-    const int nclaim = (s1e - s0 + 4 * K) / RPB;  // blocks of the pair (a multiple of NS)
+    // clamped and never stored: they only feed outputs past s1); nclaim: blocks of the pair, a
+    // multiple of NS (gol_strips.h: the expressions the host's pair_extent evaluates)
+    constexpr int TRIP = RPB * NS;  // rows per loop trip
+    const int s1e = GOL_PAIR_S1E(dir, s0, s1, K, TRIP);
+    const int nclaim = GOL_PAIR_NCLAIM(s0, s1e, K, RPB);
     const int pitch = (int)a.pitch;
     const char *mid_b = reinterpret_cast<const char *>(a.mid);
     const int64_t top_d = (reinterpret_cast<const char *>(a.top) - mid_b) + (int64_t)K * pitch;
@@ -1928,10 +1843,6 @@ __global__ void __launch_bounds__(64 * P) __attribute__((amdgpu_waves_per_eu(6, 
     if (COUNT && wv == P - 1) slot_add(a.slots, alive);
 }
 
-#ifndef GOL_BYTES_PIPE_KW
-#define GOL_BYTES_PIPE_KW 4
-#define GOL_BYTES_PIPE_P 8
-#endif
 #define BYTES_PIPE(count) (bytes_pipe_kernel<GOL_BYTES_PIPE_KW, GOL_BYTES_PIPE_P, count>)
 
 
@@ -2327,9 +2238,6 @@ __global__ void ipc_wait_kernel(IpcWaitArgs a)
 // ------------------------------------------------------------------ launchers
 using namespace golk;
 
-// Rows per wave strip are capped so a lane's 32-bit alive count cannot overflow.
-constexpr int GOL_MAX_STRIP = 1 << 24;
-
 static inline int grid_for(int64_t n, int block = 256, int64_t cap = 256 * 16)
 {
     int64_t g = (n + block - 1) / block;
@@ -2453,23 +2361,6 @@ static int64_t resident_workgroups(const void *kernel, int block)
     return n;
 }
 
-// Strip length for a one-workgroup-per-(column group, strip) kernel on a board that fills the
-// device only a few times over: the strip count is a multiple of the strips that fit in one
-// round of resident workgroups, so the last round is not a small remainder (e.g. 65536^2 at
-// k = 12: 9 groups x 228 strips = 2052 workgroups was 2 rounds + 4 workgroups).  Boards of
-// many rounds keep `fallback` (their tail is a small fraction already).
-static int64_t round_tiled_strip(int64_t rows, int64_t ngroups, int64_t slots, int64_t min_rows, int64_t cap,
-                                 int64_t fallback)
-{
-    if (slots <= 0 || rows <= 0) return fallback;
-    const int64_t per_round = std::max<int64_t>(1, slots / ngroups);
-    const int64_t rounds = (rows + per_round * cap - 1) / (per_round * cap);
-    if (rounds > 4) return fallback;
-    const int64_t nstrips = per_round * rounds;
-    const int64_t strip = (rows + nstrips - 1) / nstrips;
-    return std::min(rows, std::max(strip, min_rows));
-}
-
 // Arguments of a step launch (golk_bits_step, golk_band_step, golk_rule_step): waves of U output
 // words, strips of `strip` rows (<= 0: golk_auto_strip), no strip map, error word or CU slots.
 static BitsArgs step_args(const uint32_t *top, const uint32_t *mid, const uint32_t *bot, uint32_t *dst, int64_t R,
@@ -2527,11 +2418,6 @@ static int device_cus()
     return cus;
 }
 
-// Rank-weighted strips for a launch of exactly one round (StripMap): every CU takes one column
-// group x `period` rows and its per_cu workgroups split them in proportion to `weight[rank]`,
-// the measured relative speed of the rank-th arrival on a CU.  Used when the strips of one
-// column group can be spread over the CUs with little waste (ngroups x strips per group >= 94 %
-// of the CUs) and every rank still gets >= min_rows rows; else false (equal strips).
 // Claim counters of the paired ranks (StripMap), one zeroed buffer per stream: launches on one
 // stream run in order and leave their counters zeroed; launches on different streams may run
 // at once and must not share counters.  The buffer is zeroed ON that stream (stream-ordered
@@ -2621,178 +2507,38 @@ hipError_t golk_reset_claims_device(int device)
     return e;
 }
 
-static bool rank_split(int64_t rows, int64_t ngroups, int cus, int per_cu, const double *weight, int64_t min_rows,
-                       int64_t max_strip, StripMap &sm, bool paired, uint32_t *claims = nullptr, int chunk = 0,
-                       int max_rounds = 2)
-{
-    if (cus <= 0 || cus % 8 || per_cu < 1 || per_cu > 4 || ngroups > cus || rows <= 0) return false;
-    // only boards that fill the device at most max_rounds times with strips of max_strip rows: on
-    // bigger boards workgroups refill the CUs as they finish, and only the last round has the tail
-    if (ngroups * ((rows + max_strip - 1) / max_strip) > max_rounds * (int64_t)cus * per_cu) return false;
-    const int64_t t = cus / ngroups;  // strips per column group, one CU each
-    if (t * ngroups * 100 < (int64_t)cus * 94) return false;
-    const int64_t period = (rows + t - 1) / t;
-    double wsum = 0;
-    for (int r = 0; r < per_cu; ++r) wsum += weight[r];
-    StripMap m{};
-    m.ranked = 1;
-    m.cus = cus;
-    m.per_cu = per_cu;
-    m.period = (int32_t)period;
-    if (paired && per_cu >= 2) {
-        // pairs walking one range from both ends: per_cu 2: (0, 1); 3: (0, 2) + rank 1 alone;
-        // 4: (0, 3) + (1, 2).  A pair's range gets the sum of its ranks' weights.
-        static const int pa[4][2] = {{0, 0}, {0, 0}, {0, 1}, {0, 2}};
-        int ga[2][2];
-        int ng = 0;
-        if (per_cu == 4) { ga[0][0] = 0; ga[0][1] = 3; ga[1][0] = 1; ga[1][1] = 2; ng = 2; }
-        else { ga[0][0] = pa[per_cu][0]; ga[0][1] = pa[per_cu][1]; ng = 1; }
-        m.claims = claims;
-        m.chunk = chunk;
-        int64_t off = 0;
-        double wused = 0;
-        for (int g = 0; g < ng; ++g) {
-            const double w = weight[ga[g][0]] + weight[ga[g][1]];
-            wused += w;
-            const int64_t len = (g == ng - 1 && per_cu != 3) ? period - off : (int64_t)(period * wused / wsum + 0.5) - off;
-            if (len < min_rows) return false;
-            for (int j = 0; j < 2; ++j) {
-                const int r = ga[g][j];
-                m.off[r] = (int32_t)off;
-                m.len[r] = (int32_t)len;
-                m.dir[r] = j == 0 ? 1 : -1;
-                m.pslot[r] = g;
-            }
-            off += len;
-        }
-        if (per_cu == 3) {  // rank 1: the rest, a static strip
-            if (period - off < min_rows) return false;
-            m.off[1] = (int32_t)off;
-            m.len[1] = (int32_t)(period - off);
-        }
-        sm = m;
-        return true;
-    }
-    int64_t off = 0;
-    for (int r = 0; r < per_cu; ++r) {
-        const int64_t len = r == per_cu - 1 ? period - off : (int64_t)(period * weight[r] / wsum + 0.5);
-        if (len < min_rows) return false;
-        m.len[r] = (int32_t)len;
-        m.off[r] = (int32_t)off;
-        off += len;
-    }
-    sm = m;
-    return true;
-}
-
-// Rows per arrival rank, from measurements (tools/timeline.py, same-box A/B with tools/ab.py):
-// one round of equal strips ended the ranks' workgroups at T_r (band 247 / 298 / 388 / 482 us,
-// bytes 96 / 136 / 174 us), so the static split gives rank r a share ~ 1 / T_r, refined by
-// re-measuring (w_r <- w_r T_mean / T_r).  With paired ranks (StripMap) only the sum over a
-// pair matters: band pairs (0, 3) and (1, 2) ran at equal speed (65536^2: 0.54 / 0.46 ended
-// them at 425 / 360 us; 50 / 50: 110.3 TCUPS vs 106.2 for the static split, same box); bytes
-// pair (0, 2) with rank 1 alone on 0.31 of the rows.
-#ifndef GOL_BAND_RANK_W
-#define GOL_BAND_RANK_W 0.25, 0.25, 0.25, 0.25
-#endif
-#ifndef GOL_BYTES_RANK_W
-#define GOL_BYTES_RANK_W 0.4457, 0.33, 0.2449, 0.0  // lone rank 1: 0.31 -> 0.33 after the fill skip (+1.3 %)
-#endif
-static const double BAND_PIPE_RANK_W[4] = {GOL_BAND_RANK_W};
-static const double BYTES_PIPE_RANK_W[4] = {GOL_BYTES_RANK_W};
-
-// Rounds of short tail strips (StripMap.tail_*), 1 / GOL_BAND_TAIL_DIV of a strip's rows each.
-// Round 3, half-length strips, same box, 2^17 x 2^20: none 137.2 TCUPS, 0.5 round 138.8, 1.0
-// 138.8, 1.5 138.6; 262144^2: 132.2 / 133.6 / 133.2 / 133.0.  Round 6, weak board, two boxes, 3 + 4
-// reps against half-length strips for 0.5 round: quarter-length strips for 1 round +0.5 / +0.6 %,
-// for 0.5 round +0.1 %, 0.25 round -1.1 %, 1.5 rounds -0.4 %; third-length -0.3 %, eighth-length
-// -0.1 % (profiles/r06/r06_ab_tail.log).
-#ifndef GOL_BAND_TAIL
-#define GOL_BAND_TAIL 1.0
-#endif
-#ifndef GOL_BAND_TAIL_DIV
-#define GOL_BAND_TAIL_DIV 4
-#endif
-#ifndef GOL_BAND_PAIRED
-#define GOL_BAND_PAIRED 1
-#endif
-#ifndef GOL_BYTES_PAIRED
-#define GOL_BYTES_PAIRED 1
-#endif
 // bytes_pipe_kernel lives in its own translation unit (gol_bytes_pipe.hip: another scheduler)
 const void *golk_bytes_pipe_fn(bool count);
 hipError_t golk_bytes_pipe_launch(bool count, unsigned nwg, const BytesKArgs &a, hipStream_t s);
-// Rows per strip of the band pipeline's launches of many rounds (same box, weak board, 3 reps:
-// 1024 148.4 TCUPS, 2048 148.3, 4096 147.0; profiles/r04/r04d_ab_rounds.jsonl)
-#ifndef GOL_BAND_STRIP
-#define GOL_BAND_STRIP 1024
-#endif
-// Band launches of up to this many rounds of strips run as one round of rank-weighted, paired
-// ranges instead, when their column groups spread over the CUs (rank_split).  Same box, 3 reps
-// each: config 4's N = 4 share 65536 x 262144 (2.95 rounds of 781-row strips) 134.2 -> 148.3
-// TCUPS at 4 rounds; at 16 rounds the N = 2 share 131072 x 262144 (4.5 rounds) 142.0 -> 150.2
-// and the whole 262144^2 board (9 rounds) 145.3 -> 149.4 (profiles/r04/r04d_ab_*.jsonl).  The
-// weak board's 133 column groups spread over 256 CUs only one per CU (52 %): strips.
-#ifndef GOL_BAND_RANK_ROUNDS
-#define GOL_BAND_RANK_ROUNDS 16
-#endif
-static constexpr int BAND_RANK_ROUNDS = GOL_BAND_RANK_ROUNDS;
-static constexpr int BYTES_PIPE_P = GOL_BYTES_PIPE_P;
-
-// The band pipeline's one-round launch (rank_split) of `rows` rows, when it applies; claims:
-// the paired ranks' counters (null: only ask whether it applies).
-static bool band_rank_map(int64_t rows, int64_t ngroups, int64_t pitch, int cus, int64_t slots, uint32_t *claims,
-                          StripMap &sm)
-{
-    constexpr int KW = GOL_BAND_KW, P = GOL_BAND_P;
-    if (cus <= 0 || slots <= 0) return false;
-    StripMap m{};
-    if (!rank_split(rows, ngroups, cus, (int)(slots / cus), BAND_PIPE_RANK_W, 8 * KW * P, 1024, m, GOL_BAND_PAIRED,
-                    claims, GOL_BAND_NS, BAND_RANK_ROUNDS))
-        return false;
-    if ((int64_t)m.period * pitch * 4 >= (int64_t(1) << 31)) return false;  // a range's stores: one 32-bit buffer
-    sm = m;
-    return true;
-}
-
 // band_pipe_kernel lives in its own translation unit (gol_band_pipe.hip: another scheduler)
 const void *golk_band_pipe_fn(bool contig, bool count);
 hipError_t golk_band_pipe_launch(bool contig, bool count, unsigned nwg, const BitsArgs &a, hipStream_t s);
 
-// k = 12 on the band layout: 4 waves x 3 stages (band_pipe_kernel).
-static hipError_t launch_band_pipe(bool contig, BitsArgs a, hipStream_t s, bool auto_strip)
+// The device a pipelined launch is scheduled for: this one (as_cus = as_slots = 0), or a
+// pretended smaller one of as_cus CUs (a multiple of 8) holding as_slots resident workgroups of
+// `kernel`; false: it asks for more than this device has.
+static bool pipe_device(const void *kernel, int block, int as_cus, int64_t as_slots, int &cus, int64_t &slots)
 {
-    constexpr int KW = GOL_BAND_KW, P = GOL_BAND_P;
-    const bool count = a.slots != nullptr;
-    const void *kf = golk_band_pipe_fn(contig, count);
-    int64_t nwg = 0;
-    const int cus = device_cus();
-    const int64_t slots = resident_workgroups(kf, 64 * P);
-    uint32_t *claims = auto_strip && GOL_BAND_PAIRED && cus > 0 ? claim_counters(s, cus) : nullptr;
-    if (auto_strip && (claims || !GOL_BAND_PAIRED) && band_rank_map(a.rows, a.ngroups, a.pitch, cus, slots, claims, a.sm)) {
-        nwg = (int64_t)cus * a.sm.per_cu;
-    } else {
-        if (auto_strip) a.strip = (int)round_tiled_strip(a.rows, a.ngroups, slots, 8 * KW * P, 1024, a.strip);
-        nwg = (int64_t)a.ngroups * ((a.rows + a.strip - 1) / a.strip);
-        if (auto_strip && GOL_BAND_TAIL > 0 && slots > 0 && nwg > 4 * slots) {
-            // the last ~GOL_BAND_TAIL rounds of workgroups run strips of 1 / GOL_BAND_TAIL_DIV of the rows
-            const int64_t ts = std::max<int64_t>(8 * KW * P, a.strip / GOL_BAND_TAIL_DIV);
-            const int64_t nt = (int64_t)(GOL_BAND_TAIL * (double)slots / a.ngroups + 0.999);  // tail strips per group
-            const int64_t tail_rows = std::min<int64_t>(a.rows / 2, nt * ts);
-            const int64_t big = a.rows - tail_rows;
-            const int64_t nbig = (big + a.strip - 1) / a.strip;
-            a.sm.tail_l = (int32_t)(a.ngroups * nbig);
-            a.sm.tail_row = (int32_t)big;
-            a.sm.tail_strip = (int32_t)ts;
-            nwg = a.sm.tail_l + a.ngroups * ((tail_rows + ts - 1) / ts);
-        }
-    }
-    return golk_band_pipe_launch(contig, count, (unsigned)nwg, a, s);
+    cus = device_cus();
+    slots = resident_workgroups(kernel, block);
+    if (!as_cus && !as_slots) return true;
+    if (as_cus <= 0 || as_cus % 8 || as_cus > cus || as_slots <= 0 || as_slots > slots) return false;
+    cus = as_cus;
+    slots = as_slots;
+    return true;
+}
+
+bool golk_pipe_limits(bool band, bool contig, bool count, int *cus, int64_t *slots)
+{
+    *cus = device_cus();
+    *slots = band ? resident_workgroups(golk_band_pipe_fn(contig, count), 64 * GOL_BAND_P)
+                  : resident_workgroups(golk_bytes_pipe_fn(count), 64 * GOL_BYTES_PIPE_P);
+    return *cus > 0 && *slots > 0;
 }
 
 hipError_t golk_band_step(const uint32_t *top, const uint32_t *mid, const uint32_t *bot, uint32_t *dst, int64_t R,
                           int64_t Wd, int64_t pitch, int64_t row0, int64_t rows, int k, int dw, int strip,
-                          uint64_t *slots, uint32_t *err, hipStream_t s)
+                          uint64_t *slots, uint32_t *err, hipStream_t s, int as_cus, int64_t as_slots)
 {
     if (rows <= 0) return hipSuccess;
     BitsArgs a = step_args(top, mid, bot, dst, R, Wd, pitch, row0, rows, band_useful_words(k, dw), k, strip, slots);
@@ -2804,23 +2550,23 @@ hipError_t golk_band_step(const uint32_t *top, const uint32_t *mid, const uint32
     }
     const bool contig = top + (int64_t)k * pitch == mid && bot == mid + R * pitch;
     if (dw == 4 && k == GOL_BAND_KW * GOL_BAND_P) {
-        // one workgroup per (column group, strip): strips up to 1024 rows (measured best at k = 12)
-        // Boards with fewer than ~256 tiles of 8k rows are latency-bound (a launch lasts one
-        // pipeline's walk over strip + 2k rows): ~512 tiles of >= 2 rows instead, without the
-        // one-round rank split (1024^2: 2.6 us per turn vs 5.1 at 96 rows; 4096^2: 3.0 vs 5.2;
-        // 8192^2: 4.1 vs 5.3; 16384^2 keeps the rank split: 6.0 vs 6.4 with 96-row tiles;
-        // profiles/r03/r03q_small.jsonl)
-        const int64_t work = rows * a.ngroups;
-        const bool small = strip <= 0 && work < (int64_t)8 * k * 256;
-        if (small)
-            a.strip = (int)std::min<int64_t>(rows, std::max<int64_t>(2, work / 512));
-        else
-            a.strip = strip > 0 ? std::min(strip, GOL_MAX_STRIP)
-                                : (int)std::min<int64_t>(rows, std::max<int64_t>(8 * k, std::min<int64_t>(GOL_BAND_STRIP, rows * a.ngroups / 2048)));
-        // the pipe kernel's stores address a strip as one buffer (32-bit range)
-        a.strip = (int)std::max<int64_t>(1, std::min<int64_t>(a.strip, (int64_t(1) << 30) / (pitch * 4)));
-        return launch_band_pipe(contig, a, s, strip <= 0 && !small);
+        // k = 12 on the band layout: 4 waves x 3 stages (band_pipe_kernel), one workgroup per
+        // (column group, range of rows): band_strip_plan.  The claim counters are sized by the
+        // device itself, whichever device the launch is scheduled for.
+        const bool count = a.slots != nullptr;
+        int cus = 0;
+        int64_t resident = 0;
+        if (!pipe_device(golk_band_pipe_fn(contig, count), 64 * GOL_BAND_P, as_cus, as_slots, cus, resident))
+            return hipErrorInvalidValue;
+        StripPlan p = band_strip_plan(rows, Wd, pitch, k, strip, cus, resident);
+        uint32_t *claims = p.mode == GOL_STRIPS_RANKED_PAIRED ? claim_counters(s, device_cus()) : nullptr;
+        if (p.mode == GOL_STRIPS_RANKED_PAIRED && !claims) p = band_strip_plan(rows, Wd, pitch, k, strip, cus, resident, false);
+        a.strip = p.strip;
+        a.sm = p.sm;
+        a.sm.claims = claims;
+        return golk_band_pipe_launch(contig, count, (unsigned)p.nwg, a, s);
     }
+    if (as_cus || as_slots) return hipErrorInvalidValue;
     dim3 grid((a.ngroups + 3) / 4, (int)((rows + a.strip - 1) / a.strip));
     if (dw == 2) return contig ? launch_band<2, true>(k, grid, a, s) : launch_band<2, false>(k, grid, a, s);
     if (dw == 4) return contig ? launch_band<4, true>(k, grid, a, s) : launch_band<4, false>(k, grid, a, s);
@@ -2863,13 +2609,10 @@ hipError_t golk_rule_step(const uint32_t *top, const uint32_t *mid, const uint32
 double golk_step_rounds(bool band, int64_t rows, int64_t Wd, int64_t pitch, int k, int dw, int strip)
 {
     if (!band || dw != 4 || k != GOL_BAND_KW * GOL_BAND_P || rows <= 0) return 1e9;
-    const int64_t ngroups = (Wd + band_useful_words(k, dw) - 1) / band_useful_words(k, dw);
     const int64_t slots = resident_workgroups(golk_band_pipe_fn(true, true), 64 * GOL_BAND_P);
     if (slots <= 0) return 1e9;
-    StripMap sm{};
-    if (strip <= 0 && band_rank_map(rows, ngroups, pitch, device_cus(), slots, nullptr, sm)) return 1.0;
-    const int64_t st = strip > 0 ? strip : GOL_BAND_STRIP;  // launch_band_pipe's strips
-    return (double)(ngroups * ((rows + st - 1) / st)) / (double)slots;
+    const StripPlan p = band_strip_plan(rows, Wd, pitch, k, strip, device_cus(), slots);  // the launch's own plan
+    return p.sm.ranked ? 1.0 : (double)p.nwg / (double)slots;
 }
 
 hipError_t golk_band_convert(bool to_band, const uint32_t *src, uint32_t *dst, int64_t rows, int64_t Wd,
@@ -2913,7 +2656,7 @@ hipError_t golk_bytes_step(const uint8_t *world, int64_t H, int64_t W, int64_t s
 
 hipError_t golk_bytes_blocked(const uint8_t *top, const uint8_t *mid, const uint8_t *bot, uint8_t *dst, int64_t R,
                               int64_t W, int64_t pitch, int64_t row0, int64_t rows, int k, int strip, uint64_t *slots,
-                              uint32_t *err, hipStream_t s)
+                              uint32_t *err, hipStream_t s, int as_cus, int64_t as_slots)
 {
     BytesKArgs a;
     a.top = top; a.mid = mid; a.bot = bot; a.dst = dst;
@@ -2926,31 +2669,22 @@ hipError_t golk_bytes_blocked(const uint8_t *top, const uint8_t *mid, const uint
     if (!a.err) return hipErrorOutOfMemory;
     a.sm = StripMap{};
     if (k == 32) {
-        // one workgroup of GOL_BYTES_PIPE_P waves per (column group, strip): rank-weighted strips
-        // in one round, else round-tiled strips >= 4k rows
+        // one workgroup of GOL_BYTES_PIPE_P waves per (column group, strip): bytes_strip_plan
         const bool count = a.slots != nullptr;
-        const void *kf = golk_bytes_pipe_fn(count);
-        const int cus = device_cus();
-        const int64_t slots = resident_workgroups(kf, 64 * BYTES_PIPE_P);
-        int64_t nwg = 0;
-        uint32_t *claims = GOL_BYTES_PAIRED ? claim_counters(s, cus) : nullptr;
-        // the last wave stores a strip through one buffer descriptor: strip rows x pitch < 2^31
-        const int64_t max_rows = std::max<int64_t>(1, ((int64_t(1) << 31) - 1) / pitch - 1);
-        if (strip <= 0 && cus > 0 &&
-            rank_split(rows, a.ngroups, cus, (int)std::min<int64_t>(GOL_BYTES_PER_CU, slots / cus), BYTES_PIPE_RANK_W,
-                       2 * k, 1024, a.sm, claims != nullptr, claims, GOL_BYTES_NS) && a.sm.period <= max_rows) {
-            nwg = (int64_t)cus * a.sm.per_cu;
-        } else {
-            a.sm = StripMap{};
-            if (strip <= 0) {
-                a.strip = (int)std::min<int64_t>(rows, std::max<int64_t>(8 * k, rows * a.ngroups / 1024));
-                a.strip = (int)round_tiled_strip(rows, a.ngroups, slots, 4 * k, 1024, a.strip);
-            }
-            a.strip = (int)std::min<int64_t>(a.strip, max_rows);
-            nwg = (int64_t)a.ngroups * ((rows + a.strip - 1) / a.strip);
-        }
-        return golk_bytes_pipe_launch(count, (unsigned)nwg, a, s);
+        int cus = 0;
+        int64_t resident = 0;
+        if (!pipe_device(golk_bytes_pipe_fn(count), 64 * GOL_BYTES_PIPE_P, as_cus, as_slots, cus, resident))
+            return hipErrorInvalidValue;
+        // (the claim counters are sized by the device itself, whichever device the launch is scheduled for)
+        StripPlan p = bytes_strip_plan(rows, W, pitch, k, strip, cus, resident);
+        uint32_t *claims = p.mode == GOL_STRIPS_RANKED_PAIRED ? claim_counters(s, device_cus()) : nullptr;
+        if (p.mode == GOL_STRIPS_RANKED_PAIRED && !claims) p = bytes_strip_plan(rows, W, pitch, k, strip, cus, resident, false);
+        a.strip = p.strip;
+        a.sm = p.sm;
+        a.sm.claims = claims;
+        return golk_bytes_pipe_launch(count, (unsigned)p.nwg, a, s);
     }
+    if (as_cus || as_slots) return hipErrorInvalidValue;
     const int nstrips = (int)((rows + a.strip - 1) / a.strip);
     dim3 grid((a.ngroups + 3) / 4, nstrips);
     switch (k) {

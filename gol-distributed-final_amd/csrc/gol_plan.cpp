@@ -9,8 +9,11 @@
 // gloo tests drive on the CPU, so both run one schedule.
 #include <stdint.h>
 
+#include <vector>
+
 #include "golhip.h"
 #include "gol_internal.h"
+#include "gol_strips.h"
 
 extern "C" int gol_halo_plan(int64_t H, int32_t nranks, int32_t rank, int32_t k, gol_halo_op *ops, int32_t cap,
                              int32_t *n)
@@ -92,5 +95,44 @@ extern "C" int gol_view_plan(int64_t H, int32_t nranks, int32_t rank, int64_t y0
         ++m;
     }
     *n = m;
+    return GOL_OK;
+}
+
+// The strip schedule of a pipelined launch (include/golhip.h, gol_strip_plan): the plan the
+// launchers make (gol_strips.h band_strip_plan / bytes_strip_plan) and, per workgroup id, what the
+// kernels' own work_item / work_dir / pair_extent give for it.
+extern "C" int gol_strip_plan(int32_t kernel, int64_t rows, int64_t row0, int64_t width, int64_t pitch, int32_t k,
+                              int32_t strip_rows, int32_t cus, int32_t slots, gol_strip_info *info, gol_strip_rec *recs,
+                              int64_t cap, int64_t *n)
+{
+    using namespace golk;
+    const bool band = kernel == GOL_STRIP_KERNEL_BAND;
+    const int K = band ? GOL_BAND_KW * GOL_BAND_P : GOL_BYTES_PIPE_KW * GOL_BYTES_PIPE_P;
+    if (!n || !info || (!band && kernel != GOL_STRIP_KERNEL_BYTES) || k != K || rows < 1 || row0 < 0 || width < 1 ||
+        pitch < 1 || row0 + rows > INT32_MAX || (band ? pitch < width || width % 4 : pitch < width || width % 32) ||
+        cus < 0 || slots < 0 || cap < 0 || (cap > 0 && !recs))
+        return gol_set_error(GOL_EINVAL, "bad strip plan arguments (kernel %d, rows %lld at %lld, width %lld, pitch %lld, k %d)",
+                             kernel, (long long)rows, (long long)row0, (long long)width, (long long)pitch, k);
+    const StripPlan p = band ? band_strip_plan(rows, width, pitch, k, strip_rows, cus, slots)
+                             : bytes_strip_plan(rows, width, pitch, k, strip_rows, cus, slots);
+    const int RPB = band ? GOL_BAND_RPB : GOL_BYTES_RPB, NS = band ? GOL_BAND_NS : GOL_BYTES_NS;
+    *info = gol_strip_info{p.mode, p.ngroups, p.strip, K, RPB, NS, p.sm.per_cu, p.sm.period, p.sm.tail_l, p.sm.tail_row,
+                           p.sm.tail_strip, 0};
+    if (p.nwg > INT32_MAX) return gol_set_error(GOL_EINVAL, "the launch would take %lld workgroups", (long long)p.nwg);
+    StripMap sm = p.sm;
+    std::vector<uint32_t> counters((size_t)(sm.ranked ? sm.cus : 0) * 2 * 16 + 1);  // as the launchers size them: 16 words each
+    sm.claims = counters.data();
+    for (int64_t l = 0; l < p.nwg && l < cap; ++l) {
+        gol_strip_rec r{};
+        int rot = 0;
+        uint32_t *ctr = nullptr;
+        work_item(sm, p.ngroups, row0, rows, p.strip, (int)l, [&] { return p.nwg; }, r.group, r.s0, r.s1, rot);
+        r.dir = work_dir(sm, (int)l, ctr);
+        r.claim = r.dir ? (int32_t)((ctr - counters.data()) / 16) : -1;
+        if (band) pair_extent<GOL_BAND_KW * GOL_BAND_P, GOL_BAND_RPB, GOL_BAND_NS>(r.dir, r.s0, r.s1, r.s1e, r.nclaim);
+        else pair_extent<GOL_BYTES_PIPE_KW * GOL_BYTES_PIPE_P, GOL_BYTES_RPB, GOL_BYTES_NS>(r.dir, r.s0, r.s1, r.s1e, r.nclaim);
+        recs[l] = r;
+    }
+    *n = p.nwg;
     return GOL_OK;
 }

@@ -5,6 +5,7 @@
 * ``GameOfLifeOperations`` worker RPC service mirror (worker.go:73-86)
 * ``ShardedBoard``         torch.distributed mirror of the sharded step (runs the library's plans)
 * ``halo_plan`` / ``step_plan``  the sharded step's schedule as data (gol_halo_plan, gol_step_plan)
+* ``strip_plan``           which workgroup of a pipelined launch computes which rows (gol_strip_plan)
 * ``Engine.view`` / ``Operations.view``  viewport frames of the running board (gol_engine_view; ``view_plan``)
 * ``Engine(rule=)`` / ``Engine.set_rule`` / ``parse_rule`` / ``format_rule``  life-like rules (B/S masks, gol_engine_set_rule)
 * ``Engine.paste`` / ``Engine.fill`` / ``Operations.paste`` / ``parse_rle`` / ``format_rle``  edits of the running board in place (gol_engine_paste) and the RLE pattern codec
@@ -14,7 +15,7 @@
 Everything runs through libgolhip.so (hipcc, gfx950); there is no CPU fallback.
 """
 from ._lib import (GolError, device_count, format_rle, format_rule, halo_plan, lib, parse_rle, parse_rule,  # noqa: F401
-                   step_plan, view_plan)
+                   step_plan, strip_plan, view_plan)
 from .broker import Operations  # noqa: F401
 from .engine import Engine, next_state_slab, partition_rows  # noqa: F401
 from .pgm import read_pgm, write_pgm_bytes  # noqa: F401

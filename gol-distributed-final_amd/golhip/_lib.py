@@ -42,6 +42,11 @@ GOL_LAUNCH_MAIN, GOL_LAUNCH_EDGE = 0, 1
 VIEW_LAYOUTS = {0: "bytes", 1: "standard", 2: "band"}  # *src_layout of the view calls
 GOL_RULE_GENERIC = 1  # gol_engine_set_rule flag: B3/S23 on the rule kernels too
 GOL_PASTE_COPY, GOL_PASTE_OR, GOL_PASTE_XOR, GOL_PASTE_ANDNOT = 0, 1, 2, 3
+GOL_STRIP_KERNEL_BAND, GOL_STRIP_KERNEL_BYTES = 0, 1
+STRIP_KERNELS = {"band": GOL_STRIP_KERNEL_BAND, "bytes": GOL_STRIP_KERNEL_BYTES}
+# gol_strip_info.mode (GOL_STRIPS_*)
+STRIP_MODES = {0: "small", 1: "explicit", 2: "plain", 3: "round_tiled", 4: "tail", 5: "ranked_static",
+               6: "ranked_paired"}
 PASTE_OPS = {"copy": GOL_PASTE_COPY, "or": GOL_PASTE_OR, "xor": GOL_PASTE_XOR, "andnot": GOL_PASTE_ANDNOT}
 
 _NAMES = {
@@ -93,6 +98,15 @@ class gol_launch(ctypes.Structure):
 
 class gol_view_run(ctypes.Structure):
     _fields_ = [("row", ctypes.c_int64), ("rows", ctypes.c_int64), ("vrow", ctypes.c_int64)]
+
+
+class gol_strip_info(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("mode", "ngroups", "strip", "K", "RPB", "NS", "per_cu", "period",
+                                               "tail_first", "tail_row", "tail_strip", "reserved")]
+
+
+class gol_strip_rec(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("group", "s0", "s1", "dir", "claim", "s1e", "nclaim")]
 
 
 _i64 = ctypes.c_int64
@@ -152,6 +166,8 @@ SIGNATURES = [
     ("gol_halo_plan", ctypes.c_int, [_i64, _i32, _i32, _i32, _P(gol_halo_op), _i32, _P(_i32)]),
     ("gol_step_plan", ctypes.c_int, [_i64, _i32, _i32, _i32, _P(gol_launch), _i32, _P(_i32)]),
     ("gol_view_plan", ctypes.c_int, [_i64, _i32, _i32, _i64, _i64, _P(gol_view_run), _i32, _P(_i32)]),
+    ("gol_strip_plan", ctypes.c_int,
+     [_i32, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _P(gol_strip_info), _vp, _i64, _P(_i64)]),
     ("gol_dev_bits_step", ctypes.c_int,
      [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _vp, _vp]),
     ("gol_dev_random_fill", ctypes.c_int, [_vp, _i64, _i64, _i64, _i64, _u64, _vp]),
@@ -164,6 +180,11 @@ SIGNATURES = [
      [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _vp, _vp]),
     ("gol_dev_band_step", ctypes.c_int,
      [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _vp, _vp]),
+    ("gol_dev_band_step_on", ctypes.c_int,
+     [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _i32, _i32]),
+    ("gol_dev_bytes_step_k_on", ctypes.c_int,
+     [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _vp, _vp, _i32, _i32]),
+    ("gol_dev_pipe_limits", ctypes.c_int, [_i32, _i32, _i32, _P(_i32), _P(_i32)]),
     ("gol_dev_rule_step", ctypes.c_int,
      [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i32, _i32, ctypes.c_uint32, ctypes.c_uint32, _i32, _i32, _vp,
       _vp]),
@@ -255,6 +276,38 @@ def view_plan(H: int, nranks: int, rank: int, y0: int, vrows: int) -> list[tuple
     n = ctypes.c_int32()
     check(lib().gol_view_plan(H, nranks, rank, y0, vrows, runs, 2, ctypes.byref(n)))
     return [(r.row, r.rows, r.vrow) for r in runs[:n.value]]
+
+
+def strip_plan(kernel: str, rows: int, row0: int, width: int, pitch: int, cus: int, slots: int, strip_rows: int = 0,
+               k: int | None = None, records: bool = True):
+    """gol_strip_plan: the schedule of a pipelined launch (kernel "band": k = 12, width and pitch in
+    words; "bytes": k = 32, in cells and bytes) on a device of `cus` CUs holding `slots` resident
+    workgroups, as (info, recs): info a dict of gol_strip_info with the mode by name and the
+    workgroup count `nwg`, recs a numpy record array (group, s0, s1, dir, claim, s1e, nclaim), one
+    record per workgroup id (None with records=False).  Host code: no GPU needed."""
+    import numpy as np
+    kid = STRIP_KERNELS[kernel]
+    k = (12 if kernel == "band" else 32) if k is None else k
+    info = gol_strip_info()
+    n = ctypes.c_int64()
+    check(lib().gol_strip_plan(kid, rows, row0, width, pitch, k, strip_rows, cus, slots, ctypes.byref(info), None, 0,
+                               ctypes.byref(n)))
+    recs = None
+    if records:
+        recs = np.zeros(n.value, dtype=np.dtype([(f, "<i4") for f, _ in gol_strip_rec._fields_]))
+        check(lib().gol_strip_plan(kid, rows, row0, width, pitch, k, strip_rows, cus, slots, ctypes.byref(info),
+                                   recs.ctypes.data, n.value, ctypes.byref(n)))
+    d = {f: getattr(info, f) for f, _ in gol_strip_info._fields_ if f != "reserved"}
+    d["mode"] = STRIP_MODES[info.mode]
+    d["nwg"] = int(n.value)
+    return d, recs
+
+
+def pipe_limits(kernel: str, contiguous: bool = True, counted: bool = False) -> tuple[int, int]:
+    """gol_dev_pipe_limits: (CUs, resident workgroups of the pipeline kernel) of the current device."""
+    c, n = ctypes.c_int32(), ctypes.c_int32()
+    check(lib().gol_dev_pipe_limits(STRIP_KERNELS[kernel], int(contiguous), int(counted), ctypes.byref(c), ctypes.byref(n)))
+    return c.value, n.value
 
 
 def _lib_check(L, rc: int) -> None:

@@ -488,6 +488,72 @@ typedef struct gol_view_run {
 } gol_view_run;
 int gol_view_plan(int64_t H, int32_t nranks, int32_t rank, int64_t y0, int64_t vrows, gol_view_run *runs, int32_t cap,
                   int32_t *n);
+/* gol_strip_plan: which workgroup of a pipelined launch computes which output
+ * rows.  The two pipeline kernels (k = 12 of gol_dev_band_step at 128 cells per
+ * lane, k = 32 of gol_dev_bytes_step_k) run one workgroup per (column group,
+ * range of rows), and the launch code picks one of several schedules from the
+ * launch's shape and two device properties: the CU count `cus` and `slots`, the
+ * workgroups of the kernel resident on the whole device at once.  This is that
+ * choice and its outcome as data, from the functions the launchers and the
+ * kernels themselves run (csrc/gol_strips.h); no GPU needed.  (Added without a
+ * version bump: GOL_ABI_VERSION stays 6; probe for gol_strip_plan,
+ * gol_dev_band_step_on and gol_dev_bytes_step_k_on by symbol.)
+ * Arguments as the kernel's launcher takes them: `width` and `pitch` are Wd and
+ * pitch in words (band), W in cells and stride in bytes (bytes); rows
+ * [row0, row0 + rows) are written; strip_rows > 0 asks for strips of that
+ * length.  k must be the pipeline's (12 / 32); cus >= 0, slots >= 0.
+ * The modes:
+ *  - SMALL: ~512 tiles of >= 2 rows on a latency-bound board (band only);
+ *  - EXPLICIT: strip_rows > 0;
+ *  - PLAIN: strips of the default length, a launch of many rounds with no tail;
+ *  - ROUND_TILED: at most 4 rounds of workgroups, the strip count a multiple of
+ *    a round;
+ *  - TAIL: strips, the last round of workgroups on shorter ones from row
+ *    tail_row on (band only);
+ *  - RANKED_STATIC: one round of cus x per_cu workgroups; a CU takes `period`
+ *    rows of one column group and splits them over its workgroups by arrival
+ *    rank;
+ *  - RANKED_PAIRED: as RANKED_STATIC, with pairs of workgroups that walk one
+ *    range from both ends and claim blocks of RPB rows, NS blocks at a time,
+ *    from a counter of the pair until nclaim blocks are claimed.  A walker that
+ *    claimed n blocks stores RPB*n - 2K rows: from s0 down (dir +1), from s1e
+ *    up (dir -1), clipped to [s0, s1).
+ * Record l is workgroup id l: column group, rows [s0, s1) (s0 >= s1: the
+ * workgroup has no rows and leaves at once), dir 0 (a strip of its own) or +1 /
+ * -1 (a pair's walkers), claim = index of the pair's counter (-1 without),
+ * s1e, nclaim (dir 0: s1e = s1).  Writes min(*n, cap) records; recs may be NULL
+ * with cap 0 (the two-call form). */
+#define GOL_STRIP_KERNEL_BAND 0
+#define GOL_STRIP_KERNEL_BYTES 1
+#define GOL_STRIPS_SMALL 0
+#define GOL_STRIPS_EXPLICIT 1
+#define GOL_STRIPS_PLAIN 2
+#define GOL_STRIPS_ROUND_TILED 3
+#define GOL_STRIPS_TAIL 4
+#define GOL_STRIPS_RANKED_STATIC 5
+#define GOL_STRIPS_RANKED_PAIRED 6
+typedef struct gol_strip_info {
+    int32_t mode;       /* GOL_STRIPS_* */
+    int32_t ngroups;    /* column groups */
+    int32_t strip;      /* rows per strip (ranked modes: unused) */
+    int32_t K, RPB, NS; /* the kernel's turns, rows per block, blocks per claim */
+    int32_t per_cu;     /* ranked modes: workgroups per CU, */
+    int32_t period;     /*   rows of a column group per CU */
+    int32_t tail_first; /* TAIL: first workgroup id of the tail, */
+    int32_t tail_row;   /*   its first row (relative to row0), */
+    int32_t tail_strip; /*   its rows per strip */
+    int32_t reserved;
+} gol_strip_info;
+typedef struct gol_strip_rec {
+    int32_t group;
+    int32_t s0, s1;
+    int32_t dir;
+    int32_t claim;
+    int32_t s1e, nclaim;
+} gol_strip_rec;
+int gol_strip_plan(int32_t kernel, int64_t rows, int64_t row0, int64_t width, int64_t pitch, int32_t k,
+                   int32_t strip_rows, int32_t cus, int32_t slots, gol_strip_info *info, gol_strip_rec *recs,
+                   int64_t cap, int64_t *n);
 
 /* ---------------------------------------------------------------- device launchers
  * Asynchronous kernel launches on caller-owned device memory and a caller
@@ -551,6 +617,26 @@ int gol_dev_bytes_step_k(const uint8_t *top, const uint8_t *mid, const uint8_t *
 int gol_dev_band_step(const uint32_t *top, const uint32_t *mid, const uint32_t *bot, uint32_t *dst,
                       int64_t R, int64_t Wd, int64_t pitch, int64_t row0, int64_t rows, int32_t k,
                       int32_t cells_per_lane, int32_t strip_rows, uint64_t *count_slots, void *stream);
+/* gol_dev_band_step / gol_dev_bytes_step_k with the launch scheduled as for a
+ * device of `cus` CUs holding `slots` resident workgroups of the kernel
+ * (gol_strip_plan with the same arguments is the schedule it runs); 0, 0 = this
+ * device, the plain call.  GOL_EINVAL unless cus % 8 == 0, cus <= the device's
+ * CU count, slots <= the device's resident count for the kernel, and k is the
+ * pipelined one (12 at 128 cells per lane / 32).  Per-call arguments: no
+ * process-wide state.  Paired workgroups never wait for each other, so a
+ * pretended device computes the same rows whatever else is resident.
+ * gol_dev_pipe_limits reports the current device's two values for the kernel
+ * (GOL_STRIP_KERNEL_*) as a launch with contiguous ghost rows (band: top + k
+ * rows == mid and bot == mid + R rows; the byte kernel has one form) and with
+ * count_slots (`counted`) runs it.  No version bump: probe by symbol. */
+int gol_dev_band_step_on(const uint32_t *top, const uint32_t *mid, const uint32_t *bot, uint32_t *dst,
+                         int64_t R, int64_t Wd, int64_t pitch, int64_t row0, int64_t rows, int32_t k,
+                         int32_t cells_per_lane, int32_t strip_rows, uint64_t *count_slots, void *stream,
+                         int32_t cus, int32_t slots);
+int gol_dev_bytes_step_k_on(const uint8_t *top, const uint8_t *mid, const uint8_t *bot, uint8_t *dst, int64_t R,
+                            int64_t W, int64_t stride, int64_t row0, int64_t rows, int32_t k, int32_t strip_rows,
+                            uint64_t *count_slots, void *stream, int32_t cus, int32_t slots);
+int gol_dev_pipe_limits(int32_t kernel, int32_t contiguous, int32_t counted, int32_t *cus, int32_t *slots);
 /* k turns (1, 2, 4 or 8) of a life-like rule (birth / survive: 9-bit masks, see
  * "life-like rules") on a bit board in the standard (GOL_LAYOUT_STANDARD) or
  * the band (GOL_LAYOUT_BAND) layout; row addressing and count_slots as
