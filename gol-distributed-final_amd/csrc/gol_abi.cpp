@@ -1,6 +1,6 @@
 // gol_abi.cpp -- C ABI of libgolhip.so: library entry points, the worker's slab
 // step, the row partition and the device launchers (include/golhip.h).  The
-// board engine (one GPU or row shards) is gol_engine.cpp.
+// board engine (one GPU or row shards) is gol_engine.cpp and the files it names.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -9,9 +9,7 @@
 #include <string>
 #include <vector>
 
-#include "golhip.h"
-#include "gol_internal.h"
-#include "gol_kernels.h"
+#include "gol_engine_int.h"
 #include "gol_rule.h"
 
 // ------------------------------------------------------------------ errors
@@ -27,14 +25,6 @@ int gol_set_error(int code, const char *fmt, ...)
     g_err = buf;
     return code;
 }
-
-#define HIPCHK(expr)                                                                              \
-    do {                                                                                          \
-        hipError_t e_ = (expr);                                                                   \
-        if (e_ != hipSuccess)                                                                     \
-            return gol_set_error(GOL_EHIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), \
-                                 __FILE__, __LINE__);                                             \
-    } while (0)
 
 extern "C" int gol_abi_version(void) { return GOL_ABI_VERSION; }
 extern "C" const char *gol_last_error(void) { return g_err.c_str(); }

@@ -2,7 +2,7 @@
 //
 // gol_engine_create_rank builds one of two transports (include/golhip.h):
 //  * RCCL (production, one process per GPU): the halo rows travel by ncclSend/ncclRecv in
-//    gol_engine.cpp's exchange(), the collectives below are ncclAllReduce on the shard's stream;
+//    gol_exchange.cpp's exchange(), the collectives below are ncclAllReduce on the shard's stream;
 //  * IPC (ranks of one node, possibly sharing a GPU): each rank maps its ring neighbours' two
 //    bit buffers and their flag words through HIP IPC handles and pulls its ghost rows out of
 //    their HBM; the collectives run on the host through a POSIX shared-memory segment.
@@ -33,7 +33,7 @@ gol_comm *gol_comm_rccl(ncclComm_t c);
 // READY = the last exchange whose send rows this rank has written into its send buffer (its
 // peers may pull them).  A sequence number, compared wrap-safe.  (Until round 5 a PULLED word
 // also ordered board writes behind the peers' pulls; since the peers read only the send buffer,
-// that order is implied by READY, gol_engine.cpp exchange_ipc.)
+// that order is implied by READY, gol_exchange.cpp exchange_ipc.)
 enum { GOL_IPC_READY = 0, GOL_IPC_FLAG_WORDS = 16 };
 
 struct gol_ipc_seg;

@@ -22,7 +22,7 @@ class gol_ipc;
 #define GOL_DEFAULT_DW 2       // standard layout: 64 cells per lane
 
 // A step whose launch runs more rounds of workgroups than this overlaps its edge launches with
-// the interior (GOL_STEP_OVERLAP), else it runs as one launch (gol_engine.cpp step_mode).
+// the interior (GOL_STEP_OVERLAP), else it runs as one launch (gol_step.cpp step_mode).
 #define GOL_OVERLAP_ROUNDS 4.0
 
 // Ghost rows kept above and below each bit buffer: the halo (received from the neighbouring
@@ -35,7 +35,7 @@ class gol_ipc;
 #define GOL_HOST_WORDS 16
 
 // Timing events per shard before the recorded steps are folded into running sums (at the start
-// of a timed stepping call; within one call the pool grows instead, gol_engine.cpp timing_event).
+// of a timed stepping call; within one call the pool grows instead, gol_timing.cpp timing_event).
 #define GOL_TIMING_EVENTS 512
 
 // One row shard: rows [y0, y1) of the board on one GPU.
@@ -145,5 +145,9 @@ struct gol_engine {
 };
 
 int gol_set_error(int code, const char *fmt, ...);
+// gol_plan.cpp: the index in `theirs` (the plan of mine[j].peer) of the send that pairs with my
+// receive mine[j], or -1 with the error set.
+__attribute__((visibility("hidden"))) int gol_halo_match(const gol_halo_op *mine, int j, const gol_halo_op *theirs,
+                                                         int n_theirs, int my_rank);
 // Enqueue `turns` turns on the shards' streams without synchronising.
 int gol_engine_step_async(gol_engine *e, int64_t turns);

@@ -4,7 +4,7 @@
 // (broker.go:135-206, 143-157).  The sharded engine applies the same partition once and, per
 // k-turn step, exchanges kx halo rows with the ring neighbours.  What a shard sends and
 // receives (gol_halo_plan) and which launches make up a step (gol_step_plan) are computed
-// here, in plain host code: the engine (gol_engine.cpp exchange() / launch_k()) executes
+// here, in plain host code: the engine (gol_exchange.cpp exchange(), gol_step.cpp launch_k()) executes
 // exactly these plans, and so does the Python mirror (golhip.sharded) that the multi-process
 // gloo tests drive on the CPU, so both run one schedule.
 #include <stdint.h>
@@ -41,6 +41,23 @@ extern "C" int gol_halo_plan(int64_t H, int32_t nranks, int32_t rank, int32_t k,
     for (int i = 0; i < 4 && i < cap; ++i) ops[i] = plan[i];
     *n = 4;
     return GOL_OK;
+}
+
+// The matching rule above, for a transport that pairs the operations itself (gol_exchange.cpp: the
+// device copies of LOCAL / LOOPBACK, the IPC pulls): receive mine[j] is my n-th from its peer, so it
+// meets the n-th send to my_rank in `theirs`, that peer's plan.  Returns the send's index there;
+// -1 (error set) when there is none or it carries other rows.
+int gol_halo_match(const gol_halo_op *mine, int j, const gol_halo_op *theirs, int n_theirs, int my_rank)
+{
+    int nth = 0;
+    for (int jj = 0; jj < j; ++jj) nth += mine[jj].kind == GOL_HALO_RECV && mine[jj].peer == mine[j].peer;
+    for (int m = 0, cnt = 0; m < n_theirs; ++m)
+        if (theirs[m].kind == GOL_HALO_SEND && theirs[m].peer == my_rank && cnt++ == nth) {
+            if (theirs[m].rows == mine[j].rows) return m;
+            break;
+        }
+    (void)gol_set_error(GOL_EINVAL, "halo plan: unmatched receive");
+    return -1;
 }
 
 extern "C" int gol_step_plan(int64_t R, int32_t k, int32_t kx, int32_t flags, gol_launch *out, int32_t cap,

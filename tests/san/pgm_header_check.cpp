@@ -1,13 +1,31 @@
-// Differential / sanitizer driver for the native PGM header parser (gol_engine.cpp,
-// parse_pgm_header: gol/io.go:97-117 rules).  Built only by `make -C gol-distributed-final_amd/csrc
-// asan` with AddressSanitizer + UndefinedBehaviorSanitizer (host code; no GPU call is made) and run
-// by tests/test_sanitizers_cpu.py, which compares every verdict with golhip.pgm.pgm_header.
+// Differential / sanitizer driver for the native PGM header parser (gol_pgm.cpp,
+// gol_pgm_parse_header: gol/io.go:97-117 rules).  A stand-alone program: built only by
+// `make -C gol-distributed-final_amd/csrc asan` from this file and gol_pgm.cpp with AddressSanitizer +
+// UndefinedBehaviorSanitizer, linked without the GPU runtime, and run by
+// tests/test_sanitizers_cpu.py, which compares every verdict with golhip.pgm.pgm_header.
 //
 // stdin: records of  int64 W, int64 H, uint32 n, n header bytes.
 // stdout: one line per record: "<rc> <offset>" (offset -1 on error).
-#include "../../gol-distributed-final_amd/csrc/gol_engine.cpp"
+#include <stdarg.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <string.h>
 
-#include <cstdio>
+#include <vector>
+
+#include "golhip.h"
+
+int gol_pgm_parse_header(const uint8_t *h, size_t n, int64_t W, int64_t H, int64_t *off);
+
+static char g_msg[512];
+int gol_set_error(int code, const char *fmt, ...)
+{
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_msg, sizeof g_msg, fmt, ap);
+    va_end(ap);
+    return code;
+}
 
 int main()
 {
@@ -21,7 +39,7 @@ int main()
         uint8_t *h = new uint8_t[n ? n : 1];
         memcpy(h, buf.data(), n);
         int64_t off = -1;
-        const int rc = parse_pgm_header(h, n, wh[0], wh[1], &off);
+        const int rc = gol_pgm_parse_header(h, n, wh[0], wh[1], &off);
         delete[] h;
         printf("%d %lld\n", rc, (long long)(rc == GOL_OK ? off : -1));
     }

@@ -228,6 +228,45 @@ def test_load_pgm_fields_rules(G, tmp_path):
             e.load_pgm(str(p))
 
 
+def test_uneven_shards_exact_rows_from_pgm(G, tmp_path):
+    """A 7 x 64 board from a PGM file over 3 uneven shards (the 2-row shards cap k) with a byte 7 in
+    the last row of shard 0 and in row 0 of shard 2, so the rows kept for the exact first turn cross
+    a shard boundary and the torus wrap.  Before turn 1 every query reads each shard's kept bytes
+    from its own row 0 (not from the halo row stored above it); turn 1 is the literal oracle's
+    (worker.go:15-42); a whitespace byte in one shard's rows fails the load for all."""
+    H, W = 7, 64
+    rng = np.random.default_rng(12)
+    board = (rng.random((H, W)) < 0.4).astype(np.uint8) * 255
+    p = tmp_path / "b.pgm"
+    with _sharded(G, H, W, 3) as e:
+        rows = [(e.shard(i)["y0"], e.shard(i)["y1"]) for i in range(3)]
+        assert sorted(b - a for a, b in rows) == [2, 2, 3] and e.info()["turns_per_launch"] <= 2
+        board[rows[0][1] - 1, 10] = 7
+        board[rows[2][0], 20] = 7
+        p.write_bytes(O.pgm_bytes(board))
+        nxt = O.next_state_slab(board, 0, H)
+        e.load_pgm(str(p))
+        assert np.array_equal(e.store_bytes(), board)
+        assert np.array_equal(e.view_counts(0, 0, 1, W, H), (board != 0).astype(np.uint32))
+        assert np.array_equal(e.view_counts(60, 5, 2, 4, 2),  # wraps in x, and from the last shard to the first
+                              np.roll(board != 0, (-5, -60), (0, 1))[:4, :8].reshape(2, 2, 4, 2).sum(axis=(1, 3)))
+        assert [tuple(c) for c in e.alive_cells().tolist()] == O.alive_cells(board)
+        assert e.alive_count() == int(np.count_nonzero(board))
+        assert e.hash() == O.hash_words(O.pack(np.where(board == 255, 255, 0).astype(np.uint8)))
+        e.step(1)
+        assert np.array_equal(e.store_bytes(), nxt)
+        e.step(5)
+        assert np.array_equal(e.store_bytes(), O.run(board, 6))
+        e.load_pgm(str(p))  # the same first turn as a list of flips
+        assert [tuple(c) for c in e.step_flips().tolist()] == O.flipped_cells(board, nxt)
+        assert np.array_equal(e.store_bytes(), nxt)
+        ws = board.copy()
+        ws[rows[1][0], 3] = 32
+        p.write_bytes(O.pgm_bytes(ws))
+        with pytest.raises(G.GolError, match="whitespace"):
+            e.load_pgm(str(p))
+
+
 def test_rccl_transport_self(G):
     """The RCCL halo path on one GPU: one shard whose ncclSend/ncclRecv go to itself (the torus
     wrap), in-process (ncclCommInitAll) and as a one-rank Engine.rank (ncclCommInitRank)."""

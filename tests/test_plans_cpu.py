@@ -66,7 +66,7 @@ def test_halo_plan_fills_every_ghost_row(G, n, H, k):
 
 def test_halo_plan_two_ranks_same_peer_order(G):
     """nranks = 2: both neighbours are one peer; the issue order is what pairs the top rows
-    with the peer's bottom ghost rows (gol_engine.cpp exchange(), ncclSend/ncclRecv)."""
+    with the peer's bottom ghost rows (gol_exchange.cpp exchange(), ncclSend/ncclRecv)."""
     plan = G.halo_plan(64, 2, 0, 12)
     assert plan == [("send", 1, 0, 12), ("recv", 1, 32, 12), ("send", 1, 20, 12), ("recv", 1, -12, 12)]
     assert G.halo_plan(64, 1, 0, 4) == [("send", 0, 0, 4), ("recv", 0, 64, 4), ("send", 0, 60, 4), ("recv", 0, -4, 4)]

@@ -2,13 +2,14 @@
 race/sanitizer checks; the build runs its host code under ASan/UBSan here, CPU only -- GPU
 sanitizers are not available).
 
-`make -C gol-distributed-final_amd/csrc asan` (run by __graft_entry__.build()) instruments
-gol_abi.cpp, gol_engine.cpp and gol_host.cpp:
+`make -C gol-distributed-final_amd/csrc asan` (run by __graft_entry__.build()) instruments the
+host sources (gol_abi.cpp, the engine's files from gol_engine.cpp to gol_pgm.cpp, gol_host.cpp, ...):
   * golhip/libgolhip_asan.so -- the C ABI with instrumented host code, driven here through ctypes in
     a child Python with the clang ASan runtime preloaded: every entry point that runs without a GPU
     (partition, argument and state errors, the worker's and broker's request checks, engine
     creation failing cleanly);
-  * build/asan/pgm_header_check -- the native P5 header parser (io.go:97-117 rules) on random and
+  * build/asan/pgm_header_check -- the native P5 header parser (gol_pgm.cpp alone, a stand-alone
+    program without the GPU runtime; io.go:97-117 rules) on random and
     mutated headers, each verdict compared with golhip.pgm.pgm_header (differential).
 Any sanitizer report fails the test (UBSan without recovery, ASan aborts).
 """
