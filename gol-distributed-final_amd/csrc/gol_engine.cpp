@@ -77,6 +77,8 @@ static void shard_release(gol_shard &s)
     if (s.view_host) (void)hipHostFree(s.view_host);
     if (s.edit_dev) (void)hipFree(s.edit_dev);
     if (s.edit_host) (void)hipHostFree(s.edit_host);
+    if (s.read_dev) (void)hipFree(s.read_dev);
+    if (s.read_host) (void)hipHostFree(s.read_host);
     for (auto ev : s.tev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : {s.ev_start, s.ev_edge, s.ev_halo})
         if (ev) (void)hipEventDestroy(ev);

@@ -245,6 +245,26 @@ struct Operations {
         return gol_engine_paste(eng, x0, y0, w, h, pattern, stride, op, changed, nullptr);
     }
 
+    // The region reads of the resident board (gol_engine_copy, gol_engine_bounds), between the chunks
+    // of a Run like View: they see the board after turn cTurn; a cut lands there as a Paste does.
+    int Copy(int64_t x0, int64_t y0, int64_t w, int64_t h, uint64_t *pattern, int64_t stride, int32_t flags, int64_t *alive,
+             int64_t *turns_completed)
+    {
+        Access acc(*this);
+        if (!have_world) return gol_set_error(GOL_ESTATE, "no board: Operations.Run has not been called");
+        if (turns_completed) *turns_completed = cTurn;
+        return gol_engine_copy(eng, x0, y0, w, h, pattern, stride, flags, alive, nullptr);
+    }
+
+    int Bounds(int64_t x0, int64_t y0, int64_t w, int64_t h, int64_t *bx, int64_t *by, int64_t *bw, int64_t *bh,
+               int64_t *alive, int64_t *turns_completed)
+    {
+        Access acc(*this);
+        if (!have_world) return gol_set_error(GOL_ESTATE, "no board: Operations.Run has not been called");
+        if (turns_completed) *turns_completed = cTurn;
+        return gol_engine_bounds(eng, x0, y0, w, h, bx, by, bw, bh, alive, nullptr);
+    }
+
     int Pause()  // broker.go:251-254
     {
         Access acc(*this);
@@ -371,6 +391,20 @@ extern "C" int gol_broker_paste(gol_broker *b, int64_t x0, int64_t y0, int64_t w
 {
     if (!b) return gol_set_error(GOL_EINVAL, "NULL argument");
     return b->ops.Paste(x0, y0, w, h, pattern, stride, op, changed, turns_completed);
+}
+
+extern "C" int gol_broker_copy(gol_broker *b, int64_t x0, int64_t y0, int64_t w, int64_t h, uint64_t *pattern,
+                               int64_t stride, int32_t flags, int64_t *alive, int64_t *turns_completed)
+{
+    if (!b) return gol_set_error(GOL_EINVAL, "NULL argument");
+    return b->ops.Copy(x0, y0, w, h, pattern, stride, flags, alive, turns_completed);
+}
+
+extern "C" int gol_broker_bounds(gol_broker *b, int64_t x0, int64_t y0, int64_t w, int64_t h, int64_t *bx, int64_t *by,
+                                 int64_t *bw, int64_t *bh, int64_t *alive, int64_t *turns_completed)
+{
+    if (!b) return gol_set_error(GOL_EINVAL, "NULL argument");
+    return b->ops.Bounds(x0, y0, w, h, bx, by, bw, bh, alive, turns_completed);
 }
 
 extern "C" int gol_worker_update(const gol_request *req, gol_response *res)

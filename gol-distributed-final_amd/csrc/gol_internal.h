@@ -75,6 +75,12 @@ struct gol_shard {
     uint64_t *edit_dev = nullptr;     // device
     uint64_t *edit_host = nullptr;    // pinned host: the staged pattern rows, the counter's readback
     int64_t edit_cap = 0;
+    // region reads (gol_engine_copy, _bounds): 8 header words (READ_HDR of gol_frames.cpp: the alive
+    // counter, the bounds' row and column extremes), then read_cap words (the staged pattern rows; the
+    // bounds' column occupancy); grown on demand
+    uint64_t *read_dev = nullptr;     // device
+    uint64_t *read_host = nullptr;    // pinned host copy
+    int64_t read_cap = 0;
     ncclComm_t nccl = nullptr;
     // timing (gol_engine_set_timing): events on `stream` around the timed launches
     std::vector<hipEvent_t> tev;

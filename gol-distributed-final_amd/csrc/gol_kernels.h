@@ -121,6 +121,25 @@ hipError_t golk_paste(int form, void *dst, int64_t pitch, int64_t W, int64_t x0,
                       int64_t prow, const uint64_t *pattern, int64_t pstride, int32_t op, uint64_t *changed,
                       hipStream_t s);
 
+// Region reads (gol_copy.hip; form, src, pitch, W, x0, w, row, rows as golk_paste; nothing is written
+// to the board).  golk_copy gathers the rectangle's cells of rows [row, row + rows) into pattern rows
+// [prow, prow + rows) (pstride uint64 words per row, bit c % 64 of word c / 64 = cell c): it writes
+// every 32-bit half that holds a cell c < w, bits at c >= w zero, and no other half -- the caller
+// clears the pattern first -- and adds the alive cells gathered to *alive (a device counter).
+hipError_t golk_copy(int form, const void *src, int64_t pitch, int64_t W, int64_t x0, int64_t w, int64_t row, int64_t rows,
+                     int64_t prow, uint64_t *pattern, int64_t pstride, uint64_t *alive, hipStream_t s);
+// The bounding box of the rectangle's alive cells in two passes.  hdr: 5 device words, zeroed by
+// the caller: [0] += alive cells, [1] = max of ~r and [2] = max of r over the rows r (rows of the
+// rectangle: vrow + the row's offset from `row`) that hold one, [3] = max of ~c and [4] = max of c
+// over the rectangle's columns that hold one.  golk_bounds_rows (once per run of rows) fills [0 .. 2]
+// and ORs the columns seen into occ, golk_bounds_lanes(..) zeroed uint32 words; golk_bounds_cols
+// (once, after them, with the same form, src and pitch) turns occ into [3] and [4].
+hipError_t golk_bounds_rows(int form, const void *src, int64_t pitch, int64_t W, int64_t x0, int64_t w, int64_t row,
+                            int64_t rows, int64_t vrow, uint32_t *occ, uint64_t *hdr, hipStream_t s);
+int64_t golk_bounds_lanes(int form, const void *src, int64_t pitch, int64_t W, int64_t x0, int64_t w);
+hipError_t golk_bounds_cols(int form, const void *src, int64_t pitch, int64_t W, int64_t x0, int64_t w, const uint32_t *occ,
+                            uint64_t *hdr, hipStream_t s);
+
 // IPC transport (gol_comm.h): set *flag = value with release ordering at system scope after the
 // stream's earlier work; wait (one wave on the stream) until every flags[i] (i < n <= 4, other
 // processes' flag words mapped through IPC) has reached `want` (wrap-safe sequence compare),

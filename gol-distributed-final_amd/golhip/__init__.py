@@ -9,6 +9,7 @@
 * ``Engine.view`` / ``Operations.view``  viewport frames of the running board (gol_engine_view; ``view_plan``)
 * ``Engine(rule=)`` / ``Engine.set_rule`` / ``parse_rule`` / ``format_rule``  life-like rules (B/S masks, gol_engine_set_rule)
 * ``Engine.paste`` / ``Engine.fill`` / ``Operations.paste`` / ``parse_rle`` / ``format_rle``  edits of the running board in place (gol_engine_paste) and the RLE pattern codec
+* ``Engine.copy`` / ``Engine.cut`` / ``Engine.bounds`` / ``Engine.to_rle`` / ``Operations.copy`` / ``Operations.bounds``  exact reads of a region of the running board in place (gol_engine_copy, gol_engine_bounds)
 * ``distributor``          controller mirror (gol/gol.go + gol/distributor.go) over the broker API
 * ``next_state_slab`` / ``partition_rows``  worker.go:15-70 / broker.go:135-206
 

@@ -47,6 +47,7 @@ STRIP_KERNELS = {"band": GOL_STRIP_KERNEL_BAND, "bytes": GOL_STRIP_KERNEL_BYTES}
 # gol_strip_info.mode (GOL_STRIPS_*)
 STRIP_MODES = {0: "small", 1: "explicit", 2: "plain", 3: "round_tiled", 4: "tail", 5: "ranked_static",
                6: "ranked_paired"}
+GOL_COPY_CUT = 1  # flags of gol_engine_copy / gol_broker_copy
 PASTE_OPS = {"copy": GOL_PASTE_COPY, "or": GOL_PASTE_OR, "xor": GOL_PASTE_XOR, "andnot": GOL_PASTE_ANDNOT}
 
 _NAMES = {
@@ -161,6 +162,10 @@ SIGNATURES = [
     ("gol_engine_rule", ctypes.c_int, [_vp, _P(ctypes.c_uint32), _P(ctypes.c_uint32), _P(_i32)]),
     ("gol_engine_paste", ctypes.c_int, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _i32, _P(_i64), _P(_i32)]),
     ("gol_paste_host", ctypes.c_int, [_i32, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _i64, _i32, _P(_i64)]),
+    ("gol_engine_copy", ctypes.c_int, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _i32, _P(_i64), _P(_i32)]),
+    ("gol_engine_bounds", ctypes.c_int, [_vp, _i64, _i64, _i64, _i64, _P(_i64), _P(_i64), _P(_i64), _P(_i64), _P(_i64), _P(_i32)]),
+    ("gol_copy_host", ctypes.c_int, [_i32, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _i64, _P(_i64)]),
+    ("gol_bounds_host", ctypes.c_int, [_i32, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _P(_i64), _P(_i64), _P(_i64), _P(_i64), _P(_i64)]),
     ("gol_rle_parse", ctypes.c_int, [ctypes.c_char_p, _i64, _P(_i64), _P(_i64), _vp, _i64, _i64, ctypes.c_char_p, _i64]),
     ("gol_rle_format", ctypes.c_int, [_vp, _i64, _i64, _i64, ctypes.c_char_p, ctypes.c_char_p, _i64, _P(_i64)]),
     ("gol_halo_plan", ctypes.c_int, [_i64, _i32, _i32, _i32, _P(gol_halo_op), _i32, _P(_i32)]),
@@ -201,6 +206,8 @@ SIGNATURES = [
     ("gol_broker_paused", ctypes.c_int, [_vp, _P(_i32)]),
     ("gol_broker_view", ctypes.c_int, [_vp, _i64, _i64, _i32, _i32, _i32, _vp, _i64, _P(_i64), _P(_i32)]),
     ("gol_broker_paste", ctypes.c_int, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _i32, _P(_i64), _P(_i64)]),
+    ("gol_broker_copy", ctypes.c_int, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _i32, _P(_i64), _P(_i64)]),
+    ("gol_broker_bounds", ctypes.c_int, [_vp, _i64, _i64, _i64, _i64, _P(_i64), _P(_i64), _P(_i64), _P(_i64), _P(_i64), _P(_i64)]),
     ("gol_worker_update", ctypes.c_int, [_P(gol_request), _P(gol_response)]),
 ]
 
@@ -374,10 +381,17 @@ def format_rle(cells, rule=None, library=None) -> str:
     """gol_rle_format: a 2-D array of cells (non-zero = alive) as RLE text, with `rule` in the
     header when given; lines of at most 70 characters, ending in "!\\n"."""
     import numpy as np
-    L = library or lib()
     cells = np.asarray(cells)
-    words = pack_pattern(cells)
-    h, w = cells.shape
+    return format_rle_words(pack_pattern(cells), cells.shape[1], rule, library)
+
+
+def format_rle_words(words, w: int, rule=None, library=None) -> str:
+    """format_rle of a pattern that is already bit-packed: (h, >= ceil(w / 64)) uint64 rows as
+    pack_pattern and Engine.copy_words give them."""
+    import numpy as np
+    L = library or lib()
+    words = np.ascontiguousarray(words, dtype=np.uint64)
+    h = words.shape[0]
     r = None if rule is None else str(rule).encode()
     need = ctypes.c_int64()
     _lib_check(L, L.gol_rle_format(words.ctypes.data, words.shape[1], w, h, r, None, 0, ctypes.byref(need)))

@@ -11,8 +11,8 @@ import ctypes
 
 import numpy as np
 
-from ._lib import (GOL_EINVAL, LAYOUTS, PASTE_OPS, TRANSPORTS, VIEW_LAYOUTS, GolError, check, gol_config, gol_request,
-                   gol_response, lib, pack_pattern, parse_rle)
+from ._lib import (GOL_COPY_CUT, GOL_EINVAL, LAYOUTS, PASTE_OPS, TRANSPORTS, VIEW_LAYOUTS, GolError, check, gol_config, gol_request,
+                   gol_response, lib, pack_pattern, parse_rle, unpack_pattern)
 from .stubs import CellList, Request, Response
 
 
@@ -120,6 +120,28 @@ class Operations:
         check(lib().gol_broker_paste(self._h, x0, y0, w, h, None if words is None else words.ctypes.data, stride,
                                      PASTE_OPS[op], ctypes.byref(n), ctypes.byref(turns)))
         return n.value, turns.value
+
+    def copy(self, x0: int, y0: int, w: int, h: int, *, cut: bool = False):
+        """Engine.copy on the broker's board (gol_broker_copy; no reference counterpart), served
+        between the chunks of a running Run: ((h, w) bool cells, the turn they were read after).
+        cut=True clears the rectangle after reading it."""
+        if w < 1 or h < 1 or w * h > 1 << 26:
+            raise GolError(GOL_EINVAL, f"bad copy size {w} x {h} cells (at most 2^26)")
+        out = np.empty((h, (w + 63) // 64), dtype=np.uint64)
+        turns = ctypes.c_int64()
+        check(lib().gol_broker_copy(self._h, x0, y0, w, h, out.ctypes.data, out.shape[1], GOL_COPY_CUT if cut else 0, None,
+                                    ctypes.byref(turns)))
+        return unpack_pattern(out, w), turns.value
+
+    def cut(self, x0: int, y0: int, w: int, h: int):
+        """copy with cut=True."""
+        return self.copy(x0, y0, w, h, cut=True)
+
+    def bounds(self, x0: int, y0: int, w: int, h: int):
+        """Engine.bounds on the broker's board (gol_broker_bounds): ((bx, by, bw, bh, alive), turn)."""
+        v = [ctypes.c_int64() for _ in range(6)]
+        check(lib().gol_broker_bounds(self._h, x0, y0, w, h, *(ctypes.byref(x) for x in v)))
+        return tuple(x.value for x in v[:5]), v[5].value
 
     def Pause(self, req: Request | None = None) -> Response:  # broker.go:251-254
         check(lib().gol_broker_pause(self._h))

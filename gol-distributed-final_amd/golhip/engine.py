@@ -15,9 +15,10 @@ import ctypes
 
 import numpy as np
 
-from ._lib import (GOL_EINVAL, GOL_IPC_ID_BYTES, GOL_RCCL_ID_BYTES, GOL_RULE_GENERIC, GOL_SHARDS_SAME_DEVICE,
+from ._lib import (GOL_COPY_CUT, GOL_EINVAL, GOL_IPC_ID_BYTES, GOL_RCCL_ID_BYTES, GOL_RULE_GENERIC, GOL_SHARDS_SAME_DEVICE,
                    GOL_TIMING_EXCHANGE, GOL_WRITE_FN, LAYOUTS, PASTE_OPS, STEP_MODES, TRANSPORT_NAMES, TRANSPORTS,
-                   VIEW_LAYOUTS, GolError, check, format_rule, gol_config, lib, pack_pattern, parse_rle, parse_rule)
+                   VIEW_LAYOUTS, GolError, check, format_rle_words, format_rule, gol_config, lib, pack_pattern, parse_rle, parse_rule,
+                   unpack_pattern)
 
 
 def rccl_unique_id(library=None) -> bytes:
@@ -288,6 +289,55 @@ class Engine:
         """paste with every pattern cell alive: "copy" / "or" set the w x h rectangle at (x0, y0),
         "andnot" clears it, "xor" inverts it.  Returns the number of cells that changed."""
         return self._paste(x0, y0, w, h, None, 0, op, return_layout)
+
+    # -- reads of a region of the running board
+    def copy_words(self, x0: int, y0: int, w: int, h: int, *, cut: bool = False, return_layout: bool = False):
+        """The exact cells of the w x h rectangle at (x0, y0) (cell (c, r) = board cell ((x0 + c) mod
+        W, (y0 + r) mod H)) as bit-packed rows (gol_engine_copy): ((h, ceil(w / 64)) uint64 words as
+        paste_words takes them, alive cells), gathered on the GPU from the board as it is stepped; the
+        board, its layout and the turn counter stay.  cut=True clears the rectangle after reading
+        it.  With ranks in several processes: this rank's rows, the others zero.  return_layout=True
+        appends what was read: "bytes", "standard" or "band"."""
+        if w < 1 or h < 1 or w * h > 1 << 26:  # (before the pattern is allocated here)
+            raise GolError(GOL_EINVAL, f"bad copy size {w} x {h} cells (at most 2^26)")
+        out = np.empty((h, (w + 63) // 64), dtype=np.uint64)
+        n, lay = ctypes.c_int64(), ctypes.c_int32()
+        self._check(self._L.gol_engine_copy(self._h, x0, y0, w, h, out.ctypes.data, out.shape[1], GOL_COPY_CUT if cut else 0,
+                                            ctypes.byref(n), ctypes.byref(lay)))
+        return (out, n.value, VIEW_LAYOUTS[lay.value]) if return_layout else (out, n.value)
+
+    def copy(self, x0: int, y0: int, w: int, h: int, *, cut: bool = False, return_layout: bool = False):
+        """copy_words as an (h, w) bool array (with return_layout=True: the array and the layout read)."""
+        words, _, lay = self.copy_words(x0, y0, w, h, cut=cut, return_layout=True)
+        cells = unpack_pattern(words, w)
+        return (cells, lay) if return_layout else cells
+
+    def cut(self, x0: int, y0: int, w: int, h: int, *, return_layout: bool = False):
+        """copy, then the rectangle is cleared (as fill(..., "andnot"): the next step exchanges its halo again)."""
+        return self.copy(x0, y0, w, h, cut=True, return_layout=return_layout)
+
+    def bounds(self, x0: int = 0, y0: int = 0, w: int | None = None, h: int | None = None):
+        """(bx, by, bw, bh, alive): the smallest box, in the rectangle's own coordinates, that holds
+        every alive cell of the w x h rectangle at (x0, y0) (default: the rest of the board from
+        there), and their number (gol_engine_bounds); (0, 0, 0, 0, 0) if there is none.  With ranks in
+        several processes: of this rank's rows."""
+        w = self.W - x0 if w is None else w
+        h = self.H - y0 if h is None else h
+        v = [ctypes.c_int64() for _ in range(5)]
+        self._check(self._L.gol_engine_bounds(self._h, x0, y0, w, h, *(ctypes.byref(x) for x in v), None))
+        return tuple(x.value for x in v)
+
+    def to_rle(self, x0: int = 0, y0: int = 0, w: int | None = None, h: int | None = None, *, trim: bool = True) -> str:
+        """The rectangle (default: as bounds) as RLE text under the engine's current rule; trim=True
+        cuts it to the bounding box of its alive cells first (none: the 1 x 1 dead pattern).  A box
+        above 2^26 cells raises the copy's GolError."""
+        w = self.W - x0 if w is None else w
+        h = self.H - y0 if h is None else h
+        if trim:
+            bx, by, bw, bh, _ = self.bounds(x0, y0, w, h)
+            x0, y0, w, h = (x0 + bx) % self.W, (y0 + by) % self.H, max(bw, 1), max(bh, 1)
+        words, _ = self.copy_words(x0, y0, w, h)
+        return format_rle_words(words, w, self.rule, self._L)
 
     def hash(self) -> int:
         h = ctypes.c_uint64()

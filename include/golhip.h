@@ -425,6 +425,76 @@ int gol_rle_parse(const char *text, int64_t len, int64_t *w, int64_t *h,
 int gol_rle_format(const uint64_t *pattern, int64_t stride, int64_t w, int64_t h,
                    const char *rule, char *buf, int64_t len, int64_t *need);
 
+/* ---------------------------------------------------------------- region reads
+ * (Added after ABI 6 without a version bump, like the viewport, rule and edit
+ * calls: GOL_ABI_VERSION stays 6; probe for gol_engine_copy, gol_engine_bounds,
+ * gol_copy_host, gol_bounds_host, gol_broker_copy and gol_broker_bounds by
+ * symbol.)
+ *
+ * gol_engine_copy: the exact cells of a w x h rectangle of the running board as
+ * bit-packed rows, read where the board is and as it is (the read-side twin of
+ * gol_engine_paste at cell precision; store_words / store_rows return whole rows
+ * in the standard layout, the views one byte per pixel).  Bit c % 64 of
+ * pattern[r*stride + c/64] is board cell ((x0 + c) mod W, (y0 + r) mod H), 0 <= c
+ * < w, 0 <= r < h: the pattern gol_engine_paste takes, so a copy followed by a
+ * paste under GOL_PASTE_COPY at the same place is the identity.  Words
+ * [0, ceil(w/64)) of every row are written whole, the bits at c >= w zero; the
+ * words from ceil(w/64) to stride are not touched.  A cell is alive if its bit
+ * is set, on byte rows if its byte is non-zero (what the views count; this holds
+ * for a bit-capable board whose exact first turn is pending, too).  *alive (may
+ * be NULL) = the alive cells copied; *src_layout (may be NULL) as the views'.
+ * Valid: 1 <= w <= W, 1 <= h <= H, 0 <= x0 < W, 0 <= y0 < H, w*h <= 2^26,
+ * stride >= ceil(w/64), pattern != NULL, flags 0 or GOL_COPY_CUT; anything else
+ * is GOL_EINVAL before any GPU work.
+ * The rectangle is gathered on the GPU from the layout the board is currently
+ * stepped in, reading only the rows and words it covers.  Blocking; ordered
+ * after the last step.  A plain copy changes nothing: the buffer, the layout,
+ * the turn counter and the halo stay, and the next step pays nothing for it.
+ *  - GOL_COPY_CUT: the rectangle is cleared after it is read -- exactly
+ *    gol_engine_paste(e, x0, y0, w, h, NULL, 0, GOL_PASTE_ANDNOT, ..), queued
+ *    behind the read, with one host synchronisation for the call.  It makes the
+ *    halo stale as a paste does, and *alive is that paste's `changed`.  On a
+ *    bit-capable board loaded with bytes other than 0/255, its exact first turn
+ *    pending, a cut is GOL_ESTATE and changes nothing (a plain copy is allowed);
+ *  - several local shards each read their own rows (gol_view_plan) on their own
+ *    GPU; with ranks in several processes the call is not collective (like
+ *    view_counts and paste): the pattern rows this process does not hold are
+ *    written as zero, *alive counts its rows only, and the caller ORs the
+ *    ranks' patterns.
+ *
+ * gol_engine_bounds: the smallest box that holds every alive cell of the
+ * rectangle, in the rectangle's own coordinates: those cells are the rectangle
+ * cells (c, r) with bx <= c < bx + bw, by <= r < by + bh.  (A minimal box on a
+ * torus is ambiguous; relative to a rectangle the caller names it is not.  (0, 0,
+ * W, H) gives plain board coordinates.)  No alive cell: bx = by = bw = bh = 0.
+ * *alive = the alive cells of the rectangle; for the whole board,
+ * gol_engine_alive_count.  Valid as for the copy, without the w*h limit and
+ * without a pattern: the whole board is legal.  Reads only: the halo stays, and
+ * the call is allowed while the exact first turn is pending.  Several local
+ * shards are unioned; with ranks in several processes the box is that of this
+ * process's rows, still in rectangle coordinates, and the caller unions.  Every
+ * output pointer may be NULL. */
+#define GOL_COPY_CUT 1
+int gol_engine_copy(gol_engine *e, int64_t x0, int64_t y0, int64_t w, int64_t h,
+                    uint64_t *pattern, int64_t stride, int32_t flags,
+                    int64_t *alive, int32_t *src_layout);
+int gol_engine_bounds(gol_engine *e, int64_t x0, int64_t y0, int64_t w, int64_t h,
+                      int64_t *bx, int64_t *by, int64_t *bw, int64_t *bh,
+                      int64_t *alive, int32_t *src_layout);
+/* The per-unit mapping of the region-read kernels (csrc/gol_copy.h) applied to a
+ * host buffer (host functions, no GPU needed); layout, board, pitch, W, row,
+ * rows, prow, x0, w, pattern and stride as for gol_paste_host, with board rows
+ * [row, row + rows) read into pattern rows [prow, prow + rows).
+ * gol_bounds_host returns the inclusive minima and maxima of the alive cells'
+ * columns and rows relative to x0 and `row` (any pointer may be NULL); rows
+ * without an alive cell give *cmin > *cmax and *rmin > *rmax. */
+int gol_copy_host(int32_t layout, const void *board, int64_t pitch, int64_t W,
+                  int64_t row, int64_t rows, int64_t prow, int64_t x0, int64_t w,
+                  uint64_t *pattern, int64_t stride, int64_t *alive);
+int gol_bounds_host(int32_t layout, const void *board, int64_t pitch, int64_t W,
+                    int64_t row, int64_t rows, int64_t x0, int64_t w,
+                    int64_t *cmin, int64_t *cmax, int64_t *rmin, int64_t *rmax, int64_t *alive);
+
 /* ---------------------------------------------------------------- plans
  * The schedule of a sharded step as data (host functions, no GPU needed).  The
  * engine runs exactly these plans; golhip.sharded (the torch.distributed
@@ -710,6 +780,14 @@ int gol_broker_view(gol_broker *b, int64_t x0, int64_t y0, int32_t scale, int32_
 int gol_broker_paste(gol_broker *b, int64_t x0, int64_t y0, int64_t w, int64_t h,
                      const uint64_t *pattern, int64_t stride, int32_t op,
                      int64_t *changed, int64_t *turns_completed);
+/* gol_engine_copy and gol_engine_bounds of the broker's board, served between
+ * the chunks of a running Run like gol_broker_view and gol_broker_paste;
+ * *turns_completed (may be NULL) = cTurn, the turn the read saw (a cut lands
+ * after it).  GOL_ESTATE with no board.  No reference counterpart. */
+int gol_broker_copy(gol_broker *b, int64_t x0, int64_t y0, int64_t w, int64_t h, uint64_t *pattern,
+                    int64_t stride, int32_t flags, int64_t *alive, int64_t *turns_completed);
+int gol_broker_bounds(gol_broker *b, int64_t x0, int64_t y0, int64_t w, int64_t h, int64_t *bx, int64_t *by,
+                      int64_t *bw, int64_t *bh, int64_t *alive, int64_t *turns_completed);
 int gol_worker_update(const gol_request *req, gol_response *res);                 /* GameOfLifeOperations.Update, worker.go:77-80 */
 
 #ifdef __cplusplus
