@@ -226,7 +226,10 @@ int gol_engine_write_pgm_to(gol_engine *e, gol_write_fn sink, void *user);
 /* Bit-packed rows [y0, y1) (global, held by this process) in or out: 64 cells
  * per uint64 (LSB = lowest x), `stride` uint64 words per row, W % 64 == 0.
  * load_words overwrites those rows of the current board (several calls may
- * load a board piece by piece), resets the turn counter to 0.  store_words
+ * load a board piece by piece), resets the turn counter to 0.  On a board
+ * loaded with bytes other than 0/255, its exact first turn pending, load_words
+ * ends that state: the rows it does not load keep their cells equal to 255,
+ * every other byte is dead, and the board is a bit board at turn 0.  store_words
  * reads them (GOL_ESTATE before turn 1 of a board loaded with bytes other than
  * 0/255: use store_bytes).  One eighth of the PCIe traffic of the byte calls. */
 int gol_engine_load_words(gol_engine *e, int64_t y0, int64_t y1, const uint64_t *words, int64_t stride);
