@@ -170,7 +170,9 @@ int gol_engine_shard(gol_engine *e, int32_t i, int32_t *device, int64_t *y0, int
 /* Load a byte board (operations.Run's req.World, broker.go:65) and reset the
  * turn counter to 0.  Any byte value is accepted (exact semantics above).
  * `world` is the whole H x W board (as the reference ships it to every
- * worker); every rank reads its own rows. */
+ * worker); every rank reads its own rows.  Only the first W bytes of a row are
+ * read: with stride > W the bytes between the rows are ignored, whatever they
+ * hold (they neither count as cells nor leave the exact first turn pending). */
 int gol_engine_load_bytes(gol_engine *e, const uint8_t *world, int64_t stride);
 /* Load images/<W>x<H>.pgm-style P5 (readPgmImage, gol/io.go:90-126: fields
  * "P5", W, H, 255, then the raster): every shard streams its own rows from
@@ -198,17 +200,23 @@ int gol_engine_alive_count(gol_engine *e, uint64_t *count);
 /* Copy the board out as bytes (0/255, or the loaded bytes before turn 1).
  * Needs every row local (not with nranks > 1 ranks: use store_rows). */
 int gol_engine_store_bytes(gol_engine *e, uint8_t *out, int64_t stride);
-/* Rows [y0, y1) of the board (global row numbers, all held by this process). */
+/* Rows [y0, y1) of the board (global row numbers, all held by this process):
+ * row y goes to out + (y - y0)*stride, W bytes of it; with stride > W the bytes
+ * between the rows are not touched, and y0 == y1 writes nothing. */
 int gol_engine_store_rows(gol_engine *e, int64_t y0, int64_t y1, uint8_t *out, int64_t stride);
 /* calculateAliveCells (broker.go:47-58): (x, y) int32 pairs in row-major
- * order; writes min(n, cap) pairs, *n = total alive cells.  With ranks in
+ * order; writes min(n, cap) pairs, *n = total alive cells whatever cap is (the
+ * pairs past min(n, cap) of xy are not touched; cap == 0 allows xy == NULL and
+ * returns the total alone; with several local shards the cap runs across them:
+ * the pairs are the row-major prefix of the whole list).  With ranks in
  * several processes: the cells of this rank's rows. */
 int gol_engine_alive_cells(gol_engine *e, int32_t *xy, int64_t cap, int64_t *n);
 /* Advance exactly one turn and list the cells whose state changed, (x, y) int32
  * pairs in row-major order: the CellFlipped{CompletedTurns, Cell} events of
  * that turn (gol/event.go:50-60; sent per flipped cell by the controller the
  * reference never finished, README.md:260-262).  Writes min(n, cap) pairs,
- * *n = number of flipped cells (of this rank's rows with several processes). */
+ * *n = number of flipped cells (of this rank's rows with several processes);
+ * cap and xy as for gol_engine_alive_cells, and the turn is taken whatever cap is. */
 int gol_engine_step_flips(gol_engine *e, int32_t *xy, int64_t cap, int64_t *n);
 /* writePgmImage byte stream (gol/io.go:52-81): "P5\n<W> <H>\n255\n" + H*W
  * bytes, streamed from the device in chunks; with several processes every
@@ -231,7 +239,9 @@ int gol_engine_write_pgm_to(gol_engine *e, gol_write_fn sink, void *user);
  * ends that state: the rows it does not load keep their cells equal to 255,
  * every other byte is dead, and the board is a bit board at turn 0.  store_words
  * reads them (GOL_ESTATE before turn 1 of a board loaded with bytes other than
- * 0/255: use store_bytes).  One eighth of the PCIe traffic of the byte calls. */
+ * 0/255: use store_bytes).  One eighth of the PCIe traffic of the byte calls.
+ * Only W/64 words of a row are read or written: with stride > W/64 the words
+ * between the rows are ignored by load_words and not touched by store_words. */
 int gol_engine_load_words(gol_engine *e, int64_t y0, int64_t y1, const uint64_t *words, int64_t stride);
 int gol_engine_store_words(gol_engine *e, int64_t y0, int64_t y1, uint64_t *words, int64_t stride);
 /* Order-independent board hash (same definition as oracle_hash_words):
@@ -633,6 +643,9 @@ int gol_strip_plan(int32_t kernel, int64_t rows, int64_t row0, int64_t width, in
  * stream (hipStream_t passed as void*; NULL = default stream).  These are the
  * building blocks of the row-sharded multi-GPU board (one process per GPU;
  * broker.go:135-206's partition applied to GPUs) and of bench.py.
+ * Arguments are checked before anything is launched (GOL_EINVAL); rows == 0 (an
+ * empty slab) is GOL_OK and launches nothing.  With a pitch or stride larger than
+ * the width the words or bytes between the rows are neither read nor written.
  *
  * Bit board of one shard: R local rows, Wd = W/32 uint32 words per row, row
  * pitch `pitch` words.  Input row y of the shard (-k <= y < R + k) is read
@@ -648,23 +661,32 @@ int gol_dev_bits_step(const uint32_t *top, const uint32_t *mid, const uint32_t *
                       int32_t cells_per_lane, int32_t strip_rows, uint64_t *count_slots,
                       void *stream);
 /* Fill rows [0, rows) of a bit board with the synthetic board rows
- * [grow0, grow0 + rows) of a W-wide torus (W % 64 == 0). */
+ * [grow0, grow0 + rows) of a W-wide torus (W % 64 == 0; pitch even, dst 8-byte
+ * aligned: a row is written as 64-bit words). */
 int gol_dev_random_fill(uint32_t *dst, int64_t rows, int64_t grow0, int64_t W, int64_t pitch,
                         uint64_t seed, void *stream);
-/* Add popcount(rows x Wd words) to slots (GOL_COUNT_SLOTS*8 uint64). */
+/* Add popcount(rows x Wd words) to slots (GOL_COUNT_SLOTS*8 uint64: sum them
+ * all); any Wd >= 1, odd ones too. */
 int gol_dev_popcount(const uint32_t *src, int64_t rows, int64_t Wd, int64_t pitch,
                      uint64_t *slots, void *stream);
-/* Add the board-hash contribution of rows whose first global row is grow0. */
+/* Add the board-hash contribution of rows whose first global row is grow0 to
+ * slots (as gol_dev_popcount; sums are modulo 2^64, so the parts of any split of
+ * the rows add up to the whole).  Wd and pitch even, src 8-byte aligned. */
 int gol_dev_hash(const uint32_t *src, int64_t rows, int64_t grow0, int64_t Wd, int64_t pitch,
                  uint64_t *slots, void *stream);
-/* Bytes <-> bits for rows x W cells; pack also ORs 1 into *nonbinary when a
- * byte other than 0/255 is seen (may be NULL). */
+/* Bytes <-> bits for rows x W cells (W % 32 == 0): bit = (byte == 255), byte =
+ * 0 or 255; pack also ORs 1 into *nonbinary when a byte other than 0/255 is
+ * seen inside the rows x W cells (may be NULL).  The byte rows may start at any
+ * address and have any stride >= W (unpack stores 16 bytes at a time where a
+ * row is 16-byte aligned and single bytes elsewhere). */
 int gol_dev_pack(const uint8_t *bytes, int64_t rows, int64_t W, int64_t stride, uint32_t *bits,
                  int64_t pitch, uint32_t *nonbinary, void *stream);
 int gol_dev_unpack(const uint32_t *bits, int64_t rows, int64_t W, int64_t pitch, uint8_t *bytes,
                    int64_t stride, void *stream);
 /* One exact-semantics byte turn (worker.go:15-70) for rows [y0, y1) of an
- * H x W byte torus; out row i = next state of row y0 + i. */
+ * H x W byte torus; out row i = next state of row y0 + i.  Any W, strides and
+ * addresses: 16 cells per lane when W, both strides and both pointers are
+ * multiples of 16, one cell per thread otherwise, with the same result. */
 int gol_dev_bytes_step(const uint8_t *world, int64_t H, int64_t W, int64_t stride, int64_t y0,
                        int64_t y1, uint8_t *out, int64_t out_stride, void *stream);
 
