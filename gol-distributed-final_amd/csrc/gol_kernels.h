@@ -1,4 +1,5 @@
-// gol_kernels.h -- internal launcher interface of gol_kernels.hip (not part of the C ABI).
+// gol_kernels.h -- internal launcher interface of the kernel units (gol_kernels.hip holds every
+// launcher; not part of the C ABI).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -18,7 +19,7 @@ uint32_t *golk_device_err_word(int device);
 uint32_t *golk_cu_slots(int device);
 // Zero them again on `s` (after a faulted launch whose workgroups may not have freed their slots).
 hipError_t golk_reset_cu_slots(int device, hipStream_t s);
-// Paired-rank claim counters (one buffer per launch stream, gol_kernels.hip StripMap).
+// Paired-rank claim counters (one buffer per launch stream; gol_strips.h StripMap).
 // golk_reset_claims: zero the buffer of stream s, ordered on s (after a faulted launch).
 // golk_release_claims: free it (the caller has synchronised s; an engine destroying its streams).
 // golk_own_stream: mark s as an engine's stream; golk_reset_claims_device (gol_dev_error, after a

@@ -16,160 +16,27 @@
 // round 1 (vertical-first stages, barrier-synchronised split pipeline, centred
 // standard-layout stages, per-role profiling builds) are recorded in DESIGN.md
 // and live in git history (commit 297b13e).
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+//
+// This unit: the step kernels (bits_step_kernel, band_step_kernel) with their rules, the layout
+// conversion, the blocked and exact byte kernels, the board utilities, the list kernels, the IPC
+// flag kernels, and every launcher with its host state.  The two split pipelines are units of
+// their own (gol_band_pipe.hip, gol_bytes_pipe.hip; entry points declared in gol_device.h).
+// gol_device.h holds what the units share, gol_pipe.h what only the pipelines share.
 #include <stdlib.h>
 
 #include <algorithm>
 #include <map>
 #include <mutex>
 #include <set>
-#include <type_traits>
 #include <utility>
 
-#include "gol_kernels.h"
+#include "gol_device.h"
 #include "gol_rule.h"
-#include "gol_strips.h"
-
-// Polls of a pipeline flag before a wave gives up (sets GOLK_ERR_SPIN in the launch's error
-// word and leaves; the host turns that into GOL_EHIP).  A test build sets 0 to force the path.
-#ifndef GOL_SPIN_LIMIT
-#define GOL_SPIN_LIMIT (1 << 22)
-#endif
-// s_sleep argument between two polls of a pipeline flag (units of 64 shader cycles): 0 (the
-// poll's own LDS round trip paces it) measured +1 % on 65536^2, +0.3 % on 16384^2 bytes, equal on
-// the weak board, over 1; 2 was slower (same box, tools/ab.py)
-#ifndef GOL_BYTES_SPIN_SLEEP
-#define GOL_BYTES_SPIN_SLEEP 0  // (the byte pipeline's polls, spin_until_ge<true>)
-#endif
-#ifndef GOL_SPIN_SLEEP
-#define GOL_SPIN_SLEEP 0
-#endif
 
 namespace golk {
 
-// ------------------------------------------------------------------ helpers
-// v_bitop3_b32 truth tables: operand 0 -> 0xF0, operand 1 -> 0xCC, operand 2 -> 0xAA.
-constexpr unsigned TT_XOR3 = 0x96;  // a ^ b ^ c
-constexpr unsigned TT_MAJ = 0xE8;   // majority(a, b, c)
-// The rule tail (tools/rule_search.c, tests/test_rule_circuit_cpu.py): with T = t0 + 2(k0 + u +
-// 2v) the 3x3 sum including the cell, alive' = (T == 3) | (cell & T == 4)
-//   = (t0 | cell) & G2,  G2 = TT_G2(u, v, G1),  G1 = TT_G1(t0, k0, v)  (exactly one of t0, k0, v).
-// Three gates instead of the four of t0 ? [S == 1] : cell & [S == 2]: an exhaustive search over
-// 3-gate circuits finds them only when it may use that the centre row's horizontal sum includes
-// the cell (a centre sum of 0 means a dead cell, 3 a live one), which holds in every kernel here.
-constexpr unsigned TT_G1 = 0x16;    // exactly one of a, b, c
-constexpr unsigned TT_G2 = 0x29;    // (~a & ~b & ~c) | (~a & b & c) | (a & ~b & c)
-constexpr unsigned TT_OUT = 0xA8;   // (a | b) & c
-
-template <unsigned TT>
-__device__ __forceinline__ uint32_t bitop3(uint32_t a, uint32_t b, uint32_t c)
-{
-    return __builtin_amdgcn_bitop3_b32(a, b, c, TT);
-}
-// lane i receives lane i-1's value (lane 0 receives 0)
-__device__ __forceinline__ uint32_t from_lower_lane(uint32_t v)
-{
-    return __builtin_amdgcn_mov_dpp(v, 0x138 /* wave_shr:1 */, 0xf, 0xf, true);
-}
-// lane i receives lane i+1's value (lane 63 receives 0)
-__device__ __forceinline__ uint32_t from_upper_lane(uint32_t v)
-{
-    return __builtin_amdgcn_mov_dpp(v, 0x130 /* wave_shl:1 */, 0xf, 0xf, true);
-}
-
-__device__ __forceinline__ uint64_t splitmix64(uint64_t x)
-{
-    uint64_t z = x + 0x9E3779B97F4A7C15ULL;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-    return z ^ (z >> 31);
-}
-
-__device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-// One atomic per wave into one of GOL_COUNT_SLOTS slots (64 B apart).
-__device__ __forceinline__ void slot_add(uint64_t *slots, uint64_t v)
-{
-    v = wave_sum_u64(v);
-    if ((threadIdx.x & 63) == 0 && v) {
-        unsigned wave = (blockIdx.x + blockIdx.y * gridDim.x) * (blockDim.x >> 6) + (threadIdx.x >> 6);
-        atomicAdd((unsigned long long *)&slots[(wave % GOL_COUNT_SLOTS) * 8], (unsigned long long)v);
-    }
-}
-
-// Error word of a launch: flags ORed by lane 0 of a failing wave (a vector global atomic).
-__device__ __forceinline__ void raise_error(uint32_t *err, uint32_t flag)
-{
-    if ((threadIdx.x & 63) == 0) atomicOr(err, flag);
-}
-
-template <int DW> struct VecT;
-template <> struct VecT<1> { typedef uint32_t type; };
-template <> struct VecT<2> { typedef uint2 type; };
-template <> struct VecT<4> { typedef uint4 type; };
-
-template <int DW>
-__device__ __forceinline__ void load_words(const uint32_t *p, uint32_t (&w)[DW])
-{
-    typedef typename VecT<DW>::type V;
-    V v = *reinterpret_cast<const V *>(p);
-    if constexpr (DW == 1) { w[0] = v; }
-    if constexpr (DW == 2) { w[0] = v.x; w[1] = v.y; }
-    if constexpr (DW == 4) { w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w; }
-}
-template <int DW>
-__device__ __forceinline__ void store_words(uint32_t *p, const uint32_t (&w)[DW])
-{
-    typedef typename VecT<DW>::type V;
-    V v;
-    if constexpr (DW == 1) { v = w[0]; }
-    if constexpr (DW == 2) { v.x = w[0]; v.y = w[1]; }
-    if constexpr (DW == 4) { v.x = w[0]; v.y = w[1]; v.z = w[2]; v.w = w[3]; }
-    *reinterpret_cast<V *>(p) = v;
-}
-
-// B3/S23 from three horizontal sums (rows above/middle/below, value = h0 + 2*h1 in 0..3 per
-// cell; the middle one includes the cell) and the middle cell.  T = sum of the 3x3 block
-// including the cell = t0 + 2*(k0 + u + 2v); alive' = (T == 3) | (cell & T == 4): 7 gates.
-__device__ __forceinline__ uint32_t rule(uint32_t a0, uint32_t a1, uint32_t b0, uint32_t b1,
-                                         uint32_t c0, uint32_t c1, uint32_t cell)
-{
-    const uint32_t t0 = bitop3<TT_XOR3>(a0, b0, c0);
-    const uint32_t k0 = bitop3<TT_MAJ>(a0, b0, c0);
-    const uint32_t u = bitop3<TT_XOR3>(a1, b1, c1);
-    const uint32_t v = bitop3<TT_MAJ>(a1, b1, c1);
-    const uint32_t g1 = bitop3<TT_G1>(t0, k0, v);
-    const uint32_t g2 = bitop3<TT_G2>(u, v, g1);
-    return bitop3<TT_OUT>(t0, cell, g2);
-}
-
-// ------------------------------------------------------------------ register pipeline
-// State of stage g (generation g+1): a ring of 3 rows of horizontal sums plus the cells of
-// those rows.  Slot s = step % 3 holds the row received at this step; the stage emits the
-// next state of the row received one step ago.
-template <int K, int DW>
-struct Pipe {
-    uint32_t h0[K][3][DW];
-    uint32_t h1[K][3][DW];
-    uint32_t cc[K][3][DW];
-};
-
-template <int K, int DW>
-__device__ __forceinline__ void pipe_init(Pipe<K, DW> &p)
-{
-#pragma unroll
-    for (int g = 0; g < K; ++g)
-#pragma unroll
-        for (int s = 0; s < 3; ++s)
-#pragma unroll
-            for (int j = 0; j < DW; ++j) { p.h0[g][s][j] = 0; p.h1[g][s][j] = 0; p.cc[g][s][j] = 0; }
-}
+// Truth tables, lane helpers, rule(), Pipe, the band stage (hsum_band, bstage), BitsArgs,
+// BytesKArgs, pack32 / unpack32: gol_device.h
 
 // Standard layout, shifted frame: the horizontal 3-sum is formed from the cell and its two
 // LEFT neighbours, S'[p] = c[p] + c[p-1] + c[p-2] = the 3-sum centred on p-1, so a stage
@@ -203,60 +70,6 @@ __device__ __forceinline__ void sstage(Pipe<K, DW> &p, const int g, uint32_t (&c
         cur[j] = rule(p.h0[g][SA][j], p.h1[g][SA][j], p.h0[g][SM][j], p.h1[g][SM][j], p.h0[g][S][j],
                       p.h1[g][S][j], p.cc[g][SM][j]);
 }
-
-// Step W of a 3-row wavefront over K shifted-frame stages, one word per lane: row r (ring slot
-// r) is at stage W - r.  The three rows' stages are independent within a step, and each op is
-// written for all active rows before the next (a one-word stage is a dependent chain of 13
-// ops; row after row, the compiler kept the chains apart and one wave issued at the
-// dependent-op latency).
-template <int K, int NSTG, int W>
-__device__ __forceinline__ void sstage_wave3(Pipe<K, 1> &p, uint32_t (&c)[3])
-{
-    static_assert(NSTG <= K, "stages of the pipe state");
-    constexpr bool on[3] = {W < NSTG, W >= 1 && W - 1 < NSTG, W >= 2 && W - 2 < NSTG};
-    constexpr int g[3] = {on[0] ? W : 0, on[1] ? W - 1 : 0, on[2] ? W - 2 : 0};
-    uint32_t wl[3], L1[3], L2[3], t0[3], k0[3], u[3], v[3], e1[3], e2[3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) if (on[r]) wl[r] = from_lower_lane(c[r]);
-#pragma unroll
-    for (int r = 0; r < 3; ++r) if (on[r]) L1[r] = __builtin_amdgcn_alignbit(c[r], wl[r], 31);
-#pragma unroll
-    for (int r = 0; r < 3; ++r) if (on[r]) L2[r] = __builtin_amdgcn_alignbit(c[r], wl[r], 30);
-#pragma unroll
-    for (int r = 0; r < 3; ++r) if (on[r]) p.h0[g[r]][r][0] = bitop3<TT_XOR3>(L1[r], c[r], L2[r]);
-#pragma unroll
-    for (int r = 0; r < 3; ++r) if (on[r]) p.h1[g[r]][r][0] = bitop3<TT_MAJ>(L1[r], c[r], L2[r]);
-#pragma unroll
-    for (int r = 0; r < 3; ++r) if (on[r]) p.cc[g[r]][r][0] = L1[r];
-#define GOL_ROWS3(expr) _Pragma("unroll") for (int r = 0; r < 3; ++r) if (on[r]) { const int A = (r + 1) % 3, M = (r + 2) % 3; (void)A; (void)M; expr; }
-    GOL_ROWS3(k0[r] = bitop3<TT_MAJ>(p.h0[g[r]][A][0], p.h0[g[r]][M][0], p.h0[g[r]][r][0]))
-    GOL_ROWS3(u[r] = bitop3<TT_XOR3>(p.h1[g[r]][A][0], p.h1[g[r]][M][0], p.h1[g[r]][r][0]))
-    GOL_ROWS3(v[r] = bitop3<TT_MAJ>(p.h1[g[r]][A][0], p.h1[g[r]][M][0], p.h1[g[r]][r][0]))
-    GOL_ROWS3(t0[r] = bitop3<TT_XOR3>(p.h0[g[r]][A][0], p.h0[g[r]][M][0], p.h0[g[r]][r][0]))
-    GOL_ROWS3(e1[r] = bitop3<TT_G1>(t0[r], k0[r], v[r]))
-    GOL_ROWS3(e2[r] = bitop3<TT_G2>(u[r], v[r], e1[r]))
-    GOL_ROWS3(c[r] = bitop3<TT_OUT>(t0[r], p.cc[g[r]][M][0], e2[r]))
-#undef GOL_ROWS3
-}
-// All NSTG stages of one 3-row block (steps 0 .. NSTG + 1).
-template <int K, int NSTG, int... W>
-__device__ __forceinline__ void sstage_waves3(Pipe<K, 1> &p, uint32_t (&c)[3], std::integer_sequence<int, W...>)
-{
-    (sstage_wave3<K, NSTG, W>(p, c), ...);
-}
-
-// StripMap, work_item, work_dir, pair_extent: gol_strips.h (shared with the host)
-
-struct BitsArgs {
-    const uint32_t *top, *mid, *bot;
-    uint32_t *dst;
-    int64_t R, Wd, pitch, row0, rows;
-    int32_t strip, ngroups;
-    uint64_t *slots;
-    uint32_t *err;
-    uint32_t *cu_slots;  // band pipeline: per-CU masks of the workgroup slots in use (GOL_CU_SLOT_WORDS)
-    StripMap sm;
-};
 
 // ------------------------------------------------------------------ the rule of a step kernel
 // bits_step_kernel and band_step_kernel are generic over the rule (B3S23 and TableRule, below
@@ -389,75 +202,6 @@ __device__ __forceinline__ void store_row_masked(char *row, uint32_t nbytes, uin
     } else {
         static_assert(DW == 4 || DW == 2, "band lanes hold 2 or 4 words");
     }
-}
-
-// ------------------------------------------------------------------ band-layout bit board
-// Column-band layout: a row is Wd = W/32 words and bit b of word w is cell x = b*Wd + w (32
-// bands of Wd columns, one per bit).  The horizontal neighbours of a cell are the SAME bit
-// of the neighbouring words, so a generation is pure bitwise logic: no v_alignbit (which
-// issues at half the rate of v_bitop3 on gfx950) and the centre cell is the
-// word itself.  The column torus wraps band b's last column onto band b+1's first:
-// band-space column c = q*Wd + r reads word r rotated right by q (one v_alignbit per word
-// per LOAD, only in the waves that straddle the wrap).  Cost: the horizontal halo is k words
-// (k columns) instead of one 32-cell word, so a wave of 64 lanes x DW words keeps
-// 64 - 2*ceil(k/DW) lanes of output.
-template <int DW>
-__device__ __forceinline__ void hsum_band(const uint32_t (&c)[DW], uint32_t (&h0)[DW], uint32_t (&h1)[DW])
-{
-    const uint32_t left_in = from_lower_lane(c[DW - 1]);
-    const uint32_t right_in = from_upper_lane(c[0]);
-#pragma unroll
-    for (int j = 0; j < DW; ++j) {
-        const uint32_t L = (j == 0) ? left_in : c[j - 1];
-        const uint32_t R = (j == DW - 1) ? right_in : c[j + 1];
-        h0[j] = bitop3<TT_XOR3>(L, c[j], R);
-        h1[j] = bitop3<TT_MAJ>(L, c[j], R);
-    }
-}
-
-// The rule written op by op across the DW words (each op has DW-1 independent neighbours):
-// per word the 8 ops form a dependent chain, and one wave issues a dependent VALU op ~1.7x
-// slower than an independent one (MI355X_MICROARCH.md, constants table).
-template <int K, int DW, int S>
-__device__ __forceinline__ void bstage(Pipe<K, DW> &p, const int g, uint32_t (&cur)[DW])
-{
-    constexpr int SA = (S + 1) % 3, SM = (S + 2) % 3;
-#pragma unroll
-    for (int j = 0; j < DW; ++j) p.cc[g][S][j] = cur[j];
-    hsum_band<DW>(p.cc[g][S], p.h0[g][S], p.h1[g][S]);
-    const uint32_t (&a0)[DW] = p.h0[g][SA], (&a1)[DW] = p.h1[g][SA];
-    const uint32_t (&b0)[DW] = p.h0[g][SM], (&b1)[DW] = p.h1[g][SM];
-    const uint32_t (&c0)[DW] = p.h0[g][S], (&c1)[DW] = p.h1[g][S];
-    uint32_t t0[DW], k0[DW], u[DW], v[DW], e1[DW], e2[DW];
-#pragma unroll
-    for (int j = 0; j < DW; ++j) k0[j] = bitop3<TT_MAJ>(a0[j], b0[j], c0[j]);
-#pragma unroll
-    for (int j = 0; j < DW; ++j) u[j] = bitop3<TT_XOR3>(a1[j], b1[j], c1[j]);
-#pragma unroll
-    for (int j = 0; j < DW; ++j) v[j] = bitop3<TT_MAJ>(a1[j], b1[j], c1[j]);
-#pragma unroll
-    for (int j = 0; j < DW; ++j) t0[j] = bitop3<TT_XOR3>(a0[j], b0[j], c0[j]);
-#pragma unroll
-    for (int j = 0; j < DW; ++j) e1[j] = bitop3<TT_G1>(t0[j], k0[j], v[j]);
-#pragma unroll
-    for (int j = 0; j < DW; ++j) e2[j] = bitop3<TT_G2>(u[j], v[j], e1[j]);
-#pragma unroll
-    for (int j = 0; j < DW; ++j) cur[j] = bitop3<TT_OUT>(t0[j], p.cc[g][SM][j], e2[j]);
-}
-
-// Same stage with the rule evaluated word by word (fewer live temporaries than bstage; at
-// 4 waves per SIMD a dependent op issues as fast as an independent one).
-template <int K, int DW, int S>
-__device__ __forceinline__ void bstage_seq(Pipe<K, DW> &p, const int g, uint32_t (&cur)[DW])
-{
-    constexpr int SA = (S + 1) % 3, SM = (S + 2) % 3;
-#pragma unroll
-    for (int j = 0; j < DW; ++j) p.cc[g][S][j] = cur[j];
-    hsum_band<DW>(p.cc[g][S], p.h0[g][S], p.h1[g][S]);
-#pragma unroll
-    for (int j = 0; j < DW; ++j)
-        cur[j] = rule(p.h0[g][SA][j], p.h1[g][SA][j], p.h0[g][SM][j], p.h1[g][SM][j], p.h0[g][S][j],
-                      p.h1[g][S][j], p.cc[g][SM][j]);
 }
 
 // The same stage for a life-like rule as data (gol_rule.h): the full 4-bit count of the 3x3 block
@@ -629,632 +373,6 @@ __global__ void __launch_bounds__(256) band_step_kernel(typename Rule::Args a)
 }
 #undef GOL_STAGE_BLOCK
 
-// ------------------------------------------------------------------ LDS helpers of the pipelines
-// LDS accesses of the pipelines are inline asm: the compiler treats a global_load_lds in
-// flight as a pending LDS write and would put vmcnt(0) before every LDS access it can see
-// (which, on the storing wave, also waits for its HBM stores).
-typedef __attribute__((address_space(3))) uint32_t lds_u32;
-// ceil(a / d) for a >= 0 (else 0) and floor(a / d) for any a (d > 0)
-__device__ __forceinline__ int div_ceil_nn(int a, int d) { return a > 0 ? (a + d - 1) / d : 0; }
-__device__ __forceinline__ int div_floor(int a, int d) { return a >= 0 ? a / d : -((-a + d - 1) / d); }
-typedef __attribute__((ext_vector_type(4))) uint32_t v4u32;
-__device__ __forceinline__ v4u32 lds_rd128(const lds_u32 *p)
-{
-    v4u32 r;
-    asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(r) : "v"(p) : "memory");
-    return r;
-}
-// Wait for a read with N younger LDS operations allowed in flight (LDS operations of a wave
-// complete in order, and these kernels issue no scalar loads in the loop; the assembly check
-// tools/check_lds_wait.py confirms the latter).  The value is an in-out operand, so every
-// use of it is ordered after the wait.
-template <int N>
-__device__ __forceinline__ void lds_wait_n(v4u32 &r)
-{
-    if constexpr (N == 0) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(r)::"memory");
-    else asm volatile("s_waitcnt lgkmcnt(1)" : "+v"(r)::"memory");
-}
-__device__ __forceinline__ void lds_wait1() { asm volatile("s_waitcnt lgkmcnt(1)" ::: "memory"); }
-
-// Wait until `r` (an issued read) has landed, N younger LDS operations left in flight: at a loop
-// back edge, so that the compiler's copies of the loop-carried register read the landed value.
-template <int N>
-__device__ __forceinline__ void lds_settle(v4u32 &r) { asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(r) : "i"(N) : "memory"); }
-// Immediate-offset forms (byte offsets < 64 KiB): ring slots and rows at compile-time offsets
-// from one per-lane address register.
-template <int OFF>
-__device__ __forceinline__ v4u32 lds_rd128_issue_o(const lds_u32 *p)
-{
-    v4u32 r;
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(r) : "v"(p), "i"(OFF) : "memory");
-    return r;
-}
-template <int OFF>
-__device__ __forceinline__ void lds_wr128_o(lds_u32 *p, v4u32 v)
-{
-    asm volatile("ds_write_b128 %0, %1 offset:%2" ::"v"(p), "v"(v), "i"(OFF) : "memory");
-}
-template <int OFF>
-__device__ __forceinline__ void lds_wr32_o(lds_u32 *p, uint32_t v)
-{
-    asm volatile("ds_write_b32 %0, %1 offset:%2" ::"v"(p), "v"(v), "i"(OFF) : "memory");
-}
-template <int OFF>
-__device__ __forceinline__ uint32_t lds_rd32_issue_o(const lds_u32 *p)
-{
-    uint32_t r;
-    asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(r) : "v"(p), "i"(OFF) : "memory");
-    return r;
-}
-// Two-instruction forms (one asm statement: one conservative hazard s_nop after it, not two):
-// the band pipeline's block reads, writes, settle and middle-wave flags through these measured
-// weak 163.3 -> 165.2 TCUPS, 262144^2 +0.2 % (same box, profiles/r05/r05g_ab_lds_pairs.jsonl).
-template <int OFF0, int OFF1>
-__device__ __forceinline__ void lds_rd128x2_issue_o(const lds_u32 *p, v4u32 &a, v4u32 &b)
-{
-    asm volatile("ds_read_b128 %0, %2 offset:%3\n\tds_read_b128 %1, %2 offset:%4" : "=&v"(a), "=&v"(b) : "v"(p), "i"(OFF0), "i"(OFF1) : "memory");
-}
-template <int OFF0, int OFF1>
-__device__ __forceinline__ void lds_wr128x2_o(lds_u32 *p, v4u32 a, v4u32 b)
-{
-    asm volatile("ds_write_b128 %0, %1 offset:%3\n\tds_write_b128 %0, %2 offset:%4" ::"v"(p), "v"(a), "v"(b), "i"(OFF0), "i"(OFF1) : "memory");
-}
-__device__ __forceinline__ void lds_settle2(v4u32 &a, v4u32 &b) { asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(b)::"memory"); }
-__device__ __forceinline__ void lds_flag_wr2(lds_u32 *p, int v, lds_u32 *q, int w)
-{
-    asm volatile("ds_write_b32 %0, %1\n\tds_write_b32 %2, %3" ::"v"(p), "v"(v), "v"(q), "v"(w) : "memory");
-}
-// Flag write without an exec mask: lane 0's address is the flag, the other lanes write their
-// own scratch word (one ds_write, no saveexec / branch around it).
-__device__ __forceinline__ void lds_flag_wr(lds_u32 *p, int v) { asm volatile("ds_write_b32 %0, %1" ::"v"(p), "v"(v) : "memory"); }
-__device__ __forceinline__ int lds_rd32(const lds_u32 *p)
-{
-    int r;
-    asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(r) : "v"(p) : "memory");
-    return r;
-}
-__device__ __forceinline__ void lds_wr32(lds_u32 *p, int v) { asm volatile("ds_write_b32 %0, %1" ::"v"(p), "v"(v) : "memory"); }
-// Wait until flag f >= v; returns the value seen (callers cache it: a producer is usually
-// several blocks ahead, so most blocks need no flag read), or -1 after GOL_SPIN_LIMIT polls.
-// A wave that sees -1 leaves its loop, every wave waiting on it times out the same way, and
-// each records GOLK_ERR_SPIN in the launch's error word on its way out (once, after the loop:
-// an atomic inside the loop costs the pipeline registers), so the host reports the launch as
-// failed (GOL_EHIP) instead of returning a board with unwritten strips.
-// YIELD (the byte pipeline, whose waves run at priority 1): the polling wave drops to priority 0,
-// so the computing waves of its SIMD win the issue arbitration (+1.5 % on 16384^2 bytes; the band
-// pipeline measured 0 / -1 %, same box).
-template <bool YIELD = false>
-__device__ __forceinline__ int spin_until_ge(const lds_u32 *f, int v)
-{
-    if constexpr (YIELD) __builtin_amdgcn_s_setprio(0);
-#pragma clang loop unroll(disable)
-    for (int n = 0; n < GOL_SPIN_LIMIT; ++n) {
-        const int x = __builtin_amdgcn_readfirstlane(lds_rd32(f));
-        if (x >= v) {
-            if constexpr (YIELD) __builtin_amdgcn_s_setprio(1);
-            return x;
-        }
-        __builtin_amdgcn_s_sleep(YIELD ? GOL_BYTES_SPIN_SLEEP : GOL_SPIN_SLEEP);
-    }
-    if constexpr (YIELD) __builtin_amdgcn_s_setprio(1);
-    return -1;
-}
-
-// ------------------------------------------------------------------ band layout, split pipeline
-// Pair step of one stage.  The stage's input stream x_0, x_1, ... arrives in
-// pairs (x_2m, x_2m+1) = (r0, r1); its state holds the horizontal 3-sums of x_2m-2 (a) and
-// x_2m-1 (b) and the cells of x_2m-1 (cb).  It emits the next state of rows 2m-1 and 2m in
-// place of r0, r1 (one row of delay per stage, as a row-by-row stage) and moves its state on by
-// two rows.  The two outputs share the sum of their common rows P = b + c = p0 + 2 p1 + 4 p2
-// (c = x_2m's 3-sums; 4 gates), then each takes a 4-gate tail over (P, the third row's sums, its
-// cell) found by exhaustive search (tools/rule_search_pair.c; tests/test_rule_circuit_cpu.py
-// checks it on every 4 x 3 neighbourhood): with the 2 gates of each row's horizontal sum a
-// generation is 8 ops per 32 cells instead of 9.  The tail relies on the cell's row being one of
-// the pair (the pair sum of a live cell is >= 1, of a dead one <= 5), which holds for both outputs.
-constexpr unsigned TT_PG1 = 0x43;   // (p0, x0, cell)
-constexpr unsigned TT_PG2 = 0x25;   // (p1, p2, x1)
-constexpr unsigned TT_PG3 = 0x8D;   // (p2, cell, g1)
-constexpr unsigned TT_POUT = 0x90;  // (g3, g1, g2)
-__device__ __forceinline__ uint32_t pair_tail(uint32_t p0, uint32_t p1, uint32_t p2, uint32_t x0, uint32_t x1,
-                                              uint32_t cell)
-{
-    const uint32_t g1 = bitop3<TT_PG1>(p0, x0, cell);
-    const uint32_t g2 = bitop3<TT_PG2>(p1, p2, x1);
-    const uint32_t g3 = bitop3<TT_PG3>(p2, cell, g1);
-    return bitop3<TT_POUT>(g3, g1, g2);
-}
-template <int DW>
-struct PairState {
-    uint32_t a0[DW], a1[DW], b0[DW], b1[DW], cb[DW];
-};
-template <int DW>
-__device__ __forceinline__ void pstage(PairState<DW> &s, uint32_t (&r0)[DW], uint32_t (&r1)[DW])
-{
-    // word by word, so that few temporaries are live at once (the pipeline holds 5 KW DW state
-    // registers beside this); the outputs go to o0 / o1 because a word's 3-sums need its
-    // neighbour words' old values.  (Writing the lane's edge words first -- the next stage's DPP
-    // moves read them, and a DPP move right after the VALU op that wrote its source waits on an
-    // s_nop -- cut the s_nops per trip from 43 to 15 and measured equal, same box.)
-    const uint32_t l0 = from_lower_lane(r0[DW - 1]), u0 = from_upper_lane(r0[0]);
-    const uint32_t l1 = from_lower_lane(r1[DW - 1]), u1 = from_upper_lane(r1[0]);
-    uint32_t o0[DW], o1[DW];
-#pragma unroll
-    for (int j = 0; j < DW; ++j) {
-        const uint32_t x0 = r0[j], x1 = r1[j];
-        const uint32_t w0 = j == 0 ? l0 : r0[j - 1], w1 = j == 0 ? l1 : r1[j - 1];
-        const uint32_t n0 = j == DW - 1 ? u0 : r0[j + 1], n1 = j == DW - 1 ? u1 : r1[j + 1];
-        const uint32_t c0 = bitop3<TT_XOR3>(w0, x0, n0), c1 = bitop3<TT_MAJ>(w0, x0, n0);
-        const uint32_t d0 = bitop3<TT_XOR3>(w1, x1, n1), d1 = bitop3<TT_MAJ>(w1, x1, n1);
-        const uint32_t k = s.b0[j] & c0;
-        const uint32_t p0 = s.b0[j] ^ c0;
-        const uint32_t p1 = bitop3<TT_XOR3>(s.b1[j], c1, k);
-        const uint32_t p2 = bitop3<TT_MAJ>(s.b1[j], c1, k);
-        o0[j] = pair_tail(p0, p1, p2, s.a0[j], s.a1[j], s.cb[j]);  // row 2m-1: above = x_2m-2
-        o1[j] = pair_tail(p0, p1, p2, d0, d1, x0);                 // row 2m: below = x_2m+1
-        s.a0[j] = c0;
-        s.a1[j] = c1;
-        s.b0[j] = d0;
-        s.b1[j] = d1;
-        s.cb[j] = x1;
-    }
-#pragma unroll
-    for (int j = 0; j < DW; ++j) {
-        r0[j] = o0[j];
-        r1[j] = o1[j];
-    }
-}
-
-// The K = KW*P stages split over the P waves of one workgroup: wave w runs stages
-// [w*KW, (w+1)*KW) and hands every block of RPB = 2 rows (one pair step) to wave w+1 through an
-// LDS ring of NS = 4 slots.  A wave then holds 5*KW*4 pipeline VGPRs instead of 5*K*4, which fits
-// 4 waves per SIMD.  Wave 0 stages its input rows HBM -> LDS with global_load_lds (no VGPRs),
-// wave P-1 stores to HBM.  Synchronisation is per ring, by LDS flags: ready[e] = blocks
-// published into ring e, consumed[e] = blocks taken out of it; a producer fills slot b % NS
-// once block b-NS is consumed.  Every spin is bounded (spin_until_ge).  1-D grid of work items
-// (work_item).
-// COUNT: the last wave adds the alive cells of the rows it stores to a.slots (branch-free: a
-// per-row uniform select, no branch around the count as a null-slots check made it).
-// Role placement (GOL_BAND_PLACE): a workgroup of the band pipeline claims a free slot q (0..3) in
-// its CU's mask and each wave takes pipeline role (its SIMD + q) % 4, so that the (up to) four
-// workgroups resident on a CU put one wave of every role on every SIMD.  (Roles by wave index +
-// a per-workgroup rotation put two waves of one role on a SIMD for 64-75 % of the waves,
-// tools/timeline.py, profiles/r03/r03h_tl_roles.jsonl.)  Vector atomics of lane 0.
-#ifndef GOL_BAND_PLACE
-#define GOL_BAND_PLACE 1
-#endif
-__device__ __forceinline__ uint32_t cu_slot_index()
-{
-    const uint32_t hw = __builtin_amdgcn_s_getreg((31 << 11) | 4);  // HW_ID
-    const uint32_t xcc = __builtin_amdgcn_s_getreg((31 << 11) | 20) & 7u;  // XCC_ID
-    return (xcc << 8) | (((hw >> 13) & 7u) << 5) | (((hw >> 12) & 1u) << 4) | ((hw >> 8) & 0xFu);
-}
-__device__ __forceinline__ int claim_cu_slot(uint32_t *m)
-{
-    uint32_t cur = __hip_atomic_load(m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    for (int i = 0; i < 8; ++i) {
-        const uint32_t fr = ~cur & 0xFu;
-        if (!fr) return -1;
-        const int b = __ffs(fr) - 1;
-        const uint32_t old = atomicCAS(m, cur, cur | (1u << b));
-        if (old == cur) return b;
-        cur = old;
-    }
-    return -1;
-}
-
-// Cache policy bits of the band pipeline's output stores (2 = nt, streaming) and input loads.
-#ifndef GOL_BAND_STORE_AUX
-#define GOL_BAND_STORE_AUX 2
-#endif
-#ifndef GOL_BAND_LOAD_AUX
-#define GOL_BAND_LOAD_AUX 0
-#endif
-// (Pipeline shape of k = 12, GOL_BAND_KW / _P / _RPB / _NS: gol_strips.h.)
-// The loader issues block b + GOL_BAND_PREFETCH at block b (its in_ring slot was read at the start
-// of block b + GOL_BAND_PREFETCH - NS, so up to NS) and waits for block b + 1 only.  Same box, 3
-// reps: 3 against 2 weak 163.6-164.1 vs 163.1-163.7 TCUPS, 262144^2 +0.6 %, 65536^2 +1.2 %; 4 as 3
-// (profiles/r05/r05d_ab_prefetch.jsonl).
-#ifndef GOL_BAND_PREFETCH
-#define GOL_BAND_PREFETCH 3
-#endif
-template <int KW, int P, bool CONTIG, bool COUNT>
-__global__ void __launch_bounds__(64 * P)
-__attribute__((amdgpu_waves_per_eu(KW >= 4 ? 3 : 4, 8)))  // 5 KW DW pipeline VGPRs
-band_pipe_kernel(BitsArgs a)
-{
-    constexpr int DW = 4;
-    constexpr int K = KW * P;
-    constexpr int HL = band_halo_lanes(K, DW);
-    constexpr int U = band_useful_words(K, DW);
-    constexpr int ROW = 64 * DW;
-    constexpr int RPB = GOL_BAND_RPB;  // rows per block: one pair step
-    constexpr int NS = GOL_BAND_NS;    // (the loops below are unrolled over the NS slots)
-    static_assert(RPB == 2, "a block is one pair step");
-    __shared__ uint32_t in_ring[NS][RPB][ROW];
-    __shared__ uint32_t ring_[P - 1][NS][RPB][ROW];  // ring e+1 in the text = ring[e] here
-    __shared__ int ready_[P], consumed_[P];
-    __shared__ int flag_scratch[64];  // dummy target of lanes 1..63's flag writes (never read; all waves share it)
-    __shared__ int place_[P + 2];  // GOL_BAND_PLACE: SIMD of each wave, the CU slot, the mask index
-
-    const int lane = threadIdx.x & 63;
-    const int litem = (int)blockIdx.x;
-    int group, s0, s1, rotv;
-    const bool has_rows = work_item(a.sm, a.ngroups, a.row0, a.rows, a.strip, litem, [] { return gridDim.x; }, group, s0, s1, rotv);
-    uint32_t *ctr;
-    const int dir = work_dir(a.sm, litem, ctr);  // 0: static strip, +1 / -1: paired (StripMap)
-    // Pipeline position of this wave, rotated per workgroup (role placement below refines it)
-    int wv = __builtin_amdgcn_readfirstlane(((threadIdx.x >> 6) + rotv) % P);
-    constexpr bool PLACE = GOL_BAND_PLACE && P == 4;
-
-    const int64_t col_raw = (int64_t)group * U + (int64_t)(lane - HL) * DW;
-    const int64_t band_q = col_raw >= 0 ? col_raw / a.Wd : -((-col_raw + a.Wd - 1) / a.Wd);
-    const int64_t col = col_raw - band_q * a.Wd;
-    const uint32_t rot = (uint32_t)band_q & 31u;
-    const bool wrap = __ballot(rot != 0) != 0;
-    const bool writer = lane >= HL && lane < 64 - HL && col_raw < a.Wd;
-
-    const int R = (int)a.R;
-    const int first_in = s0 - K;
-    const int last_in = s1 + K - 1;
-    // the stream: input row first_in + t at stream step t (walking up, dir -1: s1e + K - 1 - t);
-    // output row first_in + t - K (s1e - 1 + 2K - t), valid from step 2K on
-    const int nblk = ((s1 - s0) + 2 * K + RPB - 1) / RPB;
-    // a pair's range, stretched to s1e so that TRIP divides its len + 4K (whole loop trips); rows
-    // past s1 are read clamped and never stored; nclaim: blocks of the pair, a multiple of NS
-    // (gol_strips.h: the expressions the host's pair_extent evaluates)
-    constexpr int TRIP = RPB * NS;  // rows per loop trip
-    const int s1e = GOL_PAIR_S1E(dir, s0, s1, K, TRIP);
-    const int nclaim = GOL_PAIR_NCLAIM(s0, s1e, K, RPB);
-
-    const int pitch_b = (int)a.pitch * 4;
-    const char *mid_b = reinterpret_cast<const char *>(a.mid);
-    const int64_t top_d = (reinterpret_cast<const char *>(a.top) - mid_b) + (int64_t)K * pitch_b;
-    const int64_t bot_d = (reinterpret_cast<const char *>(a.bot) - mid_b) - (int64_t)R * pitch_b;
-    const uint32_t lane_off = (uint32_t)col * 4u;
-    char *dst_b = reinterpret_cast<char *>(a.dst);
-    const uint32_t st_off = writer ? lane_off : 0x80000000u;
-
-    // wave 0: block b -> in_ring[b % NS] (global_load_lds).  The slot is an argument: a lambda
-    // that captures a __shared__ array silently loses the kernel's host-side stub.
-    // Interior blocks (both rows inside [first_in, last_in] and, unless CONTIG, inside the shard's
-    // own rows: every block but the first and last few of a strip) take the row address carried
-    // from the previous block (uniform) plus the lane's offset; the others clamp and pick the row's
-    // segment per row.  stage_in is called for blocks 0, 1, 2, ... in order.
-    // The slot is an LDS-typed pointer (a generic one costs a null check per load: 4 SALU).  The
-    // interior blocks are one range [ib_lo, ib_lo + ib_n) of block numbers, found here once.
-    const int in_lo = CONTIG ? first_in : max(first_in, 0), in_hi = CONTIG ? last_in : min(last_in, R - 1);
-    const int64_t row_step = dir >= 0 ? (int64_t)pitch_b : -(int64_t)pitch_b;
-    const int y_first = dir >= 0 ? first_in : s1e + K - 1;  // first row of block 0
-    const int ib_lo = dir >= 0 ? div_ceil_nn(in_lo - y_first, RPB) : div_ceil_nn(y_first - in_hi, RPB);
-    const int ib_hi = dir >= 0 ? div_floor(in_hi - (RPB - 1) - y_first, RPB) : div_floor(y_first - (RPB - 1) - in_lo, RPB);
-    const uint32_t ib_n = ib_hi >= ib_lo ? (uint32_t)(ib_hi - ib_lo + 1) : 0u;
-    const char *st_row = mid_b + (int64_t)y_first * pitch_b;  // the next block's first row (used when interior)
-    auto stage_in = [&](int b, lds_u32 *slot) {
-        const char *g0 = st_row;
-        st_row += RPB * row_step;
-        if ((uint32_t)(b - ib_lo) < ib_n) {
-            // The block's two rows as two LDS-DMA loads in the SGPR-base form (the row address in
-            // an SGPR pair, the lane's 32-bit offset in a VGPR): the builtin's address computation
-            // made the compiler use the 64-bit VGPR-address form here, one v_lshl_add_u64 and a
-            // VGPR pair read per load.  Same box, 3 reps: weak +0.6-1.0 %, 262144^2 +-0
-            // (profiles/r06/r06_ab_saddr.jsonl).  M0 (the LDS destination) is written and
-            // restored inside the statement, one wait state before each load (the hazard scan of
-            // tools/check_lds_wait.py checks it); s_nop 4 first covers an SGPR base that a VALU
-            // (readfirstlane) may have written.
-            static_assert(RPB == 2 && GOL_BAND_LOAD_AUX == 0, "two rows per block, default cache policy");
-            uint32_t keep;
-            const char *g1 = g0 + row_step;
-            asm volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
-                         "global_load_lds_dwordx4 %1, %3\n\ts_mov_b32 m0, %4\n\ts_nop 0\n\t"
-                         "global_load_lds_dwordx4 %1, %5\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep)
-                         : "v"(lane_off), "s"(slot), "s"(g0), "s"(slot + ROW), "s"(g1)
-                         : "memory");
-            return;
-        }
-#pragma unroll
-        for (int s = 0; s < RPB; ++s) {
-            const int t = RPB * b + s;  // stream position
-            int y = dir >= 0 ? first_in + t : s1e + K - 1 - t;
-            y = y > last_in ? last_in : (y < first_in ? first_in : y);
-            const int64_t d = CONTIG ? 0 : (y < 0 ? top_d : (y >= R ? bot_d : 0));
-            const char *g = mid_b + (d + (int64_t)y * pitch_b) + lane_off;
-            __builtin_amdgcn_global_load_lds(reinterpret_cast<const void *>(g), slot + s * ROW, 16, 0, GOL_BAND_LOAD_AUX);
-        }
-    };
-
-    if (!has_rows) return;  // whole workgroup (no barrier after this point)
-    if (threadIdx.x < P) { ready_[threadIdx.x] = 0; consumed_[threadIdx.x] = 0; }
-    if constexpr (PLACE) {
-        if (lane == 0) place_[threadIdx.x >> 6] = (int)((__builtin_amdgcn_s_getreg((31 << 11) | 4) >> 4) & 3u);
-        if (threadIdx.x == 0) {
-            const uint32_t idx = cu_slot_index();
-            place_[P] = a.cu_slots ? claim_cu_slot(a.cu_slots + idx) : -1;
-            place_[P + 1] = (int)idx;
-        }
-    }
-    __syncthreads();
-    if constexpr (PLACE) {
-        const int q = place_[P];
-        const int m = (1 << place_[0]) | (1 << place_[1]) | (1 << place_[2]) | (1 << place_[3]);
-        if (q >= 0 && m == 0xF) wv = __builtin_amdgcn_readfirstlane((place_[threadIdx.x >> 6] + q) & 3);
-    }
-    lds_u32 *const ring_l = (lds_u32 *)&ring_[0][0][0][0];
-    lds_u32 *const in_l = (lds_u32 *)&in_ring[0][0][0];
-    lds_u32 *const ready_l = (lds_u32 *)&ready_[0];
-    lds_u32 *const consumed_l = (lds_u32 *)&consumed_[0];
-    constexpr int SLOT = RPB * ROW;  // uint32 per slot (one block)
-
-    PairState<DW> st[KW];
-#pragma unroll
-    for (int g = 0; g < KW; ++g)
-#pragma unroll
-        for (int j = 0; j < DW; ++j) { st[g].a0[j] = 0; st[g].a1[j] = 0; st[g].b0[j] = 0; st[g].b1[j] = 0; st[g].cb[j] = 0; }
-    uint32_t alive = 0;
-    const uint32_t st_mask = writer ? 0xFFFFFFFFu : 0u;
-    int seen_ready = 0, seen_free = 0;  // cached flag values (ring wv ready, ring wv+1 consumed)
-    const uint32_t nrows = (uint32_t)(s1 - s0);
-    // One loop per role (0 = loader, 1 = middle, 2 = last), unrolled over the NS ring slots so
-    // every LDS address is a per-lane register plus an immediate offset and every wait count is
-    // a constant.  Per block b (LDS operations of a wave complete in order):
-    //  * wait for block b's two rows (read at the end of block b-1, the wave's youngest LDS
-    //    operations: lgkmcnt(0), which also completes block b-1's row writes);
-    //  * readers: write "block b consumed"; writers: publish "blocks < b ready";
-    //  * compute the pair through the wave's KW stages;
-    //  * writers: make sure slot b % NS is free, write the two rows; the last wave stores them
-    //    to HBM;
-    //  * readers: make sure block b+1 is published; the loader instead refills block b-2's slot
-    //    with block b+2 (global_load_lds) and waits (vmcnt) for block b+1's; read block b+1's rows;
-    //  * the block count is padded to a multiple of NS: padding blocks read clamped rows and
-    //    their stores fall outside the strip's buffer range.
-    //  (Reading the next rows before the compute instead holds 8 more VGPRs across it: the kernel
-    //  then spills at 128.)
-    const int nblkT = (nblk + NS - 1) / NS * NS;
-    constexpr int SB = SLOT * 4, RB = ROW * 4;  // slot and row strides in bytes
-    lds_u32 *const scratch = (lds_u32 *)&flag_scratch[0] + lane;
-    lds_u32 *const rdy_addr = lane == 0 ? ready_l + wv + 1 : scratch;  // writer: ring wv+1 ready
-    lds_u32 *const cns_addr = lane == 0 ? consumed_l + wv : scratch;   // reader: ring wv consumed
-    lds_u32 *const in_base = in_l + lane * 4;
-    lds_u32 *const rd_base = ring_l + (wv - 1) * NS * SLOT + lane * 4;  // ring wv (wv >= 1)
-    lds_u32 *const wr_base = ring_l + wv * NS * SLOT + lane * 4;        // ring wv+1 (wv < P-1)
-    auto unpack = [&](const v4u32 v, uint32_t (&cur)[DW]) { cur[0] = v.x; cur[1] = v.y; cur[2] = v.z; cur[3] = v.w; };
-    auto pack = [&](const uint32_t (&cur)[DW]) { return v4u32{cur[0], cur[1], cur[2], cur[3]}; };
-    // last wave: output row y = s0 + 2b + S - 2K, stored at voffset lane_off + (y - s0) * pitch
-    // of a buffer spanning the strip's rows: rows before s0 (negative offsets, as unsigned
-    // >= 2^32 - 2K * pitch) and from s1 on fall outside it, and so does a halo lane's 2^31.
-    const __amdgpu_buffer_rsrc_t strip_rs = __builtin_amdgcn_make_buffer_rsrc(
-        dst_b + (int64_t)s0 * pitch_b, (short)0, (int)(nrows * (uint32_t)pitch_b), 0x00020000);
-    // (walking up, dir -1: output row y = s1e - 1 + 2K - 2b - S, offsets decreasing)
-    // (readfirstlane: the compiler otherwise keeps this uniform row index in a VGPR and compares it
-    // with a vector compare per row)
-    int rrel = __builtin_amdgcn_readfirstlane(dir >= 0 ? -2 * K : s1e - 1 + 2 * K - s0);  // output row - s0
-    const int rstep = dir >= 0 ? 1 : -1;
-    uint32_t voff = st_off + (uint32_t)rrel * (uint32_t)pitch_b;
-    const uint32_t vstep = (uint32_t)rstep * (uint32_t)pitch_b;
-    // a row's cells onto the count: one accumulating v_bcnt per word, as one asm statement (the
-    // compiler turns the same chain in C into bcnt pairs + v_add3).  Plain VALU reading VALU
-    // results: no wait states inside (tools/check_lds_wait.py checks the pipeline kernels' asm for
-    // the VALU hazards the compiler cannot see).
-    auto count_row = [&](const uint32_t (&cur)[DW]) {
-        uint32_t c = 0;
-        asm("v_bcnt_u32_b32 %0, %1, 0\n\tv_bcnt_u32_b32 %0, %2, %0\n\tv_bcnt_u32_b32 %0, %3, %0\n\t"
-            "v_bcnt_u32_b32 %0, %4, %0"
-            : "=&v"(c)
-            : "v"(cur[0]), "v"(cur[1]), "v"(cur[2]), "v"(cur[3]));
-        return c;
-    };
-    auto count_rows2 = [&](const uint32_t (&x0)[DW], const uint32_t (&x1)[DW]) {
-        asm("v_bcnt_u32_b32 %0, %1, %0\n\tv_bcnt_u32_b32 %0, %2, %0\n\tv_bcnt_u32_b32 %0, %3, %0\n\t"
-            "v_bcnt_u32_b32 %0, %4, %0\n\tv_bcnt_u32_b32 %0, %5, %0\n\tv_bcnt_u32_b32 %0, %6, %0\n\t"
-            "v_bcnt_u32_b32 %0, %7, %0\n\tv_bcnt_u32_b32 %0, %8, %0"
-            : "+v"(alive)
-            : "v"(x0[0]), "v"(x0[1]), "v"(x0[2]), "v"(x0[3]), "v"(x1[0]), "v"(x1[1]), "v"(x1[2]), "v"(x1[3]));
-    };
-    // the block's two output rows to HBM, and the fused count of the rows this strip stores (halo
-    // lanes are masked once at the end): one v_bcnt chain of 8 words onto the count, and a block at
-    // a strip's end (a row outside it: a uniform branch) takes the count of that row off again.
-    // (Round 5's per-row select cost 15 VALU per block instead of 8: the count in bcnt pairs +
-    // v_add3, a vector compare and a select per row.)
-    auto emit2 = [&](const uint32_t (&x0)[DW], const uint32_t (&x1)[DW]) {
-        __builtin_amdgcn_raw_buffer_store_b128(pack(x0), strip_rs, voff, 0, GOL_BAND_STORE_AUX);
-        __builtin_amdgcn_raw_buffer_store_b128(pack(x1), strip_rs, voff + vstep, 0, GOL_BAND_STORE_AUX);
-        if constexpr (COUNT) {
-            count_rows2(x0, x1);
-            const bool in0 = (uint32_t)rrel < nrows, in1 = (uint32_t)(rrel + rstep) < nrows;  // wave-uniform
-            if (!(in0 && in1)) alive -= (in0 ? 0u : count_row(x0)) + (in1 ? 0u : count_row(x1));
-        }
-        voff += 2 * vstep;
-        rrel += 2 * rstep;
-    };
-    lds_u32 *const src_base = wv == 0 ? in_base : rd_base;
-    // paired: the loader's claims, NS blocks (one loop trip) each, one in flight (issued at a
-    // trip's first block, used at the next trip's start); the first before block 0's loads
-    constexpr int FINAL = 1 << 30;  // ready flag = FINAL + blocks: the stream has ended
-    // (lane 0 claims; the kernels are built without the atomic optimizer, which broadcast the
-    // claim's return at once and so waited for it right there: an atomic round trip per trip)
-    uint32_t pending = 0;
-    if (wv == 0 && dir && lane == 0) pending = atomicAdd(ctr, (uint32_t)NS);
-    // block 0's rows, read to completion here (the compiler copies the loop-carried registers
-    // on loop entry, which must not happen while a read is in flight)
-    constexpr int PF = GOL_BAND_PREFETCH;
-    static_assert(PF >= 2 && PF <= NS, "blocks b+1 .. b+PF in flight in NS slots");
-    if (wv == 0) {
-        stage_in(0, in_l);
-        stage_in(1, in_l + SLOT);
-        if constexpr (PF > 2) stage_in(2, in_l + (2 % NS) * SLOT);
-        if constexpr (PF > 3) stage_in(3, in_l + (3 % NS) * SLOT);
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(RPB * (PF - 1)) : "memory");  // block 0 (and the claim)
-    } else if (seen_ready < 1) {
-        seen_ready = spin_until_ge(ready_l + wv, 1);
-        if (seen_ready < 0) {
-            raise_error(a.err, GOLK_ERR_SPIN);
-            return;
-        }
-    }
-    v4u32 nx0 = lds_rd128_issue_o<0>(src_base);
-    v4u32 nx1 = lds_rd128_issue_o<RB>(src_base);
-    lds_wait_n<0>(nx0);
-    lds_wait_n<0>(nx1);
-    // readers: the block the loop is about to run exists (an empty paired stream ends at once)
-    bool more = !(seen_ready >= FINAL && seen_ready - FINAL == 0);
-    auto step = [&](int b, auto u_c, auto role_c, auto dyn_c, auto skip_c) -> bool {
-        constexpr int US = decltype(u_c)::value;
-        constexpr int ROLE = decltype(role_c)::value;
-        constexpr bool DYN = decltype(dyn_c)::value;
-        constexpr bool SKIP = decltype(skip_c)::value;  // a fill block: no rule (see run)
-        constexpr bool LAST = ROLE == 2;
-        constexpr int NXT = (US + 1) % NS;
-        uint32_t r0[DW], r1[DW];
-        // block b's rows, the youngest LDS operations of this wave: once they are in, so are
-        // block b-1's row writes, and both flags can go out at once
-        lds_settle2(nx0, nx1);
-        unpack(nx0, r0);
-        unpack(nx1, r1);
-        if constexpr (ROLE == 1) lds_flag_wr2(cns_addr, b + 1, rdy_addr, b);
-        else if constexpr (ROLE != 0) lds_flag_wr(cns_addr, b + 1);  // block b's slot is free
-        else lds_flag_wr(rdy_addr, b);          // blocks < b are in ring wv+1
-        if constexpr (ROLE == 0) {
-            if (wrap) {
-#pragma unroll
-                for (int j = 0; j < DW; ++j) {
-                    r0[j] = __builtin_amdgcn_alignbit(r0[j], r0[j], rot);
-                    r1[j] = __builtin_amdgcn_alignbit(r1[j], r1[j], rot);
-                }
-            }
-        }
-        if constexpr (!SKIP) {
-#pragma unroll
-            for (int g = 0; g < KW; ++g) pstage<DW>(st[g], r0, r1);
-        }
-        if constexpr (LAST) {
-            emit2(r0, r1);
-        } else {
-            if (seen_free < b + 1 - NS) {  // slot b % NS: block b - NS consumed
-                seen_free = spin_until_ge(consumed_l + wv + 1, b + 1 - NS);
-                if (seen_free < 0) return false;
-            }
-            lds_wr128x2_o<US * SB, US * SB + RB>(wr_base, pack(r0), pack(r1));
-        }
-        // block b+1's rows: read now, waited for at the next block's start (the compute of the
-        // other waves of the SIMD covers the LDS latency)
-        if constexpr (ROLE == 0) {
-            stage_in(b + PF, in_l + ((US + PF) % NS) * SLOT);  // refills block b+PF-NS's slot (clamped past the end)
-            // block b+1 landed, b+2 .. b+PF in flight (and, paired, at US 1 the claim issued at US 0)
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(RPB * (PF - 1) + (DYN && US == 1 ? 1 : 0)) : "memory");
-            if constexpr (DYN && US == 0) {
-                if (lane == 0) pending = atomicAdd(ctr, (uint32_t)NS);
-            }
-        } else {
-            // the next block exists unless the writer's flag says the stream ended before it
-            if (seen_ready < b + 2) {
-                seen_ready = spin_until_ge(ready_l + wv, b + 2);
-                if (seen_ready < 0) return false;
-            }
-            more = seen_ready < FINAL || b + 1 < seen_ready - FINAL;
-        }
-        lds_rd128x2_issue_o<NXT * SB, NXT * SB + RB>(src_base, nx0, nx1);  // (past the stream's end: a stale slot, unused)
-        return true;
-    };
-    // blocks the loader has: nblkT, or (paired) the claims granted so far
-    auto grant = [&](uint32_t c) { return c >= (uint32_t)nclaim ? 0 : NS; };
-    auto trip = [&](int b, auto role_c, auto dyn_c, auto skip_c) -> bool {
-        return step(b, std::integral_constant<int, 0>(), role_c, dyn_c, skip_c) &&
-               step(b + 1, std::integral_constant<int, 1>(), role_c, dyn_c, skip_c) &&
-               step(b + 2, std::integral_constant<int, 2>(), role_c, dyn_c, skip_c) &&
-               step(b + 3, std::integral_constant<int, 3>(), role_c, dyn_c, skip_c);
-    };
-    static_assert(NS == 4, "trip() runs NS steps");
-    auto run = [&](auto role_c, auto dyn_c) -> bool {
-        constexpr int ROLE = decltype(role_c)::value;
-        constexpr bool DYN = decltype(dyn_c)::value;
-        int nb = DYN ? 0 : nblkT;
-        int b = 0;
-        // Fill blocks: stage g's input is valid from stream step 2g on, and a stage whose state
-        // missed the steps before S emits garbage only up to step S + 1, which no later stage uses
-        // if S <= 2g (stage g's outputs are read from step 2g + 2 on; the last stage's rows before
-        // step 2K fall outside the strip).  A wave whose first stage is g0 = KW * wv therefore
-        // passes the blocks before step 2 g0 (2b + 1 < 2 g0: b < g0) on without the rule -- whole
-        // loop trips of them, in a loop of their own (a branch per block inside the main loop made
-        // the compiler spill).
-        if constexpr (ROLE != 0) {
-            const int nskip = KW * wv;
-            for (; b + NS <= nskip; b += NS) {
-                if (!more) break;
-                if (!trip(b, role_c, dyn_c, std::true_type())) return false;
-            }
-        }
-        for (;; b += NS) {
-            if constexpr (ROLE == 0) {
-                if constexpr (DYN) nb += grant(__builtin_amdgcn_readfirstlane(pending));
-                if (b >= nb) break;
-            } else {
-                if (!more) break;
-            }
-            if (!trip(b, role_c, dyn_c, std::false_type())) return false;
-        }
-        // the last block's reads of the next slot are still in flight: land them before their
-        // registers are used for anything else
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        if constexpr (ROLE != 2) {
-            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-            lds_flag_wr(rdy_addr, FINAL + b);
-        }
-        if constexpr (ROLE == 0 && DYN) {
-            if (lane == 0 && atomicAdd(ctr + 1, 1u) == 1u) {  // both loaders' claims are over
-                atomicExch(ctr, 0u);
-                atomicExch(ctr + 1, 0u);
-            }
-        }
-        return true;
-    };
-    // (paired or not changes only the loader's loop: the readers' loops are one instantiation,
-    // 65 -> 44 KB of code per kernel; measured equal, same box: weak -0.5 %, 262144^2 +0.8 %,
-    // 65536^2 -0.6 %, profiles/r05/r05b_ab_dedupe_bytes.jsonl)
-    auto run_role = [&](auto role_c) -> bool {
-        if constexpr (decltype(role_c)::value != 0) return run(role_c, std::false_type());
-        else return dir ? run(role_c, std::true_type()) : run(role_c, std::false_type());
-    };
-    bool ok;
-    if (wv == 0) ok = run_role(std::integral_constant<int, 0>());
-    else if (wv == P - 1) ok = run_role(std::integral_constant<int, 2>());
-    else ok = run_role(std::integral_constant<int, 1>());
-    if (!ok) raise_error(a.err, GOLK_ERR_SPIN);
-    alive &= st_mask;  // halo lanes' rows are not this group's
-    if (wv == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (COUNT && wv == P - 1) slot_add(a.slots, alive);
-    if constexpr (PLACE) {  // the last wave of the pipeline frees the workgroup's CU slot
-        if (wv == P - 1 && lane == 0 && place_[P] >= 0) atomicAnd(a.cu_slots + place_[P + 1], ~(1u << place_[P]));
-    }
-}
-
-#ifdef GOL_TU_BAND_PIPE
-}  // namespace golk
-
-// gol_band_pipe.hip: this file up to here, compiled on its own with the max-ILP machine
-// scheduler (Makefile BANDFLAGS): band_pipe_kernel's instantiations, their host stubs and launch.
-// The scheduler choice is per translation unit, and it is a per-kernel one: same box, 2 reps,
-// max-ILP ran the band boards 1.0-1.9 % faster (weak 148.3 vs 146.8, 262144^2 151.5 vs 148.9,
-// 65536^2 139.8 vs 137.2) and the byte pipeline 4.5 % slower (56.8 vs 59.4);
-// profiles/r04/r04h_sched.jsonl.
-using namespace golk;
-const void *golk_band_pipe_fn(bool contig, bool count)
-{
-    constexpr int KW = GOL_BAND_KW, P = GOL_BAND_P;
-    return contig ? (count ? (const void *)band_pipe_kernel<KW, P, true, true> : (const void *)band_pipe_kernel<KW, P, true, false>)
-                  : (count ? (const void *)band_pipe_kernel<KW, P, false, true> : (const void *)band_pipe_kernel<KW, P, false, false>);
-}
-hipError_t golk_band_pipe_launch(bool contig, bool count, unsigned nwg, const BitsArgs &a, hipStream_t s)
-{
-    constexpr int KW = GOL_BAND_KW, P = GOL_BAND_P;
-    const dim3 g(nwg), blk(64 * P);
-    if (contig && count) hipLaunchKernelGGL((band_pipe_kernel<KW, P, true, true>), g, blk, 0, s, a);
-    else if (contig) hipLaunchKernelGGL((band_pipe_kernel<KW, P, true, false>), g, blk, 0, s, a);
-    else if (count) hipLaunchKernelGGL((band_pipe_kernel<KW, P, false, true>), g, blk, 0, s, a);
-    else hipLaunchKernelGGL((band_pipe_kernel<KW, P, false, false>), g, blk, 0, s, a);
-    return hipGetLastError();
-}
-#else  // the rest of the kernels and the host side
-
 // 32 x 32 bit-matrix transpose in registers: afterwards x[i] bit b = (before) x[b] bit i.
 __device__ __forceinline__ void transpose32(uint32_t (&x)[32])
 {
@@ -1313,61 +431,6 @@ __global__ void band_convert_kernel(const uint32_t *src, uint32_t *dst, int64_t 
 // packs 32 bytes of a row into one 32-cell word (bit i = byte i & 1), runs the same K-stage
 // shifted-frame register pipeline as the standard bit board and unpacks the result to 0/255
 // bytes.  HBM traffic: 2 bytes per cell per K turns.
-__device__ __forceinline__ uint32_t pack32(const uint4 lo, const uint4 hi)
-{
-    const uint32_t d[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-    uint32_t b[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q)  // byte q of the word = cells 8q..8q+7
-        b[q] = __builtin_amdgcn_udot4(d[2 * q] & 0x01010101u, 0x08040201u,
-                                      __builtin_amdgcn_udot4(d[2 * q + 1] & 0x01010101u, 0x80402010u, 0u, false),
-                                      false);
-    return b[0] | (b[1] << 8) | (b[2] << 16) | (b[3] << 24);
-}
-// Same for bytes that are exactly 0x00 or 0xFF (-1 as int8): weights -2^i give +2^i per set byte.
-// (Builtins, not inline asm: a v_dot4 result read by another VALU needs 3 wait states, which the
-// compiler's hazard recognizer inserts only for instructions it can see.  The inline-asm VOP3P
-// form measured +1.5 % and then +-0 on another box, and under the post-RA scheduler it read
-// stale sums: profiles/r05/r05y_ab_bytes_sched.jsonl.)
-__device__ __forceinline__ uint32_t pack32_ff(const uint4 lo, const uint4 hi)
-{
-    const uint32_t d[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-    uint32_t b[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-        b[q] = (uint32_t)__builtin_amdgcn_sdot4((int)d[2 * q], (int)0xF8FCFEFFu,
-                                               __builtin_amdgcn_sdot4((int)d[2 * q + 1], (int)0x80C0E0F0u, 0, false), false);
-    return b[0] | (b[1] << 8) | (b[2] << 16) | (b[3] << 24);
-}
-
-__device__ __forceinline__ void unpack32(const uint32_t w, uint4 &lo, uint4 &hi)
-{
-    uint32_t o[8];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-        const uint32_t n = (w >> (4 * q)) & 0xFu;
-        const uint32_t sp = __umul24(n, 0x00204081u) & 0x01010101u;  // bit i -> byte i
-        o[q] = (sp << 8) - sp;                                       // 0x01 -> 0xFF
-    }
-    lo = make_uint4(o[0], o[1], o[2], o[3]);
-    hi = make_uint4(o[4], o[5], o[6], o[7]);
-}
-
-struct BytesKArgs {
-    const uint8_t *top, *mid, *bot;
-    uint8_t *dst;
-    int64_t R, Wd, pitch, row0, rows;  // Wd = W / 32 words, pitch in bytes
-    int32_t strip, ngroups;
-    uint64_t *slots;
-    uint32_t *err;
-    StripMap sm;
-};
-
-// Byte rows of one lane: 32 bytes = two 16-byte loads, packed to a word at use.
-struct Raw32 {
-    uint4 lo, hi;
-};
-
 // One wave = all K stages (k = 1..16), 62 column words per wave.
 template <int K>
 __global__ void __launch_bounds__(256) bytes_blocked_kernel(BytesKArgs a)
@@ -1448,425 +511,6 @@ __global__ void __launch_bounds__(256) bytes_blocked_kernel(BytesKArgs a)
     }
     if (a.slots) slot_add(a.slots, alive);
 }
-
-// f(integral_constant<0>), .., f(integral_constant<N-1>), unrolled
-template <int N, int I = 0, typename F>
-__device__ __forceinline__ void static_for(F &&f)
-{
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>());
-        static_for<N, I + 1>(f);
-    }
-}
-
-// Byte board, split pipeline: K = KW * P turns per launch, P waves per workgroup on one
-// column group of 62 words (32 cells per lane, standard bit layout in registers, shifted
-// frame), KW stages per wave, blocks of 4 rows (two pair steps, as band_pipe_kernel's, run as a
-// wavefront: the second pair one stage behind the first, two independent pair steps in flight
-// per stage step -- one 32-cell word per lane is otherwise one dependent chain) handed on
-// through LDS rings of NS slots (256 B per row) with band_pipe_kernel's flag protocol and loop
-// shape: one loop per role, unrolled over the NS slots (every LDS address a register plus an
-// immediate, no slot arithmetic, no per-block branch for the fill blocks).  Wave 0 stages its
-// input blocks HBM -> LDS with global_load_lds and packs 32 bytes per lane into one word with
-// v_dot4_i32_i8; wave P-1 realigns (after 32 stages the frame shift is exactly one word),
-// unpacks through a 2 KiB LDS table (byte -> 8 bytes of 0x00 / 0xFF) and stores the strip
-// through one buffer descriptor with a running offset.  One 32-cell word per lane covers K <= 32
-// columns of halo, so K = 32 costs no more lanes than K = 16.
-// (Round 4's form -- 3-row blocks, one block per loop trip with running slot indices and a
-// per-block fill branch -- spent 0.44 scalar instructions per VALU: DESIGN.md §4.4.)
-//
-// Shifted-frame pair step: pstage's circuit on this frame.  A row's 3-sum at bit p is
-// c[p] + c[p-1] + c[p-2] (centred on p-1: the neighbour from the lower lane by one DPP, two
-// v_alignbit), the cell is c[p-1]; every stage moves the frame one bit to the left.
-__device__ __forceinline__ void spstage(PairState<1> &s, uint32_t &r0, uint32_t &r1)
-{
-    const uint32_t w0 = from_lower_lane(r0), w1 = from_lower_lane(r1);
-    const uint32_t l0 = __builtin_amdgcn_alignbit(r0, w0, 31), m0 = __builtin_amdgcn_alignbit(r0, w0, 30);
-    const uint32_t l1 = __builtin_amdgcn_alignbit(r1, w1, 31), m1 = __builtin_amdgcn_alignbit(r1, w1, 30);
-    const uint32_t c0 = bitop3<TT_XOR3>(l0, r0, m0), c1 = bitop3<TT_MAJ>(l0, r0, m0);
-    const uint32_t d0 = bitop3<TT_XOR3>(l1, r1, m1), d1 = bitop3<TT_MAJ>(l1, r1, m1);
-    const uint32_t k = s.b0[0] & c0;
-    const uint32_t p0 = s.b0[0] ^ c0;
-    const uint32_t p1 = bitop3<TT_XOR3>(s.b1[0], c1, k);
-    const uint32_t p2 = bitop3<TT_MAJ>(s.b1[0], c1, k);
-    r0 = pair_tail(p0, p1, p2, s.a0[0], s.a1[0], s.cb[0]);  // row 2m-1: its cell = c[p-1] of x_2m-1
-    r1 = pair_tail(p0, p1, p2, d0, d1, l0);                 // row 2m: its cell = c[p-1] of x_2m
-    s.a0[0] = c0;
-    s.a1[0] = c1;
-    s.b0[0] = d0;
-    s.b1[0] = d1;
-    s.cb[0] = l1;
-}
-
-// (Ring slots of the byte pipeline, GOL_BYTES_NS / _NSI, and GOL_BYTES_PER_CU: gol_strips.h.)
-// Cache policy bits of the byte pipeline's output stores (0: default)
-#ifndef GOL_BYTES_STORE_AUX
-#define GOL_BYTES_STORE_AUX 0
-#endif
-template <int KW, int P, bool COUNT>
-__global__ void __launch_bounds__(64 * P) __attribute__((amdgpu_waves_per_eu(6, 8))) bytes_pipe_kernel(BytesKArgs a)
-{
-    constexpr int K = KW * P;
-    static_assert(K <= 32, "one 32-cell halo word per side");
-    constexpr int RPB = GOL_BYTES_RPB;  // rows per block: two pair steps
-    static_assert(RPB == 4, "a block is two pair steps");
-    constexpr int NS = GOL_BYTES_NS;  // (the loops below are unrolled over the NS slots)
-    constexpr int NSI = GOL_BYTES_NSI;
-    static_assert(NS % NSI == 0 && NSI >= 3, "input slots: 2 blocks in flight, one being read");
-    constexpr int ROW = 64;  // uint32 per ring row
-    __shared__ uint32_t ring[P - 1][NS][RPB][ROW];
-    __shared__ uint32_t in_ring[NSI][RPB][2][256];  // byte rows: [half][lane][16 bytes]
-    __shared__ uint2 lut[256];
-    __shared__ int ready[P], consumed[P];
-    __shared__ int flag_scratch[64];  // dummy target of lanes 1..63's flag writes (lds_flag_wr; never read)
-
-    const int lane = threadIdx.x & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    int group, s0, s1, rotv;
-    if (!work_item(a.sm, a.ngroups, a.row0, a.rows, a.strip, blockIdx.x, [] { return gridDim.x; }, group, s0, s1, rotv)) return;
-    uint32_t *ctr;
-    const int dir = work_dir(a.sm, blockIdx.x, ctr);  // 0: static strip, +1 / -1: paired
-    const int64_t col_raw = (int64_t)group * 62 + (lane - 1);
-    const int64_t col = ((col_raw % a.Wd) + a.Wd) % a.Wd;
-    const bool writer = lane >= 1 && lane <= 62 && col_raw < a.Wd;
-    const int R = (int)a.R;
-    const int first_in = s0 - K, last_in = s1 + K - 1;
-    const int nblk = ((s1 - s0) + 2 * K + RPB - 1) / RPB;
-    // a pair's range, stretched to s1e so that TRIP divides its len + 4K (rows past s1 are read
-    // clamped and never stored: they only feed outputs past s1); nclaim: blocks of the pair, a
-    // multiple of NS (gol_strips.h: the expressions the host's pair_extent evaluates)
-    constexpr int TRIP = RPB * NS;  // rows per loop trip
-    const int s1e = GOL_PAIR_S1E(dir, s0, s1, K, TRIP);
-    const int nclaim = GOL_PAIR_NCLAIM(s0, s1e, K, RPB);
-    const int pitch = (int)a.pitch;
-    const char *mid_b = reinterpret_cast<const char *>(a.mid);
-    const int64_t top_d = (reinterpret_cast<const char *>(a.top) - mid_b) + (int64_t)K * pitch;
-    const int64_t bot_d = (reinterpret_cast<const char *>(a.bot) - mid_b) - (int64_t)R * pitch;
-    const uint32_t lane_off = (uint32_t)(col * 32);
-    char *dst_b = reinterpret_cast<char *>(a.dst);
-    const uint32_t st_off = writer ? lane_off : 0x80000000u;
-    const uint32_t st_mask = writer ? 0xFFFFFFFFu : 0u;
-
-    // stream position t -> input row (walking up, dir -1: from s1e + K - 1)
-    auto in_row = [&](int t) { return dir >= 0 ? first_in + t : s1e + K - 1 - t; };
-    // wave 0: block b -> an in_ring slot (the slot is an argument: a lambda that captures a
-    // __shared__ array loses the kernel's host-side stub).  Interior blocks (both rows inside the
-    // shard and inside [first_in, last_in]: every block but the first and last few of a strip) take
-    // one row address, carried from block to block and stepped by a pitch; the others clamp and
-    // pick the row's segment per row (round 4: +2.4 % on 16384^2 bytes over per-row addresses).
-    // The slot is an LDS-typed pointer (a generic one costs a null check per load: 4 SALU) and the
-    // interior blocks are one range [ib_lo, ib_lo + ib_n) of block numbers, found here once.  (The
-    // load's immediate offset moves its LDS destination too: the second 16 bytes of a lane's 32
-    // take their own address.)
-    const int in_lo = max(first_in, 0), in_hi = min(last_in, R - 1);
-    const int64_t row_step = dir >= 0 ? (int64_t)pitch : -(int64_t)pitch;
-    const int y_first = in_row(0);
-    const int ib_lo = dir >= 0 ? div_ceil_nn(in_lo - y_first, RPB) : div_ceil_nn(y_first - in_hi, RPB);
-    const int ib_hi = dir >= 0 ? div_floor(in_hi - (RPB - 1) - y_first, RPB) : div_floor(y_first - (RPB - 1) - in_lo, RPB);
-    const uint32_t ib_n = ib_hi >= ib_lo ? (uint32_t)(ib_hi - ib_lo + 1) : 0u;
-    const char *st_u = mid_b + (int64_t)y_first * pitch;  // the next block's first row (wave-uniform)
-    constexpr int IROW = 2 * 256;  // uint32 per input row in LDS (two 16-byte halves of 64 lanes)
-    auto stage_in = [&](int b, lds_u32 *slot) {
-        const char *gu = st_u;
-        st_u += RPB * row_step;
-        if ((uint32_t)(b - ib_lo) < ib_n) {
-            // The block's 8 LDS-DMA loads in the SGPR-base form, as the band loader's (row address
-            // in an SGPR pair, the lane's 32-bit offset -- and +16 for a row's second half -- in a
-            // VGPR; M0 set and restored inside, a wait state before each load): the builtin made
-            // the compiler compute a 64-bit VGPR address per load.  Same box, 3 reps: 16384^2
-            // bytes 63.0 -> 63.7 TCUPS (profiles/r06/r06_ab_bsaddr.jsonl).
-            static_assert(RPB == 4, "four rows per block");
-            // row bases, wave-uniform: readfirstlane makes that explicit for builds whose control
-            // flow hides it (GOL_SPIN_LIMIT=0: the "s" operands below would get VGPRs); it folds
-            // away where the compiler already keeps them in SGPRs
-            auto uni = [](const char *q) {
-                const uint64_t v = reinterpret_cast<uint64_t>(q);
-                const uint64_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)v);
-                const uint64_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-                return reinterpret_cast<const char *>(lo | (hi << 32));
-            };
-            const char *r0 = uni(gu), *r1 = uni(r0 + row_step), *r2 = uni(r1 + row_step), *r3 = uni(r2 + row_step);
-            uint32_t keep;
-            asm volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\t"
-                         "s_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %7\n\t"
-                         "s_add_u32 m0, %3, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %7\n\t"
-                         "s_mov_b32 m0, %4\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %8\n\t"
-                         "s_add_u32 m0, %4, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %8\n\t"
-                         "s_mov_b32 m0, %5\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %9\n\t"
-                         "s_add_u32 m0, %5, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %9\n\t"
-                         "s_mov_b32 m0, %6\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %10\n\t"
-                         "s_add_u32 m0, %6, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %10\n\t"
-                         "s_mov_b32 m0, %0"
-                         : "=&s"(keep)
-                         : "v"(lane_off), "v"(lane_off + 16u), "s"(slot), "s"(slot + IROW), "s"(slot + 2 * IROW),
-                           "s"(slot + 3 * IROW), "s"(r0), "s"(r1), "s"(r2), "s"(r3)
-                         : "memory", "scc");
-            return;
-        }
-#pragma unroll
-        for (int S = 0; S < RPB; ++S) {
-            int y = in_row(RPB * b + S);
-            y = y > last_in ? last_in : (y < first_in ? first_in : y);  // past the end: clamped, never stored
-            const int64_t d = y < 0 ? top_d : (y >= R ? bot_d : 0);
-            const char *gg = mid_b + (d + (int64_t)y * pitch) + lane_off;
-            __builtin_amdgcn_global_load_lds(reinterpret_cast<const void *>(gg), slot + S * IROW, 16, 0, 0);
-            __builtin_amdgcn_global_load_lds(reinterpret_cast<const void *>(gg + 16), slot + S * IROW + 256, 16, 0, 0);
-        }
-    };
-    __builtin_amdgcn_s_setprio(1);  // polls drop to 0 (spin_until_ge<true>)
-    for (int i = threadIdx.x; i < 256; i += 64 * P) {
-        uint32_t o[2];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const uint32_t sp = __umul24((i >> (4 * h)) & 0xF, 0x00204081u) & 0x01010101u;
-            o[h] = (sp << 8) - sp;
-        }
-        lut[i] = make_uint2(o[0], o[1]);
-    }
-    if (threadIdx.x < P) { ready[threadIdx.x] = 0; consumed[threadIdx.x] = 0; }
-    __syncthreads();
-    lds_u32 *const ring_l = (lds_u32 *)&ring[0][0][0][0];
-    lds_u32 *const in_l = (lds_u32 *)&in_ring[0][0][0][0];
-    lds_u32 *const ready_l = (lds_u32 *)&ready[0];
-    lds_u32 *const consumed_l = (lds_u32 *)&consumed[0];
-    constexpr int SLOT = RPB * ROW;        // uint32 per hand-off slot
-    constexpr int ISLOT = RPB * 2 * 256;   // uint32 per input slot
-    constexpr int SB = SLOT * 4, RB = ROW * 4, ISB = ISLOT * 4;
-    lds_u32 *const scratch = (lds_u32 *)&flag_scratch[0] + lane;
-    lds_u32 *const rdy_addr = lane == 0 ? ready_l + wv + 1 : scratch;  // ring wv+1 ready
-    lds_u32 *const cns_addr = lane == 0 ? consumed_l + wv : scratch;   // ring wv consumed
-    lds_u32 *const in_base = in_l + lane * 4;
-    lds_u32 *const rd_base = ring_l + (wv - 1) * NS * SLOT + lane;  // ring wv (wv >= 1)
-    lds_u32 *const wr_base = ring_l + wv * NS * SLOT + lane;        // ring wv+1 (wv < P-1)
-
-    PairState<1> st[KW];
-#pragma unroll
-    for (int g = 0; g < KW; ++g) { st[g].a0[0] = 0; st[g].a1[0] = 0; st[g].b0[0] = 0; st[g].b1[0] = 0; st[g].cb[0] = 0; }
-    uint32_t alive = 0;
-    const uint32_t nrows = (uint32_t)(s1 - s0);
-    // last wave: output row y stored at voffset st_off + (y - s0) * pitch of ONE buffer spanning
-    // the strip's rows (the host keeps rows x pitch < 2^31): rows before s0 (negative offsets, as
-    // unsigned >= 2^32 - 2K * pitch), from s1 on, and a halo lane's 2^31 fall outside it
-    const __amdgpu_buffer_rsrc_t strip_rs = __builtin_amdgcn_make_buffer_rsrc(
-        dst_b + (int64_t)s0 * pitch, (short)0, (int)(nrows * (uint32_t)pitch), 0x00020000);
-    int rrel = dir >= 0 ? -2 * K : s1e - 1 + 2 * K - s0;  // output row - s0 of the next row (wave-uniform)
-    const int rstep = dir >= 0 ? 1 : -1;
-    uint32_t voff = st_off + (uint32_t)rrel * (uint32_t)pitch;
-    const uint32_t vstep = (uint32_t)rstep * (uint32_t)pitch;
-    // undo the K-bit frame shift (K = 32: exactly the next lane's word; alignbit takes its shift
-    // mod 32), unpack through the LUT, store, count
-    auto emit = [&](uint32_t w) {
-        const uint32_t nxw = from_upper_lane(w);
-        const uint32_t o = K % 32 ? __builtin_amdgcn_alignbit(nxw, w, K % 32) : nxw;
-        uint2 e[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) e[q] = lut[(o >> (8 * q)) & 0xFF];
-        __builtin_amdgcn_raw_buffer_store_b128(v4u32{e[0].x, e[0].y, e[1].x, e[1].y}, strip_rs, voff, 0, GOL_BYTES_STORE_AUX);
-        __builtin_amdgcn_raw_buffer_store_b128(v4u32{e[2].x, e[2].y, e[3].x, e[3].y}, strip_rs, voff + 16u, 0, GOL_BYTES_STORE_AUX);
-        if constexpr (COUNT) {
-            const uint32_t c = __popc(o) + alive;
-            alive = (uint32_t)rrel < nrows ? c : alive;
-        }
-        voff += vstep;
-        rrel += rstep;
-    };
-    constexpr int FINAL = 1 << 30;  // ready flag = FINAL + blocks: the stream has ended
-    uint32_t pending = 0;  // the loader's claim in flight (paired)
-    if (wv == 0 && dir && lane == 0) pending = atomicAdd(ctr, (uint32_t)NS);
-    // block 0's rows read to completion here (the compiler copies loop-carried registers on loop
-    // entry, which must not happen while a read is in flight).  A reader's next block (RPB words)
-    // is read at the end of a block; the loader reads its block's 2 RPB 16-byte halves at the
-    // block's start (32 VGPRs held across the compute would spill at 6 waves per SIMD).
-    v4u32 nb[2 * RPB];  // loader
-    uint32_t nw[RPB];   // readers
-    int seen_ready = 0, seen_free = 0;
-    auto read_in = [&](auto off_c) {  // the loader's reads of one input slot
-        constexpr int OFF = decltype(off_c)::value;
-        static_assert(RPB == 4, "eight half-row reads");
-        nb[0] = lds_rd128_issue_o<OFF>(in_base);
-        nb[1] = lds_rd128_issue_o<OFF + 1024>(in_base);
-        nb[2] = lds_rd128_issue_o<OFF + 2048>(in_base);
-        nb[3] = lds_rd128_issue_o<OFF + 3072>(in_base);
-        nb[4] = lds_rd128_issue_o<OFF + 4096>(in_base);
-        nb[5] = lds_rd128_issue_o<OFF + 5120>(in_base);
-        nb[6] = lds_rd128_issue_o<OFF + 6144>(in_base);
-        nb[7] = lds_rd128_issue_o<OFF + 7168>(in_base);
-    };
-    auto read_ring = [&](auto off_c) {  // a reader's reads of one ring slot
-        constexpr int OFF = decltype(off_c)::value;
-        static_assert(RPB == 4, "four row reads");
-        nw[0] = lds_rd32_issue_o<OFF>(rd_base);
-        nw[1] = lds_rd32_issue_o<OFF + 256>(rd_base);
-        nw[2] = lds_rd32_issue_o<OFF + 512>(rd_base);
-        nw[3] = lds_rd32_issue_o<OFF + 768>(rd_base);
-    };
-    auto settle_in = [&]() {
-#pragma unroll
-        for (int h = 0; h < 2 * RPB; ++h) lds_settle<0>(nb[h]);
-    };
-    if (wv == 0) {
-        stage_in(0, in_l);
-        stage_in(1, in_l + ISLOT);
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * RPB) : "memory");  // block 0 landed (the claim before it too)
-#pragma unroll
-        for (int S = 0; S < RPB; ++S) nw[S] = 0;
-    } else {
-        seen_ready = spin_until_ge<true>(ready_l + wv, 1);
-        if (seen_ready < 0) {
-            raise_error(a.err, GOLK_ERR_SPIN);
-            return;
-        }
-        read_ring(std::integral_constant<int, 0>());
-        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(nw[0]), "+v"(nw[1]), "+v"(nw[2]), "+v"(nw[3])::"memory");
-    }
-    bool more = !(seen_ready >= FINAL && seen_ready - FINAL == 0);
-    // Fill blocks (band_pipe_kernel's rule): a wave whose first stage is g0 = KW * wv passes the
-    // blocks that end before step 2 g0 (RPB b + RPB <= 2 g0) on without the rule -- a uniform
-    // branch per block here (the byte pipeline has registers to spare; a loop of its own per role
-    // doubled the role's code)
-    const int nskip = 2 * KW * wv / RPB;
-    auto step = [&](int b, auto u_c, auto role_c, auto dyn_c) -> bool {
-        constexpr int US = decltype(u_c)::value;
-        constexpr int ROLE = decltype(role_c)::value;
-        constexpr bool DYN = decltype(dyn_c)::value;
-        constexpr bool LAST = ROLE == 2;
-        constexpr int NXT = (US + 1) % NS;
-        uint32_t r[RPB];
-        // block b's rows, the youngest LDS operations of this wave: once they are in, so are
-        // block b-1's row writes, and both flags can go out at once
-        if constexpr (ROLE == 0) {
-            read_in(std::integral_constant<int, US % NSI * ISB>());
-            settle_in();
-#pragma unroll
-            for (int S = 0; S < RPB; ++S)
-                r[S] = pack32_ff(uint4{nb[2 * S].x, nb[2 * S].y, nb[2 * S].z, nb[2 * S].w},
-                                 uint4{nb[2 * S + 1].x, nb[2 * S + 1].y, nb[2 * S + 1].z, nb[2 * S + 1].w});
-        } else {
-            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(nw[0]), "+v"(nw[1]), "+v"(nw[2]), "+v"(nw[3])::"memory");
-#pragma unroll
-            for (int S = 0; S < RPB; ++S) r[S] = nw[S];
-            lds_flag_wr(cns_addr, b + 1);  // block b's slot is free
-        }
-        if constexpr (!LAST) lds_flag_wr(rdy_addr, b);  // blocks < b are in ring wv+1
-        if (ROLE == 0 || b >= nskip) {
-            // stage step w: the first pair at stage w, the second at stage w-1 (each stage takes
-            // its pairs in stream order)
-#pragma unroll
-            for (int w = 0; w <= KW; ++w) {
-                if (w < KW) spstage(st[w], r[0], r[1]);
-                if (w >= 1) spstage(st[w - 1], r[2], r[3]);
-            }
-        }
-        if constexpr (LAST) {
-#pragma unroll
-            for (int S = 0; S < RPB; ++S) emit(r[S]);
-        } else {
-            if (seen_free < b + 1 - NS) {  // slot b % NS: block b - NS consumed
-                seen_free = spin_until_ge<true>(consumed_l + wv + 1, b + 1 - NS);
-                if (seen_free < 0) return false;
-            }
-            static_assert(RPB == 4, "four row writes");
-            lds_wr32_o<US * SB>(wr_base, r[0]);
-            lds_wr32_o<US * SB + RB>(wr_base, r[1]);
-            lds_wr32_o<US * SB + 2 * RB>(wr_base, r[2]);
-            lds_wr32_o<US * SB + 3 * RB>(wr_base, r[3]);
-        }
-        // block b+1's rows: read now, waited for at the next block's start
-        if constexpr (ROLE == 0) {
-            stage_in(b + 2, in_l + ((US + 2) % NSI) * ISLOT);  // refills block b+2-NSI's slot (clamped past the end)
-            // block b+1 landed, b+2 in flight (2 RPB loads; and, paired, at US 1 the claim issued at US 0)
-            if constexpr (DYN && US == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * RPB + 1) : "memory");
-            else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * RPB) : "memory");
-            if constexpr (DYN && US == 0) {
-                if (lane == 0) pending = atomicAdd(ctr, (uint32_t)NS);
-            }
-        } else {
-            // the next block exists unless the writer's flag says the stream ended before it
-            if (seen_ready < b + 2) {
-                seen_ready = spin_until_ge<true>(ready_l + wv, b + 2);
-                if (seen_ready < 0) return false;
-            }
-            more = seen_ready < FINAL || b + 1 < seen_ready - FINAL;
-            read_ring(std::integral_constant<int, NXT * SB>());
-        }
-        return true;
-    };
-    auto grant = [&](uint32_t c) { return c >= (uint32_t)nclaim ? 0 : NS; };
-
-    auto trip = [&](int b, auto role_c, auto dyn_c) -> bool {
-        bool ok = true;
-        static_for<NS>([&](auto u_c) {
-            if (ok) ok = step(b + decltype(u_c)::value, u_c, role_c, dyn_c);
-        });
-        return ok;
-    };
-    auto run = [&](auto role_c, auto dyn_c) -> bool {
-        constexpr int ROLE = decltype(role_c)::value;
-        constexpr bool DYN = decltype(dyn_c)::value;
-        int nb = DYN ? 0 : (nblk + NS - 1) / NS * NS;
-        int b = 0;
-        for (;; b += NS) {
-            if constexpr (ROLE == 0) {
-                if constexpr (DYN) nb += grant(__builtin_amdgcn_readfirstlane(pending));
-                if (b >= nb) break;
-            } else {
-                if (!more) break;
-            }
-            if (!trip(b, role_c, dyn_c)) return false;
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the last block's reads of the next slot
-        if constexpr (ROLE != 2) {
-            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-            lds_flag_wr(rdy_addr, FINAL + b);
-        }
-        if constexpr (ROLE == 0 && DYN) {
-            if (lane == 0 && atomicAdd(ctr + 1, 1u) == 1u) {  // both loaders' claims are over
-                atomicExch(ctr, 0u);
-                atomicExch(ctr + 1, 0u);
-            }
-        }
-        return true;
-    };
-    // (paired or not changes only the loader's loop: the readers' loops are one instantiation,
-    // which halves their code -- the I-cache holds 64 KiB for two CUs)
-    auto run_role = [&](auto role_c) -> bool {
-        if constexpr (decltype(role_c)::value != 0) return run(role_c, std::false_type());
-        else return dir ? run(role_c, std::true_type()) : run(role_c, std::false_type());
-    };
-    bool ok;
-    if (wv == 0) ok = run_role(std::integral_constant<int, 0>());
-    else if (wv == P - 1) ok = run_role(std::integral_constant<int, 2>());
-    else ok = run_role(std::integral_constant<int, 1>());
-    if (wv == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // input blocks staged past the end
-    if (!ok) raise_error(a.err, GOLK_ERR_SPIN);
-    alive &= st_mask;  // halo lanes' rows are not this group's
-    if (COUNT && wv == P - 1) slot_add(a.slots, alive);
-}
-
-#define BYTES_PIPE(count) (bytes_pipe_kernel<GOL_BYTES_PIPE_KW, GOL_BYTES_PIPE_P, count>)
-
-
-
-#ifdef GOL_TU_BYTES_PIPE
-}  // namespace golk
-
-// gol_bytes_pipe.hip: this file up to here, compiled on its own with the max-memory-clause
-// machine scheduler, bottom-up, and no post-RA scheduler (Makefile BYTEFLAGS): bytes_pipe_kernel's
-// instantiations and launch.  Same box, 3 reps each: 59.4 -> 60.4 TCUPS on 16384^2 bytes, then
-// 60.2 -> 60.6 without the post-RA pass, 60.7 -> 61.2 bottom-up; under max-ILP (the band
-// pipeline's) 56.8 (profiles/r04/r04h_sched.jsonl).
-using namespace golk;
-const void *golk_bytes_pipe_fn(bool count)
-{
-    return count ? (const void *)BYTES_PIPE(true) : (const void *)BYTES_PIPE(false);
-}
-hipError_t golk_bytes_pipe_launch(bool count, unsigned nwg, const BytesKArgs &a, hipStream_t s)
-{
-    if (count) hipLaunchKernelGGL(BYTES_PIPE(true), dim3(nwg), dim3(64 * GOL_BYTES_PIPE_P), 0, s, a);
-    else hipLaunchKernelGGL(BYTES_PIPE(false), dim3(nwg), dim3(64 * GOL_BYTES_PIPE_P), 0, s, a);
-    return hipGetLastError();
-}
-#else  // the rest of the kernels and the host side
 
 // ------------------------------------------------------------------ byte-board step (exact semantics)
 // SWAR on 4 cells per uint32.  A = (byte == 255), Z = (byte == 0), as 0x01 per byte.
@@ -2246,44 +890,38 @@ static inline int grid_for(int64_t n, int block = 256, int64_t cap = 256 * 16)
     return (int)g;
 }
 
-// Per-device error word used when a launcher is called without one (gol_dev_* launchers).
-uint32_t *golk_device_err_word(int device)
+// A per-device buffer of `words` zeroed words, allocated at its first use and kept in `bufs`.
+// Zeroed and synchronised: launches on non-blocking streams are not ordered after the null stream.
+static uint32_t *device_words(std::map<int, uint32_t *> &bufs, int device, size_t words)
 {
     static std::mutex mu;
-    static std::map<int, uint32_t *> words;
     std::lock_guard<std::mutex> lock(mu);
-    auto it = words.find(device);
-    if (it != words.end()) return it->second;
+    auto it = bufs.find(device);
+    if (it != bufs.end()) return it->second;
     int prev = 0;
     uint32_t *w = nullptr;
     if (hipGetDevice(&prev) != hipSuccess || hipSetDevice(device) != hipSuccess) return nullptr;
-    // zeroed and synchronised: launches on non-blocking streams are not ordered after the null stream
-    if (hipMalloc(&w, sizeof(uint32_t)) != hipSuccess || hipMemset(w, 0, sizeof(uint32_t)) != hipSuccess ||
+    if (hipMalloc(&w, words * sizeof(uint32_t)) != hipSuccess || hipMemset(w, 0, words * sizeof(uint32_t)) != hipSuccess ||
         hipDeviceSynchronize() != hipSuccess)
         w = nullptr;
     (void)hipSetDevice(prev);
-    if (w) words[device] = w;
+    if (w) bufs[device] = w;
     return w;
+}
+
+// Per-device error word used when a launcher is called without one (gol_dev_* launchers).
+uint32_t *golk_device_err_word(int device)
+{
+    static std::map<int, uint32_t *> words;
+    return device_words(words, device, 1);
 }
 
 // Per-device CU slot masks of the band pipeline (GOL_BAND_PLACE; zeroed once, every workgroup
 // frees its slot on exit).
 uint32_t *golk_cu_slots(int device)
 {
-    static std::mutex mu;
     static std::map<int, uint32_t *> tabs;
-    std::lock_guard<std::mutex> lock(mu);
-    auto it = tabs.find(device);
-    if (it != tabs.end()) return it->second;
-    int prev = 0;
-    uint32_t *w = nullptr;
-    if (hipGetDevice(&prev) != hipSuccess || hipSetDevice(device) != hipSuccess) return nullptr;
-    if (hipMalloc(&w, GOL_CU_SLOT_WORDS * sizeof(uint32_t)) != hipSuccess ||
-        hipMemset(w, 0, GOL_CU_SLOT_WORDS * sizeof(uint32_t)) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
-        w = nullptr;
-    (void)hipSetDevice(prev);
-    if (w) tabs[device] = w;
-    return w;
+    return device_words(tabs, device, GOL_CU_SLOT_WORDS);
 }
 
 hipError_t golk_reset_cu_slots(int device, hipStream_t s)
@@ -2507,13 +1145,6 @@ hipError_t golk_reset_claims_device(int device)
     return e;
 }
 
-// bytes_pipe_kernel lives in its own translation unit (gol_bytes_pipe.hip: another scheduler)
-const void *golk_bytes_pipe_fn(bool count);
-hipError_t golk_bytes_pipe_launch(bool count, unsigned nwg, const BytesKArgs &a, hipStream_t s);
-// band_pipe_kernel lives in its own translation unit (gol_band_pipe.hip: another scheduler)
-const void *golk_band_pipe_fn(bool contig, bool count);
-hipError_t golk_band_pipe_launch(bool contig, bool count, unsigned nwg, const BitsArgs &a, hipStream_t s);
-
 // The device a pipelined launch is scheduled for: this one (as_cus = as_slots = 0), or a
 // pretended smaller one of as_cus CUs (a multiple of 8) holding as_slots resident workgroups of
 // `kernel`; false: it asks for more than this device has.
@@ -2525,6 +1156,28 @@ static bool pipe_device(const void *kernel, int block, int as_cus, int64_t as_sl
     if (as_cus <= 0 || as_cus % 8 || as_cus > cus || as_slots <= 0 || as_slots > slots) return false;
     cus = as_cus;
     slots = as_slots;
+    return true;
+}
+
+// The strips of a pipelined launch: the device it is scheduled for (pipe_device; false: no such
+// device), `plan`'s StripPlan for it (band_strip_plan / bytes_strip_plan) and, for a paired plan,
+// the stream's claim counters -- sized by the device itself, whichever device the launch is
+// scheduled for; without them the plan is made again unpaired.
+typedef StripPlan (*StripPlanFn)(int64_t, int64_t, int64_t, int, int, int, int64_t, bool);
+static bool pipe_plan(StripPlanFn plan, const void *kernel, int block, int64_t rows, int64_t width, int64_t pitch, int k,
+                      int strip_rows, int as_cus, int64_t as_slots, hipStream_t s, int32_t &strip, StripMap &sm,
+                      unsigned &nwg)
+{
+    int cus = 0;
+    int64_t resident = 0;
+    if (!pipe_device(kernel, block, as_cus, as_slots, cus, resident)) return false;
+    StripPlan p = plan(rows, width, pitch, k, strip_rows, cus, resident, true);
+    uint32_t *claims = p.mode == GOL_STRIPS_RANKED_PAIRED ? claim_counters(s, device_cus()) : nullptr;
+    if (p.mode == GOL_STRIPS_RANKED_PAIRED && !claims) p = plan(rows, width, pitch, k, strip_rows, cus, resident, false);
+    strip = p.strip;
+    sm = p.sm;
+    sm.claims = claims;
+    nwg = (unsigned)p.nwg;
     return true;
 }
 
@@ -2551,20 +1204,13 @@ hipError_t golk_band_step(const uint32_t *top, const uint32_t *mid, const uint32
     const bool contig = top + (int64_t)k * pitch == mid && bot == mid + R * pitch;
     if (dw == 4 && k == GOL_BAND_KW * GOL_BAND_P) {
         // k = 12 on the band layout: 4 waves x 3 stages (band_pipe_kernel), one workgroup per
-        // (column group, range of rows): band_strip_plan.  The claim counters are sized by the
-        // device itself, whichever device the launch is scheduled for.
+        // (column group, range of rows): band_strip_plan.
         const bool count = a.slots != nullptr;
-        int cus = 0;
-        int64_t resident = 0;
-        if (!pipe_device(golk_band_pipe_fn(contig, count), 64 * GOL_BAND_P, as_cus, as_slots, cus, resident))
+        unsigned nwg = 0;
+        if (!pipe_plan(band_strip_plan, golk_band_pipe_fn(contig, count), 64 * GOL_BAND_P, rows, Wd, pitch, k, strip,
+                       as_cus, as_slots, s, a.strip, a.sm, nwg))
             return hipErrorInvalidValue;
-        StripPlan p = band_strip_plan(rows, Wd, pitch, k, strip, cus, resident);
-        uint32_t *claims = p.mode == GOL_STRIPS_RANKED_PAIRED ? claim_counters(s, device_cus()) : nullptr;
-        if (p.mode == GOL_STRIPS_RANKED_PAIRED && !claims) p = band_strip_plan(rows, Wd, pitch, k, strip, cus, resident, false);
-        a.strip = p.strip;
-        a.sm = p.sm;
-        a.sm.claims = claims;
-        return golk_band_pipe_launch(contig, count, (unsigned)p.nwg, a, s);
+        return golk_band_pipe_launch(contig, count, nwg, a, s);
     }
     if (as_cus || as_slots) return hipErrorInvalidValue;
     dim3 grid((a.ngroups + 3) / 4, (int)((rows + a.strip - 1) / a.strip));
@@ -2671,18 +1317,11 @@ hipError_t golk_bytes_blocked(const uint8_t *top, const uint8_t *mid, const uint
     if (k == 32) {
         // one workgroup of GOL_BYTES_PIPE_P waves per (column group, strip): bytes_strip_plan
         const bool count = a.slots != nullptr;
-        int cus = 0;
-        int64_t resident = 0;
-        if (!pipe_device(golk_bytes_pipe_fn(count), 64 * GOL_BYTES_PIPE_P, as_cus, as_slots, cus, resident))
+        unsigned nwg = 0;
+        if (!pipe_plan(bytes_strip_plan, golk_bytes_pipe_fn(count), 64 * GOL_BYTES_PIPE_P, rows, W, pitch, k, strip,
+                       as_cus, as_slots, s, a.strip, a.sm, nwg))
             return hipErrorInvalidValue;
-        // (the claim counters are sized by the device itself, whichever device the launch is scheduled for)
-        StripPlan p = bytes_strip_plan(rows, W, pitch, k, strip, cus, resident);
-        uint32_t *claims = p.mode == GOL_STRIPS_RANKED_PAIRED ? claim_counters(s, device_cus()) : nullptr;
-        if (p.mode == GOL_STRIPS_RANKED_PAIRED && !claims) p = bytes_strip_plan(rows, W, pitch, k, strip, cus, resident, false);
-        a.strip = p.strip;
-        a.sm = p.sm;
-        a.sm.claims = claims;
-        return golk_bytes_pipe_launch(count, (unsigned)p.nwg, a, s);
+        return golk_bytes_pipe_launch(count, nwg, a, s);
     }
     if (as_cus || as_slots) return hipErrorInvalidValue;
     const int nstrips = (int)((rows + a.strip - 1) / a.strip);
@@ -2817,5 +1456,3 @@ hipError_t golk_ipc_wait(const uint32_t *const *flags, int n, uint32_t want, uin
     hipLaunchKernelGGL(ipc_wait_kernel, dim3(1), dim3(64), 0, s, a);
     return hipGetLastError();
 }
-#endif  // GOL_TU_BAND_PIPE
-#endif  // GOL_TU_BYTES_PIPE

@@ -61,7 +61,7 @@ static int step_launch(gol_engine *e, gol_shard &s, hipStream_t st, int k, int64
 // The step plan of shard s (gol_step_plan flags): as configured, else OVERLAP when the shard's
 // launch runs many rounds of workgroups (the edge launches then share the CUs with the interior
 // at no cost: +1 % on the 2^17 x 2^20 board), SERIAL when it is a launch of one or a few rounds,
-// whose rank-weighted strips (gol_kernels.hip StripMap) assume they have the CUs to themselves
+// whose rank-weighted strips (gol_strips.h StripMap) assume they have the CUs to themselves
 // (a concurrent edge launch cost 7 % on a 32768 x 262144 shard, profiles/r03a_step_cost).
 static int step_mode(gol_engine *e, const gol_shard &s, int k)
 {

@@ -1,7 +1,8 @@
 // gol_strips.h -- which workgroup of a pipelined launch computes which output rows.  Shared by the
-// two pipeline kernels (band_pipe_kernel and bytes_pipe_kernel, gol_kernels.hip), the launch code
-// that picks a schedule, and the host (gol_strip_plan, include/golhip.h), so the row-range
-// arithmetic the GPU runs is tested on the CPU; the strip-level twin of gol_edit.h.
+// two pipeline kernels (band_pipe_kernel, gol_band_pipe.hip; bytes_pipe_kernel, gol_bytes_pipe.hip),
+// the launch code that picks a schedule (gol_kernels.hip), and the host (gol_strip_plan,
+// include/golhip.h), so the row-range arithmetic the GPU runs is tested on the CPU; the strip-level
+// twin of gol_edit.h.
 //
 // Two halves:
 //  - StripMap, work_item, work_dir, pair_extent: the map a launch carries and the functions that

@@ -172,7 +172,7 @@ def test_cell_list_reads_as_cells(G):
 def test_pipe_kernels_wait_before_reading_lds(tmp_path):
     """The pipe kernels' inline-asm LDS reads: no instruction may read a destination
     VGPR before its s_waitcnt (a compiler copy there read stale rows once:
-    tools/check_lds_wait.py).  Compiles gol_kernels.hip to gfx950 assembly (~20 s)."""
+    tools/check_lds_wait.py).  Compiles the three kernel units to gfx950 assembly (~20 s)."""
     import shutil
     if shutil.which("/opt/rocm/bin/hipcc") is None:
         pytest.skip("hipcc not present")

@@ -1,6 +1,6 @@
 """CPU checks of bench.py's orchestration (no GPU): the self-launch of N ranks over gloo,
-the one-line JSON contract, and the roofline bookkeeping (a PMC profile measured on another
-gol_kernels.hip is never used)."""
+the one-line JSON contract, and the roofline bookkeeping (a PMC profile measured on other
+kernel units -- gol_kernels.hip, gol_band_pipe.hip, gol_bytes_pipe.hip -- is never used)."""
 import json
 import os
 import subprocess

@@ -1,6 +1,6 @@
 """The pipelines' fill-block skip, checked on a CPU model of the row pipeline (no GPU).
 
-band_pipe_kernel (gol_kernels.hip, `run`: the fill-trip loop) and bytes_pipe_kernel (`nskip`)
+band_pipe_kernel (gol_band_pipe.hip, `run`: the fill-trip loop) and bytes_pipe_kernel (`nskip`)
 stream the rows of a strip through K stages, one generation each; stage g at stream step t
 holds its last three input rows and emits the next state of the middle one, so the last stage
 emits row t - K at generation K, valid from step 2K on (the rows stored).  (Since round 5 the

@@ -1,5 +1,5 @@
-"""The pipeline loaders' interior-block range (gol_kernels.hip, band_pipe_kernel and
-bytes_pipe_kernel `stage_in`), checked against the per-block test it replaced (no GPU).
+"""The pipeline loaders' interior-block range (band_pipe_kernel, gol_band_pipe.hip, and
+bytes_pipe_kernel, gol_bytes_pipe.hip: `stage_in`), checked against the per-block test it replaced (no GPU).
 
 A loader stages the blocks of its stream 0, 1, 2, ... (RPB rows each, walking down from
 first_in or, for the upper walker of a paired range, up from s1e + K - 1).  A block whose rows
@@ -12,11 +12,11 @@ import itertools
 import pytest
 
 
-def div_ceil_nn(a, d):  # gol_kernels.hip div_ceil_nn: ceil(a / d) for a >= 0, else 0
+def div_ceil_nn(a, d):  # gol_pipe.h div_ceil_nn: ceil(a / d) for a >= 0, else 0
     return (a + d - 1) // d if a > 0 else 0
 
 
-def div_floor(a, d):  # gol_kernels.hip div_floor (C integer division, written for a < 0)
+def div_floor(a, d):  # gol_pipe.h div_floor (C integer division, written for a < 0)
     return int(a / d) if a >= 0 else -((-a + d - 1) // d)
 
 

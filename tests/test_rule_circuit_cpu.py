@@ -1,7 +1,7 @@
 """The bit-sliced B3/S23 circuit of the gfx950 kernels, checked on the CPU over every 3x3
 neighbourhood (worker.go:26-37 / 44-70 semantics on 0/255 cells).
 
-gol_kernels.hip computes a generation from the three rows' horizontal 3-sums (h0 = xor3,
+The kernels (gol_device.h rule, gol_kernels.hip) compute a generation from the three rows' horizontal 3-sums (h0 = xor3,
 h1 = maj of a cell and its two horizontal neighbours; the centre row's sum includes the cell)
 with 7 three-input gates (v_bitop3_b32): t0, k0 (low bits), u, v (high bits), then the tail
 found by tools/rule_search.c: G1 = TT_G1(t0, k0, v), G2 = TT_G2(u, v, G1),
@@ -13,7 +13,7 @@ import os
 import re
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "gol-distributed-final_amd", "csrc", "gol_kernels.hip")
+SRC = os.path.join(ROOT, "gol-distributed-final_amd", "csrc", "gol_device.h")
 
 
 def _tables():
@@ -80,7 +80,7 @@ def _life(rows):
 
 
 def _pair_step(T, rows):
-    """gol_kernels.hip pstage on one column: rows = 4 x 3 cells (x_2m-2, x_2m-1, x_2m, x_2m+1),
+    """gol_pipe.h pstage on one column: rows = 4 x 3 cells (x_2m-2, x_2m-1, x_2m, x_2m+1),
     the outputs of rows 2m-1 and 2m."""
     h = [sum(r) for r in rows]
     a, b, c, d = [(x & 1, x >> 1) for x in h]

@@ -11,7 +11,7 @@ instruction that reads an in-flight register before the wait.
 
     python tools/check_lds_wait.py [asm.s] [--pattern REGEX]
 
-Without an argument it compiles gol_kernels.hip to device assembly first.
+Without an argument it compiles the three kernel units (UNITS) to device assembly first.
 Exit status 1 if a hazard is found.
 """
 import argparse

@@ -3,7 +3,8 @@
   pmc_summary.json       per-kernel means of the PMC passes + derived HBM bytes, clock, VALU use
 and update profiles/pmc_traffic.json, read by bench.py for the roofline (HBM bytes and wave64
 VALU instructions per launch of the step kernel).  Each entry records the sha256 prefix of the
-gol_kernels.hip it was measured on; bench.py ignores an entry whose hash differs.
+kernel units (gol_kernels.hip, gol_band_pipe.hip, gol_bytes_pipe.hip) and the Makefile it was
+measured on -- not of the headers they include; bench.py ignores an entry whose hash differs.
 
     python tools/pmc_summary.py <tag> <bench key, e.g. weak:131072x1048576:k12:band> [--clock GHZ]
 

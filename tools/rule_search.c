@@ -2,7 +2,7 @@
 // A = a0+b0+c0 and B = a1+b1+c1 (the vertical sums of the three rows' horizontal 3-sums) and the
 // cell -- be computed with 3 three-input gates (v_bitop3_b32)?  32 points (A, B, cell); the care
 // mask drops (A=0,B=0,cell=1) and (A=3,B=3,cell=0), impossible because the centre row's sum
-// includes the cell.  Result used in gol_kernels.hip (TT_G1, TT_G2, TT_OUT): encoding A0 B0.
+// includes the cell.  Result used in gol_device.h (TT_G1, TT_G2, TT_OUT): encoding A0 B0.
 //   gcc -O2 -o /tmp/rule_search tools/rule_search.c && /tmp/rule_search
 #include <stdint.h>
 #include <stdio.h>

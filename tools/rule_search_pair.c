@@ -1,5 +1,5 @@
 // Exhaustive search (tools/, not product) behind the pair step of the band pipeline
-// (gol_kernels.hip pstage / pair_tail).
+// (gol_pipe.h pstage / pair_tail).
 //
 // Two consecutive output rows n-1 and n share the rows n-1 and n of their 3 x 3 neighbourhoods.
 // With a row's horizontal 3-sum as two bits (h0 = xor3, h1 = maj of the cell and its two

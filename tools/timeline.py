@@ -53,6 +53,8 @@ STORE = """    {  // timeline: (t0, t1, hw_id, xcc_id) per wave, slot = linear w
 """
 
 
+PIPE_UNITS = {"gol_band_pipe.hip": "band_pipe_kernel(BitsArgs a)", "gol_bytes_pipe.hip": "bytes_pipe_kernel(BytesKArgs a)"}
+
 PROF_SPINS = (  # -DGOL_EXP_PROF: cycles each wave spends in its flag waits (ready -> a, free -> b)
     ("seen_free = spin_until_ge(consumed_l + wv + 1, b + 1 - NS);", "prof_b"),
     ("seen_ready = spin_until_ge(ready_l + wv, b + 2);", "prof_a"),
@@ -66,26 +68,23 @@ def build(flags="", name="libtimeline"):
     import tempfile
     os.makedirs(VARIANTS, exist_ok=True)
     OUT = tempfile.mkdtemp(prefix="gol_tl_")
-    src = open(os.path.join(CSRC, "gol_kernels.hip")).read()
-    if "GOL_EXP_PROF" in flags:
-        for stmt, acc in PROF_SPINS:
-            if stmt not in src:
-                continue
-            src = src.replace(stmt, "{ const uint64_t pt_ = __builtin_amdgcn_s_memtime(); " + stmt +
-                              f" {acc} += __builtin_amdgcn_s_memtime() - pt_; }}")
-        for kern in ("band_pipe_kernel(BitsArgs a)", "bytes_pipe_kernel(BytesKArgs a)"):
-            i = src.index(kern)
-            j = src.index("    uint32_t alive = 0;\n", i)
+    for unit, kern in PIPE_UNITS.items():  # each pipeline kernel is patched in its own unit
+        src = open(os.path.join(CSRC, unit)).read()
+        if "GOL_EXP_PROF" in flags:
+            for stmt, acc in PROF_SPINS:
+                if stmt not in src:
+                    continue
+                src = src.replace(stmt, "{ const uint64_t pt_ = __builtin_amdgcn_s_memtime(); " + stmt +
+                                  f" {acc} += __builtin_amdgcn_s_memtime() - pt_; }}")
+            j = src.index("    uint32_t alive = 0;\n", src.index(kern))
             src = src[:j] + "    uint64_t prof_a = 0, prof_b = 0;\n" + src[j:]
-    for kern in ("band_pipe_kernel(BitsArgs a)", "bytes_pipe_kernel(BytesKArgs a)"):
-        i = src.index(kern)
-        j = src.index(ENTRY, i)
+        j = src.index(ENTRY, src.index(kern))
         src = src[:j] + STAMP_T0 + src[j + len(ENTRY):]
         k = src.index(COUNT_LINE, j)  # the kernel's final fused-count slot_add: the stamps replace it
         src = src[:k] + STORE + src[k + len(COUNT_LINE):]
-    open(os.path.join(OUT, "gol_kernels.hip"), "w").write(src)
+        open(os.path.join(OUT, unit), "w").write(src)
     for f in os.listdir(CSRC):
-        if f.endswith((".cpp", ".h")) or f == "Makefile" or (f.endswith(".hip") and f != "gol_kernels.hip"):
+        if f.endswith((".cpp", ".h", ".hip")) and f not in PIPE_UNITS or f == "Makefile":
             with open(os.path.join(CSRC, f)) as a, open(os.path.join(OUT, f), "w") as b:
                 b.write(a.read())
     lib = os.path.join(VARIANTS, name + ".so")

@@ -2,7 +2,9 @@
 // stages), alone (MODE 0) and with the per-block LDS hand-off of a middle wave (MODE 1: three
 // ds_read_b32 + wait, three ds_write_b32 + wait, on the wave's own slot), at 1..8 waves per SIMD.
 //   hipcc --offload-arch=gfx950 -O3 -I../../include -I../../gol-distributed-final_amd/csrc byte_stage.hip -o byte_stage
-#include "gol_kernels.hip"
+#include <stdio.h>
+
+#include "old_stages.h"
 
 template <int KW, int MODE>
 __global__ void __launch_bounds__(256) bs_kernel(uint32_t *out, uint64_t *cyc, int iters)

@@ -11,8 +11,9 @@
 // ds_read_b32 poll that succeeds at once, readfirstlane).
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -mllvm -amdgpu-sched-strategy=max-ilp -mllvm -disable-post-ra \
 //     -I include -I gol-distributed-final_amd/csrc tools/ubench/pair_compute.hip -o tools/variants/pair_compute
-#define GOL_TU_BAND_PIPE 1  // only the band pipeline part of the kernels file
-#include "gol_kernels.hip"
+#include <stdio.h>
+
+#include "gol_pipe.h"
 
 template <int MODE>
 __global__ void __launch_bounds__(256) pc_kernel(uint32_t *out, uint64_t *cyc, int iters, const char *board)

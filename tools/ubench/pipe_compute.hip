@@ -2,7 +2,9 @@
 // 3 rows per block) with no memory traffic, at a given number of waves per SIMD: is the
 // split kernel's 2.86 cycles per VALU op the compute code's own rate or its memory/sync?
 //   hipcc --offload-arch=gfx950 -O3 -I../../include -I../../gol-distributed-final_amd/csrc pipe_compute.hip -o pipe_compute
-#include "gol_kernels.hip"
+#include <stdio.h>
+
+#include "old_stages.h"
 
 // MODE bit 2 (4): the op-by-op stage (bstage) instead of the word-by-word one (bstage_seq).
 // MODE 0: compute only.  MODE 1: + the pipe kernel's LDS hand-off per row (ds_write_b128 of

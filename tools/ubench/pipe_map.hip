@@ -8,7 +8,9 @@
 // Also prints the wave -> SIMD map of a 16-wave workgroup.  Reports SIMD cycles per
 // word-generation (10.5 VALU ops x 2 cycles = 21 at the issue peak).
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -I../../include -I../../gol-distributed-final_amd/csrc pipe_map.hip -o pipe_map
-#include "gol_kernels.hip"
+#include <stdio.h>
+
+#include "old_stages.h"
 
 using namespace golk;
 constexpr int DW = 4, KW = 3, P = 4, NS = 3, ROW = 256;

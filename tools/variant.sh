@@ -8,9 +8,11 @@
 #                                               replace the Makefile's scheduler / kernel flags)
 #   tools/variant.sh rev REV NAME               every source (and golhip.h) of a git revision
 #   tools/variant.sh patch NAME FILE [FLAGS]    current sources with FILE (a patch of csrc/, -p1) applied
-#   tools/variant.sh kernels REV NAME           current sources with gol_kernels.hip of REV (the
-#                                               kernels of REV behind today's engine and ABI; REV
-#                                               must have the rule launchers in that file)
+#   tools/variant.sh kernels REV NAME           current sources with the three kernel units of REV
+#                                               (gol_kernels.hip, gol_band_pipe.hip, gol_bytes_pipe.hip)
+#                                               and, where REV has them, its gol_device.h / gol_pipe.h:
+#                                               the kernels of REV behind today's engine and ABI (REV
+#                                               must have the rule launchers in gol_kernels.hip)
 #   tools/variant.sh res ["-DFLAG ..."]         VGPRs / LDS / scratch / occupancy of the pipe kernels
 set -e
 R=$(cd "$(dirname "$0")/.." && pwd)
@@ -53,7 +55,11 @@ case ${1:-} in
   kernels)
     REV=$2; N=$3; D=$V/src_$N
     copy_current "$D"
-    git -C "$R" show "$REV:gol-distributed-final_amd/csrc/gol_kernels.hip" > "$D/gol_kernels.hip"
+    for f in gol_kernels.hip gol_band_pipe.hip gol_bytes_pipe.hip gol_device.h gol_pipe.h; do
+      if git -C "$R" cat-file -e "$REV:gol-distributed-final_amd/csrc/$f" 2>/dev/null; then
+        git -C "$R" show "$REV:gol-distributed-final_amd/csrc/$f" > "$D/$f"
+      fi
+    done
     make -s -j8 -C "$D" ARCH=gfx950 BUILD=./obj OUT=../lib$N.so INC=$R/include
     rm -rf "$D"
     echo "$V/lib$N.so" ;;
@@ -68,5 +74,5 @@ case ${1:-} in
         grep -E "Function Name|VGPRs:|AGPRs|ScratchSize|Occupancy|LDS Size" | sed 's/.*remark: //'
     done ;;
   *)
-    sed -n '2,13p' "$0"; exit 2 ;;
+    sed -n '2,16p' "$0"; exit 2 ;;
 esac
