@@ -1,0 +1,115 @@
+// Sanitizer driver for the host twin of the batch kernel (gol_batch_host.cpp: gol_batch_step_host,
+// the row function of gol_batch.h that the kernel runs).  A stand-alone program: built only by
+// `make asan` from gol_batch_host.cpp with AddressSanitizer + UndefinedBehaviorSanitizer, linked
+// without the GPU runtime, and run as a plain child process by tests/test_batch_cpu.py.  Every buffer
+// is a heap block of its exact size -- (H - 1) * stride + ceil(W / 64) words -- so a read or write past
+// a row is a sanitizer report.  Each shape runs four turns of each rule from a random board whose
+// padding bits are set, out of place and in place, and every turn is compared with a cell-by-cell
+// count of the eight neighbours.  Exit status 0: all equal; 1: a difference (printed).
+#include <stdarg.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <string.h>
+
+#include <vector>
+
+#include "golhip.h"
+
+static char g_msg[512];
+int gol_set_error(int code, const char *fmt, ...)
+{
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_msg, sizeof g_msg, fmt, ap);
+    va_end(ap);
+    return code;
+}
+
+static uint64_t g_state = 0x9E3779B97F4A7C15ULL;
+static uint64_t rnd()
+{
+    g_state ^= g_state << 13;
+    g_state ^= g_state >> 7;
+    g_state ^= g_state << 17;
+    return g_state;
+}
+
+static int cell(const uint64_t *b, int64_t stride, int64_t y, int64_t x) { return (int)(b[y * stride + x / 64] >> (x % 64) & 1); }
+
+// the next state of the H x W cells of `in`, as a block like `in` with the padding zero
+static void naive(int64_t H, int64_t W, uint32_t birth, uint32_t survive, const uint64_t *in, uint64_t *out, int64_t stride)
+{
+    const int64_t Ww = (W + 63) / 64;
+    for (int64_t y = 0; y < H; ++y) {
+        for (int64_t w = 0; w < Ww; ++w) out[y * stride + w] = 0;
+        for (int64_t x = 0; x < W; ++x) {
+            int n = 0;
+            for (int dy = -1; dy <= 1; ++dy)
+                for (int dx = -1; dx <= 1; ++dx)
+                    if (dy || dx) n += cell(in, stride, (y + dy + H) % H, (x + dx + W) % W);
+            const uint32_t mask = cell(in, stride, y, x) ? survive : birth;
+            if (mask >> n & 1u) out[y * stride + x / 64] |= (uint64_t)1 << (x % 64);
+        }
+    }
+}
+
+static int check(int64_t H, int64_t W, int64_t pad, uint32_t birth, uint32_t survive)
+{
+    const int64_t Ww = (W + 63) / 64, stride = Ww + pad;
+    const size_t words = (size_t)((H - 1) * stride + Ww);
+    const uint64_t gap = 0xA5A5A5A5A5A5A5A5ULL;
+    uint64_t *a = new uint64_t[words], *b = new uint64_t[words], *want = new uint64_t[words];
+    for (size_t i = 0; i < words; ++i) a[i] = rnd() & rnd();  // (the padding bits of a row set, too)
+    int bad = 0;
+    for (int turn = 1; turn <= 4 && !bad; ++turn) {
+        for (size_t i = 0; i < words; ++i) want[i] = b[i] = gap;
+        naive(H, W, birth, survive, a, want, stride);
+        int rc;
+        if (turn & 1) {  // out of place
+            rc = gol_batch_step_host(H, W, birth, survive, a, b, stride);
+        } else {  // in place: the words between the rows are the input's, not the gap pattern
+            memcpy(b, a, words * sizeof(uint64_t));
+            for (int64_t y = 0; y + 1 < H; ++y)
+                for (int64_t w = Ww; w < stride; ++w) want[y * stride + w] = a[y * stride + w];
+            rc = gol_batch_step_host(H, W, birth, survive, b, b, stride);
+        }
+        if (rc != GOL_OK || memcmp(b, want, words * sizeof(uint64_t))) {
+            printf("%lldx%lld stride %lld B 0x%x S 0x%x turn %d: rc %d, differs\n", (long long)H, (long long)W, (long long)stride,
+                   birth, survive, turn, rc);
+            bad = 1;
+        }
+        memcpy(a, want, words * sizeof(uint64_t));
+        for (int64_t y = 0; y + 1 < H; ++y)  // garbage between the rows again: it is never read
+            for (int64_t w = Ww; w < stride; ++w) a[y * stride + w] = rnd();
+    }
+    delete[] a;
+    delete[] b;
+    delete[] want;
+    return bad;
+}
+
+int main()
+{
+    static const int shapes[][2] = {{1, 1}, {1, 2}, {2, 1}, {2, 2}, {3, 3}, {2, 5}, {5, 2}, {16, 16}, {7, 31}, {7, 32}, {7, 33},
+                                    {5, 63}, {5, 64}, {5, 65}, {3, 96}, {4, 511}, {4, 512}, {3, 481}, {64, 1}, {65, 31}};
+    static const uint32_t rules[][2] = {{0x008, 0x00C}, {0x048, 0x00C}, {0x1C8, 0x1D8}, {0x004, 0x000}, {0x001, 0x100},
+                                        {0x1FF, 0x1FF}};  // B3/S23 B36/S23 B3678/S34678 B2/S B0/S8 B012345678/S012345678
+    int bad = 0, n = 0;
+    for (const auto &s : shapes)
+        for (const auto &r : rules)
+            for (int pad = 0; pad <= 2; pad += 2, ++n) bad += check(s[0], s[1], pad, r[0], r[1]);
+    // the refusals write nothing
+    uint64_t w[8] = {0};
+    const int einval[] = {gol_batch_step_host(0, 8, 8, 12, w, w, 1),    gol_batch_step_host(8, 0, 8, 12, w, w, 1),
+                          gol_batch_step_host(513, 8, 8, 12, w, w, 1),  gol_batch_step_host(8, 513, 8, 12, w, w, 9),
+                          gol_batch_step_host(8, 8, 512, 12, w, w, 1),  gol_batch_step_host(8, 8, 8, 512, w, w, 1),
+                          gol_batch_step_host(8, 65, 8, 12, w, w, 1),   gol_batch_step_host(8, 8, 8, 12, nullptr, w, 1),
+                          gol_batch_step_host(8, 8, 8, 12, w, nullptr, 1)};
+    for (int rc : einval)
+        if (rc != GOL_EINVAL) {
+            printf("a bad argument returned %d\n", rc);
+            ++bad;
+        }
+    printf("batch_check: %d cases, %d bad\n", n, bad);
+    return bad ? 1 : 0;
+}

@@ -1,0 +1,109 @@
+// gol_batch.h -- one row of a small torus (1 <= H, W <= 512, any width) as up to 16 32-bit words in
+// one lane, and one turn of it: the horizontal sums of the row with the column wrap of a row that
+// ends inside a word, the tail mask, and the choice between the two rule circuits.  Shared by the
+// batch kernel (gol_batch.hip, one row per lane) and the host (gol_batch_step_host,
+// include/golhip.h), so the code the GPU runs is tested on the CPU.
+//
+// A row of W cells is nwr = ceil(W / 32) words c[0 .. nwr) (bit c % 32 of word c / 32 = cell c), held
+// in NW = nwr rounded up to 1, 2, 4, 8 or 16 words; the words from nwr on and the bits above tb =
+// (W - 1) % 32 of word nwr - 1 are zero (the padding).  The left and right neighbours of every cell,
+// as words:
+//   L[j] = (c[j] << 1) | (j > 0 ? c[j-1] >> 31 : cell W - 1)
+//   R[j] = (c[j] >> 1) | (j < nwr - 1 ? c[j+1] << 31 : cell 0 at bit tb)
+// and the row's horizontal sums h0 + 2 h1 = L + c + R per cell (the cell included, as in every
+// kernel here).  The three rows' sums go into the rule: B3/S23 the 7-gate circuit of the step
+// kernels (golk::rule), any other rule gol_rule_sum3 + gol_rule_eval (gol_rule.h).  The padding of the
+// result is cleared afterwards (a cell of the padding has neighbours, and B0 rules give birth there).
+#pragma once
+#include <stdint.h>
+
+#include "gol_rule.h"
+
+#define GOL_BATCH_HD GOL_RULE_HD
+#if defined(__HIP_DEVICE_COMPILE__)
+#define GOL_BATCH_UNROLL _Pragma("unroll")  // (a lane's words are registers: no loop may index them)
+#else
+#define GOL_BATCH_UNROLL
+#endif
+
+#define GOL_BATCH_MAX_SIDE 512  // cells: at most 16 words of a row, 8 waves of 64 rows
+#define GOL_BATCH_MAX_WAVES 8
+
+// The shape of a row: nwr words in use of nw held, the last cell's bit and the mask of the last word.
+struct gol_batch_row {
+    int32_t nwr, nw;
+    uint32_t tb, tail;
+};
+
+GOL_BATCH_HD gol_batch_row gol_batch_row_init(int64_t W)  // 1 <= W <= GOL_BATCH_MAX_SIDE
+{
+    gol_batch_row r;
+    r.nwr = (int32_t)((W + 31) / 32);
+    r.nw = 1;
+    while (r.nw < r.nwr) r.nw *= 2;
+    r.tb = (uint32_t)((W - 1) % 32);
+    r.tail = r.tb == 31 ? ~0u : (1u << (r.tb + 1)) - 1u;
+    return r;
+}
+
+GOL_BATCH_HD bool gol_batch_conway(uint32_t birth, uint32_t survive)
+{
+    return birth == GOL_RULE_BIRTH_CONWAY && survive == GOL_RULE_SURVIVE_CONWAY;
+}
+
+// The horizontal sums of a row (padding zero).  nwr and tb are wave-uniform in a kernel.
+template <int NW>
+GOL_BATCH_HD void gol_batch_hsum(const uint32_t (&c)[NW], int32_t nwr, uint32_t tb, uint32_t (&h0)[NW], uint32_t (&h1)[NW])
+{
+    uint32_t last = c[0];  // word nwr - 1, picked without a variable register index
+    GOL_BATCH_UNROLL
+    for (int j = 1; j < NW; ++j) last = j == nwr - 1 ? c[j] : last;
+    const uint32_t wl = (last >> tb) & 1u;  // cell W - 1, to the left of cell 0
+    const uint32_t wr = (c[0] & 1u) << tb;  // cell 0, to the right of cell W - 1
+    GOL_BATCH_UNROLL
+    for (int j = 0; j < NW; ++j) {
+        const uint32_t l = (c[j] << 1) | (j > 0 ? c[j > 0 ? j - 1 : 0] >> 31 : wl);
+        const uint32_t r = (c[j] >> 1) | (j + 1 < NW ? c[j + 1 < NW ? j + 1 : j] << 31 : 0u) | (j == nwr - 1 ? wr : 0u);
+        h0[j] = gol_rule_xor3(l, c[j], r);
+        h1[j] = gol_rule_maj(l, c[j], r);
+    }
+}
+
+// B3/S23 from the three rows' sums (a above, b the cell's own row, c below) and the cell.
+GOL_BATCH_HD uint32_t gol_batch_conway_next(uint32_t a0, uint32_t a1, uint32_t b0, uint32_t b1, uint32_t c0, uint32_t c1,
+                                            uint32_t cell)
+{
+#if defined(__HIP_DEVICE_COMPILE__) && defined(GOL_BATCH_CONWAY)  // (the kernel unit: golk::rule of gol_device.h)
+    return GOL_BATCH_CONWAY(a0, a1, b0, b1, c0, c1, cell);
+#else  // the same circuit in plain operators (gol_device.h: TT_G1, TT_G2, TT_OUT)
+    const uint32_t t0 = a0 ^ b0 ^ c0, k0 = (a0 & b0) | (c0 & (a0 | b0));
+    const uint32_t u = a1 ^ b1 ^ c1, v = (a1 & b1) | (c1 & (a1 | b1));
+    const uint32_t g1 = (t0 ^ k0 ^ v) & ~(t0 & k0 & v);  // exactly one of t0, k0, v
+    const uint32_t g2 = (~u & ~v & ~g1) | (~u & v & g1) | (u & ~v & g1);
+    return (t0 | cell) & g2;
+#endif
+}
+
+// One turn of a row: its next cells from the sums of the row above (a), its own (b) and the one
+// below (d).  GENERIC: the table circuit with t (gol_rule_expand), else B3/S23.  msk: all ones for a
+// row of the board, 0 for a lane without one.
+template <int NW, bool GENERIC>
+GOL_BATCH_HD void gol_batch_next(const gol_rule_tab &t, const gol_batch_row &g, const uint32_t (&a0)[NW],
+                                 const uint32_t (&a1)[NW], const uint32_t (&b0)[NW], const uint32_t (&b1)[NW],
+                                 const uint32_t (&d0)[NW], const uint32_t (&d1)[NW], const uint32_t (&cell)[NW], uint32_t msk,
+                                 uint32_t (&out)[NW])
+{
+    GOL_BATCH_UNROLL
+    for (int j = 0; j < NW; ++j) {
+        uint32_t v;
+        if (GENERIC) {
+            uint32_t t0, t1, t2, t3;
+            gol_rule_sum3(a0[j], a1[j], b0[j], b1[j], d0[j], d1[j], t0, t1, t2, t3);
+            v = gol_rule_eval(t, t0, t1, t2, t3, cell[j]);
+        } else {
+            v = gol_batch_conway_next(a0[j], a1[j], b0[j], b1[j], d0[j], d1[j], cell[j]);
+        }
+        const uint32_t keep = j < g.nwr - 1 ? ~0u : (j == g.nwr - 1 ? g.tail : 0u);  // (uniform)
+        out[j] = v & keep & msk;
+    }
+}

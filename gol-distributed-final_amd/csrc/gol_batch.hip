@@ -1,0 +1,255 @@
+// gol_batch.hip -- many small tori (1 <= H, W <= 512) stepped in one launch (include/golhip.h,
+// "batches of small boards"; the row function is gol_batch.h).
+//
+// batch_step_kernel<NW, GENERIC, SCAN>: a board never leaves its workgroup during a launch.  One
+// row per lane, NW = 1, 2, 4, 8 or 16 words of it in registers, ceil(H / 64) waves per board; boards
+// of up to 128 rows share a workgroup (4 boards of one wave, 2 of two).  The board is read from HBM
+// once, stepped `turns` times and written once, in place: no HBM traffic between the turns.
+// Per turn a lane computes the horizontal sums of its own row (gol_batch_hsum) and takes those of the
+// rows above and below from the neighbouring lanes by DPP (wave_shr:1 / wave_shl:1); only a wave's
+// first and last row cross a wave (or wrap round the torus: rows (y +- 1) mod H) and go through LDS,
+// double-buffered, so a turn has one __syncthreads() and the LDS of a workgroup is 256 NW + 64 bytes.
+// H = 1, 2 and a partly filled last wave are the same code: a lane without a row keeps zero words.
+// SCAN: the cells of the turn before stay in registers too, every lane compares its new row with
+// the row two turns back, one ballot per wave and turn says whether any word differs, and the
+// waves of a board exchange that bit through LDS under the next turn's barrier.  The first turn t
+// with state(t) == state(t - 2) goes to settled[board] unless an earlier launch of the call set it;
+// state(start - 1) of a launch comes from, and state(end - 1) goes to, a second device buffer.
+// Synchronisation is __syncthreads() alone: no workgroup waits for another one, there is no flag
+// between workgroups, no spin loop and no atomic.  Every wave of a workgroup runs every barrier (a
+// wave whose board is past the batch's end computes on zeros and stores nothing).
+//
+// The small kernels: random fill, and one wave per board for the alive count and the hash.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <algorithm>
+
+#include "gol_device.h"
+#define GOL_BATCH_CONWAY golk::rule  // B3/S23 on the step kernels' 7 gates
+#include "gol_batch.h"
+
+namespace {
+
+struct BatchArgs {
+    uint64_t *boards;  // n boards of H rows of Ww uint64 words, dense; stepped in place
+    uint64_t *prev;    // SCAN: state(start - 1) in (have_prev), state(end - 1) out (write_prev); same shape
+    int64_t *settled;  // SCAN: n turns, -1 = not settled yet
+    int64_t n, turn0;  // boards; the turn of the loaded state
+    gol_batch_row g;
+    int32_t H, Ww, wpb, bpw;  // rows, uint64 words per row, waves per board, boards per workgroup
+    int32_t turns;            // >= 1
+    int32_t have_prev, write_prev;
+    uint32_t birth, survive;
+};
+
+template <int NW>
+__device__ __forceinline__ void load_row(const uint64_t *row, int32_t Ww, bool on, uint32_t (&c)[NW])
+{
+    const uint32_t *p = (const uint32_t *)row;
+#pragma unroll
+    for (int j = 0; j < NW; ++j) c[j] = on && j < 2 * Ww ? p[j] : 0u;
+}
+
+// (a row is 2 Ww words in memory; with NW = 1 the second one is padding)
+template <int NW>
+__device__ __forceinline__ void store_row(uint64_t *row, int32_t Ww, const uint32_t (&c)[NW])
+{
+    uint32_t *p = (uint32_t *)row;
+#pragma unroll
+    for (int j = 0; j < (NW < 2 ? 2 : NW); ++j)
+        if (j < 2 * Ww) p[j] = j < NW ? c[j < NW ? j : 0] : 0u;
+}
+
+template <int NW, bool GENERIC, bool SCAN>
+__global__ __launch_bounds__(512) void batch_step_kernel(const BatchArgs a)
+{
+    // [buffer][wave][first / last row of the wave][h0 / h1][word]
+    __shared__ uint32_t edge[2][GOL_BATCH_MAX_WAVES][2][2][NW];
+    __shared__ uint32_t differs[2][GOL_BATCH_MAX_WAVES];
+
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lb = wave / a.wpb, w = wave - lb * a.wpb;  // the board's slot in the workgroup, the wave's in the board
+    const int64_t board = (int64_t)blockIdx.x * a.bpw + lb;
+    const int y = w * 64 + lane;
+    const int last = min(63, a.H - 1 - w * 64);  // the wave's last lane with a row
+    const bool on = board < a.n && y < a.H;
+    const uint32_t msk = on ? ~0u : 0u;
+    const int wup = lb * a.wpb + (w == 0 ? a.wpb - 1 : w - 1), wdn = lb * a.wpb + (w == a.wpb - 1 ? 0 : w + 1);
+    const gol_batch_row g = a.g;
+    gol_rule_tab tab;
+    gol_rule_expand(a.birth, a.survive, tab);
+
+    const int64_t off = (board * a.H + y) * a.Ww;
+    uint32_t cur[NW], old[NW];  // state(t - 1) and, SCAN, state(t - 2)
+    load_row<NW>(a.boards + (on ? off : 0), a.Ww, on, cur);
+    if (SCAN) load_row<NW>(a.prev + (on && a.have_prev ? off : 0), a.Ww, on && a.have_prev, old);
+
+    int64_t found = -1;  // uniform over the board's waves
+    bool mine = false;   // this wave's "a word differs" of the turn just computed
+    int buf = 0;
+    for (int it = 0; it < a.turns; ++it, buf ^= 1) {
+        uint32_t b0[NW], b1[NW], a0[NW], a1[NW], d0[NW], d1[NW], next[NW];
+        gol_batch_hsum<NW>(cur, g.nwr, g.tb, b0, b1);
+        if (lane == 0) {
+#pragma unroll
+            for (int j = 0; j < NW; ++j) { edge[buf][wave][0][0][j] = b0[j]; edge[buf][wave][0][1][j] = b1[j]; }
+        }
+        if (lane == last) {
+#pragma unroll
+            for (int j = 0; j < NW; ++j) { edge[buf][wave][1][0][j] = b0[j]; edge[buf][wave][1][1][j] = b1[j]; }
+        }
+        // the turn before compared its state with the one two turns back (none before the first loaded state)
+        const bool posted = SCAN && it >= (a.have_prev ? 1 : 2);
+        if (posted && lane == 0) differs[buf][wave] = mine;
+        __syncthreads();
+        if (posted && found < 0) {
+            bool any = false;
+            for (int i = 0; i < a.wpb; ++i) any |= differs[buf][lb * a.wpb + i] != 0;
+            if (!any) found = a.turn0 + it;
+        }
+#pragma unroll
+        for (int j = 0; j < NW; ++j) {
+            a0[j] = golk::from_lower_lane(b0[j]);
+            a1[j] = golk::from_lower_lane(b1[j]);
+            d0[j] = golk::from_upper_lane(b0[j]);
+            d1[j] = golk::from_upper_lane(b1[j]);
+        }
+        if (lane == 0) {
+#pragma unroll
+            for (int j = 0; j < NW; ++j) { a0[j] = edge[buf][wup][1][0][j]; a1[j] = edge[buf][wup][1][1][j]; }
+        }
+        if (lane == last) {
+#pragma unroll
+            for (int j = 0; j < NW; ++j) { d0[j] = edge[buf][wdn][0][0][j]; d1[j] = edge[buf][wdn][0][1][j]; }
+        }
+        gol_batch_next<NW, GENERIC>(tab, g, a0, a1, b0, b1, d0, d1, cur, msk, next);
+        if (SCAN) {
+            uint32_t d = 0;
+#pragma unroll
+            for (int j = 0; j < NW; ++j) {
+                d |= next[j] ^ old[j];
+                old[j] = cur[j];
+            }
+            mine = __ballot(d != 0) != 0;
+        }
+#pragma unroll
+        for (int j = 0; j < NW; ++j) cur[j] = next[j];
+    }
+    if (SCAN && (a.turns > 1 || a.have_prev)) {  // the last turn's comparison (buf: the buffer no wave reads any more)
+        if (lane == 0) differs[buf][wave] = mine;
+        __syncthreads();
+        if (found < 0) {
+            bool any = false;
+            for (int i = 0; i < a.wpb; ++i) any |= differs[buf][lb * a.wpb + i] != 0;
+            if (!any) found = a.turn0 + a.turns;
+        }
+    }
+    if (on) {
+        store_row<NW>(a.boards + off, a.Ww, cur);
+        if (SCAN && a.write_prev) store_row<NW>(a.prev + off, a.Ww, old);
+        if (SCAN && y == 0 && found >= 0 && a.settled[board] < 0) a.settled[board] = found;
+    }
+}
+
+// word(i, y, w) = splitmix64(seed ^ ((i H + y) Ww + w)), the padding of a row's last word cleared
+__global__ __launch_bounds__(256) void batch_random_kernel(uint64_t *boards, int64_t words, int32_t Ww, uint64_t tail,
+                                                           uint64_t seed)
+{
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < words; i += (int64_t)gridDim.x * 256) {
+        const uint64_t v = golk::splitmix64(seed ^ (uint64_t)i);
+        boards[i] = i % Ww == Ww - 1 ? v & tail : v;
+    }
+}
+
+// out[board] = its alive cells (HASH: sum of splitmix64(word ^ splitmix64(index in the board))); a wave per board
+template <bool HASH>
+__global__ __launch_bounds__(256) void batch_reduce_kernel(const uint64_t *boards, int64_t n, int32_t words, uint64_t *out)
+{
+    const int lane = threadIdx.x & 63;
+    for (int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); b < n; b += (int64_t)gridDim.x * 4) {
+        const uint64_t *p = boards + b * words;
+        uint64_t s = 0;
+        for (int i = lane; i < words; i += 64)
+            s += HASH ? golk::splitmix64(p[i] ^ golk::splitmix64((uint64_t)i)) : (uint64_t)__popcll(p[i]);
+        s = golk::wave_sum_u64(s);
+        if (lane == 0) out[b] = s;
+    }
+}
+
+template <int NW, bool GENERIC>
+hipError_t launch_scan(bool scan, const BatchArgs &a, dim3 grid, dim3 block, hipStream_t s)
+{
+    if (scan) batch_step_kernel<NW, GENERIC, true><<<grid, block, 0, s>>>(a);
+    else batch_step_kernel<NW, GENERIC, false><<<grid, block, 0, s>>>(a);
+    return hipGetLastError();
+}
+
+template <int NW>
+hipError_t launch_rule(bool generic, bool scan, const BatchArgs &a, dim3 grid, dim3 block, hipStream_t s)
+{
+    return generic ? launch_scan<NW, true>(scan, a, grid, block, s) : launch_scan<NW, false>(scan, a, grid, block, s);
+}
+
+}  // namespace
+
+void golk_batch_shape(int64_t H, int64_t W, int *waves_per_board, int *boards_per_wg, int *words_per_lane)
+{
+    const int wpb = (int)((H + 63) / 64);
+    *waves_per_board = wpb;
+    *boards_per_wg = std::max(1, 4 / wpb);
+    *words_per_lane = gol_batch_row_init(W).nw;
+}
+
+hipError_t golk_batch_step(uint64_t *boards, uint64_t *prev, int64_t *settled, int64_t n, int64_t H, int64_t W, int turns,
+                           int64_t turn0, bool have_prev, bool write_prev, uint32_t birth, uint32_t survive, hipStream_t s)
+{
+    if (!boards || n < 1 || n > ((int64_t)1 << 20) || H < 1 || H > GOL_BATCH_MAX_SIDE || W < 1 || W > GOL_BATCH_MAX_SIDE ||
+        turns < 1 || birth >= 512 || survive >= 512 || (settled && !prev) || ((have_prev || write_prev) && !settled))
+        return hipErrorInvalidValue;
+    BatchArgs a{};
+    int nw;
+    golk_batch_shape(H, W, &a.wpb, &a.bpw, &nw);
+    a.boards = boards;
+    a.prev = prev;
+    a.settled = settled;
+    a.n = n;
+    a.turn0 = turn0;
+    a.g = gol_batch_row_init(W);
+    a.H = (int32_t)H;
+    a.Ww = (int32_t)((W + 63) / 64);
+    a.turns = turns;
+    a.have_prev = have_prev;
+    a.write_prev = write_prev;
+    a.birth = birth;
+    a.survive = survive;
+    const dim3 grid((unsigned)((n + a.bpw - 1) / a.bpw)), block((unsigned)(a.bpw * a.wpb * 64));
+    const bool generic = !gol_batch_conway(birth, survive), scan = settled != nullptr;
+    switch (nw) {
+    case 1: return launch_rule<1>(generic, scan, a, grid, block, s);
+    case 2: return launch_rule<2>(generic, scan, a, grid, block, s);
+    case 4: return launch_rule<4>(generic, scan, a, grid, block, s);
+    case 8: return launch_rule<8>(generic, scan, a, grid, block, s);
+    default: return launch_rule<16>(generic, scan, a, grid, block, s);
+    }
+}
+
+hipError_t golk_batch_random(uint64_t *boards, int64_t n, int64_t H, int64_t W, uint64_t seed, hipStream_t s)
+{
+    if (!boards || n < 1 || H < 1 || H > GOL_BATCH_MAX_SIDE || W < 1 || W > GOL_BATCH_MAX_SIDE) return hipErrorInvalidValue;
+    const int64_t Ww = (W + 63) / 64, words = n * H * Ww;
+    const uint64_t tail = W % 64 ? ((uint64_t)1 << (W % 64)) - 1 : ~(uint64_t)0;
+    const unsigned grid = (unsigned)std::min<int64_t>((words + 255) / 256, 8192);
+    batch_random_kernel<<<grid, 256, 0, s>>>(boards, words, (int32_t)Ww, tail, seed);
+    return hipGetLastError();
+}
+
+hipError_t golk_batch_reduce(bool hash, const uint64_t *boards, int64_t n, int64_t H, int64_t W, uint64_t *out, hipStream_t s)
+{
+    if (!boards || !out || n < 1 || H < 1 || H > GOL_BATCH_MAX_SIDE || W < 1 || W > GOL_BATCH_MAX_SIDE) return hipErrorInvalidValue;
+    const int32_t words = (int32_t)(H * ((W + 63) / 64));
+    const unsigned grid = (unsigned)std::min<int64_t>((n + 3) / 4, 8192);
+    if (hash) batch_reduce_kernel<true><<<grid, 256, 0, s>>>(boards, n, words, out);
+    else batch_reduce_kernel<false><<<grid, 256, 0, s>>>(boards, n, words, out);
+    return hipGetLastError();
+}

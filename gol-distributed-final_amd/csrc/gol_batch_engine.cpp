@@ -1,0 +1,281 @@
+// gol_batch_engine.cpp -- batches of small boards (include/golhip.h): the handle, the argument
+// checks, the split of a stepping call into launches and the strided copies.  The kernels are
+// gol_batch.hip (whose object takes the name gol_batch.o), the host twin gol_batch_host.cpp.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <new>
+#include <vector>
+
+#include "gol_batch.h"
+#include "gol_engine_int.h"
+
+// A launch is bounded to about this many cell-updates (and GOL_BATCH_MAX_TURNS turns), as the
+// broker's chunks are: no launch runs long, whatever the batch.
+#define GOL_BATCH_LAUNCH_UPDATES ((int64_t)1 << 35)
+#define GOL_BATCH_MAX_TURNS 4096
+#define GOL_BATCH_MAX_BOARDS ((int64_t)1 << 20)
+// Strided loads and stores are staged through a dense host block of at most this many bytes.
+#define GOL_BATCH_STAGE_BYTES ((int64_t)64 << 20)
+
+struct gol_batch {
+    int64_t n = 0, H = 0, W = 0, Ww = 0;
+    int device = 0;
+    int tpl = 1;  // turns per launch at most
+    int wpb = 1, bpw = 1, nw = 1;
+    uint32_t birth = GOL_RULE_BIRTH_CONWAY, survive = GOL_RULE_SURVIVE_CONWAY;
+    int64_t turn = 0;
+    hipStream_t stream = nullptr;
+    uint64_t *boards = nullptr;
+    uint64_t *prev = nullptr;  // state(start - 1) between the launches of a scanning call (on demand)
+    uint64_t *aux = nullptr;   // n words: the settle turns, the counts, the hashes (on demand)
+};
+
+namespace {
+
+// The batch's device for the length of a call.
+struct OnDevice {
+    int before = -1;
+    hipError_t err;
+    explicit OnDevice(int device)
+    {
+        err = hipGetDevice(&before);
+        if (err == hipSuccess && before != device) err = hipSetDevice(device);
+    }
+    ~OnDevice()
+    {
+        if (before >= 0) (void)hipSetDevice(before);
+    }
+};
+
+int need_aux(gol_batch *b)
+{
+    if (!b->aux) HIPCHK(hipMalloc(&b->aux, (size_t)b->n * sizeof(uint64_t)));
+    return GOL_OK;
+}
+
+uint64_t tail_mask(int64_t W) { return W % 64 ? ((uint64_t)1 << (W % 64)) - 1 : ~(uint64_t)0; }
+
+int range_check(const gol_batch *b, const char *what, int64_t i0, int64_t i1, const void *words, int64_t row_stride,
+                int64_t board_stride)
+{
+    if (!b || !words || i0 < 0 || i0 > i1 || i1 > b->n || row_stride < b->Ww || board_stride < (b->H - 1) * row_stride + b->Ww)
+        return gol_set_error(GOL_EINVAL, "bad batch %s (boards [%lld, %lld) of %lld, row stride %lld, board stride %lld)", what,
+                             (long long)i0, (long long)i1, b ? (long long)b->n : 0LL, (long long)row_stride,
+                             (long long)board_stride);
+    return GOL_OK;
+}
+
+// out[0 .. n) = the alive counts or the hashes
+int reduce(gol_batch *b, bool hash, uint64_t *out, int64_t cap)
+{
+    if (!b || !out || cap < b->n)
+        return gol_set_error(GOL_EINVAL, "bad batch %s (cap %lld for %lld boards)", hash ? "hashes" : "alive_counts",
+                             (long long)cap, b ? (long long)b->n : 0LL);
+    OnDevice dev(b->device);
+    HIPCHK(dev.err);
+    const int rc = need_aux(b);
+    if (rc) return rc;
+    HIPCHK(golk_batch_reduce(hash, b->boards, b->n, b->H, b->W, b->aux, b->stream));
+    HIPCHK(hipMemcpyAsync(out, b->aux, (size_t)b->n * sizeof(uint64_t), hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    return GOL_OK;
+}
+
+}  // namespace
+
+extern "C" void gol_batch_destroy(gol_batch *b)
+{
+    if (!b) return;
+    {
+        OnDevice dev(b->device);
+        if (b->stream) (void)hipStreamSynchronize(b->stream);
+        if (b->boards) (void)hipFree(b->boards);
+        if (b->prev) (void)hipFree(b->prev);
+        if (b->aux) (void)hipFree(b->aux);
+        if (b->stream) (void)hipStreamDestroy(b->stream);
+    }
+    delete b;
+}
+
+extern "C" int gol_batch_create(int64_t n, int64_t H, int64_t W, int32_t device, int32_t turns_per_launch, gol_batch **out)
+{
+    if (!out || n < 1 || n > GOL_BATCH_MAX_BOARDS || H < 1 || H > GOL_BATCH_MAX_SIDE || W < 1 || W > GOL_BATCH_MAX_SIDE ||
+        turns_per_launch < 0 || device < -1)
+        return gol_set_error(GOL_EINVAL, "bad batch (n %lld in 1..2^20, H %lld and W %lld in 1..%d, turns per launch %d >= 0)",
+                             (long long)n, (long long)H, (long long)W, GOL_BATCH_MAX_SIDE, turns_per_launch);
+    *out = nullptr;
+    int dev = device;
+    if (dev < 0) HIPCHK(hipGetDevice(&dev));
+    int count = 0;
+    HIPCHK(hipGetDeviceCount(&count));
+    if (dev >= count) return gol_set_error(GOL_EINVAL, "device %d of %d", dev, count);
+    gol_batch *b = new (std::nothrow) gol_batch;
+    if (!b) return gol_set_error(GOL_ENOMEM, "batch handle");
+    b->n = n;
+    b->H = H;
+    b->W = W;
+    b->Ww = (W + 63) / 64;
+    b->device = dev;
+    golk_batch_shape(H, W, &b->wpb, &b->bpw, &b->nw);
+    b->tpl = turns_per_launch > 0
+                 ? turns_per_launch
+                 : (int)std::min<int64_t>(GOL_BATCH_MAX_TURNS, std::max<int64_t>(1, GOL_BATCH_LAUNCH_UPDATES / (n * H * W)));
+    auto fail = [&](int rc) {
+        gol_batch_destroy(b);
+        return rc;
+    };
+    OnDevice on(dev);
+    hipError_t e = on.err;
+    if (e == hipSuccess) e = hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipMalloc(&b->boards, (size_t)(n * H * b->Ww) * sizeof(uint64_t));
+    if (e == hipSuccess) e = hipMemsetAsync(b->boards, 0, (size_t)(n * H * b->Ww) * sizeof(uint64_t), b->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
+    if (e != hipSuccess)
+        return fail(gol_set_error(e == hipErrorOutOfMemory ? GOL_ENOMEM : GOL_EHIP, "batch of %lld boards: %s", (long long)n,
+                                  hipGetErrorString(e)));
+    *out = b;
+    return GOL_OK;
+}
+
+extern "C" int gol_batch_info(gol_batch *b, int64_t *n, int64_t *H, int64_t *W, int32_t *waves_per_board,
+                              int32_t *boards_per_workgroup, int32_t *words_per_lane, int32_t *turns_per_launch)
+{
+    if (!b) return gol_set_error(GOL_EINVAL, "batch is NULL");
+    if (n) *n = b->n;
+    if (H) *H = b->H;
+    if (W) *W = b->W;
+    if (waves_per_board) *waves_per_board = b->wpb;
+    if (boards_per_workgroup) *boards_per_workgroup = b->bpw;
+    if (words_per_lane) *words_per_lane = b->nw;
+    if (turns_per_launch) *turns_per_launch = b->tpl;
+    return GOL_OK;
+}
+
+extern "C" int gol_batch_set_rule(gol_batch *b, uint32_t birth, uint32_t survive)
+{
+    if (!b || birth >= 512 || survive >= 512)
+        return gol_set_error(GOL_EINVAL, "bad batch rule (B 0x%x, S 0x%x: masks are 9 bits)", birth, survive);
+    b->birth = birth;
+    b->survive = survive;
+    return GOL_OK;
+}
+
+extern "C" int gol_batch_rule(gol_batch *b, uint32_t *birth, uint32_t *survive)
+{
+    if (!b) return gol_set_error(GOL_EINVAL, "batch is NULL");
+    if (birth) *birth = b->birth;
+    if (survive) *survive = b->survive;
+    return GOL_OK;
+}
+
+extern "C" int gol_batch_turn(gol_batch *b, int64_t *turn)
+{
+    if (!b || !turn) return gol_set_error(GOL_EINVAL, "bad batch turn arguments (NULL)");
+    *turn = b->turn;
+    return GOL_OK;
+}
+
+extern "C" int gol_batch_load_words(gol_batch *b, int64_t i0, int64_t i1, const uint64_t *words, int64_t row_stride,
+                                    int64_t board_stride)
+{
+    const int rc = range_check(b, "load_words", i0, i1, words, row_stride, board_stride);
+    if (rc) return rc;
+    OnDevice dev(b->device);
+    HIPCHK(dev.err);
+    const int64_t bw = b->H * b->Ww;  // words of a board on the device
+    if (row_stride == b->Ww && board_stride == bw && b->W % 64 == 0) {
+        HIPCHK(hipMemcpyAsync(b->boards + i0 * bw, words, (size_t)((i1 - i0) * bw) * sizeof(uint64_t), hipMemcpyHostToDevice,
+                              b->stream));
+        HIPCHK(hipStreamSynchronize(b->stream));
+    } else {  // dense and masked on the host first
+        const int64_t per = std::max<int64_t>(1, GOL_BATCH_STAGE_BYTES / (bw * (int64_t)sizeof(uint64_t)));
+        const uint64_t tail = tail_mask(b->W);
+        std::vector<uint64_t> stage((size_t)(std::min(per, std::max<int64_t>(i1 - i0, 1)) * bw));
+        for (int64_t c0 = i0; c0 < i1; c0 += per) {
+            const int64_t c1 = std::min(i1, c0 + per);
+            for (int64_t i = c0; i < c1; ++i)
+                for (int64_t y = 0; y < b->H; ++y) {
+                    uint64_t *d = stage.data() + ((i - c0) * b->H + y) * b->Ww;
+                    memcpy(d, words + (i - i0) * board_stride + y * row_stride, (size_t)b->Ww * sizeof(uint64_t));
+                    d[b->Ww - 1] &= tail;
+                }
+            HIPCHK(hipMemcpyAsync(b->boards + c0 * bw, stage.data(), (size_t)((c1 - c0) * bw) * sizeof(uint64_t),
+                                  hipMemcpyHostToDevice, b->stream));
+            HIPCHK(hipStreamSynchronize(b->stream));  // (the stage is reused)
+        }
+    }
+    b->turn = 0;
+    return GOL_OK;
+}
+
+extern "C" int gol_batch_store_words(gol_batch *b, int64_t i0, int64_t i1, uint64_t *words, int64_t row_stride,
+                                     int64_t board_stride)
+{
+    const int rc = range_check(b, "store_words", i0, i1, words, row_stride, board_stride);
+    if (rc) return rc;
+    OnDevice dev(b->device);
+    HIPCHK(dev.err);
+    const int64_t bw = b->H * b->Ww;
+    if (row_stride == b->Ww && board_stride == bw) {
+        HIPCHK(hipMemcpyAsync(words, b->boards + i0 * bw, (size_t)((i1 - i0) * bw) * sizeof(uint64_t), hipMemcpyDeviceToHost,
+                              b->stream));
+        HIPCHK(hipStreamSynchronize(b->stream));
+        return GOL_OK;
+    }
+    const int64_t per = std::max<int64_t>(1, GOL_BATCH_STAGE_BYTES / (bw * (int64_t)sizeof(uint64_t)));
+    std::vector<uint64_t> stage((size_t)(std::min(per, std::max<int64_t>(i1 - i0, 1)) * bw));
+    for (int64_t c0 = i0; c0 < i1; c0 += per) {
+        const int64_t c1 = std::min(i1, c0 + per);
+        HIPCHK(hipMemcpyAsync(stage.data(), b->boards + c0 * bw, (size_t)((c1 - c0) * bw) * sizeof(uint64_t),
+                              hipMemcpyDeviceToHost, b->stream));
+        HIPCHK(hipStreamSynchronize(b->stream));
+        for (int64_t i = c0; i < c1; ++i)
+            for (int64_t y = 0; y < b->H; ++y)  // Ww words of a row: the words between rows and boards stay
+                memcpy(words + (i - i0) * board_stride + y * row_stride, stage.data() + ((i - c0) * b->H + y) * b->Ww,
+                       (size_t)b->Ww * sizeof(uint64_t));
+    }
+    return GOL_OK;
+}
+
+extern "C" int gol_batch_load_random(gol_batch *b, uint64_t seed)
+{
+    if (!b) return gol_set_error(GOL_EINVAL, "batch is NULL");
+    OnDevice dev(b->device);
+    HIPCHK(dev.err);
+    HIPCHK(golk_batch_random(b->boards, b->n, b->H, b->W, seed, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    b->turn = 0;
+    return GOL_OK;
+}
+
+extern "C" int gol_batch_step(gol_batch *b, int64_t turns, int64_t *settled)
+{
+    if (!b || turns < 0) return gol_set_error(GOL_EINVAL, "bad batch step (turns %lld)", (long long)turns);
+    OnDevice dev(b->device);
+    HIPCHK(dev.err);
+    int64_t *found = nullptr;
+    if (settled) {  // (turns < 2: nothing can be found, every board is -1)
+        const int rc = need_aux(b);
+        if (rc) return rc;
+        if (!b->prev) HIPCHK(hipMalloc(&b->prev, (size_t)(b->n * b->H * b->Ww) * sizeof(uint64_t)));
+        found = (int64_t *)b->aux;
+        HIPCHK(hipMemsetAsync(found, 0xff, (size_t)b->n * sizeof(int64_t), b->stream));
+    }
+    for (int64_t done = 0; done < turns;) {
+        const int k = (int)std::min<int64_t>(b->tpl, turns - done);
+        HIPCHK(golk_batch_step(b->boards, found ? b->prev : nullptr, found, b->n, b->H, b->W, k, b->turn + done, found && done > 0,
+                               found && done + k < turns, b->birth, b->survive, b->stream));
+        done += k;
+    }
+    if (found) HIPCHK(hipMemcpyAsync(settled, found, (size_t)b->n * sizeof(int64_t), hipMemcpyDeviceToHost, b->stream));
+    const hipError_t e = hipStreamSynchronize(b->stream);
+    if (e != hipSuccess) return gol_set_error(GOL_EHIP, "batch step: %s", hipGetErrorString(e));
+    b->turn += turns;
+    return GOL_OK;
+}
+
+extern "C" int gol_batch_alive_counts(gol_batch *b, uint64_t *counts, int64_t cap) { return reduce(b, false, counts, cap); }
+
+extern "C" int gol_batch_hashes(gol_batch *b, uint64_t *hashes, int64_t cap) { return reduce(b, true, hashes, cap); }

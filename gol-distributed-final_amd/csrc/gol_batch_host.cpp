@@ -1,0 +1,74 @@
+// gol_batch_host.cpp -- gol_batch_step_host (include/golhip.h): one turn of one small torus on host
+// memory with the row function of the batch kernel (gol_batch.h), in the instantiation the kernel
+// picks for the width, row by row as the lanes do.  No HIP header: a stand-alone program links this
+// file alone (batch_check.cpp).
+#include <stdint.h>
+
+#include <vector>
+
+#include "gol_batch.h"
+#include "golhip.h"
+
+int gol_set_error(int code, const char *fmt, ...);
+
+namespace {
+
+template <int NW>
+void step_host(int64_t H, const gol_batch_row &g, uint32_t birth, uint32_t survive, const uint64_t *in, uint64_t *out,
+               int64_t stride)
+{
+    const int64_t Ww = (g.nwr + 1) / 2;
+    gol_rule_tab tab;
+    gol_rule_expand(birth, survive, tab);
+    // every row's cells (the padding of the input masked off) and sums first: out may be in
+    std::vector<uint32_t> cells((size_t)H * NW), s0((size_t)H * NW), s1((size_t)H * NW);
+    for (int64_t y = 0; y < H; ++y) {
+        uint32_t c[NW], h0[NW], h1[NW];
+        for (int j = 0; j < NW; ++j) {
+            c[j] = j < g.nwr ? (uint32_t)(in[y * stride + j / 2] >> (32 * (j & 1))) : 0u;
+            if (j == g.nwr - 1) c[j] &= g.tail;
+        }
+        gol_batch_hsum<NW>(c, g.nwr, g.tb, h0, h1);
+        for (int j = 0; j < NW; ++j) {
+            cells[(size_t)y * NW + j] = c[j];
+            s0[(size_t)y * NW + j] = h0[j];
+            s1[(size_t)y * NW + j] = h1[j];
+        }
+    }
+    for (int64_t y = 0; y < H; ++y) {
+        const size_t ya = (size_t)((y + H - 1) % H) * NW, yb = (size_t)y * NW, yd = (size_t)((y + 1) % H) * NW;
+        uint32_t a0[NW], a1[NW], b0[NW], b1[NW], d0[NW], d1[NW], c[NW], next[NW];
+        for (int j = 0; j < NW; ++j) {
+            a0[j] = s0[ya + j], a1[j] = s1[ya + j];
+            b0[j] = s0[yb + j], b1[j] = s1[yb + j];
+            d0[j] = s0[yd + j], d1[j] = s1[yd + j];
+            c[j] = cells[yb + j];
+        }
+        if (gol_batch_conway(birth, survive)) gol_batch_next<NW, false>(tab, g, a0, a1, b0, b1, d0, d1, c, ~0u, next);
+        else gol_batch_next<NW, true>(tab, g, a0, a1, b0, b1, d0, d1, c, ~0u, next);
+        for (int64_t w = 0; w < Ww; ++w) {  // (an odd nwr: the upper half of the last word is padding)
+            const uint32_t lo = next[2 * w], hi = 2 * w + 1 < NW ? next[2 * w + 1 < NW ? 2 * w + 1 : 0] : 0u;
+            out[y * stride + w] = (uint64_t)lo | (uint64_t)hi << 32;
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" int gol_batch_step_host(int64_t H, int64_t W, uint32_t birth, uint32_t survive, const uint64_t *in, uint64_t *out,
+                                   int64_t row_stride)
+{
+    if (H < 1 || H > GOL_BATCH_MAX_SIDE || W < 1 || W > GOL_BATCH_MAX_SIDE || birth >= 512 || survive >= 512 || !in || !out ||
+        row_stride < (W + 63) / 64)
+        return gol_set_error(GOL_EINVAL, "bad host batch step (H %lld, W %lld, B 0x%x, S 0x%x, row stride %lld)", (long long)H,
+                             (long long)W, birth, survive, (long long)row_stride);
+    const gol_batch_row g = gol_batch_row_init(W);
+    switch (g.nw) {
+    case 1: step_host<1>(H, g, birth, survive, in, out, row_stride); break;
+    case 2: step_host<2>(H, g, birth, survive, in, out, row_stride); break;
+    case 4: step_host<4>(H, g, birth, survive, in, out, row_stride); break;
+    case 8: step_host<8>(H, g, birth, survive, in, out, row_stride); break;
+    default: step_host<16>(H, g, birth, survive, in, out, row_stride); break;
+    }
+    return GOL_OK;
+}

@@ -141,6 +141,21 @@ int64_t golk_bounds_lanes(int form, const void *src, int64_t pitch, int64_t W, i
 hipError_t golk_bounds_cols(int form, const void *src, int64_t pitch, int64_t W, int64_t x0, int64_t w, const uint32_t *occ,
                             uint64_t *hdr, hipStream_t s);
 
+// Batches of small boards (gol_batch.hip): n tori of H x W cells (1 <= H, W <= 512, n <= 2^20), board i
+// at boards + i*H*Ww, Ww = ceil(W / 64) uint64 words per row, the bits at c >= W of a row zero.
+// golk_batch_shape: waves per board, boards per workgroup and 32-bit words per lane of the step kernel.
+// golk_batch_step: `turns` >= 1 turns of every board in one launch, in place.  settled != NULL (then
+// prev != NULL, a second buffer of the boards' shape): settled[i] < 0 becomes the first turn t in
+// (turn0 + (have_prev ? 0 : 1), turn0 + turns] with state(t) == state(t - 2); have_prev: prev holds
+// state(turn0 - 1); write_prev: prev receives state(turn0 + turns - 1).
+void golk_batch_shape(int64_t H, int64_t W, int *waves_per_board, int *boards_per_wg, int *words_per_lane);
+hipError_t golk_batch_step(uint64_t *boards, uint64_t *prev, int64_t *settled, int64_t n, int64_t H, int64_t W, int turns,
+                           int64_t turn0, bool have_prev, bool write_prev, uint32_t birth, uint32_t survive, hipStream_t s);
+// word(i, y, w) = splitmix64(seed ^ ((i*H + y)*Ww + w)) masked to W
+hipError_t golk_batch_random(uint64_t *boards, int64_t n, int64_t H, int64_t W, uint64_t seed, hipStream_t s);
+// out[i] = alive cells of board i, or (hash) its oracle_hash_words
+hipError_t golk_batch_reduce(bool hash, const uint64_t *boards, int64_t n, int64_t H, int64_t W, uint64_t *out, hipStream_t s);
+
 // IPC transport (gol_comm.h): set *flag = value with release ordering at system scope after the
 // stream's earlier work; wait (one wave on the stream) until every flags[i] (i < n <= 4, other
 // processes' flag words mapped through IPC) has reached `want` (wrap-safe sequence compare),

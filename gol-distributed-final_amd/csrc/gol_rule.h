@@ -13,7 +13,7 @@
 #include <stdint.h>
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
-#define GOL_RULE_HD __host__ __device__ __forceinline__
+#define GOL_RULE_HD __host__ __device__ inline __attribute__((always_inline))  // (no HIP header needed)
 #else
 #define GOL_RULE_HD inline
 #endif

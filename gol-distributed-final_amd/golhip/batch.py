@@ -1,0 +1,164 @@
+"""Many small Game-of-Life boards stepped in one launch (ctypes wrapper of gol_batch_*).
+
+An ``Engine`` steps one board per launch, and on the reference's own boards (16² … 512²) a launch is
+latency-bound.  A ``Batch`` holds n independent H x W tori (1 <= H, W <= 512, any width, n <= 2^20) on
+one GPU, with one rule and one turn counter; a launch keeps every board resident in one workgroup
+for all its turns, and can report the turn at which each board settled into a still life or a
+period-2 oscillator.  Boards are bit-packed like ``Engine.load_words``: bit c % 64 of word c // 64 of
+a row is cell c, ceil(W / 64) uint64 words per row, the bits at c >= W zero.
+"""
+from __future__ import annotations
+
+import ctypes
+
+import numpy as np
+
+from ._lib import GOL_EINVAL, GolError, format_rule, lib, parse_rule
+
+
+class Batch:
+    def __init__(self, n: int, height: int, width: int, rule="B3/S23", device: int = 0, turns_per_launch: int = 0,
+                 library=None):
+        self.n, self.H, self.W = int(n), int(height), int(width)
+        self.Ww = (self.W + 63) // 64
+        self._L = library or lib()
+        h = ctypes.c_void_p()
+        self._check(self._L.gol_batch_create(self.n, self.H, self.W, device, turns_per_launch, ctypes.byref(h)))
+        self._h = h
+        if rule is not None:
+            try:
+                self.set_rule(rule)
+            except BaseException:
+                self.close()
+                raise
+
+    def _check(self, rc: int) -> None:
+        if rc:
+            raise GolError(rc, self._L.gol_last_error().decode(errors="replace"))
+
+    # -- lifetime
+    def close(self) -> None:
+        if getattr(self, "_h", None) and self._h.value:
+            self._L.gol_batch_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    # -- bytes <-> words (host only)
+    @staticmethod
+    def pack(boards) -> np.ndarray:
+        """uint8[..., H, W] cells (non-zero = alive) as uint64[..., H, ceil(W / 64)] words, padding zero."""
+        a = np.asarray(boards)
+        if a.ndim < 2 or a.shape[-1] < 1:
+            raise GolError(GOL_EINVAL, f"boards are arrays of at least one column, got shape {a.shape}")
+        W = a.shape[-1]
+        bits = np.zeros(a.shape[:-1] + ((W + 63) // 64 * 64,), dtype=np.uint8)
+        bits[..., :W] = a != 0
+        return np.ascontiguousarray(np.packbits(bits, axis=-1, bitorder="little")).view("<u8")
+
+    @staticmethod
+    def unpack(words, width: int) -> np.ndarray:
+        """The inverse of pack: uint8[..., H, width] of 0 / 255."""
+        w = np.ascontiguousarray(words, dtype="<u8")
+        return np.unpackbits(w.view(np.uint8), axis=-1, bitorder="little")[..., :width] * np.uint8(255)
+
+    # -- boards in / out
+    def load(self, boards, first: int = 0) -> None:
+        """Boards [first, first + len(boards)) from uint8[m, H, W] (non-zero = alive); the others stay.
+        Resets the turn counter."""
+        a = np.asarray(boards)
+        if a.ndim != 3 or a.shape[1:] != (self.H, self.W):
+            raise ValueError(f"expected (m, {self.H}, {self.W}) cells, got {a.shape}")
+        self.load_words(self.pack(a), first)
+
+    def store(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        """Boards [first, first + count) as uint8[count, H, W] of 0 / 255 (default: all from `first`)."""
+        return self.unpack(self.store_words(first, count), self.W)
+
+    def load_words(self, words, first: int = 0) -> None:
+        """Boards [first, first + m) from uint64[m, H, S] rows, S >= ceil(W / 64) (the words past
+        ceil(W / 64) of a row and set bits at c >= W are ignored).  Resets the turn counter."""
+        w = np.ascontiguousarray(words, dtype=np.uint64)
+        if w.ndim != 3 or w.shape[1] != self.H or w.shape[2] < self.Ww:
+            raise ValueError(f"expected (m, {self.H}, >= {self.Ww}) uint64 words, got {w.shape}")
+        self._check(self._L.gol_batch_load_words(self._h, first, first + w.shape[0], w.ctypes.data, w.shape[2],
+                                                 self.H * w.shape[2]))
+
+    def store_words(self, first: int = 0, count: int | None = None, out=None) -> np.ndarray:
+        """Boards [first, first + count) as uint64[count, H, ceil(W / 64)]; with `out`, a C-contiguous
+        uint64[count, H, S >= ceil(W / 64)], into it: the words past ceil(W / 64) of its rows stay."""
+        if out is None:
+            count = self.n - first if count is None else count
+            out = np.empty((max(count, 0), self.H, self.Ww), dtype=np.uint64)
+        elif (not isinstance(out, np.ndarray) or out.dtype != np.uint64 or not out.flags.c_contiguous or out.ndim != 3
+              or out.shape[1] != self.H or out.shape[2] < self.Ww or (count is not None and count != out.shape[0])):
+            raise ValueError(f"out must be C-contiguous uint64 (count, {self.H}, >= {self.Ww})")
+        self._check(self._L.gol_batch_store_words(self._h, first, first + out.shape[0], out.ctypes.data, out.shape[2],
+                                                  self.H * out.shape[2]))
+        return out
+
+    def load_random(self, seed: int) -> None:
+        """word(i, y, w) = splitmix64(seed ^ ((i*H + y)*Ww + w)) masked to W, generated on the GPU."""
+        self._check(self._L.gol_batch_load_random(self._h, seed))
+
+    # -- the rule
+    def set_rule(self, rule) -> None:
+        """The rule of every later turn: "B36/S23" or a (birth, survive) pair of 9-bit masks.  The
+        boards and the turn counter stay."""
+        birth, survive = parse_rule(rule, self._L) if isinstance(rule, str) else (int(rule[0]), int(rule[1]))
+        if not (0 <= birth < 1 << 32 and 0 <= survive < 1 << 32):
+            raise GolError(GOL_EINVAL, f"rule masks out of range ({birth}, {survive})")
+        self._check(self._L.gol_batch_set_rule(self._h, birth, survive))
+
+    @property
+    def rule(self) -> str:
+        b, s = ctypes.c_uint32(), ctypes.c_uint32()
+        self._check(self._L.gol_batch_rule(self._h, ctypes.byref(b), ctypes.byref(s)))
+        return format_rule(b.value, s.value, self._L)
+
+    # -- stepping and queries
+    def step(self, turns: int, settled: bool = False):
+        """Advance every board `turns` turns.  settled=True returns int64[n]: per board the first
+        turn t, turn + 2 <= t <= turn + turns, at which it equals its own state two turns earlier
+        (a still life or a period-2 oscillator), else -1; every board still makes all the turns."""
+        if not settled:
+            self._check(self._L.gol_batch_step(self._h, turns, None))
+            return None
+        out = np.full(self.n, -1, dtype=np.int64)
+        self._check(self._L.gol_batch_step(self._h, turns, out.ctypes.data))
+        return out
+
+    @property
+    def turn(self) -> int:
+        t = ctypes.c_int64()
+        self._check(self._L.gol_batch_turn(self._h, ctypes.byref(t)))
+        return t.value
+
+    def alive_counts(self) -> np.ndarray:
+        out = np.zeros(self.n, dtype=np.uint64)
+        self._check(self._L.gol_batch_alive_counts(self._h, out.ctypes.data, self.n))
+        return out
+
+    def hashes(self) -> np.ndarray:
+        """Per board oracle_hash_words of its zero-padded words (Engine.hash's definition)."""
+        out = np.zeros(self.n, dtype=np.uint64)
+        self._check(self._L.gol_batch_hashes(self._h, out.ctypes.data, self.n))
+        return out
+
+    def info(self) -> dict:
+        n, H, W = (ctypes.c_int64() for _ in range(3))
+        wpb, bpw, nw, tpl = (ctypes.c_int32() for _ in range(4))
+        self._check(self._L.gol_batch_info(self._h, ctypes.byref(n), ctypes.byref(H), ctypes.byref(W), ctypes.byref(wpb),
+                                           ctypes.byref(bpw), ctypes.byref(nw), ctypes.byref(tpl)))
+        return {"n": n.value, "height": H.value, "width": W.value, "waves_per_board": wpb.value,
+                "boards_per_workgroup": bpw.value, "words_per_lane": nw.value, "turns_per_launch": tpl.value}

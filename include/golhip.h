@@ -508,6 +508,77 @@ int gol_bounds_host(int32_t layout, const void *board, int64_t pitch, int64_t W,
                     int64_t row, int64_t rows, int64_t x0, int64_t w,
                     int64_t *cmin, int64_t *cmax, int64_t *rmin, int64_t *rmax, int64_t *alive);
 
+/* ---------------------------------------------------------------- batches of small boards
+ * (Added after ABI 6 without a version bump, like the viewport, rule, edit and
+ * copy calls: GOL_ABI_VERSION stays 6; probe for the gol_batch_* calls by
+ * symbol.)
+ *
+ * A batch is n independent tori, all H x W, 1 <= H <= 512, 1 <= W <= 512 (any
+ * width), 1 <= n <= 2^20, on one GPU, with one rule (default B3/S23) and one
+ * turn counter.  The engine steps one board per launch, and a launch on a board
+ * of this size is latency-bound; a batch steps all its boards
+ * in one launch, each resident in one workgroup for all the launch's turns
+ * (DESIGN.md §4.15).
+ * Board i is bit-packed in the bit order of load_words: bit c % 64 of word c / 64
+ * of a row is cell c, Ww = ceil(W / 64) uint64 words per row, H rows.  The bits
+ * at c >= W of a row's last word are zero in device memory and in everything
+ * returned.  Strides are in uint64 words: row y of board i of a caller's buffer
+ * is at words + (i - i0)*board_stride + y*row_stride.
+ *  - create: `device` as gol_config.device; turns_per_launch 0 = automatic (a
+ *    launch is bounded to a fixed number of cell-updates), else the most turns
+ *    one launch makes.  The boards start empty at turn 0.
+ *  - info: n, H, W, the waves per board, the boards per workgroup, the 32-bit
+ *    words of a row per lane and the turns-per-launch bound in use (any pointer
+ *    may be NULL).
+ *  - set_rule / rule: the 9-bit masks of "life-like rules"; masks >= 512 are
+ *    GOL_EINVAL.  Valid between stepping calls: the boards and the turn stay.  B0
+ *    rules are legal, and the padding bits still stay zero.
+ *  - load_words overwrites boards [i0, i1) only (set bits at c >= W of the
+ *    input are ignored) and resets the turn counter to 0; store_words writes Ww
+ *    words per row and touches neither the words between rows nor those between
+ *    boards.
+ *  - load_random: word(i, y, w) = splitmix64(seed ^ ((i*H + y)*Ww + w)) masked to
+ *    W, i.e. oracle_random_words(seed, 0, n*H, Ww) with the padding cleared;
+ *    generated on the GPU; resets the turn counter.
+ *  - step: every board advances exactly `turns` >= 0 turns (blocking).  settled
+ *    may be NULL; else int64_t[n]: settled[i] = the smallest turn t with turn0 +
+ *    2 <= t <= turn0 + turns (turn0: the turn before the call) at which board i
+ *    equals its own state two turns earlier, else -1: still lifes and period-2
+ *    oscillators.  The scan is per call (a board that settled in an earlier call
+ *    is found again at turn0 + 2), and every board is at turn0 + turns after
+ *    the call, whatever it settled at.
+ *  - alive_counts / hashes: one uint64 per board, cap >= n; the hash of board i
+ *    is oracle_hash_words(words_i, 0, H, Ww) (gol_engine_hash's definition on
+ *    the board's zero-padded words, for every W).
+ * GOL_EINVAL before any GPU work: n, H or W out of range, i0 > i1 or i1 > n, a
+ * row stride < Ww (a board stride < (H - 1)*row_stride + Ww), a cap < n, turns
+ * < 0, a NULL handle or buffer.  A call that fails leaves the batch and its
+ * turn as they were.  A handle is not internally synchronised. */
+typedef struct gol_batch gol_batch;
+int gol_batch_create(int64_t n, int64_t H, int64_t W, int32_t device, int32_t turns_per_launch, gol_batch **out);
+void gol_batch_destroy(gol_batch *b);
+int gol_batch_info(gol_batch *b, int64_t *n, int64_t *H, int64_t *W, int32_t *waves_per_board,
+                   int32_t *boards_per_workgroup, int32_t *words_per_lane, int32_t *turns_per_launch);
+int gol_batch_set_rule(gol_batch *b, uint32_t birth, uint32_t survive);
+int gol_batch_rule(gol_batch *b, uint32_t *birth, uint32_t *survive);
+int gol_batch_load_words(gol_batch *b, int64_t i0, int64_t i1, const uint64_t *words, int64_t row_stride,
+                         int64_t board_stride);
+int gol_batch_store_words(gol_batch *b, int64_t i0, int64_t i1, uint64_t *words, int64_t row_stride,
+                          int64_t board_stride);
+int gol_batch_load_random(gol_batch *b, uint64_t seed);
+int gol_batch_step(gol_batch *b, int64_t turns, int64_t *settled);
+int gol_batch_turn(gol_batch *b, int64_t *turn);
+int gol_batch_alive_counts(gol_batch *b, uint64_t *counts, int64_t cap);
+int gol_batch_hashes(gol_batch *b, uint64_t *hashes, int64_t cap);
+/* One turn of one H x W torus on host memory (a host function, no GPU needed)
+ * with the row function the batch kernel runs (csrc/gol_batch.h): `in` and `out`
+ * are H rows of row_stride uint64 words each (they may be the same buffer).  Set
+ * bits at c >= W of `in` are ignored; Ww words of every row of `out` are written,
+ * their padding zero, and the words between the rows are not touched.
+ * GOL_EINVAL: H or W outside 1..512, masks >= 512, row_stride < Ww, NULL. */
+int gol_batch_step_host(int64_t H, int64_t W, uint32_t birth, uint32_t survive, const uint64_t *in, uint64_t *out,
+                        int64_t row_stride);
+
 /* ---------------------------------------------------------------- plans
  * The schedule of a sharded step as data (host functions, no GPU needed).  The
  * engine runs exactly these plans; golhip.sharded (the torch.distributed
