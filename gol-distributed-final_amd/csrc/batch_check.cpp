@@ -6,6 +6,9 @@
 // a row is a sanitizer report.  Each shape runs four turns of each rule from a random board whose
 // padding bits are set, out of place and in place, and every turn is compared with a cell-by-cell
 // count of the eight neighbours.  Exit status 0: all equal; 1: a difference (printed).
+// `batch_check cycles`: gol_batch_cycles_host instead, on the same kind of buffers: every call's found,
+// period and final board against a scan written here (all states kept, the marks a list), and the mark
+// functions of gol_batch.h against that list for every d <= 1100.
 #include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -13,6 +16,7 @@
 
 #include <vector>
 
+#include "gol_batch.h"
 #include "golhip.h"
 
 static char g_msg[512];
@@ -88,8 +92,123 @@ static int check(int64_t H, int64_t W, int64_t pad, uint32_t birth, uint32_t sur
     return bad;
 }
 
-int main()
+// one call of gol_batch_cycles_host on a board of exact size (row r of `rows` at (y0, x0), 'O' alive, or
+// random cells when rows is NULL; the padding bits set), out of place or in place
+static int check_cycles(int64_t H, int64_t W, int64_t pad, uint32_t birth, uint32_t survive, const char *const *rows, int nrows,
+                        int64_t y0, int64_t x0, int64_t turns, bool in_place)
 {
+    const int64_t Ww = (W + 63) / 64, stride = Ww + pad;
+    const size_t words = (size_t)((H - 1) * stride + Ww);
+    const uint64_t gap = 0xA5A5A5A5A5A5A5A5ULL, tail = W % 64 ? ((uint64_t)1 << (W % 64)) - 1 : ~(uint64_t)0;
+    uint64_t *a = new uint64_t[words], *b = new uint64_t[words];
+    for (size_t i = 0; i < words; ++i) a[i] = rows ? 0 : rnd() & rnd();
+    for (int r = 0; r < nrows; ++r)
+        for (int64_t c = 0; rows[r][c]; ++c)
+            if (rows[r][c] == 'O') a[((y0 + r) % H) * stride + ((x0 + c) % W) / 64] |= (uint64_t)1 << (((x0 + c) % W) % 64);
+    for (int64_t y = 0; y < H; ++y) {
+        a[y * stride + Ww - 1] = (a[y * stride + Ww - 1] & tail) | (gap & ~tail);  // padding bits set: never read
+        for (int64_t w = Ww; w < stride && y + 1 < H; ++w) a[y * stride + w] = gap;
+    }
+    // the scan, naively: every state kept, the marks 0, 1, 3, 7, ... a list
+    std::vector<std::vector<uint64_t>> st(1, std::vector<uint64_t>(a, a + words));
+    for (int64_t y = 0; y < H; ++y) st[0][y * stride + Ww - 1] &= tail;
+    std::vector<int64_t> marks;
+    for (int64_t m = 0; m <= turns; m = 2 * m + 1) marks.push_back(m);
+    int64_t want_found = -1, want_period = -1;
+    for (int64_t d = 1; d <= turns; ++d) {
+        st.push_back(st[0]);
+        naive(H, W, birth, survive, st[(size_t)d - 1].data(), st[(size_t)d].data(), stride);
+        int64_t m = 0;
+        for (int64_t v : marks)
+            if (v < d) m = v;
+        if (want_found < 0 && st[(size_t)d] == st[(size_t)m]) want_found = d, want_period = d - m;
+    }
+    int64_t found = 77, period = 77;
+    for (size_t i = 0; i < words; ++i) b[i] = gap;
+    if (in_place) memcpy(b, a, words * sizeof(uint64_t));
+    const int rc = gol_batch_cycles_host(H, W, birth, survive, in_place ? b : a, b, stride, turns, &found, &period);
+    std::vector<uint64_t> want = st.back();
+    for (int64_t y = 0; y + 1 < H; ++y)
+        for (int64_t w = Ww; w < stride; ++w) want[y * stride + w] = gap;
+    int bad = rc != GOL_OK || found != want_found || period != want_period || memcmp(b, want.data(), words * sizeof(uint64_t));
+    if (bad)
+        printf("cycles %lldx%lld stride %lld B 0x%x S 0x%x turns %lld%s: rc %d, found %lld (%lld), period %lld (%lld)\n",
+               (long long)H, (long long)W, (long long)stride, birth, survive, (long long)turns, in_place ? " in place" : "", rc,
+               (long long)found, (long long)want_found, (long long)period, (long long)want_period);
+    delete[] a;
+    delete[] b;
+    return bad;
+}
+
+static int main_cycles()
+{
+    int bad = 0, n = 0;
+    // the mark functions against the list
+    std::vector<int64_t> marks;
+    for (int64_t m = 0; m <= 1100; m = 2 * m + 1) marks.push_back(m);
+    for (int64_t d = 0; d <= 1100; ++d) {
+        bool is = false;
+        int64_t last = -1;
+        for (int64_t v : marks) {
+            is = is || v == d;
+            if (v < d) last = v;
+        }
+        if (gol_batch_is_mark(d) != is || (d >= 1 && gol_batch_last_mark(d) != last)) {
+            printf("mark functions differ at d = %lld\n", (long long)d);
+            ++bad;
+        }
+    }
+    static const char *const glider[] = {".O.", "..O", "OOO"}, *const row10[] = {"OOOOOOOOOO"}, *const blinker[] = {"OOO"},
+                             *const block[] = {"OO", "OO"};
+    for (int pad = 0; pad <= 2; pad += 2)
+        for (int in_place = 0; in_place <= 1; ++in_place, n += 8) {
+            bad += check_cycles(5, 5, pad, 0x008, 0x00C, block, 0, 0, 0, 10, in_place);  // empty
+            bad += check_cycles(5, 5, pad, 0x008, 0x00C, block, 2, 1, 1, 10, in_place);
+            bad += check_cycles(5, 5, pad, 0x008, 0x00C, blinker, 1, 2, 1, 10, in_place);
+            bad += check_cycles(20, 20, pad, 0x008, 0x00C, row10, 1, 10, 5, 100, in_place);
+            bad += check_cycles(66, 33, pad, 0x008, 0x00C, row10, 1, 0, 28, 100, in_place);
+            bad += check_cycles(8, 8, pad, 0x008, 0x00C, glider, 3, 0, 0, 200, in_place);
+            bad += check_cycles(7, 9, pad, 0x008, 0x00C, glider, 3, 0, 0, 600, in_place);
+            bad += check_cycles(3, 65, pad, 0x008, 0x00C, glider, 0, 0, 0, 0, in_place);  // no turn: the board, masked
+        }
+    static const int shapes[][2] = {{1, 1}, {2, 5}, {16, 16}, {7, 33}, {5, 65}, {65, 31}, {3, 481}};
+    static const uint32_t rules[][2] = {{0x008, 0x00C}, {0x048, 0x00C}, {0x004, 0x000},
+                                        {0x001, 0x100}, {0x0AA, 0x0AA}, {0x018, 0x018}};
+    for (const auto &s : shapes)
+        for (const auto &r : rules)
+            for (int pad = 0; pad <= 2; pad += 2, ++n)
+                bad += check_cycles(s[0], s[1], pad, r[0], r[1], nullptr, 0, 0, 0, 70, pad != 0);
+    uint64_t w[8] = {0};
+    int64_t f = 77, p = 77;
+    const int einval[] = {gol_batch_cycles_host(0, 8, 8, 12, w, w, 1, 1, &f, &p),
+                          gol_batch_cycles_host(8, 513, 8, 12, w, w, 9, 1, &f, &p),
+                          gol_batch_cycles_host(8, 8, 512, 12, w, w, 1, 1, &f, &p),
+                          gol_batch_cycles_host(8, 8, 8, 512, w, w, 1, 1, &f, &p),
+                          gol_batch_cycles_host(8, 65, 8, 12, w, w, 1, 1, &f, &p),
+                          gol_batch_cycles_host(8, 8, 8, 12, nullptr, w, 1, 1, &f, &p),
+                          gol_batch_cycles_host(8, 8, 8, 12, w, nullptr, 1, 1, &f, &p),
+                          gol_batch_cycles_host(8, 8, 8, 12, w, w, 1, -1, &f, &p),
+                          gol_batch_cycles_host(8, 8, 8, 12, w, w, 1, 1, nullptr, &p)};
+    for (int rc : einval)
+        if (rc != GOL_EINVAL || f != 77 || p != 77) {
+            printf("a bad argument returned %d\n", rc);
+            ++bad;
+        }
+    if (gol_batch_cycles_host(8, 8, 8, 12, w, w, 1, 3, &f, nullptr) != GOL_OK || f != 1) {  // (period may be NULL)
+        printf("a NULL period: found %lld\n", (long long)f);
+        ++bad;
+    }
+    printf("batch_check cycles: %d cases, %d bad\n", n, bad);
+    return bad ? 1 : 0;
+}
+
+int main(int argc, char **argv)
+{
+    if (argc > 1) {
+        if (!strcmp(argv[1], "cycles")) return main_cycles();
+        printf("usage: batch_check [cycles]\n");
+        return 2;
+    }
     static const int shapes[][2] = {{1, 1}, {1, 2}, {2, 1}, {2, 2}, {3, 3}, {2, 5}, {5, 2}, {16, 16}, {7, 31}, {7, 32}, {7, 33},
                                     {5, 63}, {5, 64}, {5, 65}, {3, 96}, {4, 511}, {4, 512}, {3, 481}, {64, 1}, {65, 31}};
     static const uint32_t rules[][2] = {{0x008, 0x00C}, {0x048, 0x00C}, {0x1C8, 0x1D8}, {0x004, 0x000}, {0x001, 0x100},

@@ -14,6 +14,7 @@
 // kernel here).  The three rows' sums go into the rule: B3/S23 the 7-gate circuit of the step
 // kernels (golk::rule), any other rule gol_rule_sum3 + gol_rule_eval (gol_rule.h).  The padding of the
 // result is cleared afterwards (a cell of the padding has neighbours, and B0 rules give birth there).
+// Also here, for the same reason: the step kernel's modes and the marks of its cycle scan.
 #pragma once
 #include <stdint.h>
 
@@ -28,6 +29,24 @@
 
 #define GOL_BATCH_MAX_SIDE 512  // cells: at most 16 words of a row, 8 waves of 64 rows
 #define GOL_BATCH_MAX_WAVES 8
+
+// The step kernel's modes.  Rule: B3/S23 on 7 gates, one table rule for the batch, a table rule per
+// board.  Scan: none, state(t) == state(t - 2) (periods 1 and 2, the exact settle turn), cycles of
+// any period against a snapshot taken at the marks below.
+enum { GOL_BATCH_RULE_CONWAY = 0, GOL_BATCH_RULE_TABLE = 1, GOL_BATCH_RULE_EACH = 2 };
+enum { GOL_BATCH_SCAN_NONE = 0, GOL_BATCH_SCAN_SETTLE = 1, GOL_BATCH_SCAN_CYCLES = 2 };
+
+// The cycle scan's marks (Brent's cycle detection), in turns d >= 0 since the call began: d = 2^j - 1,
+// that is 0, 1, 3, 7, ...  A turn d >= 1 is compared with the state at the last mark before it, and
+// the state of a turn that is a mark is the snapshot of the turns after it.
+GOL_BATCH_HD bool gol_batch_is_mark(int64_t d) { return d >= 0 && ((d + 1) & d) == 0; }
+
+GOL_BATCH_HD int64_t gol_batch_last_mark(int64_t d)  // d >= 1: the largest mark < d
+{
+    int64_t p = 1;
+    while (p <= d / 2) p *= 2;  // the largest power of two <= d
+    return p - 1;
+}
 
 // The shape of a row: nwr words in use of nw held, the last cell's bit and the mask of the last word.
 struct gol_batch_row {

@@ -1,7 +1,7 @@
 // gol_batch.hip -- many small tori (1 <= H, W <= 512) stepped in one launch (include/golhip.h,
 // "batches of small boards"; the row function is gol_batch.h).
 //
-// batch_step_kernel<NW, GENERIC, SCAN>: a board never leaves its workgroup during a launch.  One
+// batch_step_kernel<NW, RULE, SCAN>: a board never leaves its workgroup during a launch.  One
 // row per lane, NW = 1, 2, 4, 8 or 16 words of it in registers, ceil(H / 64) waves per board; boards
 // of up to 128 rows share a workgroup (4 boards of one wave, 2 of two).  The board is read from HBM
 // once, stepped `turns` times and written once, in place: no HBM traffic between the turns.
@@ -15,6 +15,14 @@
 // waves of a board exchange that bit through LDS under the next turn's barrier.  The first turn t
 // with state(t) == state(t - 2) goes to settled[board] unless an earlier launch of the call set it;
 // state(start - 1) of a launch comes from, and state(end - 1) goes to, a second device buffer.
+// SCAN = GOL_BATCH_SCAN_CYCLES: the same registers hold a snapshot instead, state(m) of the last
+// mark m = 2^j - 1 of the call's own turn count (gol_batch.h), every turn is compared with it, and after
+// the comparison at a turn that is a mark the snapshot becomes that turn's state: the first turn t with
+// state(t) == state(last mark before t) goes to settled[board] (any period: Brent's cycle detection);
+// the snapshot goes through the same second buffer between the launches of a call.
+// RULE: B3/S23 on 7 gates, the table circuit with the masks of the arguments, or the table circuit
+// with the masks of the wave's own board (rules[2 board], rules[2 board + 1]), read once per launch
+// by a scalar load, so the expanded tables are wave-uniform as in the one-rule kernel.
 // Synchronisation is __syncthreads() alone: no workgroup waits for another one, there is no flag
 // between workgroups, no spin loop and no atomic.  Every wave of a workgroup runs every barrier (a
 // wave whose board is past the batch's end computes on zeros and stores nothing).
@@ -41,6 +49,8 @@ struct BatchArgs {
     int32_t turns;            // >= 1
     int32_t have_prev, write_prev;
     uint32_t birth, survive;
+    const uint32_t *rules;  // GOL_BATCH_RULE_EACH: n pairs (birth, survive)
+    int64_t done;           // GOL_BATCH_SCAN_CYCLES: the turns of the call before this launch
 };
 
 template <int NW>
@@ -61,7 +71,7 @@ __device__ __forceinline__ void store_row(uint64_t *row, int32_t Ww, const uint3
         if (j < 2 * Ww) p[j] = j < NW ? c[j < NW ? j : 0] : 0u;
 }
 
-template <int NW, bool GENERIC, bool SCAN>
+template <int NW, int RULE, int SCAN>
 __global__ __launch_bounds__(512) void batch_step_kernel(const BatchArgs a)
 {
     // [buffer][wave][first / last row of the wave][h0 / h1][word]
@@ -77,13 +87,25 @@ __global__ __launch_bounds__(512) void batch_step_kernel(const BatchArgs a)
     const uint32_t msk = on ? ~0u : 0u;
     const int wup = lb * a.wpb + (w == 0 ? a.wpb - 1 : w - 1), wdn = lb * a.wpb + (w == a.wpb - 1 ? 0 : w + 1);
     const gol_batch_row g = a.g;
+    // the board's own rule: the board's index is wave-uniform, and made scalar it turns the read into a scalar
+    // load (a wave past the batch's end reads the last board's rule, and computes on zeros)
+    uint32_t birth = a.birth, survive = a.survive;
+    if (RULE == GOL_BATCH_RULE_EACH) {
+        const uint32_t i = __builtin_amdgcn_readfirstlane((uint32_t)(board < a.n ? board : a.n - 1));
+        birth = __builtin_amdgcn_readfirstlane(a.rules[2 * (size_t)i]);
+        survive = __builtin_amdgcn_readfirstlane(a.rules[2 * (size_t)i + 1]);
+    }
     gol_rule_tab tab;
-    gol_rule_expand(a.birth, a.survive, tab);
+    gol_rule_expand(birth, survive, tab);
 
     const int64_t off = (board * a.H + y) * a.Ww;
-    uint32_t cur[NW], old[NW];  // state(t - 1) and, SCAN, state(t - 2)
+    uint32_t cur[NW], old[NW];  // state(t - 1) and, SCAN, state(t - 2) or the snapshot
     load_row<NW>(a.boards + (on ? off : 0), a.Ww, on, cur);
     if (SCAN) load_row<NW>(a.prev + (on && a.have_prev ? off : 0), a.Ww, on && a.have_prev, old);
+    if (SCAN == GOL_BATCH_SCAN_CYCLES && !a.have_prev) {  // the call's first launch: the mark d = 0
+#pragma unroll
+        for (int j = 0; j < NW; ++j) old[j] = cur[j];
+    }
 
     int64_t found = -1;  // uniform over the board's waves
     bool mine = false;   // this wave's "a word differs" of the turn just computed
@@ -99,8 +121,9 @@ __global__ __launch_bounds__(512) void batch_step_kernel(const BatchArgs a)
 #pragma unroll
             for (int j = 0; j < NW; ++j) { edge[buf][wave][1][0][j] = b0[j]; edge[buf][wave][1][1][j] = b1[j]; }
         }
-        // the turn before compared its state with the one two turns back (none before the first loaded state)
-        const bool posted = SCAN && it >= (a.have_prev ? 1 : 2);
+        // the turn before compared its state with the one two turns back (none before the first loaded state),
+        // or with the snapshot
+        const bool posted = SCAN == GOL_BATCH_SCAN_CYCLES ? it >= 1 : SCAN && it >= (a.have_prev ? 1 : 2);
         if (posted && lane == 0) differs[buf][wave] = mine;
         __syncthreads();
         if (posted && found < 0) {
@@ -123,20 +146,23 @@ __global__ __launch_bounds__(512) void batch_step_kernel(const BatchArgs a)
 #pragma unroll
             for (int j = 0; j < NW; ++j) { d0[j] = edge[buf][wdn][0][0][j]; d1[j] = edge[buf][wdn][0][1][j]; }
         }
-        gol_batch_next<NW, GENERIC>(tab, g, a0, a1, b0, b1, d0, d1, cur, msk, next);
+        gol_batch_next<NW, RULE != GOL_BATCH_RULE_CONWAY>(tab, g, a0, a1, b0, b1, d0, d1, cur, msk, next);
         if (SCAN) {
+            // (uniform) cycles: the turn just computed is a mark, its state the snapshot from now on
+            const bool keep = SCAN == GOL_BATCH_SCAN_CYCLES && !gol_batch_is_mark(a.done + it + 1);
             uint32_t d = 0;
 #pragma unroll
             for (int j = 0; j < NW; ++j) {
                 d |= next[j] ^ old[j];
-                old[j] = cur[j];
+                old[j] = SCAN == GOL_BATCH_SCAN_CYCLES ? (keep ? old[j] : next[j]) : cur[j];
             }
             mine = __ballot(d != 0) != 0;
         }
 #pragma unroll
         for (int j = 0; j < NW; ++j) cur[j] = next[j];
     }
-    if (SCAN && (a.turns > 1 || a.have_prev)) {  // the last turn's comparison (buf: the buffer no wave reads any more)
+    // the last turn's comparison (buf: the buffer no wave reads any more)
+    if (SCAN == GOL_BATCH_SCAN_CYCLES || (SCAN && (a.turns > 1 || a.have_prev))) {
         if (lane == 0) differs[buf][wave] = mine;
         __syncthreads();
         if (found < 0) {
@@ -177,18 +203,24 @@ __global__ __launch_bounds__(256) void batch_reduce_kernel(const uint64_t *board
     }
 }
 
-template <int NW, bool GENERIC>
-hipError_t launch_scan(bool scan, const BatchArgs &a, dim3 grid, dim3 block, hipStream_t s)
+template <int NW, int RULE>
+hipError_t launch_scan(int scan, const BatchArgs &a, dim3 grid, dim3 block, hipStream_t s)
 {
-    if (scan) batch_step_kernel<NW, GENERIC, true><<<grid, block, 0, s>>>(a);
-    else batch_step_kernel<NW, GENERIC, false><<<grid, block, 0, s>>>(a);
+    if (scan == GOL_BATCH_SCAN_CYCLES)
+        batch_step_kernel<NW, RULE, GOL_BATCH_SCAN_CYCLES><<<grid, block, 0, s>>>(a);
+    else if (scan == GOL_BATCH_SCAN_SETTLE)
+        batch_step_kernel<NW, RULE, GOL_BATCH_SCAN_SETTLE><<<grid, block, 0, s>>>(a);
+    else
+        batch_step_kernel<NW, RULE, GOL_BATCH_SCAN_NONE><<<grid, block, 0, s>>>(a);
     return hipGetLastError();
 }
 
 template <int NW>
-hipError_t launch_rule(bool generic, bool scan, const BatchArgs &a, dim3 grid, dim3 block, hipStream_t s)
+hipError_t launch_rule(int rule, int scan, const BatchArgs &a, dim3 grid, dim3 block, hipStream_t s)
 {
-    return generic ? launch_scan<NW, true>(scan, a, grid, block, s) : launch_scan<NW, false>(scan, a, grid, block, s);
+    if (rule == GOL_BATCH_RULE_EACH) return launch_scan<NW, GOL_BATCH_RULE_EACH>(scan, a, grid, block, s);
+    if (rule == GOL_BATCH_RULE_TABLE) return launch_scan<NW, GOL_BATCH_RULE_TABLE>(scan, a, grid, block, s);
+    return launch_scan<NW, GOL_BATCH_RULE_CONWAY>(scan, a, grid, block, s);
 }
 
 }  // namespace
@@ -202,10 +234,13 @@ void golk_batch_shape(int64_t H, int64_t W, int *waves_per_board, int *boards_pe
 }
 
 hipError_t golk_batch_step(uint64_t *boards, uint64_t *prev, int64_t *settled, int64_t n, int64_t H, int64_t W, int turns,
-                           int64_t turn0, bool have_prev, bool write_prev, uint32_t birth, uint32_t survive, hipStream_t s)
+                           int64_t turn0, bool have_prev, bool write_prev, uint32_t birth, uint32_t survive,
+                           const uint32_t *rules, int scan, int64_t done, hipStream_t s)
 {
     if (!boards || n < 1 || n > ((int64_t)1 << 20) || H < 1 || H > GOL_BATCH_MAX_SIDE || W < 1 || W > GOL_BATCH_MAX_SIDE ||
-        turns < 1 || birth >= 512 || survive >= 512 || (settled && !prev) || ((have_prev || write_prev) && !settled))
+        turns < 1 || birth >= 512 || survive >= 512 || (settled && !prev) || ((have_prev || write_prev) && !settled) ||
+        scan < GOL_BATCH_SCAN_NONE || scan > GOL_BATCH_SCAN_CYCLES || (scan != GOL_BATCH_SCAN_NONE) != (settled != nullptr) ||
+        done < 0 || (scan == GOL_BATCH_SCAN_CYCLES && have_prev != (done > 0)))
         return hipErrorInvalidValue;
     BatchArgs a{};
     int nw;
@@ -223,14 +258,18 @@ hipError_t golk_batch_step(uint64_t *boards, uint64_t *prev, int64_t *settled, i
     a.write_prev = write_prev;
     a.birth = birth;
     a.survive = survive;
+    a.rules = rules;
+    a.done = done;
     const dim3 grid((unsigned)((n + a.bpw - 1) / a.bpw)), block((unsigned)(a.bpw * a.wpb * 64));
-    const bool generic = !gol_batch_conway(birth, survive), scan = settled != nullptr;
+    const int rule = rules                             ? GOL_BATCH_RULE_EACH
+                     : gol_batch_conway(birth, survive) ? GOL_BATCH_RULE_CONWAY
+                                                        : GOL_BATCH_RULE_TABLE;
     switch (nw) {
-    case 1: return launch_rule<1>(generic, scan, a, grid, block, s);
-    case 2: return launch_rule<2>(generic, scan, a, grid, block, s);
-    case 4: return launch_rule<4>(generic, scan, a, grid, block, s);
-    case 8: return launch_rule<8>(generic, scan, a, grid, block, s);
-    default: return launch_rule<16>(generic, scan, a, grid, block, s);
+    case 1: return launch_rule<1>(rule, scan, a, grid, block, s);
+    case 2: return launch_rule<2>(rule, scan, a, grid, block, s);
+    case 4: return launch_rule<4>(rule, scan, a, grid, block, s);
+    case 8: return launch_rule<8>(rule, scan, a, grid, block, s);
+    default: return launch_rule<16>(rule, scan, a, grid, block, s);
     }
 }
 

@@ -1,5 +1,5 @@
 // gol_batch_engine.cpp -- batches of small boards (include/golhip.h): the handle, the argument
-// checks, the split of a stepping call into launches and the strided copies.  The kernels are
+// checks, the rules per board, the split of a stepping call into launches and the strided copies.  The kernels are
 // gol_batch.hip (whose object takes the name gol_batch.o), the host twin gol_batch_host.cpp.
 #include <hip/hip_runtime.h>
 
@@ -25,6 +25,10 @@ struct gol_batch {
     int tpl = 1;  // turns per launch at most
     int wpb = 1, bpw = 1, nw = 1;
     uint32_t birth = GOL_RULE_BIRTH_CONWAY, survive = GOL_RULE_SURVIVE_CONWAY;
+    // empty: every board under birth / survive; else n pairs (birth, survive), not all equal
+    std::vector<uint32_t> rules;
+    uint32_t *drules = nullptr;  // the device copy of `rules` (on demand), stale while rules_dirty
+    bool rules_dirty = false;
     int64_t turn = 0;
     hipStream_t stream = nullptr;
     uint64_t *boards = nullptr;
@@ -83,6 +87,42 @@ int reduce(gol_batch *b, bool hash, uint64_t *out, int64_t cap)
     return GOL_OK;
 }
 
+// `turns` turns of every board in launches of at most tpl; scan != GOL_BATCH_SCAN_NONE: out[0 .. n) =
+// the turn the scan found per board, else -1.  Blocks once, after the last launch.
+int step(gol_batch *b, int64_t turns, int scan, int64_t *out)
+{
+    OnDevice dev(b->device);
+    HIPCHK(dev.err);
+    int64_t *found = nullptr;
+    if (scan != GOL_BATCH_SCAN_NONE) {  // (settle scan, turns < 2: nothing can be found, every board is -1)
+        const int rc = need_aux(b);
+        if (rc) return rc;
+        if (!b->prev) HIPCHK(hipMalloc(&b->prev, (size_t)(b->n * b->H * b->Ww) * sizeof(uint64_t)));
+        found = (int64_t *)b->aux;
+        HIPCHK(hipMemsetAsync(found, 0xff, (size_t)b->n * sizeof(int64_t), b->stream));
+    }
+    const bool each = !b->rules.empty();
+    if (each && turns > 0 && (b->rules_dirty || !b->drules)) {
+        if (!b->drules) HIPCHK(hipMalloc(&b->drules, b->rules.size() * sizeof(uint32_t)));
+        HIPCHK(hipMemcpyAsync(b->drules, b->rules.data(), b->rules.size() * sizeof(uint32_t), hipMemcpyHostToDevice,
+                              b->stream));
+        HIPCHK(hipStreamSynchronize(b->stream));  // (the host copy may change after the call)
+        b->rules_dirty = false;
+    }
+    for (int64_t done = 0; done < turns;) {
+        const int k = (int)std::min<int64_t>(b->tpl, turns - done);
+        HIPCHK(golk_batch_step(b->boards, found ? b->prev : nullptr, found, b->n, b->H, b->W, k, b->turn + done, found && done > 0,
+                               found && done + k < turns, b->birth, b->survive, each ? b->drules : nullptr, scan, done,
+                               b->stream));
+        done += k;
+    }
+    if (found) HIPCHK(hipMemcpyAsync(out, found, (size_t)b->n * sizeof(int64_t), hipMemcpyDeviceToHost, b->stream));
+    const hipError_t e = hipStreamSynchronize(b->stream);
+    if (e != hipSuccess) return gol_set_error(GOL_EHIP, "batch step: %s", hipGetErrorString(e));
+    b->turn += turns;
+    return GOL_OK;
+}
+
 }  // namespace
 
 extern "C" void gol_batch_destroy(gol_batch *b)
@@ -94,6 +134,7 @@ extern "C" void gol_batch_destroy(gol_batch *b)
         if (b->boards) (void)hipFree(b->boards);
         if (b->prev) (void)hipFree(b->prev);
         if (b->aux) (void)hipFree(b->aux);
+        if (b->drules) (void)hipFree(b->drules);
         if (b->stream) (void)hipStreamDestroy(b->stream);
     }
     delete b;
@@ -159,14 +200,61 @@ extern "C" int gol_batch_set_rule(gol_batch *b, uint32_t birth, uint32_t survive
         return gol_set_error(GOL_EINVAL, "bad batch rule (B 0x%x, S 0x%x: masks are 9 bits)", birth, survive);
     b->birth = birth;
     b->survive = survive;
+    b->rules.clear();
     return GOL_OK;
 }
 
 extern "C" int gol_batch_rule(gol_batch *b, uint32_t *birth, uint32_t *survive)
 {
     if (!b) return gol_set_error(GOL_EINVAL, "batch is NULL");
+    if (!b->rules.empty()) return gol_set_error(GOL_ESTATE, "the boards of the batch have different rules (gol_batch_rules)");
     if (birth) *birth = b->birth;
     if (survive) *survive = b->survive;
+    return GOL_OK;
+}
+
+extern "C" int gol_batch_set_rules(gol_batch *b, int64_t i0, int64_t i1, const uint32_t *birth, const uint32_t *survive)
+{
+    if (!b || !birth || !survive || i0 < 0 || i0 > i1 || i1 > b->n)
+        return gol_set_error(GOL_EINVAL, "bad batch set_rules (boards [%lld, %lld) of %lld, or NULL)", (long long)i0, (long long)i1,
+                             b ? (long long)b->n : 0LL);
+    for (int64_t i = i0; i < i1; ++i)
+        if (birth[i - i0] >= 512 || survive[i - i0] >= 512)
+            return gol_set_error(GOL_EINVAL, "bad batch rule of board %lld (B 0x%x, S 0x%x: masks are 9 bits)", (long long)i,
+                                 birth[i - i0], survive[i - i0]);
+    if (i0 == i1) return GOL_OK;
+    if (b->rules.empty()) {  // one rule so far
+        bool same = true;
+        for (int64_t i = i0; i < i1 && same; ++i) same = birth[i - i0] == b->birth && survive[i - i0] == b->survive;
+        if (same) return GOL_OK;
+        try {
+            b->rules.resize((size_t)(2 * b->n));
+        } catch (const std::bad_alloc &) {
+            return gol_set_error(GOL_ENOMEM, "rules of %lld boards", (long long)b->n);
+        }
+        for (int64_t i = 0; i < b->n; ++i) b->rules[2 * i] = b->birth, b->rules[2 * i + 1] = b->survive;
+    }
+    for (int64_t i = i0; i < i1; ++i) b->rules[2 * i] = birth[i - i0], b->rules[2 * i + 1] = survive[i - i0];
+    bool same = true;
+    for (int64_t i = 1; i < b->n && same; ++i) same = b->rules[2 * i] == b->rules[0] && b->rules[2 * i + 1] == b->rules[1];
+    if (same) {  // one rule again: the launches of gol_batch_set_rule
+        b->birth = b->rules[0];
+        b->survive = b->rules[1];
+        b->rules.clear();
+    }
+    b->rules_dirty = true;
+    return GOL_OK;
+}
+
+extern "C" int gol_batch_rules(gol_batch *b, int64_t i0, int64_t i1, uint32_t *birth, uint32_t *survive)
+{
+    if (!b || !birth || !survive || i0 < 0 || i0 > i1 || i1 > b->n)
+        return gol_set_error(GOL_EINVAL, "bad batch rules (boards [%lld, %lld) of %lld, or NULL)", (long long)i0, (long long)i1,
+                             b ? (long long)b->n : 0LL);
+    for (int64_t i = i0; i < i1; ++i) {
+        birth[i - i0] = b->rules.empty() ? b->birth : b->rules[2 * i];
+        survive[i - i0] = b->rules.empty() ? b->survive : b->rules[2 * i + 1];
+    }
     return GOL_OK;
 }
 
@@ -253,26 +341,19 @@ extern "C" int gol_batch_load_random(gol_batch *b, uint64_t seed)
 extern "C" int gol_batch_step(gol_batch *b, int64_t turns, int64_t *settled)
 {
     if (!b || turns < 0) return gol_set_error(GOL_EINVAL, "bad batch step (turns %lld)", (long long)turns);
-    OnDevice dev(b->device);
-    HIPCHK(dev.err);
-    int64_t *found = nullptr;
-    if (settled) {  // (turns < 2: nothing can be found, every board is -1)
-        const int rc = need_aux(b);
-        if (rc) return rc;
-        if (!b->prev) HIPCHK(hipMalloc(&b->prev, (size_t)(b->n * b->H * b->Ww) * sizeof(uint64_t)));
-        found = (int64_t *)b->aux;
-        HIPCHK(hipMemsetAsync(found, 0xff, (size_t)b->n * sizeof(int64_t), b->stream));
-    }
-    for (int64_t done = 0; done < turns;) {
-        const int k = (int)std::min<int64_t>(b->tpl, turns - done);
-        HIPCHK(golk_batch_step(b->boards, found ? b->prev : nullptr, found, b->n, b->H, b->W, k, b->turn + done, found && done > 0,
-                               found && done + k < turns, b->birth, b->survive, b->stream));
-        done += k;
-    }
-    if (found) HIPCHK(hipMemcpyAsync(settled, found, (size_t)b->n * sizeof(int64_t), hipMemcpyDeviceToHost, b->stream));
-    const hipError_t e = hipStreamSynchronize(b->stream);
-    if (e != hipSuccess) return gol_set_error(GOL_EHIP, "batch step: %s", hipGetErrorString(e));
-    b->turn += turns;
+    return step(b, turns, settled ? GOL_BATCH_SCAN_SETTLE : GOL_BATCH_SCAN_NONE, settled);
+}
+
+extern "C" int gol_batch_step_cycles(gol_batch *b, int64_t turns, int64_t *found, int64_t *period)
+{
+    if (!b || turns < 0 || !found)
+        return gol_set_error(GOL_EINVAL, "bad batch step_cycles (turns %lld, or NULL)", (long long)turns);
+    const int64_t t0 = b->turn;
+    const int rc = step(b, turns, GOL_BATCH_SCAN_CYCLES, found);
+    if (rc) return rc;
+    if (period)  // found - the last mark before it, with the kernel's own mark function
+        for (int64_t i = 0; i < b->n; ++i)
+            period[i] = found[i] < 0 ? -1 : found[i] - t0 - gol_batch_last_mark(found[i] - t0);
     return GOL_OK;
 }
 

@@ -147,10 +147,16 @@ hipError_t golk_bounds_cols(int form, const void *src, int64_t pitch, int64_t W,
 // golk_batch_step: `turns` >= 1 turns of every board in one launch, in place.  settled != NULL (then
 // prev != NULL, a second buffer of the boards' shape): settled[i] < 0 becomes the first turn t in
 // (turn0 + (have_prev ? 0 : 1), turn0 + turns] with state(t) == state(t - 2); have_prev: prev holds
-// state(turn0 - 1); write_prev: prev receives state(turn0 + turns - 1).
+// state(turn0 - 1); write_prev: prev receives state(turn0 + turns - 1).  That is scan =
+// GOL_BATCH_SCAN_SETTLE (gol_batch.h; settled == NULL: GOL_BATCH_SCAN_NONE).  GOL_BATCH_SCAN_CYCLES: the
+// launch begins `done` turns into its call (have_prev = done > 0), prev carries the snapshot of the
+// call's last mark instead, and settled[i] < 0 becomes the first turn t in (turn0, turn0 + turns] with
+// state(t) == state(the last mark before t).  rules != NULL: n pairs (birth, survive) in device
+// memory, board i under pair i (birth and survive are not used); else every board under birth / survive.
 void golk_batch_shape(int64_t H, int64_t W, int *waves_per_board, int *boards_per_wg, int *words_per_lane);
 hipError_t golk_batch_step(uint64_t *boards, uint64_t *prev, int64_t *settled, int64_t n, int64_t H, int64_t W, int turns,
-                           int64_t turn0, bool have_prev, bool write_prev, uint32_t birth, uint32_t survive, hipStream_t s);
+                           int64_t turn0, bool have_prev, bool write_prev, uint32_t birth, uint32_t survive,
+                           const uint32_t *rules, int scan, int64_t done, hipStream_t s);
 // word(i, y, w) = splitmix64(seed ^ ((i*H + y)*Ww + w)) masked to W
 hipError_t golk_batch_random(uint64_t *boards, int64_t n, int64_t H, int64_t W, uint64_t seed, hipStream_t s);
 // out[i] = alive cells of board i, or (hash) its oracle_hash_words

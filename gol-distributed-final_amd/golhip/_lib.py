@@ -173,14 +173,18 @@ SIGNATURES = [
     ("gol_batch_info", ctypes.c_int, [_vp, _P(_i64), _P(_i64), _P(_i64), _P(_i32), _P(_i32), _P(_i32), _P(_i32)]),
     ("gol_batch_set_rule", ctypes.c_int, [_vp, ctypes.c_uint32, ctypes.c_uint32]),
     ("gol_batch_rule", ctypes.c_int, [_vp, _P(ctypes.c_uint32), _P(ctypes.c_uint32)]),
+    ("gol_batch_set_rules", ctypes.c_int, [_vp, _i64, _i64, _vp, _vp]),
+    ("gol_batch_rules", ctypes.c_int, [_vp, _i64, _i64, _vp, _vp]),
     ("gol_batch_load_words", ctypes.c_int, [_vp, _i64, _i64, _vp, _i64, _i64]),
     ("gol_batch_store_words", ctypes.c_int, [_vp, _i64, _i64, _vp, _i64, _i64]),
     ("gol_batch_load_random", ctypes.c_int, [_vp, _u64]),
     ("gol_batch_step", ctypes.c_int, [_vp, _i64, _vp]),
+    ("gol_batch_step_cycles", ctypes.c_int, [_vp, _i64, _vp, _vp]),
     ("gol_batch_turn", ctypes.c_int, [_vp, _P(_i64)]),
     ("gol_batch_alive_counts", ctypes.c_int, [_vp, _vp, _i64]),
     ("gol_batch_hashes", ctypes.c_int, [_vp, _vp, _i64]),
     ("gol_batch_step_host", ctypes.c_int, [_i64, _i64, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp, _i64]),
+    ("gol_batch_cycles_host", ctypes.c_int, [_i64, _i64, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp, _i64, _i64, _P(_i64), _P(_i64)]),
     ("gol_halo_plan", ctypes.c_int, [_i64, _i32, _i32, _i32, _P(gol_halo_op), _i32, _P(_i32)]),
     ("gol_step_plan", ctypes.c_int, [_i64, _i32, _i32, _i32, _P(gol_launch), _i32, _P(_i32)]),
     ("gol_view_plan", ctypes.c_int, [_i64, _i32, _i32, _i64, _i64, _P(gol_view_run), _i32, _P(_i32)]),

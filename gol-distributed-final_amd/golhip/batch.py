@@ -2,10 +2,11 @@
 
 An ``Engine`` steps one board per launch, and on the reference's own boards (16² … 512²) a launch is
 latency-bound.  A ``Batch`` holds n independent H x W tori (1 <= H, W <= 512, any width, n <= 2^20) on
-one GPU, with one rule and one turn counter; a launch keeps every board resident in one workgroup
-for all its turns, and can report the turn at which each board settled into a still life or a
-period-2 oscillator.  Boards are bit-packed like ``Engine.load_words``: bit c % 64 of word c // 64 of
-a row is cell c, ceil(W / 64) uint64 words per row, the bits at c >= W zero.
+one GPU, with one turn counter and one rule or a rule per board; a launch keeps every board resident
+in one workgroup for all its turns, and can report the turn at which each board settled into a still
+life or a period-2 oscillator, or find the period of any cycle it enters.  Boards are bit-packed
+like ``Engine.load_words``: bit c % 64 of word c // 64 of a row is cell c, ceil(W / 64) uint64 words per
+row, the bits at c >= W zero.
 """
 from __future__ import annotations
 
@@ -122,9 +123,34 @@ class Batch:
 
     @property
     def rule(self) -> str:
+        """The rule all boards share; GolError(GOL_ESTATE) when their rules differ (see rules())."""
         b, s = ctypes.c_uint32(), ctypes.c_uint32()
         self._check(self._L.gol_batch_rule(self._h, ctypes.byref(b), ctypes.byref(s)))
         return format_rule(b.value, s.value, self._L)
+
+    def set_rules(self, rules, first: int = 0) -> None:
+        """The rules of boards [first, first + m): a sequence of "B36/S23" strings or (birth, survive)
+        mask pairs, or a uint32[m, 2] array.  The other boards keep theirs; the boards and the turn
+        counter stay.  One bad rule and none is set."""
+        if isinstance(rules, np.ndarray):
+            if rules.ndim != 2 or rules.shape[1] != 2 or rules.dtype.kind not in "ui":
+                raise GolError(GOL_EINVAL, f"rules are an integer array of shape (m, 2), got {rules.dtype} {rules.shape}")
+            pairs = rules.astype(np.int64)
+        else:
+            pairs = np.array([parse_rule(r, self._L) if isinstance(r, str) else (int(r[0]), int(r[1])) for r in rules],
+                             dtype=np.int64).reshape(-1, 2)
+        if np.any(pairs < 0) or np.any(pairs >= 1 << 32):
+            raise GolError(GOL_EINVAL, "rule masks out of range")
+        birth = np.ascontiguousarray(pairs[:, 0], dtype=np.uint32)
+        survive = np.ascontiguousarray(pairs[:, 1], dtype=np.uint32)
+        self._check(self._L.gol_batch_set_rules(self._h, first, first + len(birth), birth.ctypes.data, survive.ctypes.data))
+
+    def rules(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        """uint32[count, 2]: (birth, survive) of boards [first, first + count) (default: all from `first`)."""
+        count = self.n - first if count is None else count
+        birth, survive = (np.zeros(max(count, 0), dtype=np.uint32) for _ in range(2))
+        self._check(self._L.gol_batch_rules(self._h, first, first + count, birth.ctypes.data, survive.ctypes.data))
+        return np.stack([birth, survive], axis=1)
 
     # -- stepping and queries
     def step(self, turns: int, settled: bool = False):
@@ -137,6 +163,19 @@ class Batch:
         out = np.full(self.n, -1, dtype=np.int64)
         self._check(self._L.gol_batch_step(self._h, turns, out.ctypes.data))
         return out
+
+    def step_cycles(self, turns: int):
+        """Advance every board `turns` turns and scan each for a cycle of any period.  Returns
+        (found, period), both int64[n]: with t0 the turn before the call and the marks t0 + 2^j - 1,
+        found is the first turn t in (t0, t0 + turns] at which the board equals its state at the
+        last mark before t, period = t minus that mark, the exact period of the board's cycle; -1 in
+        both for a board not found.  found is an upper bound of the settle turn (at most t0 +
+        3 max(mu + 1, period) for a board that enters its cycle mu turns after t0); every board makes
+        all the turns, and each call scans from its own t0."""
+        found = np.full(self.n, -1, dtype=np.int64)
+        period = np.full(self.n, -1, dtype=np.int64)
+        self._check(self._L.gol_batch_step_cycles(self._h, turns, found.ctypes.data, period.ctypes.data))
+        return found, period
 
     @property
     def turn(self) -> int:

@@ -514,8 +514,8 @@ int gol_bounds_host(int32_t layout, const void *board, int64_t pitch, int64_t W,
  * symbol.)
  *
  * A batch is n independent tori, all H x W, 1 <= H <= 512, 1 <= W <= 512 (any
- * width), 1 <= n <= 2^20, on one GPU, with one rule (default B3/S23) and one
- * turn counter.  The engine steps one board per launch, and a launch on a board
+ * width), 1 <= n <= 2^20, on one GPU, with one turn counter and one rule
+ * (default B3/S23) or a rule per board.  The engine steps one board per launch, and a launch on a board
  * of this size is latency-bound; a batch steps all its boards
  * in one launch, each resident in one workgroup for all the launch's turns
  * (DESIGN.md §4.15).
@@ -532,7 +532,17 @@ int gol_bounds_host(int32_t layout, const void *board, int64_t pitch, int64_t W,
  *    may be NULL).
  *  - set_rule / rule: the 9-bit masks of "life-like rules"; masks >= 512 are
  *    GOL_EINVAL.  Valid between stepping calls: the boards and the turn stay.  B0
- *    rules are legal, and the padding bits still stay zero.
+ *    rules are legal, and the padding bits still stay zero.  set_rule sets
+ *    every board; rule returns the rule that all boards share (also after
+ *    set_rules made them equal), and on a batch of different rules GOL_ESTATE,
+ *    its outputs untouched.
+ *  - set_rules: the masks of boards [i0, i1) from birth[i - i0] and survive[i -
+ *    i0]; the other boards keep their rules, the boards and the turn stay.
+ *    Every mask is checked first: a call that fails (NULL, i0 < 0, i0 > i1, i1 >
+ *    n, a mask >= 512) sets none.  rules returns the masks of boards [i0, i1).
+ *    A batch whose boards share one rule runs the one-rule kernels, whichever
+ *    call made it so; only boards of different rules run the kernel that reads
+ *    a rule per board (there B3/S23 boards take the table circuit, too).
  *  - load_words overwrites boards [i0, i1) only (set bits at c >= W of the
  *    input are ignored) and resets the turn counter to 0; store_words writes Ww
  *    words per row and touches neither the words between rows nor those between
@@ -547,6 +557,23 @@ int gol_bounds_host(int32_t layout, const void *board, int64_t pitch, int64_t W,
  *    oscillators.  The scan is per call (a board that settled in an earlier call
  *    is found again at turn0 + 2), and every board is at turn0 + turns after
  *    the call, whatever it settled at.
+ *  - step_cycles: every board advances exactly `turns` >= 0 turns, as in step,
+ *    and is scanned for a cycle of any period (Brent's cycle detection).  With
+ *    t0 the turn before the call and s(t) a board's state at turn t, the marks
+ *    are m_j = t0 + 2^j - 1 (t0, t0 + 1, t0 + 3, t0 + 7, ...), and for t = t0 + 1 ..
+ *    t0 + turns, m(t) is the largest mark < t.  The board is found at the
+ *    smallest t with s(t) == s(m(t)): found[i] = t and period[i] = t - m(t); a
+ *    board never found has -1 in both.  (At a turn that is itself a mark the
+ *    comparison is with the mark before it.)  It follows that period is the
+ *    exact minimal period of the board's cycle (a snapshot inside the cycle
+ *    recurs first after exactly one period), and that a board entering its
+ *    cycle mu turns after t0 with period lambda is found no later than t0 +
+ *    3*max(mu + 1, lambda).  found is therefore an upper bound of the settle
+ *    turn, not the settle turn: step(..., settled) stays the exact scan for
+ *    periods <= 2.  found and period are int64_t[n]; found must not be NULL,
+ *    period may be.  The scan is per call (a second call starts again from its
+ *    own t0), there is no early exit, turns == 0 leaves every board at -1, and
+ *    rules per board apply.
  *  - alive_counts / hashes: one uint64 per board, cap >= n; the hash of board i
  *    is oracle_hash_words(words_i, 0, H, Ww) (gol_engine_hash's definition on
  *    the board's zero-padded words, for every W).
@@ -561,12 +588,15 @@ int gol_batch_info(gol_batch *b, int64_t *n, int64_t *H, int64_t *W, int32_t *wa
                    int32_t *boards_per_workgroup, int32_t *words_per_lane, int32_t *turns_per_launch);
 int gol_batch_set_rule(gol_batch *b, uint32_t birth, uint32_t survive);
 int gol_batch_rule(gol_batch *b, uint32_t *birth, uint32_t *survive);
+int gol_batch_set_rules(gol_batch *b, int64_t i0, int64_t i1, const uint32_t *birth, const uint32_t *survive);
+int gol_batch_rules(gol_batch *b, int64_t i0, int64_t i1, uint32_t *birth, uint32_t *survive);
 int gol_batch_load_words(gol_batch *b, int64_t i0, int64_t i1, const uint64_t *words, int64_t row_stride,
                          int64_t board_stride);
 int gol_batch_store_words(gol_batch *b, int64_t i0, int64_t i1, uint64_t *words, int64_t row_stride,
                           int64_t board_stride);
 int gol_batch_load_random(gol_batch *b, uint64_t seed);
 int gol_batch_step(gol_batch *b, int64_t turns, int64_t *settled);
+int gol_batch_step_cycles(gol_batch *b, int64_t turns, int64_t *found, int64_t *period);
 int gol_batch_turn(gol_batch *b, int64_t *turn);
 int gol_batch_alive_counts(gol_batch *b, uint64_t *counts, int64_t cap);
 int gol_batch_hashes(gol_batch *b, uint64_t *hashes, int64_t cap);
@@ -578,6 +608,15 @@ int gol_batch_hashes(gol_batch *b, uint64_t *hashes, int64_t cap);
  * GOL_EINVAL: H or W outside 1..512, masks >= 512, row_stride < Ww, NULL. */
 int gol_batch_step_host(int64_t H, int64_t W, uint32_t birth, uint32_t survive, const uint64_t *in, uint64_t *out,
                         int64_t row_stride);
+/* The cycle scan of gol_batch_step_cycles on one board in host memory (a host
+ * function, no GPU needed), with the turn of gol_batch_step_host and the mark
+ * arithmetic the kernel runs (csrc/gol_batch.h), t0 = 0: `out` receives s(turns)
+ * (for turns == 0 `in` with its padding cleared), *found and *period as above
+ * (found in 1..turns or -1).  `in` and `out` as for gol_batch_step_host (they
+ * may be the same buffer); period may be NULL.  GOL_EINVAL as there, and for
+ * turns < 0 or a NULL found. */
+int gol_batch_cycles_host(int64_t H, int64_t W, uint32_t birth, uint32_t survive, const uint64_t *in, uint64_t *out,
+                          int64_t row_stride, int64_t turns, int64_t *found, int64_t *period);
 
 /* ---------------------------------------------------------------- plans
  * The schedule of a sharded step as data (host functions, no GPU needed).  The
