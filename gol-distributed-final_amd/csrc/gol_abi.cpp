@@ -103,21 +103,13 @@ extern "C" int gol_dev_bits_step(const uint32_t *top, const uint32_t *mid, const
                           (hipStream_t)stream));
 }
 
-extern "C" int gol_dev_band_step(const uint32_t *top, const uint32_t *mid, const uint32_t *bot, uint32_t *dst,
-                                 int64_t R, int64_t Wd, int64_t pitch, int64_t row0, int64_t rows, int32_t k,
-                                 int32_t cells_per_lane, int32_t strip_rows, uint64_t *count_slots, void *stream)
+// Words per lane of the band kernels for a cells_per_lane (<= 0: the default); 0: not one of theirs.
+static int band_dw(int32_t cells_per_lane)
 {
-    const int dw = cells_per_lane == 64 ? 2 : (cells_per_lane == 128 ? 4 : (cells_per_lane <= 0 ? GOL_BAND_DEFAULT_DW : 0));
-    if (!top || !mid || !bot || !dst || R <= 0 || Wd <= 0 || !dw || Wd % dw || pitch < Wd || pitch % dw ||
-        row0 < 0 || rows < 0 || row0 + rows > R ||
-        !(k == 1 || k == 2 || k == 4 || k == 8 || (k == 16 && dw == 2) || (k == 12 && dw == 4)) ||
-        k > R || (((uintptr_t)mid | (uintptr_t)top | (uintptr_t)bot | (uintptr_t)dst) & (4 * dw - 1)))
-        return gol_set_error(GOL_EINVAL, "bad band_step arguments (R=%lld Wd=%lld pitch=%lld k=%d cells_per_lane=%d)",
-                             (long long)R, (long long)Wd, (long long)pitch, k, cells_per_lane);
-    LAUNCH(golk_band_step(top, mid, bot, dst, R, Wd, pitch, row0, rows, k, dw, strip_rows, count_slots, nullptr,
-                          (hipStream_t)stream));
+    return cells_per_lane == 64 ? 2 : (cells_per_lane == 128 ? 4 : (cells_per_lane <= 0 ? GOL_BAND_DEFAULT_DW : 0));
 }
 
+// cus = slots = 0: this device
 static int pipe_on_check(bool band, bool contig, bool count, bool pipelined, int32_t cus, int32_t slots)
 {
     if (!cus && !slots) return GOL_OK;
@@ -137,7 +129,7 @@ extern "C" int gol_dev_band_step_on(const uint32_t *top, const uint32_t *mid, co
                                     int32_t cells_per_lane, int32_t strip_rows, uint64_t *count_slots, void *stream,
                                     int32_t cus, int32_t slots)
 {
-    const int dw = cells_per_lane == 64 ? 2 : (cells_per_lane == 128 ? 4 : (cells_per_lane <= 0 ? GOL_BAND_DEFAULT_DW : 0));
+    const int dw = band_dw(cells_per_lane);
     if (!top || !mid || !bot || !dst || R <= 0 || Wd <= 0 || !dw || Wd % dw || pitch < Wd || pitch % dw ||
         row0 < 0 || rows < 0 || row0 + rows > R ||
         !(k == 1 || k == 2 || k == 4 || k == 8 || (k == 16 && dw == 2) || (k == 12 && dw == 4)) ||
@@ -149,6 +141,14 @@ extern "C" int gol_dev_band_step_on(const uint32_t *top, const uint32_t *mid, co
     if (rc) return rc;
     LAUNCH(golk_band_step(top, mid, bot, dst, R, Wd, pitch, row0, rows, k, dw, strip_rows, count_slots, nullptr,
                           (hipStream_t)stream, cus, slots));
+}
+
+extern "C" int gol_dev_band_step(const uint32_t *top, const uint32_t *mid, const uint32_t *bot, uint32_t *dst,
+                                 int64_t R, int64_t Wd, int64_t pitch, int64_t row0, int64_t rows, int32_t k,
+                                 int32_t cells_per_lane, int32_t strip_rows, uint64_t *count_slots, void *stream)
+{
+    return gol_dev_band_step_on(top, mid, bot, dst, R, Wd, pitch, row0, rows, k, cells_per_lane, strip_rows, count_slots,
+                                stream, 0, 0);
 }
 
 extern "C" int gol_dev_rule_step(const uint32_t *top, const uint32_t *mid, const uint32_t *bot, uint32_t *dst,
@@ -171,7 +171,7 @@ extern "C" int gol_dev_rule_step(const uint32_t *top, const uint32_t *mid, const
 
 extern "C" int gol_band_max_k(int32_t cells_per_lane)
 {
-    const int dw = cells_per_lane == 64 ? 2 : (cells_per_lane == 128 ? 4 : (cells_per_lane <= 0 ? GOL_BAND_DEFAULT_DW : 0));
+    const int dw = band_dw(cells_per_lane);
     return dw == 2 ? 16 : (dw == 4 ? 12 : 0);
 }
 
@@ -223,19 +223,6 @@ extern "C" int gol_dev_unpack(const uint32_t *bits, int64_t rows, int64_t W, int
     LAUNCH(golk_unpack(bits, rows, W, pitch, bytes, stride, (hipStream_t)stream));
 }
 
-extern "C" int gol_dev_bytes_step_k(const uint8_t *top, const uint8_t *mid, const uint8_t *bot, uint8_t *dst,
-                                    int64_t R, int64_t W, int64_t stride, int64_t row0, int64_t rows, int32_t k,
-                                    int32_t strip_rows, uint64_t *count_slots, void *stream)
-{
-    if (!top || !mid || !bot || !dst || R <= 0 || W <= 0 || W % 32 || stride < W || stride % 16 || row0 < 0 ||
-        rows < 0 || row0 + rows > R || !(k == 1 || k == 2 || k == 4 || k == 8 || k == 16 || k == 32) || k > R ||
-        (((uintptr_t)mid | (uintptr_t)top | (uintptr_t)bot | (uintptr_t)dst) & 15))
-        return gol_set_error(GOL_EINVAL, "bad bytes_step_k arguments (R=%lld W=%lld stride=%lld k=%d)",
-                             (long long)R, (long long)W, (long long)stride, k);
-    LAUNCH(golk_bytes_blocked(top, mid, bot, dst, R, W, stride, row0, rows, k, strip_rows, count_slots, nullptr,
-                              (hipStream_t)stream));
-}
-
 extern "C" int gol_dev_bytes_step_k_on(const uint8_t *top, const uint8_t *mid, const uint8_t *bot, uint8_t *dst,
                                        int64_t R, int64_t W, int64_t stride, int64_t row0, int64_t rows, int32_t k,
                                        int32_t strip_rows, uint64_t *count_slots, void *stream, int32_t cus,
@@ -250,6 +237,13 @@ extern "C" int gol_dev_bytes_step_k_on(const uint8_t *top, const uint8_t *mid, c
     if (rc) return rc;
     LAUNCH(golk_bytes_blocked(top, mid, bot, dst, R, W, stride, row0, rows, k, strip_rows, count_slots, nullptr,
                               (hipStream_t)stream, cus, slots));
+}
+
+extern "C" int gol_dev_bytes_step_k(const uint8_t *top, const uint8_t *mid, const uint8_t *bot, uint8_t *dst,
+                                    int64_t R, int64_t W, int64_t stride, int64_t row0, int64_t rows, int32_t k,
+                                    int32_t strip_rows, uint64_t *count_slots, void *stream)
+{
+    return gol_dev_bytes_step_k_on(top, mid, bot, dst, R, W, stride, row0, rows, k, strip_rows, count_slots, stream, 0, 0);
 }
 
 extern "C" int gol_dev_pipe_limits(int32_t kernel, int32_t contiguous, int32_t counted, int32_t *cus, int32_t *slots)

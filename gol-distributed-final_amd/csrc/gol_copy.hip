@@ -15,22 +15,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <algorithm>
-
 #include "gol_copy.h"
 #include "gol_kernels.h"
 
 namespace {
 
-constexpr int COPY_BLOCK = 256;
+constexpr int COPY_BLOCK = GOL_EDIT_BLOCK;
 typedef unsigned long long u64;
-
-__device__ __forceinline__ void add_alive(uint32_t n, u64 *alive)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) n += __shfl_down(n, d, 64);
-    if ((threadIdx.x & 63) == 0 && n) atomicAdd(alive, (u64)n);
-}
 
 struct CopyArgs {
     gol_edit_geom g;
@@ -94,7 +85,7 @@ __global__ __launch_bounds__(COPY_BLOCK) void copy_kernel(const CopyArgs a)
             }
         }
     }
-    add_alive(n, a.alive);  // (every lane of the wave takes part in the shuffles)
+    gol_edit_wave_add(n, a.alive);  // (every lane of the wave takes part in the shuffles)
 }
 
 // hdr: [0] alive, [1] max of ~row, [2] max of row, [3] max of ~column, [4] max of column (rows and
@@ -138,7 +129,7 @@ __global__ __launch_bounds__(COPY_BLOCK) void bounds_rows_kernel(const BoundsArg
         atomicMax(a.hdr + 1, ~(u64)(a.vrow + first));
         atomicMax(a.hdr + 2, (u64)(a.vrow + last));
     }
-    add_alive(n, a.hdr);
+    gol_edit_wave_add(n, a.hdr);
 }
 
 __global__ __launch_bounds__(COPY_BLOCK) void bounds_cols_kernel(const gol_edit_geom g, const uint32_t *occ, u64 *hdr)
@@ -162,16 +153,6 @@ __global__ __launch_bounds__(COPY_BLOCK) void bounds_cols_kernel(const gol_edit_
         atomicMax(hdr + 3, lo);
         atomicMax(hdr + 4, hi);
     }
-}
-
-// about 2048 workgroups at most; a workgroup strides over the rows that are left (as golk_paste)
-bool grid_for(int64_t lanes, int64_t rows, dim3 *grid)
-{
-    const int64_t nxb = (lanes + COPY_BLOCK - 1) / COPY_BLOCK;
-    if (nxb > INT32_MAX) return false;
-    const int64_t ny = std::min<int64_t>(rows, std::max<int64_t>(1, 2048 / nxb));
-    *grid = dim3((unsigned)nxb, (unsigned)ny);
-    return true;
 }
 
 bool rows_ok(int form, const void *src, int64_t pitch, int64_t W, int64_t row, int64_t rows)
@@ -200,7 +181,7 @@ hipError_t golk_copy(int form, const void *src, int64_t pitch, int64_t W, int64_
     a.pstride = pstride;
     a.alive = (u64 *)alive;
     dim3 grid;
-    if (!grid_for(a.lanes, rows, &grid)) return hipErrorInvalidValue;
+    if (!gol_edit_grid(a.lanes, rows, &grid)) return hipErrorInvalidValue;
     if (form == GOL_EDIT_BAND) copy_kernel<GOL_EDIT_BAND><<<grid, COPY_BLOCK, 0, s>>>(a);
     else if (form == GOL_EDIT_STANDARD) copy_kernel<GOL_EDIT_STANDARD><<<grid, COPY_BLOCK, 0, s>>>(a);
     else copy_kernel<GOL_EDIT_BYTES><<<grid, COPY_BLOCK, 0, s>>>(a);
@@ -223,7 +204,7 @@ hipError_t golk_bounds_rows(int form, const void *src, int64_t pitch, int64_t W,
     a.occ = occ;
     a.hdr = (u64 *)hdr;
     dim3 grid;
-    if (!grid_for(a.g.T, rows, &grid)) return hipErrorInvalidValue;
+    if (!gol_edit_grid(a.g.T, rows, &grid)) return hipErrorInvalidValue;
     if (f == GOL_EDIT_BYTES4) bounds_rows_kernel<GOL_EDIT_BYTES4><<<grid, COPY_BLOCK, 0, s>>>(a);
     else if (f == GOL_EDIT_BYTES) bounds_rows_kernel<GOL_EDIT_BYTES><<<grid, COPY_BLOCK, 0, s>>>(a);
     else bounds_rows_kernel<GOL_EDIT_STANDARD><<<grid, COPY_BLOCK, 0, s>>>(a);
@@ -246,7 +227,7 @@ hipError_t golk_bounds_cols(int form, const void *src, int64_t pitch, int64_t W,
         !gol_edit_geom_init(g, GOL_EDIT_FORM(form, W, pitch, src), W, x0, w, GOL_EDIT_COPY))
         return hipErrorInvalidValue;
     dim3 grid;
-    if (!grid_for(g.T, 1, &grid)) return hipErrorInvalidValue;
+    if (!gol_edit_grid(g.T, 1, &grid)) return hipErrorInvalidValue;
     bounds_cols_kernel<<<grid, COPY_BLOCK, 0, s>>>(g, occ, (u64 *)hdr);
     return hipGetLastError();
 }

@@ -1,5 +1,5 @@
-// gol_device.h -- what more than one kernel unit uses (gol_kernels.hip, gol_band_pipe.hip,
-// gol_bytes_pipe.hip and the micro-benchmarks of tools/ubench): build knobs, the v_bitop3 truth
+// gol_device.h -- what more than one kernel unit uses (gol_kernels.hip, gol_util.hip, gol_band_pipe.hip,
+// gol_bytes_pipe.hip, gol_batch.hip and the micro-benchmarks of tools/ubench): build knobs, the v_bitop3 truth
 // tables, lane and wave helpers, the register-pipeline state with the band stage, the byte
 // packing, the argument blocks of the step and pipeline kernels and the pipeline units' entry
 // points.  Device code: included by .hip units only.
@@ -288,9 +288,7 @@ struct Raw32 {
 }  // namespace golk
 
 // The pipeline kernels live in translation units of their own (gol_band_pipe.hip,
-// gol_bytes_pipe.hip: each under its own machine scheduler, Makefile).  _fn: the kernel's host
-// handle (occupancy queries, and what _launch launches); _launch: nwg workgroups on stream s.
-const void *golk_band_pipe_fn(bool contig, bool count);
+// gol_bytes_pipe.hip: each under its own machine scheduler, Makefile).  _launch: nwg workgroups of
+// the kernel golk_*_pipe_fn names (gol_kernels.h) on stream s.
 hipError_t golk_band_pipe_launch(bool contig, bool count, unsigned nwg, const golk::BitsArgs &a, hipStream_t s);
-const void *golk_bytes_pipe_fn(bool count);
 hipError_t golk_bytes_pipe_launch(bool count, unsigned nwg, const golk::BytesKArgs &a, hipStream_t s);

@@ -185,3 +185,33 @@ GOL_EDIT_HD int gol_edit_flips4(uint32_t a, uint32_t b)
     for (int i = 0; i < 4; ++i) n += (((a >> (8 * i)) & 0xffu) != 0) != (((b >> (8 * i)) & 0xffu) != 0);
     return n;
 }
+
+#if defined(__HIPCC__)
+// ------------------------------------------------------------------ device side (gol_edit.hip, gol_copy.hip)
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+// Threads of a workgroup of the region kernels (paste, copy, bounds): lanes run along the units of a row.
+constexpr int GOL_EDIT_BLOCK = 256;
+
+// The wave's sum of n added to the device counter *sum by one lane (every lane of the wave takes
+// part in the shuffles).
+__device__ __forceinline__ void gol_edit_wave_add(uint32_t n, unsigned long long *sum)
+{
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) n += __shfl_down(n, d, 64);
+    if ((threadIdx.x & 63) == 0 && n) atomicAdd(sum, (unsigned long long)n);
+}
+
+// The grid of a region kernel over `lanes` lanes and `rows` rows: about 2048 workgroups at most; a
+// workgroup strides over the rows that are left.  false: more lanes than a grid holds.
+inline bool gol_edit_grid(int64_t lanes, int64_t rows, dim3 *grid)
+{
+    const int64_t nxb = (lanes + GOL_EDIT_BLOCK - 1) / GOL_EDIT_BLOCK;
+    if (nxb > INT32_MAX) return false;
+    const int64_t ny = std::min<int64_t>(rows, std::max<int64_t>(1, 2048 / nxb));
+    *grid = dim3((unsigned)nxb, (unsigned)ny);
+    return true;
+}
+#endif

@@ -8,14 +8,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <algorithm>
-
 #include "gol_edit.h"
 #include "gol_kernels.h"
 
 namespace {
 
-constexpr int EDIT_BLOCK = 256;
+constexpr int EDIT_BLOCK = GOL_EDIT_BLOCK;
 
 struct EditArgs {
     gol_edit_geom g;
@@ -26,13 +24,6 @@ struct EditArgs {
     int64_t pstride;
     unsigned long long *changed;
 };
-
-__device__ __forceinline__ void add_changed(uint32_t n, unsigned long long *changed)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) n += __shfl_down(n, d, 64);
-    if ((threadIdx.x & 63) == 0 && n) atomicAdd(changed, (unsigned long long)n);
-}
 
 // FORM: GOL_EDIT_BYTES (one cell per lane), GOL_EDIT_BYTES4 (an aligned 4-byte word), else the bit layouts
 template <int FORM>
@@ -62,7 +53,7 @@ __global__ __launch_bounds__(EDIT_BLOCK) void paste_kernel(const EditArgs a)
             n += (uint32_t)__popc(old ^ v);
         }
     }
-    add_changed(n, a.changed);  // (every lane of the wave takes part in the shuffles)
+    gol_edit_wave_add(n, a.changed);  // (every lane of the wave takes part in the shuffles)
 }
 
 }  // namespace
@@ -86,11 +77,8 @@ hipError_t golk_paste(int form, void *dst, int64_t pitch, int64_t W, int64_t x0,
     a.pattern = pattern;
     a.pstride = pstride;
     a.changed = (unsigned long long *)changed;
-    const int64_t nxb = (a.g.T + EDIT_BLOCK - 1) / EDIT_BLOCK;
-    if (nxb > INT32_MAX) return hipErrorInvalidValue;
-    // about 2048 workgroups at most; a workgroup strides over the rows that are left
-    const int64_t ny = std::min<int64_t>(rows, std::max<int64_t>(1, 2048 / nxb));
-    const dim3 grid((unsigned)nxb, (unsigned)ny);
+    dim3 grid;
+    if (!gol_edit_grid(a.g.T, rows, &grid)) return hipErrorInvalidValue;
     if (f == GOL_EDIT_BYTES4) paste_kernel<GOL_EDIT_BYTES4><<<grid, EDIT_BLOCK, 0, s>>>(a);
     else if (f == GOL_EDIT_BYTES) paste_kernel<GOL_EDIT_BYTES><<<grid, EDIT_BLOCK, 0, s>>>(a);
     else paste_kernel<GOL_EDIT_STANDARD><<<grid, EDIT_BLOCK, 0, s>>>(a);

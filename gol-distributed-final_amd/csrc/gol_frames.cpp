@@ -57,7 +57,13 @@ static int view_check(gol_engine *e, int64_t x0, int64_t y0, int32_t scale, int3
     return GOL_OK;
 }
 
-static int view_layout(const gol_engine *e) { return e->mode != GOL_MODE_BITS ? 0 : (e->band ? 2 : 1); }
+// How the board's rows are stored now: what the view, edit and copy kernels take as `form`, and
+// what the queries report through *src_layout (the numbers include/golhip.h documents there).
+static_assert(GOL_EDIT_BYTES == 0 && GOL_EDIT_STANDARD == 1 && GOL_EDIT_BAND == 2, "*src_layout: 0 bytes, 1 standard, 2 band");
+static int board_form(const gol_engine *e)
+{
+    return e->mode != GOL_MODE_BITS ? GOL_EDIT_BYTES : (e->band ? GOL_EDIT_BAND : GOL_EDIT_STANDARD);
+}
 
 // Every local shard counts its runs of the viewport (gol_view_plan) into its own frame and copies
 // it to its pinned buffer: the counts, or with `pixels` (one shard holding every row) the pixels.
@@ -66,7 +72,7 @@ static int view_render(gol_engine *e, int64_t x0, int64_t y0, int32_t scale, int
                        std::vector<char> &used)
 {
     const int64_t n = (int64_t)out_w * out_h, vrows = (int64_t)out_h * scale;
-    const int form = view_layout(e);  // (GOLK_VIEW_BYTES / _STANDARD / _BAND are the layouts' numbers)
+    const int form = board_form(e);
     used.assign(e->sh.size(), 0);
     for (size_t i = 0; i < e->sh.size(); ++i) {
         gol_shard &s = e->sh[i];
@@ -112,7 +118,7 @@ extern "C" int gol_engine_view_counts(gol_engine *e, int64_t x0, int64_t y0, int
         }
         if (first) memset(dst, 0, out_w * sizeof(uint32_t));  // none of this process's rows are in view
     }
-    if (src_layout) *src_layout = view_layout(e);
+    if (src_layout) *src_layout = board_form(e);
     return GOL_OK;
 }
 
@@ -140,7 +146,7 @@ extern "C" int gol_engine_view(gol_engine *e, int64_t x0, int64_t y0, int32_t sc
             dst[x] = (uint8_t)((255u * c + s2 - 1) / s2);
         }
     }
-    if (src_layout) *src_layout = view_layout(e);
+    if (src_layout) *src_layout = board_form(e);
     return GOL_OK;
 }
 
@@ -218,7 +224,7 @@ extern "C" int gol_engine_paste(gol_engine *e, int64_t x0, int64_t y0, int64_t w
     if (e->mode == GOL_MODE_EXACT)
         return gol_set_error(GOL_ESTATE, "the board holds loaded bytes other than 0/255 until turn 1: step once before editing it");
     RCCHK(invalidate_halo(e));
-    const int form = view_layout(e);
+    const int form = board_form(e);
     std::vector<char> used(e->sh.size(), 0);
     int rc = GOL_OK;
     for (size_t i = 0; i < e->sh.size() && rc == GOL_OK; ++i) {
@@ -309,7 +315,7 @@ extern "C" int gol_engine_copy(gol_engine *e, int64_t x0, int64_t y0, int64_t w,
     if (cut && e->mode == GOL_MODE_EXACT)
         return gol_set_error(GOL_ESTATE, "the board holds loaded bytes other than 0/255 until turn 1: step once before editing it");
     if (cut) RCCHK(invalidate_halo(e));
-    const int form = view_layout(e);
+    const int form = board_form(e);
     const int64_t pw = (w + 63) / 64;
     std::vector<char> used(e->sh.size(), 0);
     std::vector<read_runs> plan(e->sh.size());
@@ -345,7 +351,7 @@ extern "C" int gol_engine_bounds(gol_engine *e, int64_t x0, int64_t y0, int64_t 
                                  int64_t *bw, int64_t *bh, int64_t *alive, int32_t *src_layout)
 {
     RCCHK(region_check(e, "bounds", x0, y0, w, h));
-    const int form = view_layout(e);
+    const int form = board_form(e);
     std::vector<char> used(e->sh.size(), 0);
     int rc = GOL_OK;
     for (size_t i = 0; i < e->sh.size() && rc == GOL_OK; ++i) {

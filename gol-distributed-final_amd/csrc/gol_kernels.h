@@ -1,8 +1,10 @@
-// gol_kernels.h -- internal launcher interface of the kernel units (gol_kernels.hip holds every
-// launcher; not part of the C ABI).
+// gol_kernels.h -- internal launcher interface of the kernel units (each unit holds its own
+// launchers, gol_launch.cpp the state they share; not part of the C ABI).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "gol_edit.h"  // GOL_EDIT_BYTES / _STANDARD / _BAND: how a board's rows are stored (`form`)
 
 #ifndef GOL_COUNT_SLOTS
 #define GOL_COUNT_SLOTS 256
@@ -49,6 +51,10 @@ hipError_t golk_band_step(const uint32_t *top, const uint32_t *mid, const uint32
 // This device's CU count and resident workgroups of a pipeline kernel (band: band_pipe_kernel with
 // contiguous ghost rows or not; else bytes_pipe_kernel), with the fused count or not.
 bool golk_pipe_limits(bool band, bool contig, bool count, int *cus, int64_t *slots);
+// The pipeline kernels' host handles (gol_band_pipe.hip, gol_bytes_pipe.hip): for occupancy
+// queries, and what the units' _launch launches (gol_device.h).
+const void *golk_band_pipe_fn(bool contig, bool count);
+const void *golk_bytes_pipe_fn(bool count);
 int golk_band_useful_words(int k, int dw);
 // Rounds of resident workgroups a step launch over `rows` rows makes (the band pipeline: 1 for
 // its one-round rank-weighted launch; other kernels: 1e9, i.e. many); for the engine's choice of
@@ -102,10 +108,8 @@ hipError_t golk_alive_list(bool bits_mode, const void *board, const void *prev, 
 // are viewport rows [vrow, vrow + rows): viewport cell (c, v) is board column (x0 + c) mod W and
 // belongs to pixel (c / scale, v / scale), 0 <= c < out_w * scale <= W.  form: byte rows (alive =
 // a byte != 0; pitch in bytes), standard bit rows (W % 32 == 0) or band bit rows (W % 1024 == 0),
-// pitch in words.  Reads only the words the viewport covers.  1 <= scale <= 4096.
-#define GOLK_VIEW_BYTES 0
-#define GOLK_VIEW_STANDARD 1
-#define GOLK_VIEW_BAND 2
+// pitch in words: GOL_EDIT_BYTES / _STANDARD / _BAND (gol_edit.h).  Reads only the words the
+// viewport covers.  1 <= scale <= 4096.
 hipError_t golk_view_counts(int form, const void *src, int64_t pitch, int64_t W, int64_t x0, int32_t scale,
                             int32_t out_w, int64_t row, int64_t rows, int64_t vrow, uint32_t *frame, hipStream_t s);
 // pixels[i] = ceil(255 * frame[i] / scale^2) for i < n; both buffers hold n rounded up to 4
@@ -115,7 +119,7 @@ hipError_t golk_view_pixels(const uint32_t *frame, int64_t n, int32_t scale, uin
 // Board edits (gol_edit.hip).  golk_paste applies pattern rows [prow, prow + rows) (pstride uint64
 // words per row, bit c % 64 of word c / 64 = cell c; pattern NULL: all ones) to rows [row, row + rows)
 // of `dst` (row 0 of a shard's rows) at board columns (x0 + c) mod W, 0 <= c < w <= W, under op
-// (GOL_PASTE_*), in place; form as the views' (GOLK_VIEW_BYTES / _STANDARD / _BAND; pitch in bytes
+// (GOL_PASTE_*), in place; form as the views' (GOL_EDIT_BYTES / _STANDARD / _BAND; pitch in bytes
 // or words).  Adds the number of cells whose state changed to *changed (a device counter).  Writes
 // only units the rectangle covers; one lane per unit and row (gol_edit.h).
 hipError_t golk_paste(int form, void *dst, int64_t pitch, int64_t W, int64_t x0, int64_t w, int64_t row, int64_t rows,

@@ -110,6 +110,51 @@ def test_no_gpu_calls_fail_cleanly(G):
         G.next_state_slab(np.zeros((16, 16), np.uint8), 5, 2)  # bad bounds: EINVAL before any HIP call
 
 
+P = 0x10000  # a pointer's value, aligned; a refused call reads nothing through it
+BAND_OK = dict(top=P, mid=P, bot=P, dst=P, R=24, Wd=128, pitch=128, row0=0, rows=24, k=12, cells_per_lane=128)
+BYTES_OK = dict(top=P, mid=P, bot=P, dst=P, R=32, Wd=64, pitch=64, row0=0, rows=32, k=32)
+TWIN_REFUSALS = [
+    ("band", dict(top=0)), ("band", dict(mid=0)), ("band", dict(bot=0)), ("band", dict(dst=0)),
+    ("band", dict(row0=1)), ("band", dict(rows=25)),
+    ("band", dict(k=3)), ("band", dict(k=16)), ("band", dict(k=12, cells_per_lane=64)), ("band", dict(k=12, R=8, rows=8)),
+    ("band", dict(cells_per_lane=32)), ("band", dict(cells_per_lane=96)), ("band", dict(cells_per_lane=256)),
+    ("band", dict(mid=P + 4)), ("band", dict(top=P + 8)), ("band", dict(dst=P + 2)),
+    ("band", dict(pitch=124)), ("band", dict(Wd=130, pitch=130)),
+    ("bytes", dict(top=0)), ("bytes", dict(mid=0)), ("bytes", dict(bot=0)), ("bytes", dict(dst=0)),
+    ("bytes", dict(row0=1)), ("bytes", dict(rows=33)),
+    ("bytes", dict(k=3)), ("bytes", dict(k=12)), ("bytes", dict(k=64)), ("bytes", dict(k=32, R=16, rows=16)),
+    ("bytes", dict(mid=P + 4)), ("bytes", dict(bot=P + 8)), ("bytes", dict(dst=P + 1)),
+    ("bytes", dict(pitch=48)), ("bytes", dict(pitch=72)), ("bytes", dict(Wd=48)),
+]
+
+
+def test_step_twins_refuse_alike(G):
+    """gol_dev_band_step / gol_dev_band_step_on(..., 0, 0) and gol_dev_bytes_step_k /
+    gol_dev_bytes_step_k_on(..., 0, 0) refuse the same arguments with the same code and the same
+    gol_last_error() text, clause by clause: a NULL segment, row0 + rows > R, a k the kernels do
+    not have (or more than R), a cells_per_lane they do not have, a misaligned pointer, a pitch
+    below the width (or not a multiple of its unit).  The refusals return before any HIP call."""
+    L, lib = G._lib, G.lib()
+
+    def refusal(fn, args):
+        assert lib.gol_partition_rows(-1, 0, 0, None, None) == L.GOL_EINVAL  # (another text in between)
+        assert lib.gol_last_error().startswith(b"bad partition")
+        return fn(*args), lib.gol_last_error()
+    for family, change in TWIN_REFUSALS:
+        a = dict(BAND_OK if family == "band" else BYTES_OK, **change)
+        args = [a["top"], a["mid"], a["bot"], a["dst"], a["R"], a["Wd"], a["pitch"], a["row0"], a["rows"], a["k"]]
+        if family == "band":
+            args.append(a["cells_per_lane"])
+        args += [0, None, None]  # strip_rows, count_slots, stream
+        plain, on = ((lib.gol_dev_band_step, lib.gol_dev_band_step_on) if family == "band" else
+                     (lib.gol_dev_bytes_step_k, lib.gol_dev_bytes_step_k_on))
+        rc, text = refusal(plain, args)
+        assert rc == L.GOL_EINVAL, (family, change)
+        assert text.startswith(b"bad band_step arguments (R=" if family == "band" else b"bad bytes_step_k arguments (R=")
+        assert b"k=%d" % a["k"] in text and b"R=%d " % a["R"] in text
+        assert refusal(on, args + [0, 0]) == (rc, text), (family, change)
+
+
 def test_pgm_reader_matches_oracle_and_errors(G, golden_dir, tmp_path):
     for name in os.listdir(os.path.join(golden_dir, "check", "images")):
         p = os.path.join(golden_dir, "check", "images", name)

@@ -1,6 +1,7 @@
 """CPU checks of bench.py's orchestration (no GPU): the self-launch of N ranks over gloo,
 the one-line JSON contract, and the roofline bookkeeping (a PMC profile measured on other
-kernel units -- gol_kernels.hip, gol_band_pipe.hip, gol_bytes_pipe.hip -- is never used)."""
+sources of the step kernels' units -- gol_kernels.hip, gol_band_pipe.hip, gol_bytes_pipe.hip, the
+three bench.py hashes; the utilities of gol_util.hip are not timed -- is never used)."""
 import json
 import os
 import subprocess

@@ -97,7 +97,7 @@ def test_load_bytes_and_store_bytes_with_wide_strides(env, cid):
 
 def test_byte_board_whose_last_cells_are_a_second_loop_item(env):
     """The byte board's count and 0/255 check run one thread per cell in a grid-stride loop
-    (csrc/gol_kernels.hip: grid_for's default cap, 256 * 16 blocks of 256): three odd bytes among
+    (csrc/gol_launch.h: grid_for's default cap, 256 * 16 blocks of 256): three odd bytes among
     the cells only a second item reaches must be counted, and must send turn 1 to the exact kernel
     (read as alive they would be a blinker; under the exact rule they die and nothing is born)."""
     W = 1056  # W % 64 == 32: a byte board that steps 0/255 bytes on the k-turn kernels

@@ -248,6 +248,42 @@ def test_real_device_paired(G, kernel):
     assert info["per_cu"] == min(slots // cus, 4 if kernel == "band" else 3)
 
 
+@pytest.mark.parametrize("kernel,k,count", [("band", 12, False), ("band", 12, True), ("band", 8, False), ("band", 8, True),
+                                            ("bytes", 32, False), ("bytes", 8, False)])
+def test_plain_entry_is_the_on_entry_with_this_device(G, kernel, k, count):
+    """gol_dev_band_step and gol_dev_bytes_step_k write what their _on twins write with cus = slots
+    = 0, bit for bit, through the pipeline (band k = 12, bytes k = 32) and through the step kernel
+    (k = 8), with the fused count and without: a shard of R rows between k true ghost rows, at the
+    smallest shapes the kernels take (band: 24 rows x 4096 cells, 128 cells per lane; bytes: 32
+    rows x 64 cells)."""
+    import torch
+    L, lib = G._lib, G.lib()
+    R, W = (24, 4096) if kernel == "band" else (32, 64)
+    width, pitch = _units(kernel, W, 0)
+    words = O.random_words(5, 0, R + 2 * k, W // 64)
+    if kernel == "band":  # (any words are a band board)
+        src = torch.from_numpy(words.view(np.int32).reshape(R + 2 * k, width)).cuda()
+    else:
+        src = torch.from_numpy(O.unpack(words)).cuda()
+    st = torch.cuda.current_stream().cuda_stream
+    outs = []
+    for on in (False, True):
+        dst = torch.full((R, pitch), SENT, dtype=src.dtype, device="cuda")
+        slots_t = torch.zeros(L.GOL_COUNT_SLOTS * 8, dtype=torch.int64, device="cuda") if count else None
+        args = [src[:k].data_ptr(), src[k:k + R].data_ptr(), src[k + R:].data_ptr(), dst.data_ptr(), R, width, pitch, 0, R, k]
+        args += ([128] if kernel == "band" else []) + [0, slots_t.data_ptr() if count else None, st] + ([0, 0] if on else [])
+        name = ("gol_dev_band_step" if kernel == "band" else "gol_dev_bytes_step_k") + ("_on" if on else "")
+        L.check(getattr(lib, name)(*args))
+        torch.cuda.synchronize()
+        assert _error_word(G) == (0, 0)
+        outs.append((dst, int(slots_t.sum().item()) if count else None))
+    (plain, plain_n), (on, on_n) = outs
+    assert bool((plain != SENT).any()), "nothing was written"
+    assert torch.equal(plain, on) and plain_n == on_n
+    if count:
+        assert plain_n > 0
+
+
 @pytest.mark.parametrize("kernel", ["band", "bytes"])
 def test_counter_hand_over(G, kernel):
     """Two paired launches back to back on one stream (ping-pong), then a third paired launch of

@@ -1,4 +1,4 @@
-"""The board utilities of csrc/gol_kernels.hip through their public launchers
+"""The board utilities of csrc/gol_util.hip through their public launchers
 (gol_dev_random_fill, _popcount, _hash, _pack, _unpack, _bytes_step) on caller memory, each against
 the oracle or plain numpy.  Every parity test of the suite loads, counts, hashes and reads its board
 back through these kernels, so an error two of them share, or one at an edge the engine never
@@ -26,7 +26,7 @@ pytestmark = pytest.mark.gpu
 
 SLOT_WORDS = 256 * 8  # GOL_COUNT_SLOTS * 8 uint64: "sum them all"
 ONES32 = 0xFFFFFFFF
-# threads of each launcher's largest grid (csrc/gol_kernels.hip: grid_for(n, 256, cap), cap x 256)
+# threads of each launcher's largest grid (csrc/gol_util.hip: grid_for(n, 256, cap) of gol_launch.h, cap x 256)
 SECOND_TRIP = {"random_fill": 256 * 64 * 256, "popcount": 256 * 16 * 256, "hash": 256 * 16 * 256,
                "pack": 256 * 64 * 256, "unpack": 256 * 64 * 256, "bytes_step_scalar": 256 * 16 * 256}
 GROW0 = [0, 7, 1 << 33]

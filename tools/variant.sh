@@ -10,9 +10,10 @@
 #   tools/variant.sh patch NAME FILE [FLAGS]    current sources with FILE (a patch of csrc/, -p1) applied
 #   tools/variant.sh kernels REV NAME           current sources with the three kernel units of REV
 #                                               (gol_kernels.hip, gol_band_pipe.hip, gol_bytes_pipe.hip)
-#                                               and, where REV has them, its gol_device.h / gol_pipe.h:
-#                                               the kernels of REV behind today's engine and ABI (REV
-#                                               must have the rule launchers in gol_kernels.hip)
+#                                               and, where REV has them, its gol_util.hip, gol_launch.cpp,
+#                                               gol_launch.h, gol_device.h / gol_pipe.h: the kernels of
+#                                               REV behind today's engine and ABI (REV must have the
+#                                               launch state in gol_launch.cpp)
 #   tools/variant.sh res ["-DFLAG ..."]         VGPRs / LDS / scratch / occupancy of the pipe kernels
 set -e
 R=$(cd "$(dirname "$0")/.." && pwd)
@@ -55,7 +56,7 @@ case ${1:-} in
   kernels)
     REV=$2; N=$3; D=$V/src_$N
     copy_current "$D"
-    for f in gol_kernels.hip gol_band_pipe.hip gol_bytes_pipe.hip gol_device.h gol_pipe.h; do
+    for f in gol_kernels.hip gol_band_pipe.hip gol_bytes_pipe.hip gol_util.hip gol_launch.cpp gol_launch.h gol_device.h gol_pipe.h; do
       if git -C "$R" cat-file -e "$REV:gol-distributed-final_amd/csrc/$f" 2>/dev/null; then
         git -C "$R" show "$REV:gol-distributed-final_amd/csrc/$f" > "$D/$f"
       fi
