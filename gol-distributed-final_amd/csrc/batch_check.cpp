@@ -9,6 +9,9 @@
 // `batch_check cycles`: gol_batch_cycles_host instead, on the same kind of buffers: every call's found,
 // period and final board against a scan written here (all states kept, the marks a list), and the mark
 // functions of gol_batch.h against that list for every d <= 1100.
+// `batch_check run`: gol_batch_run_cycles_host (the retiring scheme of gol_batch_run_cycles on one board) against
+// gol_batch_cycles_host over a grid of shapes, turns and launch lengths, on the same kind of buffers: found, period and
+// the final board equal, and made the formula of golhip.h written out here.
 #include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -202,11 +205,100 @@ static int main_cycles()
     return bad ? 1 : 0;
 }
 
+// one call of gol_batch_run_cycles_host against gol_batch_cycles_host on boards of exact size
+static int check_run(int64_t H, int64_t W, int64_t pad, uint32_t birth, uint32_t survive, const char *const *rows, int nrows,
+                     int64_t turns, int64_t launch, bool in_place)
+{
+    const int64_t Ww = (W + 63) / 64, stride = Ww + pad;
+    const size_t words = (size_t)((H - 1) * stride + Ww);
+    const uint64_t gap = 0xA5A5A5A5A5A5A5A5ULL, tail = W % 64 ? ((uint64_t)1 << (W % 64)) - 1 : ~(uint64_t)0;
+    uint64_t *a = new uint64_t[words], *b = new uint64_t[words], *want = new uint64_t[words];
+    for (size_t i = 0; i < words; ++i) a[i] = rows ? 0 : rnd() & rnd();
+    for (int r = 0; r < nrows; ++r)
+        for (int64_t c = 0; rows[r][c]; ++c)
+            if (rows[r][c] == 'O') a[(r % H) * stride + (c % W) / 64] |= (uint64_t)1 << ((c % W) % 64);
+    for (int64_t y = 0; y < H; ++y) {
+        a[y * stride + Ww - 1] = (a[y * stride + Ww - 1] & tail) | (gap & ~tail);  // padding bits set: never read
+        for (int64_t w = Ww; w < stride && y + 1 < H; ++w) a[y * stride + w] = gap;
+    }
+    for (size_t i = 0; i < words; ++i) want[i] = b[i] = gap;
+    int64_t wf = 77, wp = 77, found = 77, period = 77, made = 77;
+    int rc = gol_batch_cycles_host(H, W, birth, survive, a, want, stride, turns, &wf, &wp);
+    int64_t wm = turns;
+    if (wf >= 0) {
+        int64_t at = (wf + launch - 1) / launch * launch;
+        if (at > turns) at = turns;
+        wm = at + (turns - at) % wp;
+    }
+    if (in_place) {
+        memcpy(b, a, words * sizeof(uint64_t));
+        for (int64_t y = 0; y + 1 < H; ++y)
+            for (int64_t w = Ww; w < stride; ++w) want[y * stride + w] = a[y * stride + w];
+    }
+    if (rc == GOL_OK)
+        rc = gol_batch_run_cycles_host(H, W, birth, survive, in_place ? b : a, b, stride, turns, launch, &found, &period, &made);
+    const int bad = rc != GOL_OK || found != wf || period != wp || made != wm || memcmp(b, want, words * sizeof(uint64_t));
+    if (bad)
+        printf("run %lldx%lld stride %lld B 0x%x S 0x%x turns %lld launch %lld%s: rc %d, found %lld (%lld), period %lld (%lld), "
+               "made %lld (%lld)\n",
+               (long long)H, (long long)W, (long long)stride, birth, survive, (long long)turns, (long long)launch,
+               in_place ? " in place" : "", rc, (long long)found, (long long)wf, (long long)period, (long long)wp, (long long)made,
+               (long long)wm);
+    delete[] a;
+    delete[] b;
+    delete[] want;
+    return bad;
+}
+
+static int main_run()
+{
+    int bad = 0, n = 0;
+    static const char *const glider[] = {".O.", "..O", "OOO"}, *const row10[] = {"OOOOOOOOOO"};
+    static const int shapes[][2] = {{1, 1}, {2, 5}, {16, 16}, {7, 33}, {5, 65}, {65, 31}, {3, 481}};
+    static const uint32_t rules[][2] = {{0x008, 0x00C}, {0x048, 0x00C}, {0x004, 0x000}, {0x0AA, 0x0AA}};
+    static const int64_t turns[] = {0, 1, 2, 70}, launches[] = {1, 5, 7, 64, 70, 1000};
+    for (const auto &s : shapes)
+        for (const auto &r : rules)
+            for (int64_t t : turns)
+                for (int64_t l : launches)
+                    for (int pad = 0; pad <= 2; pad += 2, ++n) bad += check_run(s[0], s[1], pad, r[0], r[1], nullptr, 0, t, l, pad != 0);
+    for (int64_t l : launches)
+        for (int pad = 0; pad <= 2; pad += 2, n += 3) {
+            bad += check_run(8, 8, pad, 0x008, 0x00C, glider, 3, 200, l, pad != 0);    // found 63, period 32
+            bad += check_run(7, 9, pad, 0x008, 0x00C, glider, 3, 1100, l, pad == 0);   // found 507, period 252
+            bad += check_run(20, 20, pad, 0x008, 0x00C, row10, 1, 100, l, pad != 0);  // found 30, period 15
+        }
+    uint64_t w[8] = {0};
+    int64_t f = 77, p = 77, m = 77;
+    const int einval[] = {gol_batch_run_cycles_host(0, 8, 8, 12, w, w, 1, 1, 1, &f, &p, &m),
+                          gol_batch_run_cycles_host(8, 513, 8, 12, w, w, 9, 1, 1, &f, &p, &m),
+                          gol_batch_run_cycles_host(8, 8, 512, 12, w, w, 1, 1, 1, &f, &p, &m),
+                          gol_batch_run_cycles_host(8, 8, 8, 512, w, w, 1, 1, 1, &f, &p, &m),
+                          gol_batch_run_cycles_host(8, 65, 8, 12, w, w, 1, 1, 1, &f, &p, &m),
+                          gol_batch_run_cycles_host(8, 8, 8, 12, nullptr, w, 1, 1, 1, &f, &p, &m),
+                          gol_batch_run_cycles_host(8, 8, 8, 12, w, nullptr, 1, 1, 1, &f, &p, &m),
+                          gol_batch_run_cycles_host(8, 8, 8, 12, w, w, 1, -1, 1, &f, &p, &m),
+                          gol_batch_run_cycles_host(8, 8, 8, 12, w, w, 1, 1, 0, &f, &p, &m),
+                          gol_batch_run_cycles_host(8, 8, 8, 12, w, w, 1, 1, 1, nullptr, &p, &m)};
+    for (int rc : einval)
+        if (rc != GOL_EINVAL || f != 77 || p != 77 || m != 77) {
+            printf("a bad argument returned %d\n", rc);
+            ++bad;
+        }
+    if (gol_batch_run_cycles_host(8, 8, 8, 12, w, w, 1, 3, 2, &f, nullptr, nullptr) != GOL_OK || f != 1) {  // (may be NULL)
+        printf("a NULL period and made: found %lld\n", (long long)f);
+        ++bad;
+    }
+    printf("batch_check run: %d cases, %d bad\n", n, bad);
+    return bad ? 1 : 0;
+}
+
 int main(int argc, char **argv)
 {
     if (argc > 1) {
         if (!strcmp(argv[1], "cycles")) return main_cycles();
-        printf("usage: batch_check [cycles]\n");
+        if (!strcmp(argv[1], "run")) return main_run();
+        printf("usage: batch_check [cycles | run]\n");
         return 2;
     }
     static const int shapes[][2] = {{1, 1}, {1, 2}, {2, 1}, {2, 2}, {3, 3}, {2, 5}, {5, 2}, {16, 16}, {7, 31}, {7, 32}, {7, 33},

@@ -267,6 +267,16 @@ extern "C" int gol_dev_bytes_step(const uint8_t *world, int64_t H, int64_t W, in
     LAUNCH(golk_bytes_step(world, H, W, stride, y0, y1, out, out_stride, (hipStream_t)stream));
 }
 
+extern "C" int gol_dev_batch_retire(const int32_t *list_in, int32_t *counts, const int64_t *found, int64_t n, int64_t t0,
+                                    int64_t t_now, int64_t t_end, int32_t *active, int32_t *finish, int64_t *left, void *stream)
+{
+    if (!list_in || !counts || !found || !active || !finish || !left || n < 1 || n > ((int64_t)1 << 20) || t0 < 0 || t0 > t_now ||
+        t_now > t_end)
+        return gol_set_error(GOL_EINVAL, "bad batch_retire arguments (n %lld, turns %lld <= %lld <= %lld, or NULL)", (long long)n,
+                             (long long)t0, (long long)t_now, (long long)t_end);
+    LAUNCH(golk_batch_retire(list_in, counts, found, n, t0, t_now, t_end, active, finish, left, (hipStream_t)stream));
+}
+
 extern "C" int gol_dev_error(int32_t device, uint32_t *flags)
 {
     if (!flags) return gol_set_error(GOL_EINVAL, "flags is NULL");

@@ -48,6 +48,11 @@ GOL_BATCH_HD int64_t gol_batch_last_mark(int64_t d)  // d >= 1: the largest mark
     return p - 1;
 }
 
+// Retirement (gol_batch_run_cycles): a board found d >= 1 turns after the call began, with period p = d - the last
+// mark before d, has s(t + p) == s(t) from turn d - p on.  Seen at a turn >= d with `rest` >= 0 turns of the call still to
+// come, its state at the call's end is its state now advanced by rest mod p turns: the turns it still has to make.
+GOL_BATCH_HD int64_t gol_batch_turns_left(int64_t d, int64_t rest) { return rest % (d - gol_batch_last_mark(d)); }
+
 // The shape of a row: nwr words in use of nw held, the last cell's bit and the mask of the last word.
 struct gol_batch_row {
     int32_t nwr, nw;

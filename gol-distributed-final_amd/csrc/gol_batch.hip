@@ -1,7 +1,7 @@
 // gol_batch.hip -- many small tori (1 <= H, W <= 512) stepped in one launch (include/golhip.h,
 // "batches of small boards"; the row function is gol_batch.h).
 //
-// batch_step_kernel<NW, RULE, SCAN>: a board never leaves its workgroup during a launch.  One
+// batch_step_kernel<NW, RULE, SCAN, LIST>: a board never leaves its workgroup during a launch.  One
 // row per lane, NW = 1, 2, 4, 8 or 16 words of it in registers, ceil(H / 64) waves per board; boards
 // of up to 128 rows share a workgroup (4 boards of one wave, 2 of two).  The board is read from HBM
 // once, stepped `turns` times and written once, in place: no HBM traffic between the turns.
@@ -23,11 +23,18 @@
 // RULE: B3/S23 on 7 gates, the table circuit with the masks of the arguments, or the table circuit
 // with the masks of the wave's own board (rules[2 board], rules[2 board + 1]), read once per launch
 // by a scalar load, so the expanded tables are wave-uniform as in the one-rule kernel.
+// LIST (gol_batch_run_cycles): a workgroup's board slots index a device list of board numbers with a device
+// count; a slot past the count has no board, like a board past n.  With the cycle scan it is the search over the
+// boards not found yet (prev, settled and the rules stay indexed by the board's own number).  Without a scan it is
+// the finish: every listed board has its own number of turns still to make (left[board]), the workgroup's loop
+// makes the most any of its boards needs (at most the launch's turns; uniform, since every wave runs every
+// barrier), a wave whose board has made its turns keeps its cells, and the turns made are taken off left[].
 // Synchronisation is __syncthreads() alone: no workgroup waits for another one, there is no flag
 // between workgroups, no spin loop and no atomic.  Every wave of a workgroup runs every barrier (a
 // wave whose board is past the batch's end computes on zeros and stores nothing).
 //
-// The small kernels: random fill, and one wave per board for the alive count and the hash.
+// The small kernels: random fill, one wave per board for the alive count and the hash, and for
+// gol_batch_run_cycles the identity list and the retire pass between its launches (one workgroup).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -51,6 +58,9 @@ struct BatchArgs {
     uint32_t birth, survive;
     const uint32_t *rules;  // GOL_BATCH_RULE_EACH: n pairs (birth, survive)
     int64_t done;           // GOL_BATCH_SCAN_CYCLES: the turns of the call before this launch
+    // LIST: the board of slot i of the grid is list[i], i < *count (a slot past the count has no board)
+    const int32_t *list, *count;
+    int64_t *left;  // LIST without a scan (the finish): per board the turns it still has to make, taken off here
 };
 
 template <int NW>
@@ -71,7 +81,7 @@ __device__ __forceinline__ void store_row(uint64_t *row, int32_t Ww, const uint3
         if (j < 2 * Ww) p[j] = j < NW ? c[j < NW ? j : 0] : 0u;
 }
 
-template <int NW, int RULE, int SCAN>
+template <int NW, int RULE, int SCAN, bool LIST>
 __global__ __launch_bounds__(512) void batch_step_kernel(const BatchArgs a)
 {
     // [buffer][wave][first / last row of the wave][h0 / h1][word]
@@ -80,10 +90,28 @@ __global__ __launch_bounds__(512) void batch_step_kernel(const BatchArgs a)
 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int lb = wave / a.wpb, w = wave - lb * a.wpb;  // the board's slot in the workgroup, the wave's in the board
-    const int64_t board = (int64_t)blockIdx.x * a.bpw + lb;
+    // LIST: the slot's board from the list, the finish's trip count and this board's own turns -- all wave-uniform,
+    // the slot made scalar like the per-board rule read below, so the reads are scalar loads
+    int64_t board = (int64_t)blockIdx.x * a.bpw + lb;
+    bool has = board < a.n;
+    int trips = a.turns, my = a.turns;  // the turns of the workgroup's loop; of them, those this wave's board makes
+    int64_t left = 0;
+    if (LIST) {
+        const uint32_t count = (uint32_t)*a.count;
+        const uint32_t slot = __builtin_amdgcn_readfirstlane((uint32_t)(blockIdx.x * a.bpw + lb));
+        has = slot < count;
+        board = has ? a.list[slot] : 0;
+        if (!SCAN) {  // every wave runs every barrier: the workgroup makes the most turns any of its boards needs
+            trips = 0;
+            for (uint32_t i = blockIdx.x * a.bpw; i < (blockIdx.x + 1) * a.bpw && i < count; ++i)
+                trips = max(trips, (int)min((int64_t)a.turns, a.left[a.list[i]]));
+            left = has ? a.left[board] : 0;
+            my = (int)min((int64_t)a.turns, left);
+        }
+    }
     const int y = w * 64 + lane;
     const int last = min(63, a.H - 1 - w * 64);  // the wave's last lane with a row
-    const bool on = board < a.n && y < a.H;
+    const bool on = has && y < a.H;
     const uint32_t msk = on ? ~0u : 0u;
     const int wup = lb * a.wpb + (w == 0 ? a.wpb - 1 : w - 1), wdn = lb * a.wpb + (w == a.wpb - 1 ? 0 : w + 1);
     const gol_batch_row g = a.g;
@@ -110,7 +138,7 @@ __global__ __launch_bounds__(512) void batch_step_kernel(const BatchArgs a)
     int64_t found = -1;  // uniform over the board's waves
     bool mine = false;   // this wave's "a word differs" of the turn just computed
     int buf = 0;
-    for (int it = 0; it < a.turns; ++it, buf ^= 1) {
+    for (int it = 0; it < trips; ++it, buf ^= 1) {
         uint32_t b0[NW], b1[NW], a0[NW], a1[NW], d0[NW], d1[NW], next[NW];
         gol_batch_hsum<NW>(cur, g.nwr, g.tb, b0, b1);
         if (lane == 0) {
@@ -158,8 +186,9 @@ __global__ __launch_bounds__(512) void batch_step_kernel(const BatchArgs a)
             }
             mine = __ballot(d != 0) != 0;
         }
+        const bool go = !LIST || SCAN || it < my;  // (uniform) the finish: a board that has made its turns keeps cur
 #pragma unroll
-        for (int j = 0; j < NW; ++j) cur[j] = next[j];
+        for (int j = 0; j < NW; ++j) cur[j] = go ? next[j] : cur[j];
     }
     // the last turn's comparison (buf: the buffer no wave reads any more)
     if (SCAN == GOL_BATCH_SCAN_CYCLES || (SCAN && (a.turns > 1 || a.have_prev))) {
@@ -175,6 +204,8 @@ __global__ __launch_bounds__(512) void batch_step_kernel(const BatchArgs a)
         store_row<NW>(a.boards + off, a.Ww, cur);
         if (SCAN && a.write_prev) store_row<NW>(a.prev + off, a.Ww, old);
         if (SCAN && y == 0 && found >= 0 && a.settled[board] < 0) a.settled[board] = found;
+        // (read before the loop's first barrier by every wave of the workgroup, written after its last one)
+        if (LIST && !SCAN && y == 0 && my > 0) a.left[board] = left - my;
     }
 }
 
@@ -203,24 +234,127 @@ __global__ __launch_bounds__(256) void batch_reduce_kernel(const uint64_t *board
     }
 }
 
-template <int NW, int RULE>
-hipError_t launch_scan(int scan, const BatchArgs &a, dim3 grid, dim3 block, hipStream_t s)
+// The boards 0 .. n - 1 as a list, and the two counts of a retiring call's start: n active, none to finish.
+__global__ __launch_bounds__(256) void batch_iota_kernel(int32_t *list, int32_t *counts, int32_t n)
 {
-    if (scan == GOL_BATCH_SCAN_CYCLES)
-        batch_step_kernel<NW, RULE, GOL_BATCH_SCAN_CYCLES><<<grid, block, 0, s>>>(a);
+    for (int32_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) list[i] = i;
+    if (blockIdx.x == 0 && threadIdx.x == 0) counts[0] = n, counts[1] = 0;
+}
+
+// The retire pass between the launches of gol_batch_run_cycles: one workgroup walks the lists in tiles of
+// RETIRE_TILE entries, in order.  First the finish list, in place: a board with left[] == 0 has made its
+// remainder and leaves.  Then the active list: a board still at found == -1 stays (active may be list_in: an
+// entry is written at or before the place it was read from, and a tile is read before a barrier and written
+// after it); a board found gets left[board] = gol_batch_turns_left and, unless that is 0, goes to the end of
+// the finish list.  The places come from a ballot per wave and a scan of the RETIRE_COUNTS wave counts of a
+// tile by wave 0 through LDS: stable, and the same on every run.  An entry outside 0 .. n - 1 is dropped.
+// counts[0]: in the entries of list_in, out those of active; counts[1]: the finish list's, in and out.
+#define RETIRE_ITEMS 16
+#define RETIRE_TILE (1024 * RETIRE_ITEMS)
+#define RETIRE_COUNTS (16 * RETIRE_ITEMS)  // wave counts of a tile, RETIRE_COUNTS / 64 per lane of wave 0
+__global__ __launch_bounds__(1024) void batch_retire_kernel(const int32_t *list_in, int32_t *counts, const int64_t *found,
+                                                            int64_t n, int64_t t0, int64_t rest, int32_t *active,
+                                                            int32_t *finish, int64_t *left)
+{
+    __shared__ int32_t cnt[2][RETIRE_COUNTS], off[2][RETIRE_COUNTS], total[2];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t cap = n < ((int64_t)1 << 20) ? n : (int64_t)1 << 20;
+    const int32_t n_in = (int32_t)max((int64_t)0, min((int64_t)counts[0], cap));
+    const int32_t f_in = (int32_t)max((int64_t)0, min((int64_t)counts[1], cap));
+    int32_t n_act = 0, n_fin = 0;  // (uniform) entries written so far
+    for (int pass = 0; pass < 2; ++pass) {
+        const int32_t *src = pass == 0 ? finish : list_in;
+        const int64_t *val = pass == 0 ? left : found;
+        const int32_t m = pass == 0 ? f_in : n_in;
+        for (int32_t base = 0; base < m; base += RETIRE_TILE) {
+            int32_t board[RETIRE_ITEMS], place[RETIRE_ITEMS];
+            int64_t v[RETIRE_ITEMS];
+            int kind[RETIRE_ITEMS];  // -1: leaves, 0: to (or stays in) the active list, 1: to (stays in) the finish list
+            // the tile's loads first, each kind together: RETIRE_ITEMS of them in flight, none behind a store
+#pragma unroll
+            for (int k = 0; k < RETIRE_ITEMS; ++k) {
+                const int32_t i = base + k * 1024 + (int32_t)threadIdx.x;
+                board[k] = i < m ? src[i] : -1;
+            }
+#pragma unroll
+            for (int k = 0; k < RETIRE_ITEMS; ++k) v[k] = board[k] >= 0 && board[k] < n ? val[board[k]] : 0;
+#pragma unroll
+            for (int k = 0; k < RETIRE_ITEMS; ++k) {
+                kind[k] = -1;
+                if (board[k] >= 0 && board[k] < n) {
+                    if (pass == 0) {
+                        kind[k] = v[k] > 0 ? 1 : -1;
+                    } else if (v[k] < 0) {
+                        kind[k] = 0;
+                    } else {
+                        const int64_t l = v[k] > t0 ? gol_batch_turns_left(v[k] - t0, rest) : 0;
+                        left[board[k]] = l;
+                        kind[k] = l > 0 ? 1 : -1;
+                    }
+                }
+                const uint64_t b0 = __ballot(kind[k] == 0), b1 = __ballot(kind[k] == 1);
+                const uint64_t below = ((uint64_t)1 << lane) - 1;
+                place[k] = __popcll((kind[k] == 0 ? b0 : b1) & below);
+                if (lane == 0) cnt[0][k * 16 + wave] = __popcll(b0), cnt[1][k * 16 + wave] = __popcll(b1);
+            }
+            __syncthreads();  // every entry of the tile is read
+            if (wave == 0) {
+#pragma unroll
+                for (int q = 0; q < 2; ++q) {
+                    int32_t c[RETIRE_COUNTS / 64], sum = 0;
+#pragma unroll
+                    for (int j = 0; j < RETIRE_COUNTS / 64; ++j) sum += c[j] = cnt[q][lane * (RETIRE_COUNTS / 64) + j];
+                    int32_t incl = sum;
+                    for (int d = 1; d < 64; d *= 2) {
+                        const int32_t up = __shfl_up(incl, d);
+                        if (lane >= d) incl += up;
+                    }
+                    int32_t at = incl - sum;
+#pragma unroll
+                    for (int j = 0; j < RETIRE_COUNTS / 64; ++j) {
+                        off[q][lane * (RETIRE_COUNTS / 64) + j] = at;
+                        at += c[j];
+                    }
+                    if (lane == 63) total[q] = incl;
+                }
+            }
+            __syncthreads();
+#pragma unroll
+            for (int k = 0; k < RETIRE_ITEMS; ++k) {
+                if (kind[k] == 0) active[n_act + off[0][k * 16 + wave] + place[k]] = board[k];
+                if (kind[k] == 1 && n_fin + off[1][k * 16 + wave] + place[k] < cap)
+                    finish[n_fin + off[1][k * 16 + wave] + place[k]] = board[k];
+            }
+            n_act += total[0];
+            n_fin += total[1];
+            __syncthreads();  // the tile is written, the counts are read
+        }
+    }
+    if (threadIdx.x == 0) counts[0] = n_act, counts[1] = n_fin;
+}
+
+template <int NW, int RULE>
+hipError_t launch_scan(int scan, bool list, const BatchArgs &a, dim3 grid, dim3 block, hipStream_t s)
+{
+    if (list && scan == GOL_BATCH_SCAN_CYCLES)
+        batch_step_kernel<NW, RULE, GOL_BATCH_SCAN_CYCLES, true><<<grid, block, 0, s>>>(a);
+    else if (list)
+        batch_step_kernel<NW, RULE, GOL_BATCH_SCAN_NONE, true><<<grid, block, 0, s>>>(a);
+    else if (scan == GOL_BATCH_SCAN_CYCLES)
+        batch_step_kernel<NW, RULE, GOL_BATCH_SCAN_CYCLES, false><<<grid, block, 0, s>>>(a);
     else if (scan == GOL_BATCH_SCAN_SETTLE)
-        batch_step_kernel<NW, RULE, GOL_BATCH_SCAN_SETTLE><<<grid, block, 0, s>>>(a);
+        batch_step_kernel<NW, RULE, GOL_BATCH_SCAN_SETTLE, false><<<grid, block, 0, s>>>(a);
     else
-        batch_step_kernel<NW, RULE, GOL_BATCH_SCAN_NONE><<<grid, block, 0, s>>>(a);
+        batch_step_kernel<NW, RULE, GOL_BATCH_SCAN_NONE, false><<<grid, block, 0, s>>>(a);
     return hipGetLastError();
 }
 
 template <int NW>
-hipError_t launch_rule(int rule, int scan, const BatchArgs &a, dim3 grid, dim3 block, hipStream_t s)
+hipError_t launch_rule(int rule, int scan, bool list, const BatchArgs &a, dim3 grid, dim3 block, hipStream_t s)
 {
-    if (rule == GOL_BATCH_RULE_EACH) return launch_scan<NW, GOL_BATCH_RULE_EACH>(scan, a, grid, block, s);
-    if (rule == GOL_BATCH_RULE_TABLE) return launch_scan<NW, GOL_BATCH_RULE_TABLE>(scan, a, grid, block, s);
-    return launch_scan<NW, GOL_BATCH_RULE_CONWAY>(scan, a, grid, block, s);
+    if (rule == GOL_BATCH_RULE_EACH) return launch_scan<NW, GOL_BATCH_RULE_EACH>(scan, list, a, grid, block, s);
+    if (rule == GOL_BATCH_RULE_TABLE) return launch_scan<NW, GOL_BATCH_RULE_TABLE>(scan, list, a, grid, block, s);
+    return launch_scan<NW, GOL_BATCH_RULE_CONWAY>(scan, list, a, grid, block, s);
 }
 
 }  // namespace
@@ -233,9 +367,11 @@ void golk_batch_shape(int64_t H, int64_t W, int *waves_per_board, int *boards_pe
     *words_per_lane = gol_batch_row_init(W).nw;
 }
 
-hipError_t golk_batch_step(uint64_t *boards, uint64_t *prev, int64_t *settled, int64_t n, int64_t H, int64_t W, int turns,
-                           int64_t turn0, bool have_prev, bool write_prev, uint32_t birth, uint32_t survive,
-                           const uint32_t *rules, int scan, int64_t done, hipStream_t s)
+// list == NULL: every board, slots = n; else the boards list[0 .. *count), *count <= slots
+static hipError_t batch_launch(uint64_t *boards, uint64_t *prev, int64_t *settled, int64_t n, int64_t H, int64_t W, int turns,
+                               int64_t turn0, bool have_prev, bool write_prev, uint32_t birth, uint32_t survive,
+                               const uint32_t *rules, int scan, int64_t done, const int32_t *list, const int32_t *count,
+                               int64_t slots, int64_t *left, hipStream_t s)
 {
     if (!boards || n < 1 || n > ((int64_t)1 << 20) || H < 1 || H > GOL_BATCH_MAX_SIDE || W < 1 || W > GOL_BATCH_MAX_SIDE ||
         turns < 1 || birth >= 512 || survive >= 512 || (settled && !prev) || ((have_prev || write_prev) && !settled) ||
@@ -260,17 +396,56 @@ hipError_t golk_batch_step(uint64_t *boards, uint64_t *prev, int64_t *settled, i
     a.survive = survive;
     a.rules = rules;
     a.done = done;
-    const dim3 grid((unsigned)((n + a.bpw - 1) / a.bpw)), block((unsigned)(a.bpw * a.wpb * 64));
+    a.list = list;
+    a.count = count;
+    a.left = left;
+    const dim3 grid((unsigned)((slots + a.bpw - 1) / a.bpw)), block((unsigned)(a.bpw * a.wpb * 64));
     const int rule = rules                             ? GOL_BATCH_RULE_EACH
                      : gol_batch_conway(birth, survive) ? GOL_BATCH_RULE_CONWAY
                                                         : GOL_BATCH_RULE_TABLE;
     switch (nw) {
-    case 1: return launch_rule<1>(rule, scan, a, grid, block, s);
-    case 2: return launch_rule<2>(rule, scan, a, grid, block, s);
-    case 4: return launch_rule<4>(rule, scan, a, grid, block, s);
-    case 8: return launch_rule<8>(rule, scan, a, grid, block, s);
-    default: return launch_rule<16>(rule, scan, a, grid, block, s);
+    case 1: return launch_rule<1>(rule, scan, list != nullptr, a, grid, block, s);
+    case 2: return launch_rule<2>(rule, scan, list != nullptr, a, grid, block, s);
+    case 4: return launch_rule<4>(rule, scan, list != nullptr, a, grid, block, s);
+    case 8: return launch_rule<8>(rule, scan, list != nullptr, a, grid, block, s);
+    default: return launch_rule<16>(rule, scan, list != nullptr, a, grid, block, s);
     }
+}
+
+hipError_t golk_batch_step(uint64_t *boards, uint64_t *prev, int64_t *settled, int64_t n, int64_t H, int64_t W, int turns,
+                           int64_t turn0, bool have_prev, bool write_prev, uint32_t birth, uint32_t survive,
+                           const uint32_t *rules, int scan, int64_t done, hipStream_t s)
+{
+    return batch_launch(boards, prev, settled, n, H, W, turns, turn0, have_prev, write_prev, birth, survive, rules, scan, done,
+                        nullptr, nullptr, n, nullptr, s);
+}
+
+hipError_t golk_batch_step_list(uint64_t *boards, uint64_t *prev, int64_t *settled, int64_t n, int64_t H, int64_t W, int turns,
+                                int64_t turn0, bool have_prev, bool write_prev, uint32_t birth, uint32_t survive,
+                                const uint32_t *rules, int64_t done, const int32_t *list, const int32_t *count, int64_t slots,
+                                int64_t *left, hipStream_t s)
+{
+    // the search (settled: the cycle scan of the listed boards) or the finish (left: each listed board's own turns)
+    if (!list || !count || slots < 1 || slots > n || (settled != nullptr) == (left != nullptr)) return hipErrorInvalidValue;
+    return batch_launch(boards, prev, settled, n, H, W, turns, turn0, have_prev, write_prev, birth, survive, rules,
+                        settled ? GOL_BATCH_SCAN_CYCLES : GOL_BATCH_SCAN_NONE, done, list, count, slots, left, s);
+}
+
+hipError_t golk_batch_iota(int32_t *list, int32_t *counts, int64_t n, hipStream_t s)
+{
+    if (!list || !counts || n < 1 || n > ((int64_t)1 << 20)) return hipErrorInvalidValue;
+    batch_iota_kernel<<<(unsigned)std::min<int64_t>((n + 255) / 256, 1024), 256, 0, s>>>(list, counts, (int32_t)n);
+    return hipGetLastError();
+}
+
+hipError_t golk_batch_retire(const int32_t *list_in, int32_t *counts, const int64_t *found, int64_t n, int64_t t0,
+                             int64_t t_now, int64_t t_end, int32_t *active, int32_t *finish, int64_t *left, hipStream_t s)
+{
+    if (!list_in || !counts || !found || !active || !finish || !left || n < 1 || n > ((int64_t)1 << 20) || t0 > t_now ||
+        t_now > t_end)
+        return hipErrorInvalidValue;
+    batch_retire_kernel<<<1, 1024, 0, s>>>(list_in, counts, found, n, t0, t_end - t_now, active, finish, left);
+    return hipGetLastError();
 }
 
 hipError_t golk_batch_random(uint64_t *boards, int64_t n, int64_t H, int64_t W, uint64_t seed, hipStream_t s)

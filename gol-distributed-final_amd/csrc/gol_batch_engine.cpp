@@ -1,5 +1,6 @@
 // gol_batch_engine.cpp -- batches of small boards (include/golhip.h): the handle, the argument
-// checks, the rules per board, the split of a stepping call into launches and the strided copies.  The kernels are
+// checks, the rules per board, the split of a stepping call into launches, the retiring call's lists and
+// readbacks, and the strided copies.  The kernels are
 // gol_batch.hip (whose object takes the name gol_batch.o), the host twin gol_batch_host.cpp.
 #include <hip/hip_runtime.h>
 
@@ -23,6 +24,7 @@ struct gol_batch {
     int64_t n = 0, H = 0, W = 0, Ww = 0;
     int device = 0;
     int tpl = 1;  // turns per launch at most
+    bool auto_tpl = false;  // the automatic length: run_cycles sizes each launch by the boards still in it
     int wpb = 1, bpw = 1, nw = 1;
     uint32_t birth = GOL_RULE_BIRTH_CONWAY, survive = GOL_RULE_SURVIVE_CONWAY;
     // empty: every board under birth / survive; else n pairs (birth, survive), not all equal
@@ -34,6 +36,10 @@ struct gol_batch {
     uint64_t *boards = nullptr;
     uint64_t *prev = nullptr;  // state(start - 1) between the launches of a scanning call (on demand)
     uint64_t *aux = nullptr;   // n words: the settle turns, the counts, the hashes (on demand)
+    // run_cycles (on demand): the active list, the finish list (n entries each) and the two counts; the turns left per board
+    int32_t *lists = nullptr;
+    int64_t *left = nullptr;
+    int32_t *hcounts = nullptr;  // pinned host memory: the two counts read back after every launch
 };
 
 namespace {
@@ -57,6 +63,11 @@ int need_aux(gol_batch *b)
 {
     if (!b->aux) HIPCHK(hipMalloc(&b->aux, (size_t)b->n * sizeof(uint64_t)));
     return GOL_OK;
+}
+
+int auto_turns(int64_t boards, int64_t H, int64_t W)
+{
+    return (int)std::min<int64_t>(GOL_BATCH_MAX_TURNS, std::max<int64_t>(1, GOL_BATCH_LAUNCH_UPDATES / (boards * H * W)));
 }
 
 uint64_t tail_mask(int64_t W) { return W % 64 ? ((uint64_t)1 << (W % 64)) - 1 : ~(uint64_t)0; }
@@ -87,6 +98,17 @@ int reduce(gol_batch *b, bool hash, uint64_t *out, int64_t cap)
     return GOL_OK;
 }
 
+// The device copy of the rules per board, brought up to date.
+int upload_rules(gol_batch *b)
+{
+    if (!b->rules_dirty && b->drules) return GOL_OK;
+    if (!b->drules) HIPCHK(hipMalloc(&b->drules, b->rules.size() * sizeof(uint32_t)));
+    HIPCHK(hipMemcpyAsync(b->drules, b->rules.data(), b->rules.size() * sizeof(uint32_t), hipMemcpyHostToDevice, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));  // (the host copy may change after the call)
+    b->rules_dirty = false;
+    return GOL_OK;
+}
+
 // `turns` turns of every board in launches of at most tpl; scan != GOL_BATCH_SCAN_NONE: out[0 .. n) =
 // the turn the scan found per board, else -1.  Blocks once, after the last launch.
 int step(gol_batch *b, int64_t turns, int scan, int64_t *out)
@@ -102,12 +124,9 @@ int step(gol_batch *b, int64_t turns, int scan, int64_t *out)
         HIPCHK(hipMemsetAsync(found, 0xff, (size_t)b->n * sizeof(int64_t), b->stream));
     }
     const bool each = !b->rules.empty();
-    if (each && turns > 0 && (b->rules_dirty || !b->drules)) {
-        if (!b->drules) HIPCHK(hipMalloc(&b->drules, b->rules.size() * sizeof(uint32_t)));
-        HIPCHK(hipMemcpyAsync(b->drules, b->rules.data(), b->rules.size() * sizeof(uint32_t), hipMemcpyHostToDevice,
-                              b->stream));
-        HIPCHK(hipStreamSynchronize(b->stream));  // (the host copy may change after the call)
-        b->rules_dirty = false;
+    if (each && turns > 0) {
+        const int rc = upload_rules(b);
+        if (rc) return rc;
     }
     for (int64_t done = 0; done < turns;) {
         const int k = (int)std::min<int64_t>(b->tpl, turns - done);
@@ -119,6 +138,65 @@ int step(gol_batch *b, int64_t turns, int scan, int64_t *out)
     if (found) HIPCHK(hipMemcpyAsync(out, found, (size_t)b->n * sizeof(int64_t), hipMemcpyDeviceToHost, b->stream));
     const hipError_t e = hipStreamSynchronize(b->stream);
     if (e != hipSuccess) return gol_set_error(GOL_EHIP, "batch step: %s", hipGetErrorString(e));
+    b->turn += turns;
+    return GOL_OK;
+}
+
+// gol_batch_run_cycles: the search over the active list in launches, a retire pass and a readback of the two counts
+// after each; then the finish list's remainders in launches of their own, each followed by the same pass (which
+// drops the boards that are done).  ends: the call's turn count at the end of every search launch.
+int run_cycles(gol_batch *b, int64_t turns, int64_t *out, std::vector<int64_t> &ends)
+{
+    OnDevice dev(b->device);
+    HIPCHK(dev.err);
+    const int rc = need_aux(b);
+    if (rc) return rc;
+    if (!b->prev) HIPCHK(hipMalloc(&b->prev, (size_t)(b->n * b->H * b->Ww) * sizeof(uint64_t)));
+    if (!b->lists) HIPCHK(hipMalloc(&b->lists, (size_t)(2 * b->n + 2) * sizeof(int32_t)));
+    if (!b->left) HIPCHK(hipMalloc(&b->left, (size_t)b->n * sizeof(int64_t)));
+    if (!b->hcounts) HIPCHK(hipHostMalloc(&b->hcounts, 2 * sizeof(int32_t), hipHostMallocDefault));
+    int64_t *found = (int64_t *)b->aux;
+    int32_t *active = b->lists, *finish = b->lists + b->n, *counts = b->lists + 2 * b->n;
+    HIPCHK(hipMemsetAsync(found, 0xff, (size_t)b->n * sizeof(int64_t), b->stream));
+    const bool each = !b->rules.empty();
+    if (each && turns > 0) {
+        const int rc2 = upload_rules(b);
+        if (rc2) return rc2;
+    }
+    const uint32_t *rules = each ? b->drules : nullptr;
+    int32_t *host = b->hcounts;  // the boards in the two lists, as the device counts them
+    host[0] = (int32_t)b->n;
+    host[1] = 0;
+    auto retire = [&](int64_t done) -> int {
+        HIPCHK(golk_batch_retire(active, counts, found, b->n, b->turn, b->turn + done, b->turn + turns, active, finish, b->left,
+                                 b->stream));
+        HIPCHK(hipMemcpyAsync(host, counts, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, b->stream));
+        HIPCHK(hipStreamSynchronize(b->stream));
+        if (host[0] < 0 || host[0] > b->n || host[1] < 0 || host[1] > b->n)
+            return gol_set_error(GOL_EHIP, "batch run_cycles: list counts %d, %d of %lld boards", host[0], host[1], (long long)b->n);
+        return GOL_OK;
+    };
+    if (turns > 0) HIPCHK(golk_batch_iota(active, counts, b->n, b->stream));
+    int64_t done = 0;
+    while (done < turns && host[0] > 0) {
+        const int k = (int)std::min<int64_t>(b->auto_tpl ? auto_turns(host[0], b->H, b->W) : b->tpl, turns - done);
+        HIPCHK(golk_batch_step_list(b->boards, b->prev, found, b->n, b->H, b->W, k, b->turn + done, done > 0, done + k < turns,
+                                    b->birth, b->survive, rules, done, active, counts, host[0], nullptr, b->stream));
+        done += k;
+        ends.push_back(done);
+        const int rc2 = retire(done);
+        if (rc2) return rc2;
+    }
+    while (host[1] > 0) {
+        const int k = b->auto_tpl ? auto_turns(host[1], b->H, b->W) : b->tpl;
+        HIPCHK(golk_batch_step_list(b->boards, nullptr, nullptr, b->n, b->H, b->W, k, b->turn + done, false, false, b->birth,
+                                    b->survive, rules, 0, finish, counts + 1, host[1], b->left, b->stream));
+        const int rc2 = retire(turns);  // (the active list: no board of it is found since the last pass, or none is left)
+        if (rc2) return rc2;
+    }
+    HIPCHK(hipMemcpyAsync(out, found, (size_t)b->n * sizeof(int64_t), hipMemcpyDeviceToHost, b->stream));
+    const hipError_t e = hipStreamSynchronize(b->stream);
+    if (e != hipSuccess) return gol_set_error(GOL_EHIP, "batch run_cycles: %s", hipGetErrorString(e));
     b->turn += turns;
     return GOL_OK;
 }
@@ -135,6 +213,9 @@ extern "C" void gol_batch_destroy(gol_batch *b)
         if (b->prev) (void)hipFree(b->prev);
         if (b->aux) (void)hipFree(b->aux);
         if (b->drules) (void)hipFree(b->drules);
+        if (b->lists) (void)hipFree(b->lists);
+        if (b->left) (void)hipFree(b->left);
+        if (b->hcounts) (void)hipHostFree(b->hcounts);
         if (b->stream) (void)hipStreamDestroy(b->stream);
     }
     delete b;
@@ -160,9 +241,8 @@ extern "C" int gol_batch_create(int64_t n, int64_t H, int64_t W, int32_t device,
     b->Ww = (W + 63) / 64;
     b->device = dev;
     golk_batch_shape(H, W, &b->wpb, &b->bpw, &b->nw);
-    b->tpl = turns_per_launch > 0
-                 ? turns_per_launch
-                 : (int)std::min<int64_t>(GOL_BATCH_MAX_TURNS, std::max<int64_t>(1, GOL_BATCH_LAUNCH_UPDATES / (n * H * W)));
+    b->auto_tpl = turns_per_launch == 0;
+    b->tpl = turns_per_launch > 0 ? turns_per_launch : auto_turns(n, H, W);
     auto fail = [&](int rc) {
         gol_batch_destroy(b);
         return rc;
@@ -354,6 +434,31 @@ extern "C" int gol_batch_step_cycles(gol_batch *b, int64_t turns, int64_t *found
     if (period)  // found - the last mark before it, with the kernel's own mark function
         for (int64_t i = 0; i < b->n; ++i)
             period[i] = found[i] < 0 ? -1 : found[i] - t0 - gol_batch_last_mark(found[i] - t0);
+    return GOL_OK;
+}
+
+extern "C" int gol_batch_run_cycles(gol_batch *b, int64_t turns, int64_t *found, int64_t *period, int64_t *made)
+{
+    if (!b || turns < 0 || !found)
+        return gol_set_error(GOL_EINVAL, "bad batch run_cycles (turns %lld, or NULL)", (long long)turns);
+    const int64_t t0 = b->turn;
+    std::vector<int64_t> ends;
+    try {  // before any GPU work (no search launch is shorter than tpl, but for the last one)
+        ends.reserve((size_t)((turns + b->tpl - 1) / b->tpl));
+    } catch (const std::exception &) {
+        return gol_set_error(GOL_ENOMEM, "batch run_cycles: the launch ends of %lld turns", (long long)turns);
+    }
+    const int rc = run_cycles(b, turns, found, ends);
+    if (rc) return rc;
+    for (int64_t i = 0; i < b->n; ++i) {
+        const int64_t d = found[i] < 0 ? 0 : found[i] - t0;
+        if (period) period[i] = d ? d - gol_batch_last_mark(d) : -1;
+        if (made && !d) made[i] = turns;
+        if (made && d) {  // the board left after the first launch that ended at or after d, and made its remainder
+            const int64_t at = *std::lower_bound(ends.begin(), ends.end(), d);
+            made[i] = at + gol_batch_turns_left(d, turns - at);
+        }
+    }
     return GOL_OK;
 }
 

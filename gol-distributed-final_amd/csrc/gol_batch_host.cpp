@@ -1,8 +1,9 @@
 // gol_batch_host.cpp -- gol_batch_step_host (include/golhip.h): one turn of one small torus on host
 // memory with the row function of the batch kernel (gol_batch.h), in the instantiation the kernel
 // picks for the width, row by row as the lanes do; and gol_batch_cycles_host: the cycle scan of one
-// board with that turn and the mark functions the kernel and the engine use.  No HIP header: a stand-alone program links this
-// file alone (batch_check.cpp).
+// board with that turn and the mark functions the kernel and the engine use; and gol_batch_run_cycles_host: the
+// retiring scheme of gol_batch_run_cycles on one board, with the remainder function the retire pass runs.  No HIP
+// header: a stand-alone program links this file alone (batch_check.cpp).
 #include <stdint.h>
 
 #include <vector>
@@ -98,6 +99,42 @@ extern "C" int gol_batch_cycles_host(int64_t H, int64_t W, uint32_t birth, uint3
         }
         if (gol_batch_is_mark(d)) snap = cur;  // (after the comparison: a mark is compared with the mark before it)
     }
+    for (int64_t y = 0; y < H; ++y)
+        for (int64_t w = 0; w < Ww; ++w) out[y * row_stride + w] = cur[(size_t)(y * Ww + w)];
+    return GOL_OK;
+}
+
+extern "C" int gol_batch_run_cycles_host(int64_t H, int64_t W, uint32_t birth, uint32_t survive, const uint64_t *in, uint64_t *out,
+                                         int64_t row_stride, int64_t turns, int64_t launch, int64_t *found, int64_t *period,
+                                         int64_t *made)
+{
+    const int64_t Ww = (W + 63) / 64;
+    if (H < 1 || H > GOL_BATCH_MAX_SIDE || W < 1 || W > GOL_BATCH_MAX_SIDE || birth >= 512 || survive >= 512 || !in || !out ||
+        row_stride < Ww || turns < 0 || !found || launch < 1)
+        return gol_set_error(GOL_EINVAL,
+                             "bad host batch run_cycles (H %lld, W %lld, B 0x%x, S 0x%x, row stride %lld, turns %lld, launch %lld)",
+                             (long long)H, (long long)W, birth, survive, (long long)row_stride, (long long)turns, (long long)launch);
+    const uint64_t tail = W % 64 ? ((uint64_t)1 << (W % 64)) - 1 : ~(uint64_t)0;
+    std::vector<uint64_t> cur((size_t)(H * Ww)), snap;
+    for (int64_t y = 0; y < H; ++y)
+        for (int64_t w = 0; w < Ww; ++w) cur[(size_t)(y * Ww + w)] = in[y * row_stride + w] & (w == Ww - 1 ? tail : ~(uint64_t)0);
+    snap = cur;
+    int64_t f = -1, did = 0;
+    // the search, in launches: the board leaves at the end of the launch it is found in
+    for (int64_t d = 1; d <= turns && !(f >= 0 && (d - 1) % launch == 0); ++d, ++did) {
+        const int rc = gol_batch_step_host(H, W, birth, survive, cur.data(), cur.data(), Ww);
+        if (rc) return rc;
+        if (f < 0 && cur == snap) f = d;
+        if (gol_batch_is_mark(d)) snap = cur;
+    }
+    // the finish: the turns of the call still to come, modulo the period
+    for (int64_t left = f < 0 ? 0 : gol_batch_turns_left(f, turns - did); left > 0; --left, ++did) {
+        const int rc = gol_batch_step_host(H, W, birth, survive, cur.data(), cur.data(), Ww);
+        if (rc) return rc;
+    }
+    *found = f;
+    if (period) *period = f < 0 ? -1 : f - gol_batch_last_mark(f);
+    if (made) *made = did;
     for (int64_t y = 0; y < H; ++y)
         for (int64_t w = 0; w < Ww; ++w) out[y * row_stride + w] = cur[(size_t)(y * Ww + w)];
     return GOL_OK;

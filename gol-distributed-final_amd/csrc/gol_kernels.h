@@ -161,6 +161,22 @@ void golk_batch_shape(int64_t H, int64_t W, int *waves_per_board, int *boards_pe
 hipError_t golk_batch_step(uint64_t *boards, uint64_t *prev, int64_t *settled, int64_t n, int64_t H, int64_t W, int turns,
                            int64_t turn0, bool have_prev, bool write_prev, uint32_t birth, uint32_t survive,
                            const uint32_t *rules, int scan, int64_t done, hipStream_t s);
+// The same launch over the boards list[0 .. *count) alone (device memory; *count <= slots <= n, which sizes the grid).
+// settled != NULL: the cycle scan of those boards (the search of gol_batch_run_cycles); left != NULL instead: no
+// scan, board i makes min(turns, left[i]) turns and left[i] loses them (the finish).  prev, settled, rules and left
+// are indexed by the board's own number.
+hipError_t golk_batch_step_list(uint64_t *boards, uint64_t *prev, int64_t *settled, int64_t n, int64_t H, int64_t W, int turns,
+                                int64_t turn0, bool have_prev, bool write_prev, uint32_t birth, uint32_t survive,
+                                const uint32_t *rules, int64_t done, const int32_t *list, const int32_t *count, int64_t slots,
+                                int64_t *left, hipStream_t s);
+// list[i] = i for i < n, counts = {n, 0}
+hipError_t golk_batch_iota(int32_t *list, int32_t *counts, int64_t n, hipStream_t s);
+// The retire pass (one workgroup, stable): counts[0] entries of list_in, counts[1] of finish.  finish loses the
+// boards with left[] == 0; a listed board with found[] < 0 goes to active (which may be list_in), one found gets left[] =
+// gol_batch_turns_left(found - t0, t_end - t_now) and, unless that is 0, goes to the end of finish.  counts receives
+// the two new counts.
+hipError_t golk_batch_retire(const int32_t *list_in, int32_t *counts, const int64_t *found, int64_t n, int64_t t0,
+                             int64_t t_now, int64_t t_end, int32_t *active, int32_t *finish, int64_t *left, hipStream_t s);
 // word(i, y, w) = splitmix64(seed ^ ((i*H + y)*Ww + w)) masked to W
 hipError_t golk_batch_random(uint64_t *boards, int64_t n, int64_t H, int64_t W, uint64_t seed, hipStream_t s);
 // out[i] = alive cells of board i, or (hash) its oracle_hash_words

@@ -180,11 +180,14 @@ SIGNATURES = [
     ("gol_batch_load_random", ctypes.c_int, [_vp, _u64]),
     ("gol_batch_step", ctypes.c_int, [_vp, _i64, _vp]),
     ("gol_batch_step_cycles", ctypes.c_int, [_vp, _i64, _vp, _vp]),
+    ("gol_batch_run_cycles", ctypes.c_int, [_vp, _i64, _vp, _vp, _vp]),
     ("gol_batch_turn", ctypes.c_int, [_vp, _P(_i64)]),
     ("gol_batch_alive_counts", ctypes.c_int, [_vp, _vp, _i64]),
     ("gol_batch_hashes", ctypes.c_int, [_vp, _vp, _i64]),
     ("gol_batch_step_host", ctypes.c_int, [_i64, _i64, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp, _i64]),
     ("gol_batch_cycles_host", ctypes.c_int, [_i64, _i64, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp, _i64, _i64, _P(_i64), _P(_i64)]),
+    ("gol_batch_run_cycles_host", ctypes.c_int, [_i64, _i64, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp, _i64, _i64, _i64, _P(_i64),
+                                                 _P(_i64), _P(_i64)]),
     ("gol_halo_plan", ctypes.c_int, [_i64, _i32, _i32, _i32, _P(gol_halo_op), _i32, _P(_i32)]),
     ("gol_step_plan", ctypes.c_int, [_i64, _i32, _i32, _i32, _P(gol_launch), _i32, _P(_i32)]),
     ("gol_view_plan", ctypes.c_int, [_i64, _i32, _i32, _i64, _i64, _P(gol_view_run), _i32, _P(_i32)]),
@@ -212,6 +215,7 @@ SIGNATURES = [
       _vp]),
     ("gol_band_max_k", ctypes.c_int, [_i32]),
     ("gol_dev_band_convert", ctypes.c_int, [_i32, _vp, _vp, _i64, _i64, _i64, _i64, _vp]),
+    ("gol_dev_batch_retire", ctypes.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
     ("gol_dev_error", ctypes.c_int, [_i32, _P(ctypes.c_uint32)]),
     ("gol_broker_create", ctypes.c_int, [_P(gol_config), _P(_vp)]),
     ("gol_broker_destroy", None, [_vp]),

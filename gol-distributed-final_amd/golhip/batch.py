@@ -177,6 +177,21 @@ class Batch:
         self._check(self._L.gol_batch_step_cycles(self._h, turns, found.ctypes.data, period.ctypes.data))
         return found, period
 
+    def run_cycles(self, turns: int, made: bool = False):
+        """step_cycles with the boards retired as they are found: the same (found, period), boards and
+        turn counter, for less work.  A board found at f with period p repeats from f - p on, so it
+        leaves the search at the end of the launch it is found in, makes (turns still to come) mod p
+        turns and is then in its state of turn t0 + turns.  made=True also returns int64[n], the turns
+        each board computed (see gol_batch_run_cycles in golhip.h for its exact value).  The host
+        reads two counts back after every launch; when most boards are never found, step_cycles is
+        the cheaper call."""
+        found = np.full(self.n, -1, dtype=np.int64)
+        period = np.full(self.n, -1, dtype=np.int64)
+        work = np.zeros(self.n, dtype=np.int64) if made else None
+        self._check(self._L.gol_batch_run_cycles(self._h, turns, found.ctypes.data, period.ctypes.data,
+                                                 work.ctypes.data if made else None))
+        return (found, period, work) if made else (found, period)
+
     @property
     def turn(self) -> int:
         t = ctypes.c_int64()

@@ -572,8 +572,38 @@ int gol_bounds_host(int32_t layout, const void *board, int64_t pitch, int64_t W,
  *    turn, not the settle turn: step(..., settled) stays the exact scan for
  *    periods <= 2.  found and period are int64_t[n]; found must not be NULL,
  *    period may be.  The scan is per call (a second call starts again from its
- *    own t0), there is no early exit, turns == 0 leaves every board at -1, and
- *    rules per board apply.
+ *    own t0), there is no early exit here (run_cycles has it), turns == 0
+ *    leaves every board at -1, and rules per board apply.
+ *  - run_cycles: step_cycles with the boards retired as they are found.  After
+ *    the call the boards, found, period, the turn counter and the rules are
+ *    exactly what step_cycles(b, turns, found, period) leaves, for every board,
+ *    one rule or a rule per board, every turns >= 0 and every
+ *    turns_per_launch; only the work differs.  A board found at f with period p
+ *    has s(t + p) == s(t) for every t >= f - p, so its state at the call's end
+ *    t_end is its state at any turn t_L >= f advanced by (t_end - t_L) mod p
+ *    turns.  The search runs in launches over a list of the boards not yet
+ *    found; after each launch a retire pass on the GPU takes the boards just
+ *    found off that list and gives each its remainder, which later launches
+ *    make (boards of one workgroup make different numbers of turns).  made is
+ *    optional (int64_t[n], may be NULL; period may be NULL as in step_cycles):
+ *    the turns each board actually computed.  With t0 the turn before the call
+ *    and a batch created with turns_per_launch = L > 0, the search runs in
+ *    launches of L turns, the last one shorter; a board found at f leaves after
+ *    the first launch that ends at t_L >= f, t_L = t0 + min(turns, L *
+ *    ceil((f - t0) / L)), and made = (t_L - t0) + ((t0 + turns - t_L) mod
+ *    period); a board never found has made = turns.  With the automatic length
+ *    (turns_per_launch 0) each launch's bound is recomputed from the boards
+ *    still in it (2^35 cell-updates / (active * H * W), clamped to 1..4096), and
+ *    made is only known to be <= turns, and >= found - t0 where found.  The
+ *    search ends when no board is left in it or turns are made.  The host
+ *    reads the two list counts back after every launch, to size the next grid
+ *    and to stop: one small blocking read per launch, where step_cycles blocks
+ *    once per call.  On a batch in which nothing is ever found the lists, the
+ *    pass and the reads are pure overhead (DESIGN.md 4.17 has the measured
+ *    points): a caller who knows that most boards outlive the horizon should
+ *    prefer step_cycles.  Refusals as step_cycles (NULL handle, NULL found,
+ *    turns < 0), the batch and the outputs untouched; turns == 0 gives found
+ *    -1, period -1, made 0.
  *  - alive_counts / hashes: one uint64 per board, cap >= n; the hash of board i
  *    is oracle_hash_words(words_i, 0, H, Ww) (gol_engine_hash's definition on
  *    the board's zero-padded words, for every W).
@@ -597,6 +627,7 @@ int gol_batch_store_words(gol_batch *b, int64_t i0, int64_t i1, uint64_t *words,
 int gol_batch_load_random(gol_batch *b, uint64_t seed);
 int gol_batch_step(gol_batch *b, int64_t turns, int64_t *settled);
 int gol_batch_step_cycles(gol_batch *b, int64_t turns, int64_t *found, int64_t *period);
+int gol_batch_run_cycles(gol_batch *b, int64_t turns, int64_t *found, int64_t *period, int64_t *made);
 int gol_batch_turn(gol_batch *b, int64_t *turn);
 int gol_batch_alive_counts(gol_batch *b, uint64_t *counts, int64_t cap);
 int gol_batch_hashes(gol_batch *b, uint64_t *hashes, int64_t cap);
@@ -617,6 +648,17 @@ int gol_batch_step_host(int64_t H, int64_t W, uint32_t birth, uint32_t survive, 
  * turns < 0 or a NULL found. */
 int gol_batch_cycles_host(int64_t H, int64_t W, uint32_t birth, uint32_t survive, const uint64_t *in, uint64_t *out,
                           int64_t row_stride, int64_t turns, int64_t *found, int64_t *period);
+/* The scheme of gol_batch_run_cycles on one board in host memory (a host
+ * function, no GPU needed), t0 = 0: the search in launches of `launch` >= 1
+ * turns with the turn and the mark arithmetic of gol_batch_cycles_host, the
+ * board retired at the end of the launch it is found in, and its remainder from
+ * the function the retire pass runs (csrc/gol_batch.h).  `out`, *found and
+ * *period are those of gol_batch_cycles_host; *made (may be NULL, as period)
+ * = the turns computed, by the formula above.  GOL_EINVAL as there, and for
+ * launch < 1. */
+int gol_batch_run_cycles_host(int64_t H, int64_t W, uint32_t birth, uint32_t survive, const uint64_t *in, uint64_t *out,
+                              int64_t row_stride, int64_t turns, int64_t launch, int64_t *found, int64_t *period,
+                              int64_t *made);
 
 /* ---------------------------------------------------------------- plans
  * The schedule of a sharded step as data (host functions, no GPU needed).  The
@@ -858,6 +900,21 @@ int gol_band_max_k(int32_t cells_per_lane);
  * != 0: standard -> band), out of place; Wd % 32 == 0 (W % 1024 == 0). */
 int gol_dev_band_convert(int32_t to_band, const uint32_t *src, uint32_t *dst, int64_t rows, int64_t Wd,
                          int64_t src_pitch, int64_t dst_pitch, void *stream);
+/* The retire pass of gol_batch_run_cycles on caller device memory (one
+ * workgroup; stable and deterministic; no version bump: probe by symbol).
+ * counts is int32_t[2] in device memory, read and written: counts[0] the entries
+ * of list_in on entry and of active on return, counts[1] those of finish on
+ * entry and on return.  Boards are numbers in 0..n-1, 1 <= n <= 2^20 (an entry
+ * outside is dropped); found and left are int64_t[n], indexed by board.  First
+ * finish loses, in place, every board whose left[] is 0.  Then, in the order of
+ * list_in: a board with found[] < 0 goes to active (which may be list_in
+ * itself); a board found gets left[] = (t_end - t_now) mod (found - the last
+ * mark before found, the marks t0 + 2^j - 1) and, unless that is 0, goes to the
+ * end of finish, which must hold n entries.  Entries past the two new counts
+ * and left[] of boards not in list_in are not written.  GOL_EINVAL: NULL, n out
+ * of range, or not 0 <= t0 <= t_now <= t_end. */
+int gol_dev_batch_retire(const int32_t *list_in, int32_t *counts, const int64_t *found, int64_t n, int64_t t0,
+                         int64_t t_now, int64_t t_end, int32_t *active, int32_t *finish, int64_t *left, void *stream);
 /* Read and clear the error word of `device` (-1 = current) that the gol_dev_*
  * launchers' kernels report into (*flags = 0: no fault; nonzero: a pipeline
  * wave timed out waiting for its neighbour, so the launch's output is not
