@@ -12,6 +12,8 @@
 // `batch_check run`: gol_batch_run_cycles_host (the retiring scheme of gol_batch_run_cycles on one board) against
 // gol_batch_cycles_host over a grid of shapes, turns and launch lengths, on the same kind of buffers: found, period and
 // the final board equal, and made the formula of golhip.h written out here.
+// `batch_check search`: gol_batch_soup_host and gol_batch_search_host (the scheme of gol_batch_search) on buffers of exact size
+// against a scan of every soup written here, over shapes, rules, slot counts and launch lengths; its splitmix64 is its own.
 #include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -293,12 +295,121 @@ static int main_run()
     return bad ? 1 : 0;
 }
 
+static uint64_t mix(uint64_t x)  // splitmix64, written out here
+{
+    uint64_t z = x + 0x9E3779B97F4A7C15ULL;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
+    return z ^ (z >> 31);
+}
+
+// one call of gol_batch_search_host on result arrays of exact size, against a scan of every soup written here: all states
+// kept, the marks a list, the census of the state at the found turn
+static int check_search(int64_t H, int64_t W, uint32_t birth, uint32_t survive, uint64_t seed, int64_t first, int64_t total,
+                        int64_t slots, int64_t launch, int64_t horizon, int nulls)
+{
+    const int64_t Ww = (W + 63) / 64, bw = H * Ww;
+    const uint64_t tail = W % 64 ? ((uint64_t)1 << (W % 64)) - 1 : ~(uint64_t)0;
+    int64_t *found = new int64_t[(size_t)total], *period = new int64_t[(size_t)total];
+    uint64_t *alive = new uint64_t[(size_t)total], *hash = new uint64_t[(size_t)total];
+    for (int64_t g = 0; g < total; ++g) found[g] = period[g] = 77, alive[g] = hash[g] = 77;
+    int rc = gol_batch_search_host(H, W, birth, survive, seed, first, total, slots, launch, horizon, found,
+                                   nulls & 1 ? nullptr : period, nulls & 2 ? nullptr : alive, nulls & 4 ? nullptr : hash);
+    int bad = rc != GOL_OK;
+    std::vector<int64_t> marks;
+    for (int64_t m = 0; m <= horizon; m = 2 * m + 1) marks.push_back(m);
+    for (int64_t g = 0; g < total && !bad; ++g) {
+        uint64_t *soup = new uint64_t[(size_t)bw];  // exact size: a write past the soup is a report
+        rc = gol_batch_soup_host(H, W, seed, first + g, soup, Ww);
+        for (int64_t y = 0; y < H; ++y)
+            for (int64_t w = 0; w < Ww; ++w) {
+                const uint64_t v = mix(seed ^ (uint64_t)(((first + g) * H + y) * Ww + w)) & (w == Ww - 1 ? tail : ~(uint64_t)0);
+                if (soup[y * Ww + w] != v) bad = 1;
+            }
+        std::vector<std::vector<uint64_t>> st(1, std::vector<uint64_t>(soup, soup + bw));
+        delete[] soup;
+        int64_t wf = -1, wp = -1;
+        uint64_t wa = 0, wh = 0;
+        for (int64_t d = 1; d <= horizon && wf < 0; ++d) {
+            st.push_back(st[0]);
+            naive(H, W, birth, survive, st[(size_t)d - 1].data(), st[(size_t)d].data(), Ww);
+            int64_t m = 0;
+            for (int64_t v : marks)
+                if (v < d) m = v;
+            if (st[(size_t)d] == st[(size_t)m]) wf = d, wp = d - m;
+        }
+        if (wf >= 0)
+            for (int64_t i = 0; i < bw; ++i) {
+                wa += (uint64_t)__builtin_popcountll(st[(size_t)wf][(size_t)i]);
+                wh += mix(st[(size_t)wf][(size_t)i] ^ mix((uint64_t)i));
+            }
+        if (rc != GOL_OK || found[g] != wf || period[g] != (nulls & 1 ? 77 : wp) || alive[g] != (nulls & 2 ? 77 : wa) ||
+            hash[g] != (nulls & 4 ? 77 : wh)) {
+            printf("search %lldx%lld B 0x%x S 0x%x soup %lld of [%lld, +%lld) slots %lld launch %lld horizon %lld: rc %d, found "
+                   "%lld (%lld), period %lld (%lld), alive %llu (%llu)\n",
+                   (long long)H, (long long)W, birth, survive, (long long)g, (long long)first, (long long)total, (long long)slots,
+                   (long long)launch, (long long)horizon, rc, (long long)found[g], (long long)wf, (long long)period[g],
+                   (long long)wp, (unsigned long long)alive[g], (unsigned long long)wa);
+            bad = 1;
+        }
+    }
+    delete[] found;
+    delete[] period;
+    delete[] alive;
+    delete[] hash;
+    return bad;
+}
+
+static int main_search()
+{
+    int bad = 0, n = 0;
+    static const int shapes[][2] = {{1, 1}, {2, 5}, {16, 16}, {7, 33}, {5, 65}, {65, 31}, {3, 481}};
+    static const uint32_t rules[][2] = {{0x008, 0x00C}, {0x048, 0x00C}, {0x000, 0x00C}, {0x0AA, 0x0AA}};
+    static const int64_t slots[] = {1, 3}, launches[] = {1, 7, 64, 200};
+    for (const auto &s : shapes)
+        for (const auto &r : rules)
+            for (int64_t k : slots)
+                for (int64_t l : launches) {
+                    bad += check_search(s[0], s[1], r[0], r[1], 1 + (uint64_t)n, n % 5 ? 0 : 1000003, 7, k, l, 70, n % 8);
+                    ++n;
+                }
+    for (int64_t l : launches) {  // the overshoot (16 x 16, seed 1: soups found at 256 and at 257), no soup, no turn
+        n += 3;
+        bad += check_search(16, 16, 0x008, 0x00C, 1, 0, 12, 5, l, 256, 0);
+        bad += check_search(16, 16, 0x008, 0x00C, 1, 0, 0, 5, l, 70, 0);
+        bad += check_search(16, 16, 0x008, 0x00C, 1, ((int64_t)1 << 40) - 3, 3, 5, l, 0, 0);
+    }
+    int64_t f[2] = {77, 77};
+    uint64_t w[8] = {0};
+    const int einval[] = {gol_batch_search_host(0, 8, 8, 12, 1, 0, 2, 1, 1, 5, f, f, w, w),
+                          gol_batch_search_host(8, 513, 8, 12, 1, 0, 2, 1, 1, 5, f, f, w, w),
+                          gol_batch_search_host(8, 8, 512, 12, 1, 0, 2, 1, 1, 5, f, f, w, w),
+                          gol_batch_search_host(8, 8, 8, 12, 1, -1, 2, 1, 1, 5, f, f, w, w),
+                          gol_batch_search_host(8, 8, 8, 12, 1, 0, -1, 1, 1, 5, f, f, w, w),
+                          gol_batch_search_host(8, 8, 8, 12, 1, 0, 2, 0, 1, 5, f, f, w, w),
+                          gol_batch_search_host(8, 8, 8, 12, 1, 0, 2, 1, 0, 5, f, f, w, w),
+                          gol_batch_search_host(8, 8, 8, 12, 1, 0, 2, 1, 1, -1, f, f, w, w),
+                          gol_batch_search_host(8, 8, 8, 12, 1, ((int64_t)1 << 40) - 1, 2, 1, 1, 5, f, f, w, w),
+                          gol_batch_search_host(8, 8, 8, 12, 1, 0, ((int64_t)1 << 26) + 1, 1, 1, 5, f, f, w, w),
+                          gol_batch_search_host(8, 8, 8, 12, 1, 0, 2, 1, 1, 5, nullptr, f, w, w),
+                          gol_batch_soup_host(8, 8, 1, -1, w, 1), gol_batch_soup_host(8, 65, 1, 0, w, 1),
+                          gol_batch_soup_host(8, 8, 1, 0, nullptr, 1)};
+    for (int rc : einval)
+        if (rc != GOL_EINVAL || f[0] != 77 || f[1] != 77 || w[0]) {
+            printf("a bad argument returned %d\n", rc);
+            ++bad;
+        }
+    printf("batch_check search: %d cases, %d bad\n", n, bad);
+    return bad ? 1 : 0;
+}
+
 int main(int argc, char **argv)
 {
     if (argc > 1) {
         if (!strcmp(argv[1], "cycles")) return main_cycles();
         if (!strcmp(argv[1], "run")) return main_run();
-        printf("usage: batch_check [cycles | run]\n");
+        if (!strcmp(argv[1], "search")) return main_search();
+        printf("usage: batch_check [cycles | run | search]\n");
         return 2;
     }
     static const int shapes[][2] = {{1, 1}, {1, 2}, {2, 1}, {2, 2}, {3, 3}, {2, 5}, {5, 2}, {16, 16}, {7, 31}, {7, 32}, {7, 33},

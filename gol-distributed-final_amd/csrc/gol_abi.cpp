@@ -277,6 +277,18 @@ extern "C" int gol_dev_batch_retire(const int32_t *list_in, int32_t *counts, con
     LAUNCH(golk_batch_retire(list_in, counts, found, n, t0, t_now, t_end, active, finish, left, (hipStream_t)stream));
 }
 
+extern "C" int gol_dev_batch_restock(int32_t *active, int32_t *counts, int64_t *found_age, int64_t *born, int32_t *soup, int64_t n,
+                                     int64_t now, int64_t horizon, int64_t total, int64_t *out_found, int64_t *out_period,
+                                     int32_t *harvest, void *stream)
+{
+    if (!active || !counts || !found_age || !born || !soup || !out_found || !out_period || !harvest || n < 1 ||
+        n > ((int64_t)1 << 20) || now < 0 || horizon < 0 || total < 0 || total > ((int64_t)1 << 26))
+        return gol_set_error(GOL_EINVAL, "bad batch_restock arguments (n %lld, now %lld, horizon %lld, total %lld, or NULL)",
+                             (long long)n, (long long)now, (long long)horizon, (long long)total);
+    LAUNCH(golk_batch_restock(active, counts, found_age, born, soup, n, now, horizon, total, out_found, out_period, harvest,
+                              (hipStream_t)stream));
+}
+
 extern "C" int gol_dev_error(int32_t device, uint32_t *flags)
 {
     if (!flags) return gol_set_error(GOL_EINVAL, "flags is NULL");

@@ -53,6 +53,33 @@ GOL_BATCH_HD int64_t gol_batch_last_mark(int64_t d)  // d >= 1: the largest mark
 // come, its state at the call's end is its state now advanced by rest mod p turns: the turns it still has to make.
 GOL_BATCH_HD int64_t gol_batch_turns_left(int64_t d, int64_t rest) { return rest % (d - gol_batch_last_mark(d)); }
 
+// Soups (gol_batch_load_soups, gol_batch_search): word (y, w) of soup g of (seed, H, Ww) is splitmix64(seed ^ ((g H + y) Ww
+// + w)), the padding of a row's last word cleared with `tail`: board g of gol_batch_load_random on a batch that holds it.
+// i = (g H + y) Ww + w is the word's index in the supply; the fill kernels and gol_batch_soup_host run this function.
+GOL_BATCH_HD uint64_t gol_batch_splitmix64(uint64_t x)
+{
+    uint64_t z = x + 0x9E3779B97F4A7C15ULL;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
+    return z ^ (z >> 31);
+}
+
+GOL_BATCH_HD uint64_t gol_batch_soup_word(uint64_t seed, uint64_t i, int64_t Ww, uint64_t tail)
+{
+    const uint64_t v = gol_batch_splitmix64(seed ^ i);
+    return i % (uint64_t)Ww == (uint64_t)Ww - 1 ? v & tail : v;
+}
+
+// The search's verdict on a slot at a launch boundary (the restock pass, gol_batch_search_host): its soup is `age` turns old,
+// the scan found it at the age `found` (< 0: not yet), and the search looks `horizon` turns far.  A soup found after the
+// horizon, in a launch that ran past it, is not a find.
+enum { GOL_BATCH_STAY = 0, GOL_BATCH_FOUND = 1, GOL_BATCH_EXPIRED = 2 };
+GOL_BATCH_HD int gol_batch_verdict(int64_t found, int64_t age, int64_t horizon)
+{
+    if (found >= 0) return found <= horizon ? GOL_BATCH_FOUND : GOL_BATCH_EXPIRED;
+    return age >= horizon ? GOL_BATCH_EXPIRED : GOL_BATCH_STAY;
+}
+
 // The shape of a row: nwr words in use of nw held, the last cell's bit and the mask of the last word.
 struct gol_batch_row {
     int32_t nwr, nw;

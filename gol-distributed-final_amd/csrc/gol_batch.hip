@@ -1,7 +1,7 @@
 // gol_batch.hip -- many small tori (1 <= H, W <= 512) stepped in one launch (include/golhip.h,
 // "batches of small boards"; the row function is gol_batch.h).
 //
-// batch_step_kernel<NW, RULE, SCAN, LIST>: a board never leaves its workgroup during a launch.  One
+// batch_step_kernel<NW, RULE, SCAN, LIST, AGED>: a board never leaves its workgroup during a launch.  One
 // row per lane, NW = 1, 2, 4, 8 or 16 words of it in registers, ceil(H / 64) waves per board; boards
 // of up to 128 rows share a workgroup (4 boards of one wave, 2 of two).  The board is read from HBM
 // once, stepped `turns` times and written once, in place: no HBM traffic between the turns.
@@ -29,12 +29,19 @@
 // the finish: every listed board has its own number of turns still to make (left[board]), the workgroup's loop
 // makes the most any of its boards needs (at most the launch's turns; uniform, since every wave runs every
 // barrier), a wave whose board has made its turns keeps its cells, and the turns made are taken off left[].
+// AGED (gol_batch_search; LIST + cycles, B3/S23 or the one-rule table): the listed boards are slots that hold soups of
+// different ages.  born[board] is the call's turn count at the launch boundary where the slot was filled, read by a scalar
+// load like the list entry; with age = done - born the mark test is per board (gol_batch_is_mark(age + it + 1)), age 0 is the
+// board's first launch (the loaded state is the snapshot, prev is not read), and settled[board] receives the age at which
+// the board is found.  Once found is known -- uniform over the board's waves, before the iteration's snapshot update --
+// the snapshot is no longer replaced, so prev[board] holds s(found) after the launch for the harvest.
 // Synchronisation is __syncthreads() alone: no workgroup waits for another one, there is no flag
 // between workgroups, no spin loop and no atomic.  Every wave of a workgroup runs every barrier (a
 // wave whose board is past the batch's end computes on zeros and stores nothing).
 //
 // The small kernels: random fill, one wave per board for the alive count and the hash, and for
-// gol_batch_run_cycles the identity list and the retire pass between its launches (one workgroup).
+// gol_batch_run_cycles the identity list and the retire pass between its launches (one workgroup); for gol_batch_search
+// the soup fills, the restock pass (one workgroup) and the harvest.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -61,6 +68,8 @@ struct BatchArgs {
     // LIST: the board of slot i of the grid is list[i], i < *count (a slot past the count has no board)
     const int32_t *list, *count;
     int64_t *left;  // LIST without a scan (the finish): per board the turns it still has to make, taken off here
+    // AGED (gol_batch_search): per board the call's turn count `done` of the launch before which it was filled
+    const int64_t *born;
 };
 
 template <int NW>
@@ -81,7 +90,7 @@ __device__ __forceinline__ void store_row(uint64_t *row, int32_t Ww, const uint3
         if (j < 2 * Ww) p[j] = j < NW ? c[j < NW ? j : 0] : 0u;
 }
 
-template <int NW, int RULE, int SCAN, bool LIST>
+template <int NW, int RULE, int SCAN, bool LIST, bool AGED>
 __global__ __launch_bounds__(512) void batch_step_kernel(const BatchArgs a)
 {
     // [buffer][wave][first / last row of the wave][h0 / h1][word]
@@ -96,6 +105,7 @@ __global__ __launch_bounds__(512) void batch_step_kernel(const BatchArgs a)
     bool has = board < a.n;
     int trips = a.turns, my = a.turns;  // the turns of the workgroup's loop; of them, those this wave's board makes
     int64_t left = 0;
+    int64_t age = a.done;  // (uniform) the turns of the scan before this launch: the call's, AGED the board's own
     if (LIST) {
         const uint32_t count = (uint32_t)*a.count;
         const uint32_t slot = __builtin_amdgcn_readfirstlane((uint32_t)(blockIdx.x * a.bpw + lb));
@@ -108,7 +118,9 @@ __global__ __launch_bounds__(512) void batch_step_kernel(const BatchArgs a)
             left = has ? a.left[board] : 0;
             my = (int)min((int64_t)a.turns, left);
         }
+        if (AGED) age = a.done - (has ? a.born[board] : 0);
     }
+    const bool have_prev = AGED ? age > 0 : a.have_prev != 0;  // AGED: a board's first launch has no snapshot to read
     const int y = w * 64 + lane;
     const int last = min(63, a.H - 1 - w * 64);  // the wave's last lane with a row
     const bool on = has && y < a.H;
@@ -129,8 +141,8 @@ __global__ __launch_bounds__(512) void batch_step_kernel(const BatchArgs a)
     const int64_t off = (board * a.H + y) * a.Ww;
     uint32_t cur[NW], old[NW];  // state(t - 1) and, SCAN, state(t - 2) or the snapshot
     load_row<NW>(a.boards + (on ? off : 0), a.Ww, on, cur);
-    if (SCAN) load_row<NW>(a.prev + (on && a.have_prev ? off : 0), a.Ww, on && a.have_prev, old);
-    if (SCAN == GOL_BATCH_SCAN_CYCLES && !a.have_prev) {  // the call's first launch: the mark d = 0
+    if (SCAN) load_row<NW>(a.prev + (on && have_prev ? off : 0), a.Ww, on && have_prev, old);
+    if (SCAN == GOL_BATCH_SCAN_CYCLES && !have_prev) {  // the call's first launch: the mark d = 0
 #pragma unroll
         for (int j = 0; j < NW; ++j) old[j] = cur[j];
     }
@@ -157,7 +169,7 @@ __global__ __launch_bounds__(512) void batch_step_kernel(const BatchArgs a)
         if (posted && found < 0) {
             bool any = false;
             for (int i = 0; i < a.wpb; ++i) any |= differs[buf][lb * a.wpb + i] != 0;
-            if (!any) found = a.turn0 + it;
+            if (!any) found = (AGED ? age : a.turn0) + it;
         }
 #pragma unroll
         for (int j = 0; j < NW; ++j) {
@@ -177,7 +189,8 @@ __global__ __launch_bounds__(512) void batch_step_kernel(const BatchArgs a)
         gol_batch_next<NW, RULE != GOL_BATCH_RULE_CONWAY>(tab, g, a0, a1, b0, b1, d0, d1, cur, msk, next);
         if (SCAN) {
             // (uniform) cycles: the turn just computed is a mark, its state the snapshot from now on
-            const bool keep = SCAN == GOL_BATCH_SCAN_CYCLES && !gol_batch_is_mark(a.done + it + 1);
+            // AGED: the board's own age counts, and once it is found its snapshot stays: s(found) for the harvest
+            const bool keep = SCAN == GOL_BATCH_SCAN_CYCLES && (!gol_batch_is_mark(age + it + 1) || (AGED && found >= 0));
             uint32_t d = 0;
 #pragma unroll
             for (int j = 0; j < NW; ++j) {
@@ -197,7 +210,7 @@ __global__ __launch_bounds__(512) void batch_step_kernel(const BatchArgs a)
         if (found < 0) {
             bool any = false;
             for (int i = 0; i < a.wpb; ++i) any |= differs[buf][lb * a.wpb + i] != 0;
-            if (!any) found = a.turn0 + a.turns;
+            if (!any) found = (AGED ? age : a.turn0) + a.turns;
         }
     }
     if (on) {
@@ -333,25 +346,216 @@ __global__ __launch_bounds__(1024) void batch_retire_kernel(const int32_t *list_
     if (threadIdx.x == 0) counts[0] = n_act, counts[1] = n_fin;
 }
 
+// ---- gol_batch_search: soups streamed through the batch's slots (a slot is a board of the batch)
+
+// boards[i] = word i0 + i of the supply (seed): gol_batch_load_soups and the search's first fill, soup first + j in slot j
+__global__ __launch_bounds__(256) void batch_soups_kernel(uint64_t *boards, int64_t words, int32_t Ww, uint64_t tail,
+                                                          uint64_t seed, uint64_t i0)
+{
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < words; i += (int64_t)gridDim.x * 256)
+        boards[i] = gol_batch_soup_word(seed, i0 + (uint64_t)i, Ww, tail);
+}
+
+// The search's start: slot i < m active with soup i, born at 0 and not found.  counts: [0] the active slots, [1] the slots
+// the last pass harvested, [2] those of them it refilled, [3] the soups handed out so far.
+__global__ __launch_bounds__(256) void batch_search_init_kernel(int32_t *active, int32_t *counts, int32_t *soup, int64_t *born,
+                                                                int64_t *found, int32_t m)
+{
+    for (int32_t i = blockIdx.x * 256 + threadIdx.x; i < m; i += gridDim.x * 256) {
+        active[i] = i;
+        soup[i] = i;
+        born[i] = 0;
+        found[i] = -1;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) counts[0] = m, counts[1] = 0, counts[2] = 0, counts[3] = m;
+}
+
+// The places of a tile's flagged entries, in the tile's order (as the retire pass has them: a ballot per wave and item, the
+// tile's RETIRE_COUNTS wave counts scanned by wave 0 through LDS); returns how many are flagged.  Every thread calls it.
+__device__ __forceinline__ int32_t tile_places(const bool (&flag)[RETIRE_ITEMS], int32_t (&place)[RETIRE_ITEMS], int32_t *cnt,
+                                               int32_t *off, int32_t *total)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < RETIRE_ITEMS; ++k) {
+        const uint64_t b = __ballot(flag[k]);
+        place[k] = __popcll(b & (((uint64_t)1 << lane) - 1));
+        if (lane == 0) cnt[k * 16 + wave] = __popcll(b);
+    }
+    __syncthreads();
+    if (wave == 0) {
+        int32_t c[RETIRE_COUNTS / 64], sum = 0;
+#pragma unroll
+        for (int j = 0; j < RETIRE_COUNTS / 64; ++j) sum += c[j] = cnt[lane * (RETIRE_COUNTS / 64) + j];
+        int32_t incl = sum;
+        for (int d = 1; d < 64; d *= 2) {
+            const int32_t up = __shfl_up(incl, d);
+            if (lane >= d) incl += up;
+        }
+        int32_t at = incl - sum;
+#pragma unroll
+        for (int j = 0; j < RETIRE_COUNTS / 64; ++j) {
+            off[lane * (RETIRE_COUNTS / 64) + j] = at;
+            at += c[j];
+        }
+        if (lane == 63) *total = incl;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < RETIRE_ITEMS; ++k) place[k] += off[k * 16 + wave];
+    const int32_t t = *total;
+    __syncthreads();  // cnt, off and total are free again
+    return t;
+}
+
+// The restock pass between the launches of gol_batch_search: one workgroup walks the active list in tiles of RETIRE_TILE
+// slots, in order.  gol_batch_verdict decides from a slot's found age, its age now - born[slot] and the horizon.  A slot that
+// is done (found or expired) writes found and period of its soup (-1, -1 when expired) and goes on the harvest list as the
+// pair (slot, soup), in the list's order; the r-th done slot of the pass takes soup next + r while that is below total
+// (born = now, found = -1, it stays active), else it leaves the active list.  So the slots refilled are the first counts[2]
+// entries of the harvest list, which is the fill list too.  The active list is compacted in place (an entry is written at
+// or before the place it was read from; a tile is read before a barrier and written after it); stable, the same on every
+// run.  A slot outside 0 .. n - 1 is dropped, a soup outside 0 .. total - 1 writes no result.
+__global__ __launch_bounds__(1024) void batch_restock_kernel(int32_t *active, int32_t *counts, int64_t *found, int64_t *born,
+                                                             int32_t *soup, int64_t n, int64_t now, int64_t horizon,
+                                                             int32_t total, int64_t *out_found, int64_t *out_period,
+                                                             int32_t *harvest)
+{
+    __shared__ int32_t cnt[RETIRE_COUNTS], off[RETIRE_COUNTS], sum;
+    const int64_t cap = n < ((int64_t)1 << 20) ? n : (int64_t)1 << 20;
+    const int32_t n_in = (int32_t)max((int64_t)0, min((int64_t)counts[0], cap));
+    const int32_t next = max(0, min(counts[3], total));  // the soups handed out before this pass
+    int32_t n_act = 0, n_done = 0;                       // (uniform) entries written so far
+    for (int32_t base = 0; base < n_in; base += RETIRE_TILE) {
+        int32_t slot[RETIRE_ITEMS], place[RETIRE_ITEMS];
+        int64_t f[RETIRE_ITEMS], b[RETIRE_ITEMS];
+        bool hit[RETIRE_ITEMS], done[RETIRE_ITEMS], kept[RETIRE_ITEMS];
+        // the tile's loads first, each kind together, none behind a store
+#pragma unroll
+        for (int k = 0; k < RETIRE_ITEMS; ++k) {
+            const int32_t i = base + k * 1024 + (int32_t)threadIdx.x;
+            slot[k] = i < n_in ? active[i] : -1;
+            if (slot[k] >= n) slot[k] = -1;
+        }
+#pragma unroll
+        for (int k = 0; k < RETIRE_ITEMS; ++k) f[k] = slot[k] >= 0 ? found[slot[k]] : -1;
+#pragma unroll
+        for (int k = 0; k < RETIRE_ITEMS; ++k) b[k] = slot[k] >= 0 ? born[slot[k]] : 0;
+#pragma unroll
+        for (int k = 0; k < RETIRE_ITEMS; ++k) {
+            const int v = slot[k] >= 0 ? gol_batch_verdict(f[k], now - b[k], horizon) : GOL_BATCH_STAY;
+            hit[k] = v == GOL_BATCH_FOUND;
+            done[k] = v != GOL_BATCH_STAY;
+        }
+        const int32_t tile_done = tile_places(done, place, cnt, off, &sum);
+#pragma unroll
+        for (int k = 0; k < RETIRE_ITEMS; ++k) {
+            kept[k] = slot[k] >= 0 && !done[k];
+            if (!done[k]) continue;
+            const int32_t r = n_done + place[k];  // < n_in <= n: the harvest list holds n pairs
+            int32_t g = soup[slot[k]];
+            if (g < 0 || g >= total) g = -1;
+            if (g >= 0) {
+                out_found[g] = hit[k] ? f[k] : -1;
+                out_period[g] = hit[k] ? f[k] - gol_batch_last_mark(f[k]) : -1;
+            }
+            harvest[2 * r] = slot[k];
+            harvest[2 * r + 1] = g;
+            if (r < total - next) {
+                soup[slot[k]] = next + r;
+                born[slot[k]] = now;
+                found[slot[k]] = -1;
+                kept[k] = true;
+            }
+        }
+        const int32_t tile_kept = tile_places(kept, place, cnt, off, &sum);
+#pragma unroll
+        for (int k = 0; k < RETIRE_ITEMS; ++k)
+            if (kept[k]) active[n_act + place[k]] = slot[k];
+        n_act += tile_kept;
+        n_done += tile_done;
+        __syncthreads();  // the tile is written before the next one is read
+    }
+    if (threadIdx.x == 0) {
+        const int32_t refilled = min(n_done, total - next);
+        counts[0] = n_act, counts[1] = n_done, counts[2] = refilled, counts[3] = next + refilled;
+    }
+}
+
+// The census of the slots the pass harvested, a wave per slot: prev[slot] holds s(found) of the soup the slot ran (the aged
+// step kernel keeps the snapshot once a board is found), and alive[soup], hash[soup] become its alive cells and its
+// oracle_hash_words (batch_reduce_kernel's sums); 0, 0 for a soup that expired.
+__global__ __launch_bounds__(256) void batch_harvest_kernel(const uint64_t *prev, const int32_t *harvest, const int32_t *counts,
+                                                            int64_t n, int32_t words, int32_t total, const int64_t *found,
+                                                            uint64_t *alive, uint64_t *hash)
+{
+    const int lane = threadIdx.x & 63;
+    const int32_t m = (int32_t)max((int64_t)0, min((int64_t)counts[1], n));
+    for (int32_t r = blockIdx.x * 4 + (threadIdx.x >> 6); r < m; r += gridDim.x * 4) {
+        const int32_t slot = harvest[2 * r], g = harvest[2 * r + 1];
+        if (slot < 0 || slot >= n || g < 0 || g >= total) continue;
+        uint64_t a = 0, h = 0;
+        if (found[g] >= 0) {
+            const uint64_t *p = prev + (int64_t)slot * words;
+            for (int i = lane; i < words; i += 64) {
+                a += (uint64_t)__popcll(p[i]);
+                h += golk::splitmix64(p[i] ^ golk::splitmix64((uint64_t)i));
+            }
+            a = golk::wave_sum_u64(a);
+            h = golk::wave_sum_u64(h);
+        }
+        if (lane == 0) alive[g] = a, hash[g] = h;
+    }
+}
+
+// The new soups of the slots the pass refilled (the first counts[2] pairs of the harvest list), soup[slot] the soup's number
+// from `first`: the words of batch_soups_kernel.
+__global__ __launch_bounds__(256) void batch_refill_kernel(uint64_t *boards, const int32_t *harvest, const int32_t *counts,
+                                                           const int32_t *soup, int64_t n, int32_t words, int32_t Ww,
+                                                           uint64_t tail, uint64_t seed, uint64_t first, int32_t total)
+{
+    const int64_t m = max((int64_t)0, min((int64_t)counts[2], n));
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < m * words; i += (int64_t)gridDim.x * 256) {
+        const int64_t r = i / words, k = i - r * words;
+        const int32_t slot = harvest[2 * r];
+        if (slot < 0 || slot >= n) continue;
+        const int32_t g = soup[slot];
+        if (g < 0 || g >= total) continue;
+        boards[(int64_t)slot * words + k] = gol_batch_soup_word(seed, (first + (uint64_t)g) * (uint64_t)words + (uint64_t)k, Ww, tail);
+    }
+}
+
 template <int NW, int RULE>
 hipError_t launch_scan(int scan, bool list, const BatchArgs &a, dim3 grid, dim3 block, hipStream_t s)
 {
     if (list && scan == GOL_BATCH_SCAN_CYCLES)
-        batch_step_kernel<NW, RULE, GOL_BATCH_SCAN_CYCLES, true><<<grid, block, 0, s>>>(a);
+        batch_step_kernel<NW, RULE, GOL_BATCH_SCAN_CYCLES, true, false><<<grid, block, 0, s>>>(a);
     else if (list)
-        batch_step_kernel<NW, RULE, GOL_BATCH_SCAN_NONE, true><<<grid, block, 0, s>>>(a);
+        batch_step_kernel<NW, RULE, GOL_BATCH_SCAN_NONE, true, false><<<grid, block, 0, s>>>(a);
     else if (scan == GOL_BATCH_SCAN_CYCLES)
-        batch_step_kernel<NW, RULE, GOL_BATCH_SCAN_CYCLES, false><<<grid, block, 0, s>>>(a);
+        batch_step_kernel<NW, RULE, GOL_BATCH_SCAN_CYCLES, false, false><<<grid, block, 0, s>>>(a);
     else if (scan == GOL_BATCH_SCAN_SETTLE)
-        batch_step_kernel<NW, RULE, GOL_BATCH_SCAN_SETTLE, false><<<grid, block, 0, s>>>(a);
+        batch_step_kernel<NW, RULE, GOL_BATCH_SCAN_SETTLE, false, false><<<grid, block, 0, s>>>(a);
     else
-        batch_step_kernel<NW, RULE, GOL_BATCH_SCAN_NONE, false><<<grid, block, 0, s>>>(a);
+        batch_step_kernel<NW, RULE, GOL_BATCH_SCAN_NONE, false, false><<<grid, block, 0, s>>>(a);
+    return hipGetLastError();
+}
+
+// the aged search of gol_batch_search: one rule for the batch (a rule per soup is not built)
+template <int NW>
+hipError_t launch_aged(int rule, const BatchArgs &a, dim3 grid, dim3 block, hipStream_t s)
+{
+    if (rule == GOL_BATCH_RULE_TABLE)
+        batch_step_kernel<NW, GOL_BATCH_RULE_TABLE, GOL_BATCH_SCAN_CYCLES, true, true><<<grid, block, 0, s>>>(a);
+    else
+        batch_step_kernel<NW, GOL_BATCH_RULE_CONWAY, GOL_BATCH_SCAN_CYCLES, true, true><<<grid, block, 0, s>>>(a);
     return hipGetLastError();
 }
 
 template <int NW>
 hipError_t launch_rule(int rule, int scan, bool list, const BatchArgs &a, dim3 grid, dim3 block, hipStream_t s)
 {
+    if (a.born) return rule == GOL_BATCH_RULE_EACH ? hipErrorInvalidValue : launch_aged<NW>(rule, a, grid, block, s);
     if (rule == GOL_BATCH_RULE_EACH) return launch_scan<NW, GOL_BATCH_RULE_EACH>(scan, list, a, grid, block, s);
     if (rule == GOL_BATCH_RULE_TABLE) return launch_scan<NW, GOL_BATCH_RULE_TABLE>(scan, list, a, grid, block, s);
     return launch_scan<NW, GOL_BATCH_RULE_CONWAY>(scan, list, a, grid, block, s);
@@ -371,7 +575,7 @@ void golk_batch_shape(int64_t H, int64_t W, int *waves_per_board, int *boards_pe
 static hipError_t batch_launch(uint64_t *boards, uint64_t *prev, int64_t *settled, int64_t n, int64_t H, int64_t W, int turns,
                                int64_t turn0, bool have_prev, bool write_prev, uint32_t birth, uint32_t survive,
                                const uint32_t *rules, int scan, int64_t done, const int32_t *list, const int32_t *count,
-                               int64_t slots, int64_t *left, hipStream_t s)
+                               int64_t slots, int64_t *left, const int64_t *born, hipStream_t s)
 {
     if (!boards || n < 1 || n > ((int64_t)1 << 20) || H < 1 || H > GOL_BATCH_MAX_SIDE || W < 1 || W > GOL_BATCH_MAX_SIDE ||
         turns < 1 || birth >= 512 || survive >= 512 || (settled && !prev) || ((have_prev || write_prev) && !settled) ||
@@ -399,6 +603,7 @@ static hipError_t batch_launch(uint64_t *boards, uint64_t *prev, int64_t *settle
     a.list = list;
     a.count = count;
     a.left = left;
+    a.born = born;
     const dim3 grid((unsigned)((slots + a.bpw - 1) / a.bpw)), block((unsigned)(a.bpw * a.wpb * 64));
     const int rule = rules                             ? GOL_BATCH_RULE_EACH
                      : gol_batch_conway(birth, survive) ? GOL_BATCH_RULE_CONWAY
@@ -417,7 +622,7 @@ hipError_t golk_batch_step(uint64_t *boards, uint64_t *prev, int64_t *settled, i
                            const uint32_t *rules, int scan, int64_t done, hipStream_t s)
 {
     return batch_launch(boards, prev, settled, n, H, W, turns, turn0, have_prev, write_prev, birth, survive, rules, scan, done,
-                        nullptr, nullptr, n, nullptr, s);
+                        nullptr, nullptr, n, nullptr, nullptr, s);
 }
 
 hipError_t golk_batch_step_list(uint64_t *boards, uint64_t *prev, int64_t *settled, int64_t n, int64_t H, int64_t W, int turns,
@@ -428,7 +633,16 @@ hipError_t golk_batch_step_list(uint64_t *boards, uint64_t *prev, int64_t *settl
     // the search (settled: the cycle scan of the listed boards) or the finish (left: each listed board's own turns)
     if (!list || !count || slots < 1 || slots > n || (settled != nullptr) == (left != nullptr)) return hipErrorInvalidValue;
     return batch_launch(boards, prev, settled, n, H, W, turns, turn0, have_prev, write_prev, birth, survive, rules,
-                        settled ? GOL_BATCH_SCAN_CYCLES : GOL_BATCH_SCAN_NONE, done, list, count, slots, left, s);
+                        settled ? GOL_BATCH_SCAN_CYCLES : GOL_BATCH_SCAN_NONE, done, list, count, slots, left, nullptr, s);
+}
+
+hipError_t golk_batch_step_aged(uint64_t *boards, uint64_t *prev, int64_t *found, const int64_t *born, int64_t n, int64_t H,
+                                int64_t W, int turns, uint32_t birth, uint32_t survive, int64_t done, const int32_t *list,
+                                const int32_t *count, int64_t slots, hipStream_t s)
+{
+    if (!list || !count || !found || !born || slots < 1 || slots > n) return hipErrorInvalidValue;
+    return batch_launch(boards, prev, found, n, H, W, turns, 0, done > 0, true, birth, survive, nullptr, GOL_BATCH_SCAN_CYCLES,
+                        done, list, count, slots, nullptr, born, s);
 }
 
 hipError_t golk_batch_iota(int32_t *list, int32_t *counts, int64_t n, hipStream_t s)
@@ -465,5 +679,67 @@ hipError_t golk_batch_reduce(bool hash, const uint64_t *boards, int64_t n, int64
     const unsigned grid = (unsigned)std::min<int64_t>((n + 3) / 4, 8192);
     if (hash) batch_reduce_kernel<true><<<grid, 256, 0, s>>>(boards, n, words, out);
     else batch_reduce_kernel<false><<<grid, 256, 0, s>>>(boards, n, words, out);
+    return hipGetLastError();
+}
+
+hipError_t golk_batch_soups(uint64_t *boards, int64_t n, int64_t H, int64_t W, uint64_t seed, int64_t first, hipStream_t s)
+{
+    if (!boards || n < 1 || H < 1 || H > GOL_BATCH_MAX_SIDE || W < 1 || W > GOL_BATCH_MAX_SIDE || first < 0 ||
+        first > ((int64_t)1 << 40))
+        return hipErrorInvalidValue;
+    const int64_t Ww = (W + 63) / 64, words = n * H * Ww;
+    const uint64_t tail = W % 64 ? ((uint64_t)1 << (W % 64)) - 1 : ~(uint64_t)0;
+    const unsigned grid = (unsigned)std::min<int64_t>((words + 255) / 256, 8192);
+    batch_soups_kernel<<<grid, 256, 0, s>>>(boards, words, (int32_t)Ww, tail, seed, (uint64_t)(first * H * Ww));
+    return hipGetLastError();
+}
+
+hipError_t golk_batch_search_init(int32_t *active, int32_t *counts, int32_t *soup, int64_t *born, int64_t *found, int64_t m,
+                                  hipStream_t s)
+{
+    if (!active || !counts || !soup || !born || !found || m < 1 || m > ((int64_t)1 << 20)) return hipErrorInvalidValue;
+    batch_search_init_kernel<<<(unsigned)std::min<int64_t>((m + 255) / 256, 1024), 256, 0, s>>>(active, counts, soup, born, found,
+                                                                                               (int32_t)m);
+    return hipGetLastError();
+}
+
+hipError_t golk_batch_restock(int32_t *active, int32_t *counts, int64_t *found, int64_t *born, int32_t *soup, int64_t n,
+                              int64_t now, int64_t horizon, int64_t total, int64_t *out_found, int64_t *out_period,
+                              int32_t *harvest, hipStream_t s)
+{
+    if (!active || !counts || !found || !born || !soup || !out_found || !out_period || !harvest || n < 1 ||
+        n > ((int64_t)1 << 20) || now < 0 || horizon < 0 || total < 0 || total > ((int64_t)1 << 26))
+        return hipErrorInvalidValue;
+    batch_restock_kernel<<<1, 1024, 0, s>>>(active, counts, found, born, soup, n, now, horizon, (int32_t)total, out_found,
+                                            out_period, harvest);
+    return hipGetLastError();
+}
+
+hipError_t golk_batch_harvest(const uint64_t *prev, const int32_t *harvest, const int32_t *counts, int64_t n, int64_t H,
+                              int64_t W, int64_t total, const int64_t *found, uint64_t *alive, uint64_t *hash, int64_t slots,
+                              hipStream_t s)
+{
+    if (!prev || !harvest || !counts || !found || !alive || !hash || n < 1 || n > ((int64_t)1 << 20) || H < 1 ||
+        H > GOL_BATCH_MAX_SIDE || W < 1 || W > GOL_BATCH_MAX_SIDE || total < 0 || total > ((int64_t)1 << 26) || slots < 1 ||
+        slots > n)
+        return hipErrorInvalidValue;
+    const unsigned grid = (unsigned)std::min<int64_t>((slots + 3) / 4, 8192);
+    batch_harvest_kernel<<<grid, 256, 0, s>>>(prev, harvest, counts, n, (int32_t)(H * ((W + 63) / 64)), (int32_t)total, found,
+                                              alive, hash);
+    return hipGetLastError();
+}
+
+hipError_t golk_batch_refill(uint64_t *boards, const int32_t *harvest, const int32_t *counts, const int32_t *soup, int64_t n,
+                             int64_t H, int64_t W, uint64_t seed, int64_t first, int64_t total, int64_t slots, hipStream_t s)
+{
+    if (!boards || !harvest || !counts || !soup || n < 1 || n > ((int64_t)1 << 20) || H < 1 || H > GOL_BATCH_MAX_SIDE || W < 1 ||
+        W > GOL_BATCH_MAX_SIDE || first < 0 || total < 0 || total > ((int64_t)1 << 26) || first + total > ((int64_t)1 << 40) ||
+        slots < 1 || slots > n)
+        return hipErrorInvalidValue;
+    const int64_t Ww = (W + 63) / 64, words = H * Ww;
+    const uint64_t tail = W % 64 ? ((uint64_t)1 << (W % 64)) - 1 : ~(uint64_t)0;
+    const unsigned grid = (unsigned)std::min<int64_t>((slots * words + 255) / 256, 8192);
+    batch_refill_kernel<<<grid, 256, 0, s>>>(boards, harvest, counts, soup, n, (int32_t)words, (int32_t)Ww, tail, seed,
+                                             (uint64_t)first, (int32_t)total);
     return hipGetLastError();
 }

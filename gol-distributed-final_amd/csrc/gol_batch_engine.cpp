@@ -1,6 +1,6 @@
 // gol_batch_engine.cpp -- batches of small boards (include/golhip.h): the handle, the argument
 // checks, the rules per board, the split of a stepping call into launches, the retiring call's lists and
-// readbacks, and the strided copies.  The kernels are
+// readbacks, the soup search's driver, and the strided copies.  The kernels are
 // gol_batch.hip (whose object takes the name gol_batch.o), the host twin gol_batch_host.cpp.
 #include <hip/hip_runtime.h>
 
@@ -40,6 +40,13 @@ struct gol_batch {
     int32_t *lists = nullptr;
     int64_t *left = nullptr;
     int32_t *hcounts = nullptr;  // pinned host memory: the two counts read back after every launch
+    // search (on demand): the active list (n), the harvest list (2 n), the soup per slot (n) and the four counts; born and
+    // the found age per slot (2 n); the result tables found, period, alive, hash (4 tab_cap words); four pinned counts
+    int32_t *slists = nullptr;
+    int64_t *sages = nullptr;
+    int64_t *tab = nullptr;
+    int64_t tab_cap = 0;
+    int32_t *scounts = nullptr;
 };
 
 namespace {
@@ -201,6 +208,61 @@ int run_cycles(gol_batch *b, int64_t turns, int64_t *out, std::vector<int64_t> &
     return GOL_OK;
 }
 
+// gol_batch_search on m = min(n, total) slots in launches of L turns: the first fill, then per launch the aged step over the
+// active list, the restock pass, the harvest and the refill of the slots it names, and a blocking read of the counts, until
+// no slot is active.  The tables live on the device and are copied out once.
+int search(gol_batch *b, uint64_t seed, int64_t first, int64_t total, int64_t horizon, int64_t m, int L, int64_t *found,
+           int64_t *period, uint64_t *alive, uint64_t *hash, gol_batch_search_stats *st)
+{
+    const int64_t n = b->n;
+    if (!b->prev) HIPCHK(hipMalloc(&b->prev, (size_t)(n * b->H * b->Ww) * sizeof(uint64_t)));
+    if (!b->slists) HIPCHK(hipMalloc(&b->slists, (size_t)(4 * n + 4) * sizeof(int32_t)));
+    if (!b->sages) HIPCHK(hipMalloc(&b->sages, (size_t)(2 * n) * sizeof(int64_t)));
+    if (!b->scounts) HIPCHK(hipHostMalloc(&b->scounts, 4 * sizeof(int32_t), hipHostMallocDefault));
+    if (b->tab_cap < total) {
+        if (b->tab) HIPCHK(hipFree(b->tab));
+        b->tab = nullptr;
+        b->tab_cap = 0;
+        HIPCHK(hipMalloc(&b->tab, (size_t)(4 * total) * sizeof(int64_t)));
+        b->tab_cap = total;
+    }
+    int32_t *active = b->slists, *harvest = b->slists + n, *soup = b->slists + 3 * n, *counts = b->slists + 4 * n;
+    int64_t *born = b->sages, *age = b->sages + n;
+    int64_t *tfound = b->tab, *tperiod = b->tab + total;
+    uint64_t *talive = (uint64_t *)(b->tab + 2 * total), *thash = (uint64_t *)(b->tab + 3 * total);
+    HIPCHK(hipMemsetAsync(tfound, 0xff, (size_t)(2 * total) * sizeof(int64_t), b->stream));
+    HIPCHK(hipMemsetAsync(talive, 0, (size_t)(2 * total) * sizeof(uint64_t), b->stream));
+    HIPCHK(golk_batch_soups(b->boards, m, b->H, b->W, seed, first, b->stream));
+    HIPCHK(golk_batch_search_init(active, counts, soup, born, age, m, b->stream));
+    int32_t *host = b->scounts;
+    host[0] = (int32_t)m;
+    for (int64_t done = 0; host[0] > 0;) {
+        const int64_t in = host[0];
+        HIPCHK(golk_batch_step_aged(b->boards, b->prev, age, born, n, b->H, b->W, L, b->birth, b->survive, done, active, counts,
+                                    in, b->stream));
+        done += L;
+        st->launches += 1;
+        st->board_turns += in * L;
+        HIPCHK(golk_batch_restock(active, counts, age, born, soup, n, done, horizon, total, tfound, tperiod, harvest, b->stream));
+        HIPCHK(golk_batch_harvest(b->prev, harvest, counts, n, b->H, b->W, total, tfound, talive, thash, in, b->stream));
+        HIPCHK(golk_batch_refill(b->boards, harvest, counts, soup, n, b->H, b->W, seed, first, total, in, b->stream));
+        HIPCHK(hipMemcpyAsync(host, counts, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, b->stream));
+        HIPCHK(hipStreamSynchronize(b->stream));
+        if (host[0] < 0 || host[0] > in || host[1] < 0 || host[1] > in || host[2] < 0 || host[2] > host[1] || host[3] < m ||
+            host[3] > total)
+            return gol_set_error(GOL_EHIP, "batch search: counts %d, %d, %d, %d of %lld slots, %lld soups", host[0], host[1],
+                                 host[2], host[3], (long long)in, (long long)total);
+    }
+    st->full_turns = st->launches * m * L;
+    const size_t bytes = (size_t)total * sizeof(int64_t);
+    HIPCHK(hipMemcpyAsync(found, tfound, bytes, hipMemcpyDeviceToHost, b->stream));
+    if (period) HIPCHK(hipMemcpyAsync(period, tperiod, bytes, hipMemcpyDeviceToHost, b->stream));
+    if (alive) HIPCHK(hipMemcpyAsync(alive, talive, bytes, hipMemcpyDeviceToHost, b->stream));
+    if (hash) HIPCHK(hipMemcpyAsync(hash, thash, bytes, hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    return GOL_OK;
+}
+
 }  // namespace
 
 extern "C" void gol_batch_destroy(gol_batch *b)
@@ -216,6 +278,10 @@ extern "C" void gol_batch_destroy(gol_batch *b)
         if (b->lists) (void)hipFree(b->lists);
         if (b->left) (void)hipFree(b->left);
         if (b->hcounts) (void)hipHostFree(b->hcounts);
+        if (b->slists) (void)hipFree(b->slists);
+        if (b->sages) (void)hipFree(b->sages);
+        if (b->tab) (void)hipFree(b->tab);
+        if (b->scounts) (void)hipHostFree(b->scounts);
         if (b->stream) (void)hipStreamDestroy(b->stream);
     }
     delete b;
@@ -415,6 +481,53 @@ extern "C" int gol_batch_load_random(gol_batch *b, uint64_t seed)
     HIPCHK(golk_batch_random(b->boards, b->n, b->H, b->W, seed, b->stream));
     HIPCHK(hipStreamSynchronize(b->stream));
     b->turn = 0;
+    return GOL_OK;
+}
+
+extern "C" int gol_batch_load_soups(gol_batch *b, uint64_t seed, int64_t first)
+{
+    if (!b || first < 0 || first + b->n > ((int64_t)1 << 40))
+        return gol_set_error(GOL_EINVAL, "bad batch load_soups (first %lld: soups in 0..2^40)", (long long)first);
+    OnDevice dev(b->device);
+    HIPCHK(dev.err);
+    HIPCHK(golk_batch_soups(b->boards, b->n, b->H, b->W, seed, first, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    b->turn = 0;
+    return GOL_OK;
+}
+
+extern "C" int gol_batch_search(gol_batch *b, uint64_t seed, int64_t first, int64_t total, int64_t horizon, int64_t *found,
+                                int64_t *period, uint64_t *alive, uint64_t *hash, gol_batch_search_stats *stats)
+{
+    if (!b || !found || first < 0 || total < 0 || horizon < 0 || first > ((int64_t)1 << 40) || total > ((int64_t)1 << 26) ||
+        first + total > ((int64_t)1 << 40))
+        return gol_set_error(GOL_EINVAL, "bad batch search (soups [%lld, +%lld) in 0..2^40, at most 2^26, horizon %lld, or NULL)",
+                             (long long)first, (long long)total, (long long)horizon);
+    if (!b->rules.empty()) return gol_set_error(GOL_ESTATE, "batch search: the boards of the batch have different rules");
+    OnDevice dev(b->device);
+    HIPCHK(dev.err);
+    const int64_t m = std::min(b->n, total);
+    // every launch makes L turns (no longer than the horizon), so ages are multiples of L
+    const int64_t L = std::max<int64_t>(1, std::min<int64_t>(b->auto_tpl ? auto_turns(std::max<int64_t>(m, 1), b->H, b->W) : b->tpl,
+                                                             horizon));
+    gol_batch_search_stats st{};
+    st.slots = m;
+    st.launch_turns = L;
+    if (total > 0 && horizon > 0) {
+        const int rc = search(b, seed, first, total, horizon, m, (int)L, found, period, alive, hash, &st);
+        if (rc) return rc;
+    } else {  // nothing to run: every soup is at -1
+        for (int64_t g = 0; g < total; ++g) {
+            found[g] = -1;
+            if (period) period[g] = -1;
+            if (alive) alive[g] = 0;
+            if (hash) hash[g] = 0;
+        }
+    }
+    HIPCHK(hipMemsetAsync(b->boards, 0, (size_t)(b->n * b->H * b->Ww) * sizeof(uint64_t), b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    b->turn = 0;
+    if (stats) *stats = st;
     return GOL_OK;
 }
 

@@ -2,7 +2,8 @@
 // memory with the row function of the batch kernel (gol_batch.h), in the instantiation the kernel
 // picks for the width, row by row as the lanes do; and gol_batch_cycles_host: the cycle scan of one
 // board with that turn and the mark functions the kernel and the engine use; and gol_batch_run_cycles_host: the
-// retiring scheme of gol_batch_run_cycles on one board, with the remainder function the retire pass runs.  No HIP
+// retiring scheme of gol_batch_run_cycles on one board, with the remainder function the retire pass runs; and gol_batch_soup_host and
+// gol_batch_search_host: a soup from the fill kernels' word function, and the scheme of gol_batch_search.  No HIP
 // header: a stand-alone program links this file alone (batch_check.cpp).
 #include <stdint.h>
 
@@ -137,5 +138,106 @@ extern "C" int gol_batch_run_cycles_host(int64_t H, int64_t W, uint32_t birth, u
     if (made) *made = did;
     for (int64_t y = 0; y < H; ++y)
         for (int64_t w = 0; w < Ww; ++w) out[y * row_stride + w] = cur[(size_t)(y * Ww + w)];
+    return GOL_OK;
+}
+
+extern "C" int gol_batch_verdict_host(int64_t found, int64_t age, int64_t horizon) { return gol_batch_verdict(found, age, horizon); }
+
+extern "C" int gol_batch_soup_host(int64_t H, int64_t W, uint64_t seed, int64_t index, uint64_t *out, int64_t row_stride)
+{
+    const int64_t Ww = (W + 63) / 64;
+    if (H < 1 || H > GOL_BATCH_MAX_SIDE || W < 1 || W > GOL_BATCH_MAX_SIDE || index < 0 || index > ((int64_t)1 << 40) || !out ||
+        row_stride < Ww)
+        return gol_set_error(GOL_EINVAL, "bad host batch soup (H %lld, W %lld, index %lld, row stride %lld)", (long long)H,
+                             (long long)W, (long long)index, (long long)row_stride);
+    const uint64_t tail = W % 64 ? ((uint64_t)1 << (W % 64)) - 1 : ~(uint64_t)0;
+    for (int64_t y = 0; y < H; ++y)
+        for (int64_t w = 0; w < Ww; ++w)
+            out[y * row_stride + w] = gol_batch_soup_word(seed, (uint64_t)((index * H + y) * Ww + w), Ww, tail);
+    return GOL_OK;
+}
+
+// gol_batch_search on host memory: the slots, the launches, the restock pass in the list's order and the census of the
+// kept snapshot, as the kernels and the driver of gol_batch_engine.cpp have them
+extern "C" int gol_batch_search_host(int64_t H, int64_t W, uint32_t birth, uint32_t survive, uint64_t seed, int64_t first,
+                                     int64_t total, int64_t slots, int64_t launch, int64_t horizon, int64_t *found,
+                                     int64_t *period, uint64_t *alive, uint64_t *hash)
+{
+    if (H < 1 || H > GOL_BATCH_MAX_SIDE || W < 1 || W > GOL_BATCH_MAX_SIDE || birth >= 512 || survive >= 512 || !found ||
+        first < 0 || total < 0 || horizon < 0 || first > ((int64_t)1 << 40) || total > ((int64_t)1 << 26) ||
+        first + total > ((int64_t)1 << 40) || slots < 1 || launch < 1)
+        return gol_set_error(GOL_EINVAL,
+                             "bad host batch search (H %lld, W %lld, B 0x%x, S 0x%x, soups [%lld, +%lld), slots %lld, launch %lld, "
+                             "horizon %lld)",
+                             (long long)H, (long long)W, birth, survive, (long long)first, (long long)total, (long long)slots,
+                             (long long)launch, (long long)horizon);
+    const int64_t Ww = (W + 63) / 64, bw = H * Ww, m = slots < total ? slots : total;
+    for (int64_t g = 0; g < total; ++g) {
+        found[g] = -1;
+        if (period) period[g] = -1;
+        if (alive) alive[g] = 0;
+        if (hash) hash[g] = 0;
+    }
+    if (total == 0 || horizon == 0) return GOL_OK;
+    struct Slot {
+        std::vector<uint64_t> cur, snap;
+        int64_t soup, born, found;
+    };
+    std::vector<Slot> slot((size_t)m);
+    std::vector<int64_t> active;
+    auto fill = [&](Slot &s, int64_t g, int64_t now) {
+        s.cur.resize((size_t)bw);
+        const int rc = gol_batch_soup_host(H, W, seed, first + g, s.cur.data(), Ww);
+        s.snap = s.cur;  // the mark at age 0
+        s.soup = g;
+        s.born = now;
+        s.found = -1;
+        return rc;
+    };
+    for (int64_t i = 0; i < m; ++i) {
+        const int rc = fill(slot[(size_t)i], i, 0);
+        if (rc) return rc;
+        active.push_back(i);
+    }
+    int64_t next = m;
+    for (int64_t done = 0; !active.empty();) {
+        for (int64_t i : active) {  // one launch of the aged step kernel
+            Slot &s = slot[(size_t)i];
+            for (int64_t age = done - s.born + 1; age <= done - s.born + launch; ++age) {
+                const bool known = s.found >= 0;  // (before this turn's comparison: the snapshot stays from then on)
+                const int rc = gol_batch_step_host(H, W, birth, survive, s.cur.data(), s.cur.data(), Ww);
+                if (rc) return rc;
+                if (!known && s.cur == s.snap) s.found = age;
+                if (gol_batch_is_mark(age) && !known) s.snap = s.cur;
+            }
+        }
+        done += launch;
+        std::vector<int64_t> stay;  // the restock pass
+        for (int64_t i : active) {
+            Slot &s = slot[(size_t)i];
+            const int v = gol_batch_verdict(s.found, done - s.born, horizon);
+            if (v == GOL_BATCH_STAY) {
+                stay.push_back(i);
+                continue;
+            }
+            if (v == GOL_BATCH_FOUND) {  // the harvest: s(found) is the snapshot
+                uint64_t a = 0, h = 0;
+                for (int64_t k = 0; k < bw; ++k) {
+                    a += (uint64_t)__builtin_popcountll(s.snap[(size_t)k]);
+                    h += gol_batch_splitmix64(s.snap[(size_t)k] ^ gol_batch_splitmix64((uint64_t)k));
+                }
+                found[s.soup] = s.found;
+                if (period) period[s.soup] = s.found - gol_batch_last_mark(s.found);
+                if (alive) alive[s.soup] = a;
+                if (hash) hash[s.soup] = h;
+            }
+            if (next < total) {
+                const int rc = fill(s, next++, done);
+                if (rc) return rc;
+                stay.push_back(i);
+            }
+        }
+        active.swap(stay);
+    }
     return GOL_OK;
 }

@@ -181,6 +181,30 @@ hipError_t golk_batch_retire(const int32_t *list_in, int32_t *counts, const int6
 hipError_t golk_batch_random(uint64_t *boards, int64_t n, int64_t H, int64_t W, uint64_t seed, hipStream_t s);
 // out[i] = alive cells of board i, or (hash) its oracle_hash_words
 hipError_t golk_batch_reduce(bool hash, const uint64_t *boards, int64_t n, int64_t H, int64_t W, uint64_t *out, hipStream_t s);
+// gol_batch_search (a slot is a board of the batch; a soup's number counts from the search's `first`).
+// golk_batch_soups: board j = soup first + j (gol_batch_soup_word, gol_batch.h), j < n.
+// golk_batch_search_init: slots 0 .. m - 1 active with soups 0 .. m - 1, born at 0, not found; counts = {m, 0, 0, m}.
+// golk_batch_step_aged: the list launch of the cycle scan with an age per board: done - born[board] turns of the board's
+// scan lie before the launch (0: the loaded state is the snapshot and prev is not read), found[board] < 0 becomes the age at
+// which the board is found, prev[board] the snapshot after the launch, which stays s(found) once the board is found.
+// golk_batch_restock: the pass between the launches (include/golhip.h, gol_dev_batch_restock).  golk_batch_harvest: alive
+// and hash of prev[slot] into the tables for the counts[1] pairs (slot, soup) of the harvest list, 0, 0 where found[soup] <
+// 0.  golk_batch_refill: the soup words of the slots of its first counts[2] pairs.  slots: an upper bound of those counts
+// (the active slots before the pass), which sizes the grids.
+hipError_t golk_batch_soups(uint64_t *boards, int64_t n, int64_t H, int64_t W, uint64_t seed, int64_t first, hipStream_t s);
+hipError_t golk_batch_search_init(int32_t *active, int32_t *counts, int32_t *soup, int64_t *born, int64_t *found, int64_t m,
+                                  hipStream_t s);
+hipError_t golk_batch_step_aged(uint64_t *boards, uint64_t *prev, int64_t *found, const int64_t *born, int64_t n, int64_t H,
+                                int64_t W, int turns, uint32_t birth, uint32_t survive, int64_t done, const int32_t *list,
+                                const int32_t *count, int64_t slots, hipStream_t s);
+hipError_t golk_batch_restock(int32_t *active, int32_t *counts, int64_t *found, int64_t *born, int32_t *soup, int64_t n,
+                              int64_t now, int64_t horizon, int64_t total, int64_t *out_found, int64_t *out_period,
+                              int32_t *harvest, hipStream_t s);
+hipError_t golk_batch_harvest(const uint64_t *prev, const int32_t *harvest, const int32_t *counts, int64_t n, int64_t H,
+                              int64_t W, int64_t total, const int64_t *found, uint64_t *alive, uint64_t *hash, int64_t slots,
+                              hipStream_t s);
+hipError_t golk_batch_refill(uint64_t *boards, const int32_t *harvest, const int32_t *counts, const int32_t *soup, int64_t n,
+                             int64_t H, int64_t W, uint64_t seed, int64_t first, int64_t total, int64_t slots, hipStream_t s);
 
 // IPC transport (gol_comm.h): set *flag = value with release ordering at system scope after the
 // stream's earlier work; wait (one wave on the stream) until every flags[i] (i < n <= 4, other

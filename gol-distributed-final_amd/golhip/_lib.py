@@ -178,6 +178,8 @@ SIGNATURES = [
     ("gol_batch_load_words", ctypes.c_int, [_vp, _i64, _i64, _vp, _i64, _i64]),
     ("gol_batch_store_words", ctypes.c_int, [_vp, _i64, _i64, _vp, _i64, _i64]),
     ("gol_batch_load_random", ctypes.c_int, [_vp, _u64]),
+    ("gol_batch_load_soups", ctypes.c_int, [_vp, _u64, _i64]),
+    ("gol_batch_search", ctypes.c_int, [_vp, _u64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
     ("gol_batch_step", ctypes.c_int, [_vp, _i64, _vp]),
     ("gol_batch_step_cycles", ctypes.c_int, [_vp, _i64, _vp, _vp]),
     ("gol_batch_run_cycles", ctypes.c_int, [_vp, _i64, _vp, _vp, _vp]),
@@ -188,6 +190,10 @@ SIGNATURES = [
     ("gol_batch_cycles_host", ctypes.c_int, [_i64, _i64, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp, _i64, _i64, _P(_i64), _P(_i64)]),
     ("gol_batch_run_cycles_host", ctypes.c_int, [_i64, _i64, ctypes.c_uint32, ctypes.c_uint32, _vp, _vp, _i64, _i64, _i64, _P(_i64),
                                                  _P(_i64), _P(_i64)]),
+    ("gol_batch_soup_host", ctypes.c_int, [_i64, _i64, _u64, _i64, _vp, _i64]),
+    ("gol_batch_search_host", ctypes.c_int, [_i64, _i64, ctypes.c_uint32, ctypes.c_uint32, _u64, _i64, _i64, _i64, _i64, _i64, _vp,
+                                             _vp, _vp, _vp]),
+    ("gol_batch_verdict_host", ctypes.c_int, [_i64, _i64, _i64]),
     ("gol_halo_plan", ctypes.c_int, [_i64, _i32, _i32, _i32, _P(gol_halo_op), _i32, _P(_i32)]),
     ("gol_step_plan", ctypes.c_int, [_i64, _i32, _i32, _i32, _P(gol_launch), _i32, _P(_i32)]),
     ("gol_view_plan", ctypes.c_int, [_i64, _i32, _i32, _i64, _i64, _P(gol_view_run), _i32, _P(_i32)]),
@@ -216,6 +222,7 @@ SIGNATURES = [
     ("gol_band_max_k", ctypes.c_int, [_i32]),
     ("gol_dev_band_convert", ctypes.c_int, [_i32, _vp, _vp, _i64, _i64, _i64, _i64, _vp]),
     ("gol_dev_batch_retire", ctypes.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
+    ("gol_dev_batch_restock", ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
     ("gol_dev_error", ctypes.c_int, [_i32, _P(ctypes.c_uint32)]),
     ("gol_broker_create", ctypes.c_int, [_P(gol_config), _P(_vp)]),
     ("gol_broker_destroy", None, [_vp]),

@@ -112,6 +112,45 @@ class Batch:
         """word(i, y, w) = splitmix64(seed ^ ((i*H + y)*Ww + w)) masked to W, generated on the GPU."""
         self._check(self._L.gol_batch_load_random(self._h, seed))
 
+    def load_soups(self, seed: int, first: int = 0) -> None:
+        """Board i becomes soup first + i of `seed`: board first + i of load_random(seed) on a batch large
+        enough to hold it.  Resets the turn counter."""
+        self._check(self._L.gol_batch_load_soups(self._h, seed, first))
+
+    @staticmethod
+    def soup(height: int, width: int, seed: int, index: int, library=None) -> np.ndarray:
+        """Soup `index` of (seed, height, width) as uint64[height, ceil(width / 64)] words, made on the
+        host with the word function the fill kernels run (no GPU needed)."""
+        L = library or lib()
+        out = np.zeros((max(int(height), 0), (max(int(width), 0) + 63) // 64), dtype=np.uint64)
+        rc = L.gol_batch_soup_host(height, width, seed, index, out.ctypes.data, out.shape[1])
+        if rc:
+            raise GolError(rc, L.gol_last_error().decode(errors="replace"))
+        return out
+
+    def search(self, seed: int, total: int, horizon: int, first: int = 0, stats: bool = False):
+        """Run soups [first, first + total) of `seed` through the batch's boards as slots: a slot whose
+        soup is found, or has outlived `horizon`, hands over its result and takes the next soup at the
+        same launch boundary.  Returns (found, period, alive, hash), arrays of `total` entries indexed
+        g - first: found and period as step_cycles defines them from t0 = 0 (int64), alive and hash the
+        alive cells and oracle_hash_words of the soup's state at `found` (uint64); -1, -1, 0, 0 for a soup
+        not found within the horizon.  stats=True appends a dict: launches, slots, launch_turns,
+        board_turns, full_turns and occupancy = board_turns / full_turns.  Afterwards every board is
+        empty and the turn counter is 0."""
+        m = max(int(total), 0)
+        found = np.full(m, -1, dtype=np.int64)
+        period = np.full(m, -1, dtype=np.int64)
+        alive = np.zeros(m, dtype=np.uint64)
+        hashes = np.zeros(m, dtype=np.uint64)
+        st = (ctypes.c_int64 * 5)()
+        self._check(self._L.gol_batch_search(self._h, seed, first, total, horizon, found.ctypes.data, period.ctypes.data,
+                                             alive.ctypes.data, hashes.ctypes.data, ctypes.addressof(st) if stats else None))
+        if not stats:
+            return found, period, alive, hashes
+        d = dict(zip(("launches", "slots", "launch_turns", "board_turns", "full_turns"), (int(v) for v in st)))
+        d["occupancy"] = d["board_turns"] / d["full_turns"] if d["full_turns"] else 0.0
+        return found, period, alive, hashes, d
+
     # -- the rule
     def set_rule(self, rule) -> None:
         """The rule of every later turn: "B36/S23" or a (birth, survive) pair of 9-bit masks.  The

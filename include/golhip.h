@@ -604,6 +604,40 @@ int gol_bounds_host(int32_t layout, const void *board, int64_t pitch, int64_t W,
  *    prefer step_cycles.  Refusals as step_cycles (NULL handle, NULL found,
  *    turns < 0), the batch and the outputs untouched; turns == 0 gives found
  *    -1, period -1, made 0.
+ *  - load_soups: board i becomes soup first + i (below); load_random(seed) is
+ *    this call with first = 0 and keeps its own code path.  Resets the turn
+ *    counter.  GOL_EINVAL: first < 0 or first + n > 2^40.
+ *  - search: soups.  Soup g of (seed, H, W) is the board whose word (y, w) is
+ *    splitmix64(seed ^ ((g*H + y)*Ww + w)), masked to W: board g of
+ *    load_random(seed) on a batch large enough to hold it.  For soup g let s(0)
+ *    be the soup; the scan is step_cycles' own, with t0 = 0, over `horizon`
+ *    turns, under the batch's one rule.  The results are found[g] and period[g]
+ *    exactly as step_cycles defines them, alive[g] = the cells alive in
+ *    s(found), and hash[g] = oracle_hash_words of s(found), the definition
+ *    hashes uses.  A soup not found within `horizon` has -1, -1, 0, 0; it can be
+ *    re-made from its index (load_soups, gol_batch_soup_host).  The results do
+ *    not depend on the number of slots, on turns_per_launch, or on which slot
+ *    a soup ran in.
+ *    gol_batch_search runs soups [first, first + total) through the batch's n
+ *    boards as slots, min(n, total) of them: a slot whose soup is found, or
+ *    has outlived the horizon, hands its result to a table indexed by soup
+ *    number and takes the next soup of the supply at the same launch boundary,
+ *    so the GPU stays full until the supply runs out.  The output arrays have
+ *    `total` entries, indexed g - first; period, alive and hash may each be
+ *    NULL.  Every launch makes L turns: L = turns_per_launch, or with the
+ *    automatic length the create bound computed for min(n, total) boards, in
+ *    both cases at most `horizon`.  A soup's age at a launch boundary is a
+ *    multiple of L; a soup found in a launch that ran past the horizon, at an
+ *    age above it, is not a find.  stats may be NULL; it receives the launches,
+ *    the slots used, L, the board-turns computed (summed over the launches as
+ *    boards in the launch x L) and the board-turns a full grid would have made
+ *    (launches x slots x L).  The call blocks (the host reads four counts back
+ *    after every launch).  Afterwards every board is empty, the turn counter is
+ *    0 and the rule stays.  Refused before any GPU work, the batch and the
+ *    outputs untouched: GOL_EINVAL for a NULL handle or found, first, total or
+ *    horizon < 0, first + total > 2^40, total > 2^26; GOL_ESTATE for a batch
+ *    with differing rules per board (a rule per soup is not built).  total == 0
+ *    and horizon == 0 are legal; with horizon == 0 every soup is at -1.
  *  - alive_counts / hashes: one uint64 per board, cap >= n; the hash of board i
  *    is oracle_hash_words(words_i, 0, H, Ww) (gol_engine_hash's definition on
  *    the board's zero-padded words, for every W).
@@ -625,6 +659,16 @@ int gol_batch_load_words(gol_batch *b, int64_t i0, int64_t i1, const uint64_t *w
 int gol_batch_store_words(gol_batch *b, int64_t i0, int64_t i1, uint64_t *words, int64_t row_stride,
                           int64_t board_stride);
 int gol_batch_load_random(gol_batch *b, uint64_t seed);
+int gol_batch_load_soups(gol_batch *b, uint64_t seed, int64_t first);
+typedef struct gol_batch_search_stats {
+    int64_t launches;     /* step launches of the call */
+    int64_t slots;        /* min(n, total) */
+    int64_t launch_turns; /* L, the turns of every launch */
+    int64_t board_turns;  /* sum over the launches of (boards in the launch) * L */
+    int64_t full_turns;   /* launches * slots * L: what a full grid would have made */
+} gol_batch_search_stats;
+int gol_batch_search(gol_batch *b, uint64_t seed, int64_t first, int64_t total, int64_t horizon, int64_t *found,
+                     int64_t *period, uint64_t *alive, uint64_t *hash, gol_batch_search_stats *stats);
 int gol_batch_step(gol_batch *b, int64_t turns, int64_t *settled);
 int gol_batch_step_cycles(gol_batch *b, int64_t turns, int64_t *found, int64_t *period);
 int gol_batch_run_cycles(gol_batch *b, int64_t turns, int64_t *found, int64_t *period, int64_t *made);
@@ -659,6 +703,27 @@ int gol_batch_cycles_host(int64_t H, int64_t W, uint32_t birth, uint32_t survive
 int gol_batch_run_cycles_host(int64_t H, int64_t W, uint32_t birth, uint32_t survive, const uint64_t *in, uint64_t *out,
                               int64_t row_stride, int64_t turns, int64_t launch, int64_t *found, int64_t *period,
                               int64_t *made);
+/* One soup on host memory (a host function, no GPU needed): soup `index` of
+ * (seed, H, W) into H rows of row_stride uint64 words, Ww of each written, with
+ * the word function the fill kernels run (csrc/gol_batch.h).  GOL_EINVAL: H or
+ * W outside 1..512, index outside 0..2^40, row_stride < Ww, NULL. */
+int gol_batch_soup_host(int64_t H, int64_t W, uint64_t seed, int64_t index, uint64_t *out, int64_t row_stride);
+/* The scheme of gol_batch_search on host memory (a host function, no GPU
+ * needed): soups [first, first + total) through `slots` >= 1 slots in launches
+ * of `launch` >= 1 turns, with the row function of gol_batch_step_host, the mark
+ * functions and the verdict function the restock pass runs (csrc/gol_batch.h),
+ * the snapshot kept once a soup is found as the kernel keeps it, and the
+ * refills in the pass's order.  Outputs and refusals as gol_batch_search
+ * (period, alive and hash may be NULL); also GOL_EINVAL for H or W outside
+ * 1..512, masks >= 512, slots or launch < 1. */
+int gol_batch_search_host(int64_t H, int64_t W, uint32_t birth, uint32_t survive, uint64_t seed, int64_t first, int64_t total,
+                          int64_t slots, int64_t launch, int64_t horizon, int64_t *found, int64_t *period, uint64_t *alive,
+                          uint64_t *hash);
+/* The verdict of the restock pass on one slot (a host function; the function of
+ * csrc/gol_batch.h): 0 the soup stays, 1 it is found (0 <= found <= horizon), 2 it
+ * has expired (not found and age >= horizon, or found at an age above horizon).
+ * found < 0: not found yet. */
+int gol_batch_verdict_host(int64_t found, int64_t age, int64_t horizon);
 
 /* ---------------------------------------------------------------- plans
  * The schedule of a sharded step as data (host functions, no GPU needed).  The
@@ -915,6 +980,27 @@ int gol_dev_band_convert(int32_t to_band, const uint32_t *src, uint32_t *dst, in
  * of range, or not 0 <= t0 <= t_now <= t_end. */
 int gol_dev_batch_retire(const int32_t *list_in, int32_t *counts, const int64_t *found, int64_t n, int64_t t0,
                          int64_t t_now, int64_t t_end, int32_t *active, int32_t *finish, int64_t *left, void *stream);
+/* The restock pass of gol_batch_search on caller device memory (one workgroup;
+ * stable and deterministic; no version bump: probe by symbol).  Slots are
+ * numbers in 0..n-1, 1 <= n <= 2^20 (an entry outside is dropped); found_age,
+ * born (int64_t[n]) and soup (int32_t[n], a soup's number in 0..total-1, total <=
+ * 2^26) are indexed by slot, out_found and out_period (int64_t[total]) by soup.
+ * counts is int32_t[4] in device memory: [0] the entries of `active`, read and
+ * written; [1] written: the slots that are done; [2] written: those of them
+ * refilled; [3] the soups handed out so far, read and written.  In the order
+ * of `active`: a slot's verdict comes from found_age[slot], its age now -
+ * born[slot] and horizon (gol_batch_verdict_host).  A slot that stays stays.  A
+ * slot that is done writes out_found and out_period of its soup (the found age
+ * and found age - the last mark before it, or -1, -1 when expired) and goes on
+ * the harvest list (int32_t[2 n]) as the pair (slot, soup); the r-th done slot
+ * takes soup counts[3] + r while that is below total (soup[slot] that number,
+ * born[slot] = now, found_age[slot] = -1; it stays in `active`), else it leaves
+ * `active`, which is compacted in place.  The refilled slots are therefore the
+ * first counts[2] pairs of the harvest list.  Entries past the new counts are
+ * not written.  GOL_EINVAL: NULL, n or total out of range, now or horizon < 0. */
+int gol_dev_batch_restock(int32_t *active, int32_t *counts, int64_t *found_age, int64_t *born, int32_t *soup, int64_t n,
+                          int64_t now, int64_t horizon, int64_t total, int64_t *out_found, int64_t *out_period,
+                          int32_t *harvest, void *stream);
 /* Read and clear the error word of `device` (-1 = current) that the gol_dev_*
  * launchers' kernels report into (*flags = 0: no fault; nonzero: a pipeline
  * wave timed out waiting for its neighbour, so the launch's output is not
