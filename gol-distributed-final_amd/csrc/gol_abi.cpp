@@ -9,6 +9,7 @@
 #include <string>
 #include <vector>
 
+#include "gol_batch.h"
 #include "gol_engine_int.h"
 #include "gol_rule.h"
 
@@ -287,6 +288,34 @@ extern "C" int gol_dev_batch_restock(int32_t *active, int32_t *counts, int64_t *
                              (long long)n, (long long)now, (long long)horizon, (long long)total);
     LAUNCH(golk_batch_restock(active, counts, found_age, born, soup, n, now, horizon, total, out_found, out_period, harvest,
                               (hipStream_t)stream));
+}
+
+extern "C" int gol_dev_batch_step(uint64_t *boards, uint64_t *prev, int64_t *settled, int64_t n, int64_t H, int64_t W, int32_t turns,
+                                  int64_t turn0, int32_t have_prev, int32_t write_prev, uint32_t birth, uint32_t survive,
+                                  const uint32_t *rules, int32_t scan, int64_t done, const int32_t *list, const int32_t *count,
+                                  int64_t slots, int64_t *left, const int64_t *born, void *stream)
+{
+    // which of the three launchers the arguments name; what a launcher does not take must be at its only value
+    const bool listed = list || count || left || born;
+    bool ok = true;
+    if (born) ok = scan == GOL_BATCH_SCAN_CYCLES && !left && !rules && turn0 == 0 && write_prev && (have_prev != 0) == (done > 0);
+    else if (listed) ok = scan == (settled ? GOL_BATCH_SCAN_CYCLES : GOL_BATCH_SCAN_NONE);
+    else ok = slots == 0;
+    hipError_t e = hipErrorInvalidValue;
+    if (ok && born)
+        e = golk_batch_step_aged(boards, prev, settled, born, n, H, W, turns, birth, survive, done, list, count, slots,
+                                 (hipStream_t)stream);
+    else if (ok && listed)
+        e = golk_batch_step_list(boards, prev, settled, n, H, W, turns, turn0, have_prev != 0, write_prev != 0, birth, survive,
+                                 rules, done, list, count, slots, left, (hipStream_t)stream);
+    else if (ok)
+        e = golk_batch_step(boards, prev, settled, n, H, W, turns, turn0, have_prev != 0, write_prev != 0, birth, survive, rules,
+                            scan, done, (hipStream_t)stream);
+    if (e == hipErrorInvalidValue)  // the launchers' own checks: nothing was launched
+        return gol_set_error(GOL_EINVAL, "bad batch_step arguments (n %lld, %lld x %lld, %d turns, scan %d, done %lld, slots %lld, or a pointer)",
+                             (long long)n, (long long)H, (long long)W, turns, scan, (long long)done, (long long)slots);
+    if (e != hipSuccess) return gol_set_error(GOL_EHIP, "batch_step: %s", hipGetErrorString(e));
+    return GOL_OK;
 }
 
 extern "C" int gol_dev_error(int32_t device, uint32_t *flags)

@@ -223,6 +223,8 @@ SIGNATURES = [
     ("gol_dev_band_convert", ctypes.c_int, [_i32, _vp, _vp, _i64, _i64, _i64, _i64, _vp]),
     ("gol_dev_batch_retire", ctypes.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
     ("gol_dev_batch_restock", ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
+    ("gol_dev_batch_step", ctypes.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i32, _i64, _i32, _i32, ctypes.c_uint32,
+                                          ctypes.c_uint32, _vp, _i32, _i64, _vp, _vp, _i64, _vp, _vp, _vp]),
     ("gol_dev_error", ctypes.c_int, [_i32, _P(ctypes.c_uint32)]),
     ("gol_broker_create", ctypes.c_int, [_P(gol_config), _P(_vp)]),
     ("gol_broker_destroy", None, [_vp]),

@@ -1001,6 +1001,58 @@ int gol_dev_batch_retire(const int32_t *list_in, int32_t *counts, const int64_t 
 int gol_dev_batch_restock(int32_t *active, int32_t *counts, int64_t *found_age, int64_t *born, int32_t *soup, int64_t n,
                           int64_t now, int64_t horizon, int64_t total, int64_t *out_found, int64_t *out_period,
                           int32_t *harvest, void *stream);
+/* One launch of the batch step kernel on caller device memory (the launch the
+ * gol_batch_* stepping calls are made of; no version bump: probe by symbol).
+ * boards: n boards (1 <= n <= 2^20) of H rows of Ww = ceil(W / 64) uint64 words,
+ * dense, in the batch's bit order, padding bits zero; 1 <= H, W <= 512.  Board b
+ * holds s_b(turn0) before the launch; s_b(t + 1) is one turn of s_b(t) under the
+ * board's rule: rules == NULL: birth / survive (9-bit masks) for every board, else
+ * rules is uint32_t[2 n], board b under birth rules[2 b], survive rules[2 b + 1].
+ * turns >= 1.  prev has the shape of boards, settled, left and born are int64_t[n],
+ * all indexed by the board's own number.  The mode is in the arguments:
+ *  - plain (scan 0; settled, list, count, left, born NULL; slots 0; have_prev
+ *    and write_prev 0): every board becomes s(turn0 + turns).  prev is not used.
+ *  - settle (scan 1, settled and prev not NULL, no list): every board becomes
+ *    s(turn0 + turns).  have_prev != 0: prev[b] holds s_b(turn0 - 1), and f is the
+ *    smallest t in turn0 + 1 .. turn0 + turns with s(t) == s(t - 2); have_prev ==
+ *    0: prev is not read and t starts at turn0 + 2.  write_prev != 0: prev[b]
+ *    becomes s_b(turn0 + turns - 1); else prev is not written.
+ *  - cycles (scan 2, settled and prev not NULL; done >= 0 the turns of the scan
+ *    before this launch, have_prev == (done > 0)): every board becomes s(turn0 +
+ *    turns).  The board's snapshot is prev[b] when done > 0, else s_b(turn0).  For
+ *    it = 1 .. turns in turn: s(turn0 + it) is compared with the snapshot, f is
+ *    the first turn0 + it at which they are equal, and after the comparison, if
+ *    done + it is a mark (2^j - 1), the snapshot becomes s(turn0 + it).
+ *    write_prev != 0: prev[b] becomes the snapshot after the last turn.
+ *  - list + cycles (list, count, settled and prev not NULL, left and born NULL,
+ *    scan 2, 1 <= slots <= n): cycles on the boards list[0 .. *count) alone.
+ *  - finish (list, count and left not NULL, settled and born NULL, scan 0,
+ *    have_prev and write_prev 0, 1 <= slots <= n): a listed board b makes m =
+ *    min(turns, left[b]) turns, to s_b(turn0 + m), and left[b] becomes left[b] - m
+ *    (left[b] >= 0; it is not written when m == 0).
+ *  - aged (born not NULL: list + cycles with turn0 == 0, rules == NULL, write_prev
+ *    != 0, have_prev == (done > 0)): a listed board b has the age a = done -
+ *    born[b] >= 0 before the launch and becomes s_b(a + turns), its turns counted
+ *    in its own age.  Its snapshot is prev[b] when a > 0, else the board as
+ *    loaded (prev[b] is not read).  For it = 1 .. turns: s(a + it) is compared with
+ *    the snapshot, f is the first age a + it at which they are equal, and after
+ *    the comparison, if a + it is a mark and the launch has not found the board
+ *    at a + it or before, the snapshot becomes s(a + it).  prev[b] becomes the
+ *    snapshot: s(f) for a board this launch found.
+ * In every scanning mode settled[b] (the found turn; aged: the found age) becomes
+ * f where the launch has an f for board b and settled[b] was negative; it is
+ * written in no other case.  A slot at or past *count, and every board not listed,
+ * is left untouched in every buffer; list, count, born and rules are only read.
+ * Not checked (the caller's part): the entries list[0 .. *count) are distinct
+ * board numbers in 0 .. n - 1, 0 <= *count <= slots, left[] >= 0 and born[] <= done
+ * of the listed boards, and all pointers are device memory of the stated sizes
+ * (list: at least *count entries).  GOL_EINVAL, nothing launched: a combination of
+ * arguments that is none of the modes above, n, H, W out of range, turns < 1, a
+ * mask >= 512, done < 0, slots outside 1 .. n with a list. */
+int gol_dev_batch_step(uint64_t *boards, uint64_t *prev, int64_t *settled, int64_t n, int64_t H, int64_t W, int32_t turns,
+                       int64_t turn0, int32_t have_prev, int32_t write_prev, uint32_t birth, uint32_t survive,
+                       const uint32_t *rules, int32_t scan, int64_t done, const int32_t *list, const int32_t *count,
+                       int64_t slots, int64_t *left, const int64_t *born, void *stream);
 /* Read and clear the error word of `device` (-1 = current) that the gol_dev_*
  * launchers' kernels report into (*flags = 0: no fault; nonzero: a pipeline
  * wave timed out waiting for its neighbour, so the launch's output is not

@@ -15,9 +15,10 @@ import rule_ref
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BATCH_CHECK = os.path.join(ROOT, "gol-distributed-final_amd", "build", "asan", "batch_check")
 
-# degenerate wraps, one to sixteen words per row, a last word partly and wholly used, more than 64 rows
+# degenerate wraps, one to sixteen words per row, a last word partly and wholly used, more than 64 rows; five to
+# eight words (the 8-word row function) and an odd count of words below the 8 or 16 held
 SHAPES = [(1, 1), (1, 2), (2, 1), (2, 2), (3, 3), (2, 5), (5, 2), (16, 16), (7, 31), (7, 32), (7, 33), (5, 63), (5, 64),
-          (5, 65), (3, 96), (4, 511), (4, 512), (3, 481), (64, 1), (65, 31)]
+          (5, 65), (3, 96), (4, 511), (4, 512), (3, 481), (64, 1), (65, 31), (5, 129), (3, 150), (4, 256), (3, 270)]
 RULES = ["B3/S23", "B36/S23", "B3678/S34678", "B2/S", "B0/S8", "B012345678/S012345678"]
 TURNS = 4
 GAP = np.uint64(0xA5A5A5A5A5A5A5A5)

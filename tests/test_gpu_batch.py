@@ -15,9 +15,10 @@ from test_batch_cpu import tail_mask, to_words
 pytestmark = pytest.mark.gpu
 
 # degenerate wraps; one, two, three and eight waves per board; a partly filled last wave; one to
-# sixteen words per lane; a partly used last word; the largest board
+# sixteen words per lane; a partly used last word; the largest board; eight words per lane and an odd count of
+# words below the eight or sixteen held
 SHAPES = [(1, 1), (2, 5), (5, 2), (3, 3), (16, 16), (63, 33), (64, 32), (64, 64), (65, 31), (129, 65), (100, 512),
-          (512, 32), (511, 481), (512, 512)]
+          (512, 32), (511, 481), (512, 512), (5, 129), (3, 150), (4, 256), (3, 270)]
 GAP = np.uint64(0x5A5A5A5A5A5A5A5A)
 
 
