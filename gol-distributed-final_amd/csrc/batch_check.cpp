@@ -14,6 +14,8 @@
 // the final board equal, and made the formula of golhip.h written out here.
 // `batch_check search`: gol_batch_soup_host and gol_batch_search_host (the scheme of gol_batch_search) on buffers of exact size
 // against a scan of every soup written here, over shapes, rules, slot counts and launch lengths; its splitmix64 is its own.
+// `batch_check launch FILE`: gol_batch_launch_ok (gol_batch.h) and its export gol_batch_step_check_host on the launches of
+// a file that tests/test_batch_ref_cpu.py writes: the case table's launches and the refusal list, each with its answer.
 #include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -403,13 +405,54 @@ static int main_search()
     return bad ? 1 : 0;
 }
 
+// gol_batch_launch_ok on the launches of a file: a line per launch, the expected answer (1 accepted, 0 refused) and the
+// 20 arguments of gol_dev_batch_step without the stream, a pointer as an integer (0: NULL) that is never dereferenced
+static int main_launch(const char *path)
+{
+    FILE *f = fopen(path, "r");
+    if (!f) {
+        printf("batch_check launch: cannot read %s\n", path);
+        return 2;
+    }
+    int bad = 0, n[2] = {0, 0};
+    long long v[21];
+    for (;;) {
+        int got = 0;
+        while (got < 21 && fscanf(f, "%lld", &v[got]) == 1) ++got;
+        if (got == 0) break;
+        if (got < 21 || (v[0] != 0 && v[0] != 1)) {
+            printf("launch line %d: %d fields\n", n[0] + n[1] + 1, got);
+            ++bad;
+            break;
+        }
+        const gol_batch_launch l = {(uint64_t *)(uintptr_t)v[1], (uint64_t *)(uintptr_t)v[2], (int64_t *)(uintptr_t)v[3], v[4], v[5], v[6],
+                                    (int32_t)v[7], v[8], v[9] != 0, v[10] != 0, (uint32_t)v[11], (uint32_t)v[12],
+                                    (const uint32_t *)(uintptr_t)v[13], (int32_t)v[14], v[15], (const int32_t *)(uintptr_t)v[16],
+                                    (const int32_t *)(uintptr_t)v[17], v[18], (int64_t *)(uintptr_t)v[19],
+                                    (const int64_t *)(uintptr_t)v[20]};
+        // the function, and its export: one answer
+        const int rc = gol_batch_step_check_host(l.boards, l.prev, l.settled, l.n, l.H, l.W, l.turns, l.turn0, l.have_prev,
+                                                 l.write_prev, l.birth, l.survive, l.rules, l.scan, l.done, l.list, l.count, l.slots,
+                                                 l.left, l.born);
+        if (gol_batch_launch_ok(l) != (v[0] == 1) || rc != (v[0] == 1 ? GOL_OK : GOL_EINVAL)) {
+            printf("launch line %d: expected %lld, rc %d\n", n[0] + n[1] + 1, v[0], rc);
+            ++bad;
+        }
+        ++n[v[0]];
+    }
+    fclose(f);
+    printf("batch_check launch: %d accepted, %d refused, %d bad\n", n[1], n[0], bad);
+    return bad || !n[0] || !n[1] ? 1 : 0;
+}
+
 int main(int argc, char **argv)
 {
+    if (argc > 2 && !strcmp(argv[1], "launch")) return main_launch(argv[2]);
     if (argc > 1) {
         if (!strcmp(argv[1], "cycles")) return main_cycles();
         if (!strcmp(argv[1], "run")) return main_run();
         if (!strcmp(argv[1], "search")) return main_search();
-        printf("usage: batch_check [cycles | run | search]\n");
+        printf("usage: batch_check [cycles | run | search | launch FILE]\n");
         return 2;
     }
     static const int shapes[][2] = {{1, 1}, {1, 2}, {2, 1}, {2, 2}, {3, 3}, {2, 5}, {5, 2}, {16, 16}, {7, 31}, {7, 32}, {7, 33},

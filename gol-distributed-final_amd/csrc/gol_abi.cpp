@@ -271,7 +271,7 @@ extern "C" int gol_dev_bytes_step(const uint8_t *world, int64_t H, int64_t W, in
 extern "C" int gol_dev_batch_retire(const int32_t *list_in, int32_t *counts, const int64_t *found, int64_t n, int64_t t0,
                                     int64_t t_now, int64_t t_end, int32_t *active, int32_t *finish, int64_t *left, void *stream)
 {
-    if (!list_in || !counts || !found || !active || !finish || !left || n < 1 || n > ((int64_t)1 << 20) || t0 < 0 || t0 > t_now ||
+    if (!list_in || !counts || !found || !active || !finish || !left || !gol_batch_shape_ok(n, 1, 1) || t0 < 0 || t0 > t_now ||
         t_now > t_end)
         return gol_set_error(GOL_EINVAL, "bad batch_retire arguments (n %lld, turns %lld <= %lld <= %lld, or NULL)", (long long)n,
                              (long long)t0, (long long)t_now, (long long)t_end);
@@ -282,8 +282,8 @@ extern "C" int gol_dev_batch_restock(int32_t *active, int32_t *counts, int64_t *
                                      int64_t now, int64_t horizon, int64_t total, int64_t *out_found, int64_t *out_period,
                                      int32_t *harvest, void *stream)
 {
-    if (!active || !counts || !found_age || !born || !soup || !out_found || !out_period || !harvest || n < 1 ||
-        n > ((int64_t)1 << 20) || now < 0 || horizon < 0 || total < 0 || total > ((int64_t)1 << 26))
+    if (!active || !counts || !found_age || !born || !soup || !out_found || !out_period || !harvest ||
+        !gol_batch_shape_ok(n, 1, 1) || now < 0 || horizon < 0 || total < 0 || total > ((int64_t)1 << 26))
         return gol_set_error(GOL_EINVAL, "bad batch_restock arguments (n %lld, now %lld, horizon %lld, total %lld, or NULL)",
                              (long long)n, (long long)now, (long long)horizon, (long long)total);
     LAUNCH(golk_batch_restock(active, counts, found_age, born, soup, n, now, horizon, total, out_found, out_period, harvest,
@@ -295,23 +295,10 @@ extern "C" int gol_dev_batch_step(uint64_t *boards, uint64_t *prev, int64_t *set
                                   const uint32_t *rules, int32_t scan, int64_t done, const int32_t *list, const int32_t *count,
                                   int64_t slots, int64_t *left, const int64_t *born, void *stream)
 {
-    // which of the three launchers the arguments name; what a launcher does not take must be at its only value
-    const bool listed = list || count || left || born;
-    bool ok = true;
-    if (born) ok = scan == GOL_BATCH_SCAN_CYCLES && !left && !rules && turn0 == 0 && write_prev && (have_prev != 0) == (done > 0);
-    else if (listed) ok = scan == (settled ? GOL_BATCH_SCAN_CYCLES : GOL_BATCH_SCAN_NONE);
-    else ok = slots == 0;
-    hipError_t e = hipErrorInvalidValue;
-    if (ok && born)
-        e = golk_batch_step_aged(boards, prev, settled, born, n, H, W, turns, birth, survive, done, list, count, slots,
-                                 (hipStream_t)stream);
-    else if (ok && listed)
-        e = golk_batch_step_list(boards, prev, settled, n, H, W, turns, turn0, have_prev != 0, write_prev != 0, birth, survive,
-                                 rules, done, list, count, slots, left, (hipStream_t)stream);
-    else if (ok)
-        e = golk_batch_step(boards, prev, settled, n, H, W, turns, turn0, have_prev != 0, write_prev != 0, birth, survive, rules,
-                            scan, done, (hipStream_t)stream);
-    if (e == hipErrorInvalidValue)  // the launchers' own checks: nothing was launched
+    const gol_batch_launch l = {boards, prev, settled, n, H, W, turns, turn0, have_prev != 0, write_prev != 0, birth, survive,
+                                rules, scan, done, list, count, slots, left, born};
+    const hipError_t e = golk_batch_step(l, (hipStream_t)stream);
+    if (e == hipErrorInvalidValue)  // gol_batch_launch_ok said no: nothing was launched
         return gol_set_error(GOL_EINVAL, "bad batch_step arguments (n %lld, %lld x %lld, %d turns, scan %d, done %lld, slots %lld, or a pointer)",
                              (long long)n, (long long)H, (long long)W, turns, scan, (long long)done, (long long)slots);
     if (e != hipSuccess) return gol_set_error(GOL_EHIP, "batch_step: %s", hipGetErrorString(e));

@@ -14,7 +14,8 @@
 // kernel here).  The three rows' sums go into the rule: B3/S23 the 7-gate circuit of the step
 // kernels (golk::rule), any other rule gol_rule_sum3 + gol_rule_eval (gol_rule.h).  The padding of the
 // result is cleared afterwards (a cell of the padding has neighbours, and B0 rules give birth there).
-// Also here, for the same reason: the step kernel's modes and the marks of its cycle scan.
+// Also here, for the same reason: the step kernel's modes and the marks of its cycle scan, the soup words and the
+// census, and the descriptor of one launch with the one check of what makes it valid (no HIP header is needed).
 #pragma once
 #include <stdint.h>
 
@@ -29,6 +30,15 @@
 
 #define GOL_BATCH_MAX_SIDE 512  // cells: at most 16 words of a row, 8 waves of 64 rows
 #define GOL_BATCH_MAX_WAVES 8
+#define GOL_BATCH_MAX_BOARDS ((int64_t)1 << 20)
+
+// A batch's shape: n boards of H x W cells.  The mask of a row's last uint64 word (the padding above cell W - 1 clear).
+GOL_BATCH_HD bool gol_batch_shape_ok(int64_t n, int64_t H, int64_t W)
+{
+    return n >= 1 && n <= GOL_BATCH_MAX_BOARDS && H >= 1 && H <= GOL_BATCH_MAX_SIDE && W >= 1 && W <= GOL_BATCH_MAX_SIDE;
+}
+
+GOL_BATCH_HD uint64_t gol_batch_tail64(int64_t W) { return W % 64 ? ((uint64_t)1 << (W % 64)) - 1 : ~(uint64_t)0; }
 
 // The step kernel's modes.  Rule: B3/S23 on 7 gates, one table rule for the batch, a table rule per
 // board.  Scan: none, state(t) == state(t - 2) (periods 1 and 2, the exact settle turn), cycles of
@@ -48,10 +58,13 @@ GOL_BATCH_HD int64_t gol_batch_last_mark(int64_t d)  // d >= 1: the largest mark
     return p - 1;
 }
 
+// The period of a board found d >= 1 turns into its scan: state(d) == state(the last mark before d).
+GOL_BATCH_HD int64_t gol_batch_period(int64_t d) { return d - gol_batch_last_mark(d); }
+
 // Retirement (gol_batch_run_cycles): a board found d >= 1 turns after the call began, with period p = d - the last
 // mark before d, has s(t + p) == s(t) from turn d - p on.  Seen at a turn >= d with `rest` >= 0 turns of the call still to
 // come, its state at the call's end is its state now advanced by rest mod p turns: the turns it still has to make.
-GOL_BATCH_HD int64_t gol_batch_turns_left(int64_t d, int64_t rest) { return rest % (d - gol_batch_last_mark(d)); }
+GOL_BATCH_HD int64_t gol_batch_turns_left(int64_t d, int64_t rest) { return rest % gol_batch_period(d); }
 
 // Soups (gol_batch_load_soups, gol_batch_search): word (y, w) of soup g of (seed, H, Ww) is splitmix64(seed ^ ((g H + y) Ww
 // + w)), the padding of a row's last word cleared with `tail`: board g of gol_batch_load_random on a batch that holds it.
@@ -70,6 +83,30 @@ GOL_BATCH_HD uint64_t gol_batch_soup_word(uint64_t seed, uint64_t i, int64_t Ww,
     return i % (uint64_t)Ww == (uint64_t)Ww - 1 ? v & tail : v;
 }
 
+// The census of a board: its alive cells, and its hash (oracle_hash_words) the sum over its H Ww words of this term of
+// word i.  The kernels sum the terms over a wave's lanes (gol_batch_pass.hip), gol_batch_census over a dense host board.
+GOL_BATCH_HD uint64_t gol_batch_hash_term(uint64_t word, uint64_t i) { return gol_batch_splitmix64(word ^ gol_batch_splitmix64(i)); }
+
+GOL_BATCH_HD void gol_batch_census(const uint64_t *board, int64_t words, uint64_t *alive, uint64_t *hash)
+{
+    *alive = *hash = 0;
+    for (int64_t i = 0; i < words; ++i) {
+        *alive += (uint64_t)__builtin_popcountll(board[i]);
+        *hash += gol_batch_hash_term(board[i], (uint64_t)i);
+    }
+}
+
+// The results of a search before it has run: no soup found.  period, alive and hash may be NULL.
+GOL_BATCH_HD void gol_batch_no_results(int64_t total, int64_t *found, int64_t *period, uint64_t *alive, uint64_t *hash)
+{
+    for (int64_t g = 0; g < total; ++g) {
+        found[g] = -1;
+        if (period) period[g] = -1;
+        if (alive) alive[g] = 0;
+        if (hash) hash[g] = 0;
+    }
+}
+
 // The search's verdict on a slot at a launch boundary (the restock pass, gol_batch_search_host): its soup is `age` turns old,
 // the scan found it at the age `found` (< 0: not yet), and the search looks `horizon` turns far.  A soup found after the
 // horizon, in a launch that ran past it, is not a find.
@@ -78,6 +115,47 @@ GOL_BATCH_HD int gol_batch_verdict(int64_t found, int64_t age, int64_t horizon)
 {
     if (found >= 0) return found <= horizon ? GOL_BATCH_FOUND : GOL_BATCH_EXPIRED;
     return age >= horizon ? GOL_BATCH_EXPIRED : GOL_BATCH_STAY;
+}
+
+// One launch of the step kernel, as gol_dev_batch_step takes it (include/golhip.h, where every field is described);
+// the pointers are device memory.  The drivers fill one per call and change per launch what differs.
+struct gol_batch_launch {
+    uint64_t *boards, *prev;  // n boards of H rows of ceil(W / 64) words; the scan's second buffer
+    int64_t *settled;         // the scan's result per board
+    int64_t n, H, W;
+    int32_t turns;
+    int64_t turn0;
+    bool have_prev, write_prev;
+    uint32_t birth, survive;
+    const uint32_t *rules;  // a rule per board, or NULL
+    int32_t scan;           // GOL_BATCH_SCAN_*
+    int64_t done;
+    const int32_t *list, *count;  // the boards of the launch, or NULL: every board
+    int64_t slots;                // with a list: the grid's board slots, >= *count; else 0 (the grid is sized by n)
+    int64_t *left;                // the finish
+    const int64_t *born;          // the aged search
+};
+
+// What makes a launch valid, per mode; everything else is refused and nothing is launched.
+GOL_BATCH_HD bool gol_batch_launch_ok(const gol_batch_launch &l)
+{
+    if (!l.boards || !gol_batch_shape_ok(l.n, l.H, l.W) || l.turns < 1 || l.birth >= 512 || l.survive >= 512 || l.done < 0)
+        return false;
+    // a scan has its result and its second buffer; without one there is no scan mode and neither prev flag
+    const bool scans = l.settled != nullptr;
+    if (scans ? !l.prev || (l.scan != GOL_BATCH_SCAN_SETTLE && l.scan != GOL_BATCH_SCAN_CYCLES)
+              : l.scan != GOL_BATCH_SCAN_NONE || l.have_prev || l.write_prev)
+        return false;
+    // the cycle scan's snapshot comes from the launch before, which the call's first launch does not have
+    if (l.scan == GOL_BATCH_SCAN_CYCLES && l.have_prev != (l.done > 0)) return false;
+    // plain, settle, cycles: every board, nothing of a list
+    if (!l.list && !l.count && !l.left && !l.born) return l.slots == 0;
+    // a list has its count and its slots, and no settle scan
+    if (!l.list || !l.count || l.slots < 1 || l.slots > l.n || l.scan == GOL_BATCH_SCAN_SETTLE) return false;
+    // aged: the cycle scan in the boards' own ages, one rule, the snapshot always written
+    if (l.born) return scans && !l.left && !l.rules && l.turn0 == 0 && l.write_prev;
+    // list + cycles, or the finish with its turns left and no scan
+    return scans != (l.left != nullptr);
 }
 
 // The shape of a row: nwr words in use of nw held, the last cell's bit and the mask of the last word.

@@ -1,7 +1,8 @@
 // gol_batch_engine.cpp -- batches of small boards (include/golhip.h): the handle, the argument
-// checks, the rules per board, the split of a stepping call into launches, the retiring call's lists and
-// readbacks, the soup search's driver, and the strided copies.  The kernels are
-// gol_batch.hip (whose object takes the name gol_batch.o), the host twin gol_batch_host.cpp.
+// checks, the rules per board, the split of a stepping call into launches (one gol_batch_launch per call,
+// gol_batch.h), the retiring call's lists and readbacks, the soup search's driver, and the strided copies.
+// The kernels are gol_batch.hip (the step kernel) and gol_batch_pass.hip (the rest), the host twin
+// gol_batch_host.cpp.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -16,7 +17,6 @@
 // broker's chunks are: no launch runs long, whatever the batch.
 #define GOL_BATCH_LAUNCH_UPDATES ((int64_t)1 << 35)
 #define GOL_BATCH_MAX_TURNS 4096
-#define GOL_BATCH_MAX_BOARDS ((int64_t)1 << 20)
 // Strided loads and stores are staged through a dense host block of at most this many bytes.
 #define GOL_BATCH_STAGE_BYTES ((int64_t)64 << 20)
 
@@ -66,9 +66,12 @@ struct OnDevice {
     }
 };
 
-int need_aux(gol_batch *b)
+// An on-demand device buffer of the batch (prev, aux, lists, left, slists, sages, drules): allocated at its first use,
+// freed by gol_batch_destroy.
+template <class T>
+int need(T *&p, int64_t count)
 {
-    if (!b->aux) HIPCHK(hipMalloc(&b->aux, (size_t)b->n * sizeof(uint64_t)));
+    if (!p) HIPCHK(hipMalloc(&p, (size_t)count * sizeof(T)));
     return GOL_OK;
 }
 
@@ -76,8 +79,6 @@ int auto_turns(int64_t boards, int64_t H, int64_t W)
 {
     return (int)std::min<int64_t>(GOL_BATCH_MAX_TURNS, std::max<int64_t>(1, GOL_BATCH_LAUNCH_UPDATES / (boards * H * W)));
 }
-
-uint64_t tail_mask(int64_t W) { return W % 64 ? ((uint64_t)1 << (W % 64)) - 1 : ~(uint64_t)0; }
 
 int range_check(const gol_batch *b, const char *what, int64_t i0, int64_t i1, const void *words, int64_t row_stride,
                 int64_t board_stride)
@@ -97,7 +98,7 @@ int reduce(gol_batch *b, bool hash, uint64_t *out, int64_t cap)
                              (long long)cap, b ? (long long)b->n : 0LL);
     OnDevice dev(b->device);
     HIPCHK(dev.err);
-    const int rc = need_aux(b);
+    const int rc = need(b->aux, b->n);
     if (rc) return rc;
     HIPCHK(golk_batch_reduce(hash, b->boards, b->n, b->H, b->W, b->aux, b->stream));
     HIPCHK(hipMemcpyAsync(out, b->aux, (size_t)b->n * sizeof(uint64_t), hipMemcpyDeviceToHost, b->stream));
@@ -105,14 +106,29 @@ int reduce(gol_batch *b, bool hash, uint64_t *out, int64_t cap)
     return GOL_OK;
 }
 
-// The device copy of the rules per board, brought up to date.
-int upload_rules(gol_batch *b)
+// The start of a stepping call: the launch descriptor with what every launch of the call shares (the boards, the shape,
+// the rule, or the device copy of the rules per board brought up to date), and for a scan (scan != GOL_BATCH_SCAN_NONE)
+// its result per board (aux) at -1 and its second buffer.  The drivers set per launch the fields that differ.
+int begin_call(gol_batch *b, int scan, int64_t turns, gol_batch_launch *l)
 {
-    if (!b->rules_dirty && b->drules) return GOL_OK;
-    if (!b->drules) HIPCHK(hipMalloc(&b->drules, b->rules.size() * sizeof(uint32_t)));
-    HIPCHK(hipMemcpyAsync(b->drules, b->rules.data(), b->rules.size() * sizeof(uint32_t), hipMemcpyHostToDevice, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));  // (the host copy may change after the call)
-    b->rules_dirty = false;
+    *l = {b->boards, nullptr, nullptr, b->n, b->H, b->W, 0, 0, false, false, b->birth, b->survive, nullptr, scan};  // (the rest 0)
+    if (scan != GOL_BATCH_SCAN_NONE) {  // (settle scan, turns < 2: nothing can be found, every board is -1)
+        int rc = need(b->aux, b->n);
+        if (!rc) rc = need(b->prev, b->n * b->H * b->Ww);
+        if (rc) return rc;
+        l->prev = b->prev;
+        l->settled = (int64_t *)b->aux;
+        HIPCHK(hipMemsetAsync(l->settled, 0xff, (size_t)b->n * sizeof(int64_t), b->stream));
+    }
+    if (b->rules.empty() || turns == 0) return GOL_OK;
+    if (b->rules_dirty || !b->drules) {
+        const int rc = need(b->drules, (int64_t)b->rules.size());
+        if (rc) return rc;
+        HIPCHK(hipMemcpyAsync(b->drules, b->rules.data(), b->rules.size() * sizeof(uint32_t), hipMemcpyHostToDevice, b->stream));
+        HIPCHK(hipStreamSynchronize(b->stream));  // (the host copy may change after the call)
+        b->rules_dirty = false;
+    }
+    l->rules = b->drules;
     return GOL_OK;
 }
 
@@ -122,27 +138,17 @@ int step(gol_batch *b, int64_t turns, int scan, int64_t *out)
 {
     OnDevice dev(b->device);
     HIPCHK(dev.err);
-    int64_t *found = nullptr;
-    if (scan != GOL_BATCH_SCAN_NONE) {  // (settle scan, turns < 2: nothing can be found, every board is -1)
-        const int rc = need_aux(b);
-        if (rc) return rc;
-        if (!b->prev) HIPCHK(hipMalloc(&b->prev, (size_t)(b->n * b->H * b->Ww) * sizeof(uint64_t)));
-        found = (int64_t *)b->aux;
-        HIPCHK(hipMemsetAsync(found, 0xff, (size_t)b->n * sizeof(int64_t), b->stream));
+    gol_batch_launch l;
+    const int rc = begin_call(b, scan, turns, &l);
+    if (rc) return rc;
+    const bool scans = scan != GOL_BATCH_SCAN_NONE;
+    for (int64_t done = 0; done < turns; done += l.turns) {
+        l.turns = (int)std::min<int64_t>(b->tpl, turns - done);
+        l.turn0 = b->turn + done, l.done = done;
+        l.have_prev = scans && done > 0, l.write_prev = scans && done + l.turns < turns;
+        HIPCHK(golk_batch_step(l, b->stream));
     }
-    const bool each = !b->rules.empty();
-    if (each && turns > 0) {
-        const int rc = upload_rules(b);
-        if (rc) return rc;
-    }
-    for (int64_t done = 0; done < turns;) {
-        const int k = (int)std::min<int64_t>(b->tpl, turns - done);
-        HIPCHK(golk_batch_step(b->boards, found ? b->prev : nullptr, found, b->n, b->H, b->W, k, b->turn + done, found && done > 0,
-                               found && done + k < turns, b->birth, b->survive, each ? b->drules : nullptr, scan, done,
-                               b->stream));
-        done += k;
-    }
-    if (found) HIPCHK(hipMemcpyAsync(out, found, (size_t)b->n * sizeof(int64_t), hipMemcpyDeviceToHost, b->stream));
+    if (scans) HIPCHK(hipMemcpyAsync(out, l.settled, (size_t)b->n * sizeof(int64_t), hipMemcpyDeviceToHost, b->stream));
     const hipError_t e = hipStreamSynchronize(b->stream);
     if (e != hipSuccess) return gol_set_error(GOL_EHIP, "batch step: %s", hipGetErrorString(e));
     b->turn += turns;
@@ -156,21 +162,14 @@ int run_cycles(gol_batch *b, int64_t turns, int64_t *out, std::vector<int64_t> &
 {
     OnDevice dev(b->device);
     HIPCHK(dev.err);
-    const int rc = need_aux(b);
+    gol_batch_launch l;
+    int rc = begin_call(b, GOL_BATCH_SCAN_CYCLES, turns, &l);
+    if (!rc) rc = need(b->lists, 2 * b->n + 2);
+    if (!rc) rc = need(b->left, b->n);
     if (rc) return rc;
-    if (!b->prev) HIPCHK(hipMalloc(&b->prev, (size_t)(b->n * b->H * b->Ww) * sizeof(uint64_t)));
-    if (!b->lists) HIPCHK(hipMalloc(&b->lists, (size_t)(2 * b->n + 2) * sizeof(int32_t)));
-    if (!b->left) HIPCHK(hipMalloc(&b->left, (size_t)b->n * sizeof(int64_t)));
     if (!b->hcounts) HIPCHK(hipHostMalloc(&b->hcounts, 2 * sizeof(int32_t), hipHostMallocDefault));
-    int64_t *found = (int64_t *)b->aux;
+    int64_t *found = l.settled;
     int32_t *active = b->lists, *finish = b->lists + b->n, *counts = b->lists + 2 * b->n;
-    HIPCHK(hipMemsetAsync(found, 0xff, (size_t)b->n * sizeof(int64_t), b->stream));
-    const bool each = !b->rules.empty();
-    if (each && turns > 0) {
-        const int rc2 = upload_rules(b);
-        if (rc2) return rc2;
-    }
-    const uint32_t *rules = each ? b->drules : nullptr;
     int32_t *host = b->hcounts;  // the boards in the two lists, as the device counts them
     host[0] = (int32_t)b->n;
     host[1] = 0;
@@ -185,21 +184,26 @@ int run_cycles(gol_batch *b, int64_t turns, int64_t *out, std::vector<int64_t> &
     };
     if (turns > 0) HIPCHK(golk_batch_iota(active, counts, b->n, b->stream));
     int64_t done = 0;
+    l.list = active, l.count = counts;
     while (done < turns && host[0] > 0) {
-        const int k = (int)std::min<int64_t>(b->auto_tpl ? auto_turns(host[0], b->H, b->W) : b->tpl, turns - done);
-        HIPCHK(golk_batch_step_list(b->boards, b->prev, found, b->n, b->H, b->W, k, b->turn + done, done > 0, done + k < turns,
-                                    b->birth, b->survive, rules, done, active, counts, host[0], nullptr, b->stream));
-        done += k;
+        l.turns = (int)std::min<int64_t>(b->auto_tpl ? auto_turns(host[0], b->H, b->W) : b->tpl, turns - done);
+        l.turn0 = b->turn + done, l.done = done, l.slots = host[0];
+        l.have_prev = done > 0, l.write_prev = done + l.turns < turns;
+        HIPCHK(golk_batch_step(l, b->stream));
+        done += l.turns;
         ends.push_back(done);
-        const int rc2 = retire(done);
-        if (rc2) return rc2;
+        rc = retire(done);
+        if (rc) return rc;
     }
+    // the finish: no scan, every listed board its own turns left
+    l.prev = nullptr, l.settled = nullptr, l.scan = GOL_BATCH_SCAN_NONE, l.have_prev = l.write_prev = false, l.done = 0;
+    l.list = finish, l.count = counts + 1, l.left = b->left, l.turn0 = b->turn + done;
     while (host[1] > 0) {
-        const int k = b->auto_tpl ? auto_turns(host[1], b->H, b->W) : b->tpl;
-        HIPCHK(golk_batch_step_list(b->boards, nullptr, nullptr, b->n, b->H, b->W, k, b->turn + done, false, false, b->birth,
-                                    b->survive, rules, 0, finish, counts + 1, host[1], b->left, b->stream));
-        const int rc2 = retire(turns);  // (the active list: no board of it is found since the last pass, or none is left)
-        if (rc2) return rc2;
+        l.turns = b->auto_tpl ? auto_turns(host[1], b->H, b->W) : b->tpl;
+        l.slots = host[1];
+        HIPCHK(golk_batch_step(l, b->stream));
+        rc = retire(turns);  // (the active list: no board of it is found since the last pass, or none is left)
+        if (rc) return rc;
     }
     HIPCHK(hipMemcpyAsync(out, found, (size_t)b->n * sizeof(int64_t), hipMemcpyDeviceToHost, b->stream));
     const hipError_t e = hipStreamSynchronize(b->stream);
@@ -208,16 +212,18 @@ int run_cycles(gol_batch *b, int64_t turns, int64_t *out, std::vector<int64_t> &
     return GOL_OK;
 }
 
-// gol_batch_search on m = min(n, total) slots in launches of L turns: the first fill, then per launch the aged step over the
-// active list, the restock pass, the harvest and the refill of the slots it names, and a blocking read of the counts, until
-// no slot is active.  The tables live on the device and are copied out once.
-int search(gol_batch *b, uint64_t seed, int64_t first, int64_t total, int64_t horizon, int64_t m, int L, int64_t *found,
-           int64_t *period, uint64_t *alive, uint64_t *hash, gol_batch_search_stats *st)
+// gol_batch_search on st->slots = min(n, total) slots in launches of st->launch_turns turns: the first fill, then per
+// launch the aged step over the active list, the restock pass, the harvest and the refill of the slots it names, and a
+// blocking read of the counts, until no slot is active.  The tables live on the device and are copied out once.
+int search(gol_batch *b, uint64_t seed, int64_t first, int64_t total, int64_t horizon, int64_t *found, int64_t *period,
+           uint64_t *alive, uint64_t *hash, gol_batch_search_stats *st)
 {
-    const int64_t n = b->n;
-    if (!b->prev) HIPCHK(hipMalloc(&b->prev, (size_t)(n * b->H * b->Ww) * sizeof(uint64_t)));
-    if (!b->slists) HIPCHK(hipMalloc(&b->slists, (size_t)(4 * n + 4) * sizeof(int32_t)));
-    if (!b->sages) HIPCHK(hipMalloc(&b->sages, (size_t)(2 * n) * sizeof(int64_t)));
+    const int64_t n = b->n, m = st->slots;
+    const int L = (int)st->launch_turns;
+    int rc = need(b->prev, n * b->H * b->Ww);
+    if (!rc) rc = need(b->slists, 4 * n + 4);
+    if (!rc) rc = need(b->sages, 2 * n);
+    if (rc) return rc;
     if (!b->scounts) HIPCHK(hipHostMalloc(&b->scounts, 4 * sizeof(int32_t), hipHostMallocDefault));
     if (b->tab_cap < total) {
         if (b->tab) HIPCHK(hipFree(b->tab));
@@ -234,12 +240,15 @@ int search(gol_batch *b, uint64_t seed, int64_t first, int64_t total, int64_t ho
     HIPCHK(hipMemsetAsync(talive, 0, (size_t)(2 * total) * sizeof(uint64_t), b->stream));
     HIPCHK(golk_batch_soups(b->boards, m, b->H, b->W, seed, first, b->stream));
     HIPCHK(golk_batch_search_init(active, counts, soup, born, age, m, b->stream));
+    // the aged launch: the cycle scan of the listed slots in their own ages from turn 0, the snapshot always written
+    gol_batch_launch l = {b->boards, b->prev, age, n, b->H, b->W, L, 0, false, true, b->birth, b->survive, nullptr,
+                          GOL_BATCH_SCAN_CYCLES, 0, active, counts, 0, nullptr, born};
     int32_t *host = b->scounts;
     host[0] = (int32_t)m;
     for (int64_t done = 0; host[0] > 0;) {
         const int64_t in = host[0];
-        HIPCHK(golk_batch_step_aged(b->boards, b->prev, age, born, n, b->H, b->W, L, b->birth, b->survive, done, active, counts,
-                                    in, b->stream));
+        l.have_prev = done > 0, l.done = done, l.slots = in;
+        HIPCHK(golk_batch_step(l, b->stream));
         done += L;
         st->launches += 1;
         st->board_turns += in * L;
@@ -263,6 +272,42 @@ int search(gol_batch *b, uint64_t seed, int64_t first, int64_t total, int64_t ho
     return GOL_OK;
 }
 
+// gol_batch_load_words (load) and gol_batch_store_words: boards [i0, i1) between the caller's rows, row_stride and
+// board_stride words apart, and the device.  Dense rows go in one copy (a load only when no row has padding to mask);
+// others through a dense host block of at most GOL_BATCH_STAGE_BYTES: a load masks every row's last word, a store writes
+// the Ww words of a row and leaves what lies between rows and boards.
+int copy_words(gol_batch *b, bool load, int64_t i0, int64_t i1, uint64_t *words, int64_t row_stride, int64_t board_stride)
+{
+    OnDevice dev(b->device);
+    HIPCHK(dev.err);
+    const int64_t bw = b->H * b->Ww;  // words of a board on the device
+    const hipMemcpyKind kind = load ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost;
+    auto copy = [&](uint64_t *host, int64_t c0, int64_t c1) -> int {  // (blocks: the stage is reused)
+        uint64_t *d = b->boards + c0 * bw;
+        HIPCHK(hipMemcpyAsync(load ? d : host, load ? host : d, (size_t)((c1 - c0) * bw) * sizeof(uint64_t), kind, b->stream));
+        HIPCHK(hipStreamSynchronize(b->stream));
+        return GOL_OK;
+    };
+    if (row_stride == b->Ww && board_stride == bw && !(load && b->W % 64)) return copy(words, i0, i1);
+    const int64_t per = std::max<int64_t>(1, GOL_BATCH_STAGE_BYTES / (bw * (int64_t)sizeof(uint64_t)));
+    const uint64_t tail = gol_batch_tail64(b->W);
+    std::vector<uint64_t> stage((size_t)(std::min(per, std::max<int64_t>(i1 - i0, 1)) * bw));
+    for (int64_t c0 = i0; c0 < i1; c0 += per) {
+        const int64_t c1 = std::min(i1, c0 + per);
+        int rc = load ? GOL_OK : copy(stage.data(), c0, c1);
+        if (rc) return rc;
+        for (int64_t i = c0; i < c1; ++i)
+            for (int64_t y = 0; y < b->H; ++y) {
+                uint64_t *d = stage.data() + ((i - c0) * b->H + y) * b->Ww, *w = words + (i - i0) * board_stride + y * row_stride;
+                memcpy(load ? d : w, load ? w : d, (size_t)b->Ww * sizeof(uint64_t));
+                if (load) d[b->Ww - 1] &= tail;
+            }
+        rc = load ? copy(stage.data(), c0, c1) : GOL_OK;
+        if (rc) return rc;
+    }
+    return GOL_OK;
+}
+
 }  // namespace
 
 extern "C" void gol_batch_destroy(gol_batch *b)
@@ -271,17 +316,11 @@ extern "C" void gol_batch_destroy(gol_batch *b)
     {
         OnDevice dev(b->device);
         if (b->stream) (void)hipStreamSynchronize(b->stream);
-        if (b->boards) (void)hipFree(b->boards);
-        if (b->prev) (void)hipFree(b->prev);
-        if (b->aux) (void)hipFree(b->aux);
-        if (b->drules) (void)hipFree(b->drules);
-        if (b->lists) (void)hipFree(b->lists);
-        if (b->left) (void)hipFree(b->left);
-        if (b->hcounts) (void)hipHostFree(b->hcounts);
-        if (b->slists) (void)hipFree(b->slists);
-        if (b->sages) (void)hipFree(b->sages);
-        if (b->tab) (void)hipFree(b->tab);
-        if (b->scounts) (void)hipHostFree(b->scounts);
+        void *const device[] = {b->boards, b->prev, b->aux, b->drules, b->lists, b->left, b->slists, b->sages, b->tab};
+        for (void *p : device)
+            if (p) (void)hipFree(p);
+        for (void *p : {(void *)b->hcounts, (void *)b->scounts})
+            if (p) (void)hipHostFree(p);
         if (b->stream) (void)hipStreamDestroy(b->stream);
     }
     delete b;
@@ -289,8 +328,7 @@ extern "C" void gol_batch_destroy(gol_batch *b)
 
 extern "C" int gol_batch_create(int64_t n, int64_t H, int64_t W, int32_t device, int32_t turns_per_launch, gol_batch **out)
 {
-    if (!out || n < 1 || n > GOL_BATCH_MAX_BOARDS || H < 1 || H > GOL_BATCH_MAX_SIDE || W < 1 || W > GOL_BATCH_MAX_SIDE ||
-        turns_per_launch < 0 || device < -1)
+    if (!out || !gol_batch_shape_ok(n, H, W) || turns_per_launch < 0 || device < -1)
         return gol_set_error(GOL_EINVAL, "bad batch (n %lld in 1..2^20, H %lld and W %lld in 1..%d, turns per launch %d >= 0)",
                              (long long)n, (long long)H, (long long)W, GOL_BATCH_MAX_SIDE, turns_per_launch);
     *out = nullptr;
@@ -414,75 +452,21 @@ extern "C" int gol_batch_turn(gol_batch *b, int64_t *turn)
 extern "C" int gol_batch_load_words(gol_batch *b, int64_t i0, int64_t i1, const uint64_t *words, int64_t row_stride,
                                     int64_t board_stride)
 {
-    const int rc = range_check(b, "load_words", i0, i1, words, row_stride, board_stride);
-    if (rc) return rc;
-    OnDevice dev(b->device);
-    HIPCHK(dev.err);
-    const int64_t bw = b->H * b->Ww;  // words of a board on the device
-    if (row_stride == b->Ww && board_stride == bw && b->W % 64 == 0) {
-        HIPCHK(hipMemcpyAsync(b->boards + i0 * bw, words, (size_t)((i1 - i0) * bw) * sizeof(uint64_t), hipMemcpyHostToDevice,
-                              b->stream));
-        HIPCHK(hipStreamSynchronize(b->stream));
-    } else {  // dense and masked on the host first
-        const int64_t per = std::max<int64_t>(1, GOL_BATCH_STAGE_BYTES / (bw * (int64_t)sizeof(uint64_t)));
-        const uint64_t tail = tail_mask(b->W);
-        std::vector<uint64_t> stage((size_t)(std::min(per, std::max<int64_t>(i1 - i0, 1)) * bw));
-        for (int64_t c0 = i0; c0 < i1; c0 += per) {
-            const int64_t c1 = std::min(i1, c0 + per);
-            for (int64_t i = c0; i < c1; ++i)
-                for (int64_t y = 0; y < b->H; ++y) {
-                    uint64_t *d = stage.data() + ((i - c0) * b->H + y) * b->Ww;
-                    memcpy(d, words + (i - i0) * board_stride + y * row_stride, (size_t)b->Ww * sizeof(uint64_t));
-                    d[b->Ww - 1] &= tail;
-                }
-            HIPCHK(hipMemcpyAsync(b->boards + c0 * bw, stage.data(), (size_t)((c1 - c0) * bw) * sizeof(uint64_t),
-                                  hipMemcpyHostToDevice, b->stream));
-            HIPCHK(hipStreamSynchronize(b->stream));  // (the stage is reused)
-        }
-    }
-    b->turn = 0;
-    return GOL_OK;
+    int rc = range_check(b, "load_words", i0, i1, words, row_stride, board_stride);
+    if (!rc) rc = copy_words(b, true, i0, i1, const_cast<uint64_t *>(words), row_stride, board_stride);  // (only read)
+    if (!rc) b->turn = 0;
+    return rc;
 }
 
 extern "C" int gol_batch_store_words(gol_batch *b, int64_t i0, int64_t i1, uint64_t *words, int64_t row_stride,
                                      int64_t board_stride)
 {
     const int rc = range_check(b, "store_words", i0, i1, words, row_stride, board_stride);
-    if (rc) return rc;
-    OnDevice dev(b->device);
-    HIPCHK(dev.err);
-    const int64_t bw = b->H * b->Ww;
-    if (row_stride == b->Ww && board_stride == bw) {
-        HIPCHK(hipMemcpyAsync(words, b->boards + i0 * bw, (size_t)((i1 - i0) * bw) * sizeof(uint64_t), hipMemcpyDeviceToHost,
-                              b->stream));
-        HIPCHK(hipStreamSynchronize(b->stream));
-        return GOL_OK;
-    }
-    const int64_t per = std::max<int64_t>(1, GOL_BATCH_STAGE_BYTES / (bw * (int64_t)sizeof(uint64_t)));
-    std::vector<uint64_t> stage((size_t)(std::min(per, std::max<int64_t>(i1 - i0, 1)) * bw));
-    for (int64_t c0 = i0; c0 < i1; c0 += per) {
-        const int64_t c1 = std::min(i1, c0 + per);
-        HIPCHK(hipMemcpyAsync(stage.data(), b->boards + c0 * bw, (size_t)((c1 - c0) * bw) * sizeof(uint64_t),
-                              hipMemcpyDeviceToHost, b->stream));
-        HIPCHK(hipStreamSynchronize(b->stream));
-        for (int64_t i = c0; i < c1; ++i)
-            for (int64_t y = 0; y < b->H; ++y)  // Ww words of a row: the words between rows and boards stay
-                memcpy(words + (i - i0) * board_stride + y * row_stride, stage.data() + ((i - c0) * b->H + y) * b->Ww,
-                       (size_t)b->Ww * sizeof(uint64_t));
-    }
-    return GOL_OK;
+    return rc ? rc : copy_words(b, false, i0, i1, words, row_stride, board_stride);
 }
 
-extern "C" int gol_batch_load_random(gol_batch *b, uint64_t seed)
-{
-    if (!b) return gol_set_error(GOL_EINVAL, "batch is NULL");
-    OnDevice dev(b->device);
-    HIPCHK(dev.err);
-    HIPCHK(golk_batch_random(b->boards, b->n, b->H, b->W, seed, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
-    b->turn = 0;
-    return GOL_OK;
-}
+// (the supply from its first word)
+extern "C" int gol_batch_load_random(gol_batch *b, uint64_t seed) { return gol_batch_load_soups(b, seed, 0); }
 
 extern "C" int gol_batch_load_soups(gol_batch *b, uint64_t seed, int64_t first)
 {
@@ -514,15 +498,10 @@ extern "C" int gol_batch_search(gol_batch *b, uint64_t seed, int64_t first, int6
     st.slots = m;
     st.launch_turns = L;
     if (total > 0 && horizon > 0) {
-        const int rc = search(b, seed, first, total, horizon, m, (int)L, found, period, alive, hash, &st);
+        const int rc = search(b, seed, first, total, horizon, found, period, alive, hash, &st);
         if (rc) return rc;
-    } else {  // nothing to run: every soup is at -1
-        for (int64_t g = 0; g < total; ++g) {
-            found[g] = -1;
-            if (period) period[g] = -1;
-            if (alive) alive[g] = 0;
-            if (hash) hash[g] = 0;
-        }
+    } else {  // nothing to run
+        gol_batch_no_results(total, found, period, alive, hash);
     }
     HIPCHK(hipMemsetAsync(b->boards, 0, (size_t)(b->n * b->H * b->Ww) * sizeof(uint64_t), b->stream));
     HIPCHK(hipStreamSynchronize(b->stream));
@@ -546,7 +525,7 @@ extern "C" int gol_batch_step_cycles(gol_batch *b, int64_t turns, int64_t *found
     if (rc) return rc;
     if (period)  // found - the last mark before it, with the kernel's own mark function
         for (int64_t i = 0; i < b->n; ++i)
-            period[i] = found[i] < 0 ? -1 : found[i] - t0 - gol_batch_last_mark(found[i] - t0);
+            period[i] = found[i] < 0 ? -1 : gol_batch_period(found[i] - t0);
     return GOL_OK;
 }
 
@@ -565,7 +544,7 @@ extern "C" int gol_batch_run_cycles(gol_batch *b, int64_t turns, int64_t *found,
     if (rc) return rc;
     for (int64_t i = 0; i < b->n; ++i) {
         const int64_t d = found[i] < 0 ? 0 : found[i] - t0;
-        if (period) period[i] = d ? d - gol_batch_last_mark(d) : -1;
+        if (period) period[i] = d ? gol_batch_period(d) : -1;
         if (made && !d) made[i] = turns;
         if (made && d) {  // the board left after the first launch that ended at or after d, and made its remainder
             const int64_t at = *std::lower_bound(ends.begin(), ends.end(), d);

@@ -3,7 +3,8 @@
 // picks for the width, row by row as the lanes do; and gol_batch_cycles_host: the cycle scan of one
 // board with that turn and the mark functions the kernel and the engine use; and gol_batch_run_cycles_host: the
 // retiring scheme of gol_batch_run_cycles on one board, with the remainder function the retire pass runs; and gol_batch_soup_host and
-// gol_batch_search_host: a soup from the fill kernels' word function, and the scheme of gol_batch_search.  No HIP
+// gol_batch_search_host: a soup from the fill kernels' word function, and the scheme of gol_batch_search; and
+// gol_batch_step_check_host: the check every launch of the step kernel passes (gol_batch_launch_ok).  No HIP
 // header: a stand-alone program links this file alone (batch_check.cpp).
 #include <stdint.h>
 
@@ -56,13 +57,57 @@ void step_host(int64_t H, const gol_batch_row &g, uint32_t birth, uint32_t survi
     }
 }
 
+// The twins' argument check: one board's shape and rule, and rows of row_stride words to read and to write.
+bool args_ok(int64_t H, int64_t W, uint32_t birth, uint32_t survive, const void *in, const void *out, int64_t row_stride)
+{
+    return gol_batch_shape_ok(1, H, W) && birth < 512 && survive < 512 && in && out && row_stride >= (W + 63) / 64;
+}
+
+// One board of a scheme: its shape and rule, and its cells as a dense block with the padding clear.
+struct Board {
+    int64_t H, W, Ww;
+    uint32_t birth, survive;
+    std::vector<uint64_t> cur;
+
+    Board(int64_t H, int64_t W, uint32_t birth, uint32_t survive, const uint64_t *in, int64_t row_stride)
+        : H(H), W(W), Ww((W + 63) / 64), birth(birth), survive(survive), cur((size_t)(H * Ww))
+    {
+        for (int64_t y = 0; y < H; ++y)
+            for (int64_t w = 0; w < Ww; ++w)
+                cur[(size_t)(y * Ww + w)] = in[y * row_stride + w] & (w == Ww - 1 ? gol_batch_tail64(W) : ~(uint64_t)0);
+    }
+    int step() { return gol_batch_step_host(H, W, birth, survive, cur.data(), cur.data(), Ww); }
+    void store(uint64_t *out, int64_t row_stride) const  // (the words between the rows stay)
+    {
+        for (int64_t y = 0; y < H; ++y)
+            for (int64_t w = 0; w < Ww; ++w) out[y * row_stride + w] = cur[(size_t)(y * Ww + w)];
+    }
+};
+
+// The cycle scan of a board from the mark d = 0, at most `turns` turns: *found = the first d with state(d) == state(the
+// last mark before d), else -1.  launch > 0: the scan is cut into launches and ends with the launch the board is found in
+// (gol_batch_run_cycles); 0: it runs all its turns.  *made = the turns made.
+int scan(Board &b, int64_t turns, int64_t launch, int64_t *found, int64_t *made)
+{
+    std::vector<uint64_t> snap = b.cur;
+    int64_t f = -1, d = 1;
+    for (; d <= turns && !(launch > 0 && f >= 0 && (d - 1) % launch == 0); ++d) {
+        const int rc = b.step();
+        if (rc) return rc;
+        if (f < 0 && b.cur == snap) f = d;
+        if (gol_batch_is_mark(d)) snap = b.cur;  // (after the comparison: a mark is compared with the mark before it)
+    }
+    *found = f;
+    *made = d - 1;
+    return GOL_OK;
+}
+
 }  // namespace
 
 extern "C" int gol_batch_step_host(int64_t H, int64_t W, uint32_t birth, uint32_t survive, const uint64_t *in, uint64_t *out,
                                    int64_t row_stride)
 {
-    if (H < 1 || H > GOL_BATCH_MAX_SIDE || W < 1 || W > GOL_BATCH_MAX_SIDE || birth >= 512 || survive >= 512 || !in || !out ||
-        row_stride < (W + 63) / 64)
+    if (!args_ok(H, W, birth, survive, in, out, row_stride))
         return gol_set_error(GOL_EINVAL, "bad host batch step (H %lld, W %lld, B 0x%x, S 0x%x, row stride %lld)", (long long)H,
                              (long long)W, birth, survive, (long long)row_stride);
     const gol_batch_row g = gol_batch_row_init(W);
@@ -76,68 +121,41 @@ extern "C" int gol_batch_step_host(int64_t H, int64_t W, uint32_t birth, uint32_
     return GOL_OK;
 }
 
-extern "C" int gol_batch_cycles_host(int64_t H, int64_t W, uint32_t birth, uint32_t survive, const uint64_t *in, uint64_t *out,
-                                     int64_t row_stride, int64_t turns, int64_t *found, int64_t *period)
-{
-    const int64_t Ww = (W + 63) / 64;
-    if (H < 1 || H > GOL_BATCH_MAX_SIDE || W < 1 || W > GOL_BATCH_MAX_SIDE || birth >= 512 || survive >= 512 || !in || !out ||
-        row_stride < Ww || turns < 0 || !found)
-        return gol_set_error(GOL_EINVAL, "bad host batch cycles (H %lld, W %lld, B 0x%x, S 0x%x, row stride %lld, turns %lld)",
-                             (long long)H, (long long)W, birth, survive, (long long)row_stride, (long long)turns);
-    const uint64_t tail = W % 64 ? ((uint64_t)1 << (W % 64)) - 1 : ~(uint64_t)0;
-    std::vector<uint64_t> cur((size_t)(H * Ww)), snap;  // dense, the padding clear; the snapshot of the mark d = 0
-    for (int64_t y = 0; y < H; ++y)
-        for (int64_t w = 0; w < Ww; ++w) cur[(size_t)(y * Ww + w)] = in[y * row_stride + w] & (w == Ww - 1 ? tail : ~(uint64_t)0);
-    snap = cur;
-    *found = -1;
-    if (period) *period = -1;
-    for (int64_t d = 1; d <= turns; ++d) {
-        const int rc = gol_batch_step_host(H, W, birth, survive, cur.data(), cur.data(), Ww);
-        if (rc) return rc;
-        if (*found < 0 && cur == snap) {
-            *found = d;
-            if (period) *period = d - gol_batch_last_mark(d);
-        }
-        if (gol_batch_is_mark(d)) snap = cur;  // (after the comparison: a mark is compared with the mark before it)
-    }
-    for (int64_t y = 0; y < H; ++y)
-        for (int64_t w = 0; w < Ww; ++w) out[y * row_stride + w] = cur[(size_t)(y * Ww + w)];
-    return GOL_OK;
-}
-
 extern "C" int gol_batch_run_cycles_host(int64_t H, int64_t W, uint32_t birth, uint32_t survive, const uint64_t *in, uint64_t *out,
                                          int64_t row_stride, int64_t turns, int64_t launch, int64_t *found, int64_t *period,
                                          int64_t *made)
 {
-    const int64_t Ww = (W + 63) / 64;
-    if (H < 1 || H > GOL_BATCH_MAX_SIDE || W < 1 || W > GOL_BATCH_MAX_SIDE || birth >= 512 || survive >= 512 || !in || !out ||
-        row_stride < Ww || turns < 0 || !found || launch < 1)
+    if (!args_ok(H, W, birth, survive, in, out, row_stride) || turns < 0 || !found || launch < 1)
         return gol_set_error(GOL_EINVAL,
                              "bad host batch run_cycles (H %lld, W %lld, B 0x%x, S 0x%x, row stride %lld, turns %lld, launch %lld)",
                              (long long)H, (long long)W, birth, survive, (long long)row_stride, (long long)turns, (long long)launch);
-    const uint64_t tail = W % 64 ? ((uint64_t)1 << (W % 64)) - 1 : ~(uint64_t)0;
-    std::vector<uint64_t> cur((size_t)(H * Ww)), snap;
-    for (int64_t y = 0; y < H; ++y)
-        for (int64_t w = 0; w < Ww; ++w) cur[(size_t)(y * Ww + w)] = in[y * row_stride + w] & (w == Ww - 1 ? tail : ~(uint64_t)0);
-    snap = cur;
+    Board b(H, W, birth, survive, in, row_stride);
     int64_t f = -1, did = 0;
     // the search, in launches: the board leaves at the end of the launch it is found in
-    for (int64_t d = 1; d <= turns && !(f >= 0 && (d - 1) % launch == 0); ++d, ++did) {
-        const int rc = gol_batch_step_host(H, W, birth, survive, cur.data(), cur.data(), Ww);
-        if (rc) return rc;
-        if (f < 0 && cur == snap) f = d;
-        if (gol_batch_is_mark(d)) snap = cur;
-    }
+    int rc = scan(b, turns, launch, &f, &did);
     // the finish: the turns of the call still to come, modulo the period
-    for (int64_t left = f < 0 ? 0 : gol_batch_turns_left(f, turns - did); left > 0; --left, ++did) {
-        const int rc = gol_batch_step_host(H, W, birth, survive, cur.data(), cur.data(), Ww);
-        if (rc) return rc;
-    }
+    for (int64_t left = f < 0 ? 0 : gol_batch_turns_left(f, turns - did); left > 0 && !rc; --left, ++did) rc = b.step();
+    if (rc) return rc;
     *found = f;
-    if (period) *period = f < 0 ? -1 : f - gol_batch_last_mark(f);
+    if (period) *period = f < 0 ? -1 : gol_batch_period(f);
     if (made) *made = did;
-    for (int64_t y = 0; y < H; ++y)
-        for (int64_t w = 0; w < Ww; ++w) out[y * row_stride + w] = cur[(size_t)(y * Ww + w)];
+    b.store(out, row_stride);
+    return GOL_OK;
+}
+
+// (the scan alone, all its turns: the board never leaves, so there is no remainder to make)
+extern "C" int gol_batch_cycles_host(int64_t H, int64_t W, uint32_t birth, uint32_t survive, const uint64_t *in, uint64_t *out,
+                                     int64_t row_stride, int64_t turns, int64_t *found, int64_t *period)
+{
+    if (!args_ok(H, W, birth, survive, in, out, row_stride) || turns < 0 || !found)
+        return gol_set_error(GOL_EINVAL, "bad host batch cycles (H %lld, W %lld, B 0x%x, S 0x%x, row stride %lld, turns %lld)",
+                             (long long)H, (long long)W, birth, survive, (long long)row_stride, (long long)turns);
+    Board b(H, W, birth, survive, in, row_stride);
+    int64_t made;
+    const int rc = scan(b, turns, 0, found, &made);
+    if (rc) return rc;  // (not reached: the arguments are good)
+    if (period) *period = *found < 0 ? -1 : gol_batch_period(*found);
+    b.store(out, row_stride);
     return GOL_OK;
 }
 
@@ -146,14 +164,12 @@ extern "C" int gol_batch_verdict_host(int64_t found, int64_t age, int64_t horizo
 extern "C" int gol_batch_soup_host(int64_t H, int64_t W, uint64_t seed, int64_t index, uint64_t *out, int64_t row_stride)
 {
     const int64_t Ww = (W + 63) / 64;
-    if (H < 1 || H > GOL_BATCH_MAX_SIDE || W < 1 || W > GOL_BATCH_MAX_SIDE || index < 0 || index > ((int64_t)1 << 40) || !out ||
-        row_stride < Ww)
+    if (!args_ok(H, W, 0, 0, out, out, row_stride) || index < 0 || index > ((int64_t)1 << 40))
         return gol_set_error(GOL_EINVAL, "bad host batch soup (H %lld, W %lld, index %lld, row stride %lld)", (long long)H,
                              (long long)W, (long long)index, (long long)row_stride);
-    const uint64_t tail = W % 64 ? ((uint64_t)1 << (W % 64)) - 1 : ~(uint64_t)0;
     for (int64_t y = 0; y < H; ++y)
         for (int64_t w = 0; w < Ww; ++w)
-            out[y * row_stride + w] = gol_batch_soup_word(seed, (uint64_t)((index * H + y) * Ww + w), Ww, tail);
+            out[y * row_stride + w] = gol_batch_soup_word(seed, (uint64_t)((index * H + y) * Ww + w), Ww, gol_batch_tail64(W));
     return GOL_OK;
 }
 
@@ -163,21 +179,16 @@ extern "C" int gol_batch_search_host(int64_t H, int64_t W, uint32_t birth, uint3
                                      int64_t total, int64_t slots, int64_t launch, int64_t horizon, int64_t *found,
                                      int64_t *period, uint64_t *alive, uint64_t *hash)
 {
-    if (H < 1 || H > GOL_BATCH_MAX_SIDE || W < 1 || W > GOL_BATCH_MAX_SIDE || birth >= 512 || survive >= 512 || !found ||
-        first < 0 || total < 0 || horizon < 0 || first > ((int64_t)1 << 40) || total > ((int64_t)1 << 26) ||
-        first + total > ((int64_t)1 << 40) || slots < 1 || launch < 1)
+    // (no rows of the caller's: the result arrays stand in for them)
+    if (!args_ok(H, W, birth, survive, found, found, (W + 63) / 64) || first < 0 || total < 0 || horizon < 0 ||
+        first > ((int64_t)1 << 40) || total > ((int64_t)1 << 26) || first + total > ((int64_t)1 << 40) || slots < 1 || launch < 1)
         return gol_set_error(GOL_EINVAL,
                              "bad host batch search (H %lld, W %lld, B 0x%x, S 0x%x, soups [%lld, +%lld), slots %lld, launch %lld, "
                              "horizon %lld)",
                              (long long)H, (long long)W, birth, survive, (long long)first, (long long)total, (long long)slots,
                              (long long)launch, (long long)horizon);
     const int64_t Ww = (W + 63) / 64, bw = H * Ww, m = slots < total ? slots : total;
-    for (int64_t g = 0; g < total; ++g) {
-        found[g] = -1;
-        if (period) period[g] = -1;
-        if (alive) alive[g] = 0;
-        if (hash) hash[g] = 0;
-    }
+    gol_batch_no_results(total, found, period, alive, hash);
     if (total == 0 || horizon == 0) return GOL_OK;
     struct Slot {
         std::vector<uint64_t> cur, snap;
@@ -221,13 +232,10 @@ extern "C" int gol_batch_search_host(int64_t H, int64_t W, uint32_t birth, uint3
                 continue;
             }
             if (v == GOL_BATCH_FOUND) {  // the harvest: s(found) is the snapshot
-                uint64_t a = 0, h = 0;
-                for (int64_t k = 0; k < bw; ++k) {
-                    a += (uint64_t)__builtin_popcountll(s.snap[(size_t)k]);
-                    h += gol_batch_splitmix64(s.snap[(size_t)k] ^ gol_batch_splitmix64((uint64_t)k));
-                }
+                uint64_t a, h;
+                gol_batch_census(s.snap.data(), bw, &a, &h);
                 found[s.soup] = s.found;
-                if (period) period[s.soup] = s.found - gol_batch_last_mark(s.found);
+                if (period) period[s.soup] = gol_batch_period(s.found);
                 if (alive) alive[s.soup] = a;
                 if (hash) hash[s.soup] = h;
             }
@@ -240,4 +248,17 @@ extern "C" int gol_batch_search_host(int64_t H, int64_t W, uint32_t birth, uint3
         active.swap(stay);
     }
     return GOL_OK;
+}
+
+extern "C" int gol_batch_step_check_host(const uint64_t *boards, const uint64_t *prev, const int64_t *settled, int64_t n, int64_t H,
+                                         int64_t W, int32_t turns, int64_t turn0, int32_t have_prev, int32_t write_prev,
+                                         uint32_t birth, uint32_t survive, const uint32_t *rules, int32_t scan, int64_t done,
+                                         const int32_t *list, const int32_t *count, int64_t slots, const int64_t *left,
+                                         const int64_t *born)
+{
+    // (the check reads the pointers' values alone)
+    const gol_batch_launch l = {const_cast<uint64_t *>(boards), const_cast<uint64_t *>(prev), const_cast<int64_t *>(settled), n, H, W,
+                                turns, turn0, have_prev != 0, write_prev != 0, birth, survive, rules, scan, done, list, count, slots,
+                                const_cast<int64_t *>(left), born};
+    return gol_batch_launch_ok(l) ? GOL_OK : GOL_EINVAL;
 }

@@ -145,30 +145,17 @@ int64_t golk_bounds_lanes(int form, const void *src, int64_t pitch, int64_t W, i
 hipError_t golk_bounds_cols(int form, const void *src, int64_t pitch, int64_t W, int64_t x0, int64_t w, const uint32_t *occ,
                             uint64_t *hdr, hipStream_t s);
 
-// Batches of small boards (gol_batch.hip): n tori of H x W cells (1 <= H, W <= 512, n <= 2^20), board i
-// at boards + i*H*Ww, Ww = ceil(W / 64) uint64 words per row, the bits at c >= W of a row zero.
-// golk_batch_shape: waves per board, boards per workgroup and 32-bit words per lane of the step kernel.
-// golk_batch_step: `turns` >= 1 turns of every board in one launch, in place.  settled != NULL (then
-// prev != NULL, a second buffer of the boards' shape): settled[i] < 0 becomes the first turn t in
-// (turn0 + (have_prev ? 0 : 1), turn0 + turns] with state(t) == state(t - 2); have_prev: prev holds
-// state(turn0 - 1); write_prev: prev receives state(turn0 + turns - 1).  That is scan =
-// GOL_BATCH_SCAN_SETTLE (gol_batch.h; settled == NULL: GOL_BATCH_SCAN_NONE).  GOL_BATCH_SCAN_CYCLES: the
-// launch begins `done` turns into its call (have_prev = done > 0), prev carries the snapshot of the
-// call's last mark instead, and settled[i] < 0 becomes the first turn t in (turn0, turn0 + turns] with
-// state(t) == state(the last mark before t).  rules != NULL: n pairs (birth, survive) in device
-// memory, board i under pair i (birth and survive are not used); else every board under birth / survive.
+// Batches of small boards: n tori of H x W cells (1 <= H, W <= 512, n <= 2^20), board i at boards + i*H*Ww, Ww =
+// ceil(W / 64) uint64 words per row, the bits at c >= W of a row zero.
+// The step kernel (gol_batch.hip).  golk_batch_shape: waves per board, boards per workgroup and 32-bit words per lane.
+// golk_batch_step: one launch, `turns` >= 1 turns in place, of what the descriptor says (gol_batch.h; the modes and every
+// field are those of gol_dev_batch_step, include/golhip.h): every board, or with a list the boards list[0 .. *count)
+// alone, *count <= slots <= n, where slots sizes the grid (without a list slots is 0 and n sizes it).
+// hipErrorInvalidValue, nothing launched, unless gol_batch_launch_ok accepts the descriptor.
+struct gol_batch_launch;
 void golk_batch_shape(int64_t H, int64_t W, int *waves_per_board, int *boards_per_wg, int *words_per_lane);
-hipError_t golk_batch_step(uint64_t *boards, uint64_t *prev, int64_t *settled, int64_t n, int64_t H, int64_t W, int turns,
-                           int64_t turn0, bool have_prev, bool write_prev, uint32_t birth, uint32_t survive,
-                           const uint32_t *rules, int scan, int64_t done, hipStream_t s);
-// The same launch over the boards list[0 .. *count) alone (device memory; *count <= slots <= n, which sizes the grid).
-// settled != NULL: the cycle scan of those boards (the search of gol_batch_run_cycles); left != NULL instead: no
-// scan, board i makes min(turns, left[i]) turns and left[i] loses them (the finish).  prev, settled, rules and left
-// are indexed by the board's own number.
-hipError_t golk_batch_step_list(uint64_t *boards, uint64_t *prev, int64_t *settled, int64_t n, int64_t H, int64_t W, int turns,
-                                int64_t turn0, bool have_prev, bool write_prev, uint32_t birth, uint32_t survive,
-                                const uint32_t *rules, int64_t done, const int32_t *list, const int32_t *count, int64_t slots,
-                                int64_t *left, hipStream_t s);
+hipError_t golk_batch_step(const gol_batch_launch &launch, hipStream_t s);
+// The small kernels (gol_batch_pass.hip).
 // list[i] = i for i < n, counts = {n, 0}
 hipError_t golk_batch_iota(int32_t *list, int32_t *counts, int64_t n, hipStream_t s);
 // The retire pass (one workgroup, stable): counts[0] entries of list_in, counts[1] of finish.  finish loses the
@@ -177,16 +164,11 @@ hipError_t golk_batch_iota(int32_t *list, int32_t *counts, int64_t n, hipStream_
 // the two new counts.
 hipError_t golk_batch_retire(const int32_t *list_in, int32_t *counts, const int64_t *found, int64_t n, int64_t t0,
                              int64_t t_now, int64_t t_end, int32_t *active, int32_t *finish, int64_t *left, hipStream_t s);
-// word(i, y, w) = splitmix64(seed ^ ((i*H + y)*Ww + w)) masked to W
-hipError_t golk_batch_random(uint64_t *boards, int64_t n, int64_t H, int64_t W, uint64_t seed, hipStream_t s);
 // out[i] = alive cells of board i, or (hash) its oracle_hash_words
 hipError_t golk_batch_reduce(bool hash, const uint64_t *boards, int64_t n, int64_t H, int64_t W, uint64_t *out, hipStream_t s);
 // gol_batch_search (a slot is a board of the batch; a soup's number counts from the search's `first`).
-// golk_batch_soups: board j = soup first + j (gol_batch_soup_word, gol_batch.h), j < n.
+// golk_batch_soups: board j = soup first + j (gol_batch_soup_word, gol_batch.h), j < n; first = 0: gol_batch_load_random.
 // golk_batch_search_init: slots 0 .. m - 1 active with soups 0 .. m - 1, born at 0, not found; counts = {m, 0, 0, m}.
-// golk_batch_step_aged: the list launch of the cycle scan with an age per board: done - born[board] turns of the board's
-// scan lie before the launch (0: the loaded state is the snapshot and prev is not read), found[board] < 0 becomes the age at
-// which the board is found, prev[board] the snapshot after the launch, which stays s(found) once the board is found.
 // golk_batch_restock: the pass between the launches (include/golhip.h, gol_dev_batch_restock).  golk_batch_harvest: alive
 // and hash of prev[slot] into the tables for the counts[1] pairs (slot, soup) of the harvest list, 0, 0 where found[soup] <
 // 0.  golk_batch_refill: the soup words of the slots of its first counts[2] pairs.  slots: an upper bound of those counts
@@ -194,9 +176,6 @@ hipError_t golk_batch_reduce(bool hash, const uint64_t *boards, int64_t n, int64
 hipError_t golk_batch_soups(uint64_t *boards, int64_t n, int64_t H, int64_t W, uint64_t seed, int64_t first, hipStream_t s);
 hipError_t golk_batch_search_init(int32_t *active, int32_t *counts, int32_t *soup, int64_t *born, int64_t *found, int64_t m,
                                   hipStream_t s);
-hipError_t golk_batch_step_aged(uint64_t *boards, uint64_t *prev, int64_t *found, const int64_t *born, int64_t n, int64_t H,
-                                int64_t W, int turns, uint32_t birth, uint32_t survive, int64_t done, const int32_t *list,
-                                const int32_t *count, int64_t slots, hipStream_t s);
 hipError_t golk_batch_restock(int32_t *active, int32_t *counts, int64_t *found, int64_t *born, int32_t *soup, int64_t n,
                               int64_t now, int64_t horizon, int64_t total, int64_t *out_found, int64_t *out_period,
                               int32_t *harvest, hipStream_t s);

@@ -194,6 +194,8 @@ SIGNATURES = [
     ("gol_batch_search_host", ctypes.c_int, [_i64, _i64, ctypes.c_uint32, ctypes.c_uint32, _u64, _i64, _i64, _i64, _i64, _i64, _vp,
                                              _vp, _vp, _vp]),
     ("gol_batch_verdict_host", ctypes.c_int, [_i64, _i64, _i64]),
+    ("gol_batch_step_check_host", ctypes.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i32, _i64, _i32, _i32, ctypes.c_uint32,
+                                                 ctypes.c_uint32, _vp, _i32, _i64, _vp, _vp, _i64, _vp, _vp]),
     ("gol_halo_plan", ctypes.c_int, [_i64, _i32, _i32, _i32, _P(gol_halo_op), _i32, _P(_i32)]),
     ("gol_step_plan", ctypes.c_int, [_i64, _i32, _i32, _i32, _P(gol_launch), _i32, _P(_i32)]),
     ("gol_view_plan", ctypes.c_int, [_i64, _i32, _i32, _i64, _i64, _P(gol_view_run), _i32, _P(_i32)]),

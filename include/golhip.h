@@ -724,6 +724,15 @@ int gol_batch_search_host(int64_t H, int64_t W, uint32_t birth, uint32_t survive
  * has expired (not found and age >= horizon, or found at an age above horizon).
  * found < 0: not found yet. */
 int gol_batch_verdict_host(int64_t found, int64_t age, int64_t horizon);
+/* The argument check of gol_dev_batch_step (a host function, no GPU needed; the
+ * function of csrc/gol_batch.h that every launch of the step kernel passes):
+ * the arguments of gol_dev_batch_step without the stream.  GOL_OK where that
+ * call would launch, GOL_EINVAL where it refuses.  Launches nothing and reads
+ * no memory: of a pointer only whether it is NULL counts. */
+int gol_batch_step_check_host(const uint64_t *boards, const uint64_t *prev, const int64_t *settled, int64_t n, int64_t H,
+                              int64_t W, int32_t turns, int64_t turn0, int32_t have_prev, int32_t write_prev, uint32_t birth,
+                              uint32_t survive, const uint32_t *rules, int32_t scan, int64_t done, const int32_t *list,
+                              const int32_t *count, int64_t slots, const int64_t *left, const int64_t *born);
 
 /* ---------------------------------------------------------------- plans
  * The schedule of a sharded step as data (host functions, no GPU needed).  The

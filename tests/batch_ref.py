@@ -497,3 +497,55 @@ def cases_of(inst):
         for H in (128, 512):
             out.append(_sens(inst, "sens-waves", H, wc["min"], [(64 * w + 20, 4) for w in range((H + 63) // 64)]))
     return out
+
+
+# ---------------------------------------------------------------- the arguments of gol_dev_batch_step
+
+STEP_ARGS = ("boards", "prev", "settled", "n", "H", "W", "turns", "turn0", "have_prev", "write_prev", "birth", "survive", "rules",
+             "scan", "done", "list", "count", "slots", "left", "born")  # the entry's order, without the stream
+BUFFERS = ("boards", "prev", "settled", "left", "born", "list", "count", "rules")
+
+
+def launch_args(c, ptr):
+    """The arguments of a case's launch by name: ptr(name) is the address of the buffer `name`, asked for the
+    buffers the case has (a case always has boards and prev); a buffer it does not have is NULL."""
+    has = {k: getattr(c, k) is not None for k in BUFFERS}
+    a = {k: (ptr(k) if has[k] else None) for k in BUFFERS}
+    a.update(n=c.n, H=c.H, W=c.W, turns=c.turns, turn0=c.turn0, have_prev=int(c.have_prev), write_prev=int(c.write_prev),
+             birth=c.rule[0], survive=c.rule[1], scan=c.scan, done=c.done, slots=c.slots)
+    return a
+
+
+REFUSAL_SHAPE = (5, 5, 17)  # n, H, W of the buffers the refusal list is called on
+
+
+def refusals(p):
+    """(bad, good): the argument sets of gol_dev_batch_step, each a dict by name, that the entry refuses with
+    GOL_EINVAL -- every path of its check -- and the six good ones they are made from, one per mode.  p: name ->
+    the address of that buffer of REFUSAL_SHAPE (any non-null value where nothing is launched)."""
+    n, H, W = REFUSAL_SHAPE
+    base = dict(boards=p["boards"], prev=None, settled=None, n=n, H=H, W=W, turns=3, turn0=0, have_prev=0, write_prev=0, birth=8,
+                survive=12, rules=None, scan=0, done=0, list=None, count=None, slots=0, left=None, born=None)
+    scan = dict(prev=p["prev"], settled=p["settled"])
+    lst = dict(list=p["list"], count=p["count"], slots=n)
+    cyc = dict(scan, scan=2, **lst)
+    aged = dict(cyc, born=p["born"], write_prev=1)
+    bad = [
+        # the shape, the turns, the masks
+        dict(boards=None), dict(n=0), dict(n=(1 << 20) + 1), dict(H=0), dict(H=513), dict(W=0), dict(W=513), dict(turns=0),
+        dict(turns=-1), dict(birth=512), dict(survive=512), dict(done=-1),
+        # the scan's buffers and flags
+        dict(settled=p["settled"], scan=1), dict(have_prev=1), dict(write_prev=1), dict(scan=1), dict(scan=2), dict(scan, scan=0),
+        dict(scan, scan=3), dict(scan=-1), dict(scan, scan=2, have_prev=1), dict(scan, scan=2, done=4), dict(slots=n),
+        # the list
+        dict(cyc, count=None), dict(cyc, list=None), dict(cyc, slots=0), dict(cyc, slots=n + 1), dict(cyc, left=p["left"]),
+        dict(lst), dict(cyc, scan=1), dict(cyc, scan=0), dict(lst, left=p["left"], scan=2), dict(lst, left=p["left"], have_prev=1),
+        dict(lst, left=p["left"], write_prev=1), dict(left=p["left"]),
+        # the aged launch
+        dict(aged, settled=None), dict(aged, prev=None), dict(aged, list=None), dict(aged, count=None), dict(aged, slots=0),
+        dict(aged, slots=n + 1), dict(aged, rules=p["rules"]), dict(aged, left=p["left"]), dict(aged, turn0=1), dict(aged, write_prev=0),
+        dict(aged, have_prev=1), dict(aged, done=3), dict(aged, scan=0), dict(aged, scan=1), dict(born=p["born"]),
+    ]
+    # (each family's base arguments are good)
+    good = [dict(), dict(scan, scan=1), dict(cyc), dict(lst, left=p["left"]), dict(aged), dict(aged, have_prev=1, done=3)]
+    return [dict(base, **kw) for kw in bad], [dict(base, **kw) for kw in good]

@@ -102,6 +102,52 @@ def test_cases_are_valid_and_show_their_point(inst):
         c.check()
 
 
+# ---------------------------------------------------------------- the launch check, without a launch
+
+GOL_EINVAL = -1
+
+
+def fake_ptr(name):
+    """A non-null address per buffer: the check reads no memory."""
+    return 0x1000 * (1 + B.BUFFERS.index(name))
+
+
+def check_sets():
+    """(accept, refuse): the arguments of every case's launch and the six good launches of the refusal list; the
+    refusal list.  Each a list of the arguments in the entry's order."""
+    bad, good = B.refusals({k: fake_ptr(k) for k in B.BUFFERS})
+    accept = [B.launch_args(c, fake_ptr) for inst in B.INSTANTIATIONS for c in B.cases_of(inst)] + good
+    return [[a[k] for k in B.STEP_ARGS] for a in accept], [[a[k] for k in B.STEP_ARGS] for a in bad]
+
+
+def test_the_check_accepts_every_case_and_refuses_the_list(G):
+    """gol_batch_step_check_host (gol_batch_launch_ok, the check of every launch) on the table's 1376 launches and
+    on the refusal list that tests/test_gpu_batch_kernels.py::test_refusals runs through gol_dev_batch_step."""
+    check = G.lib().gol_batch_step_check_host
+    accept, refuse = check_sets()
+    assert len(accept) == 1376 + 6 and len(refuse) == 50
+    for a in accept:
+        assert check(*a) == 0, a
+    for a in refuse:
+        assert check(*a) == GOL_EINVAL, a
+
+
+def test_the_check_under_sanitizers(tmp_path):
+    """The same two sets through gol_batch_launch_ok in the stand-alone program (build/asan/batch_check launch): a
+    line per launch, the expected answer first, NULL as 0."""
+    import os
+    import subprocess
+    from test_batch_cpu import BATCH_CHECK
+    assert os.path.exists(BATCH_CHECK), "build/asan/batch_check is missing: run __graft_entry__.build()"
+    accept, refuse = check_sets()
+    path = tmp_path / "launches.txt"
+    path.write_text("".join(" ".join(str(int(v or 0)) for v in [ok] + a) + "\n"
+                            for ok, group in ((1, accept), (0, refuse)) for a in group))
+    r = subprocess.run([BATCH_CHECK, "launch", str(path)], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    assert f"batch_check launch: {len(accept)} accepted, {len(refuse)} refused, 0 bad" in r.stdout
+
+
 def test_pack_is_the_bit_order_of_load_words():
     for H, W in [(1, 1), (3, 63), (3, 64), (2, 65), (3, 150), (2, 512)]:
         cells = R.random_board(W, H, W, 0.5)

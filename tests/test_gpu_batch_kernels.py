@@ -219,7 +219,7 @@ def test_chained_launches(G, inst):
 def test_refusals(G):
     """Every GOL_EINVAL path of the entry; nothing is launched, so every buffer stays."""
     import torch
-    n, H, W = 5, 5, 17
+    n, H, W = B.REFUSAL_SHAPE
     boards = B.pack(B._compose(n, H, W, 3))
     host = dict(boards=boards, prev=np.full_like(boards, B.GAP), settled=np.full(n, -1, np.int64), left=np.full(n, 2, np.int64),
                 born=np.zeros(n, np.int64), list=np.arange(n, dtype=np.int32), count=np.array([n], np.int32),
@@ -229,41 +229,18 @@ def test_refusals(G):
     p = {k: buf.ptr(k) for k in NAMES}
     st = torch.cuda.current_stream().cuda_stream
 
-    def call(**kw):
-        a = dict(boards=p["boards"], prev=None, settled=None, n=n, H=H, W=W, turns=3, turn0=0, have_prev=0, write_prev=0, birth=8,
-                 survive=12, rules=None, scan=0, done=0, list=None, count=None, slots=0, left=None, born=None)
-        a.update(kw)
-        return L.gol_dev_batch_step(a["boards"], a["prev"], a["settled"], a["n"], a["H"], a["W"], a["turns"], a["turn0"], a["have_prev"],
-                                    a["write_prev"], a["birth"], a["survive"], a["rules"], a["scan"], a["done"], a["list"], a["count"],
-                                    a["slots"], a["left"], a["born"], st)
+    def call(a):
+        return L.gol_dev_batch_step(*[a[k] for k in B.STEP_ARGS], st)
 
-    scan = dict(prev=p["prev"], settled=p["settled"])
-    lst = dict(list=p["list"], count=p["count"], slots=n)
-    cyc = dict(scan, scan=2, **lst)
-    aged = dict(cyc, born=p["born"], write_prev=1)
-    bad = [
-        # the shape, the turns, the masks
-        dict(boards=None), dict(n=0), dict(n=(1 << 20) + 1), dict(H=0), dict(H=513), dict(W=0), dict(W=513), dict(turns=0),
-        dict(turns=-1), dict(birth=512), dict(survive=512), dict(done=-1),
-        # the scan's buffers and flags
-        dict(settled=p["settled"], scan=1), dict(have_prev=1), dict(write_prev=1), dict(scan=1), dict(scan=2), dict(scan, scan=0),
-        dict(scan, scan=3), dict(scan=-1), dict(scan, scan=2, have_prev=1), dict(scan, scan=2, done=4), dict(slots=n),
-        # the list
-        dict(cyc, count=None), dict(cyc, list=None), dict(cyc, slots=0), dict(cyc, slots=n + 1), dict(cyc, left=p["left"]),
-        dict(lst), dict(cyc, scan=1), dict(cyc, scan=0), dict(lst, left=p["left"], scan=2), dict(lst, left=p["left"], have_prev=1),
-        dict(lst, left=p["left"], write_prev=1), dict(left=p["left"]),
-        # the aged launch
-        dict(aged, settled=None), dict(aged, prev=None), dict(aged, list=None), dict(aged, count=None), dict(aged, slots=0),
-        dict(aged, slots=n + 1), dict(aged, rules=p["rules"]), dict(aged, left=p["left"]), dict(aged, turn0=1), dict(aged, write_prev=0),
-        dict(aged, have_prev=1), dict(aged, done=3), dict(aged, scan=0), dict(aged, scan=1), dict(born=p["born"]),
-    ]
-    for kw in bad:
-        assert call(**kw) == GOL_EINVAL, sorted(kw)
+    bad, good = B.refusals(p)  # (the list of tests/test_batch_ref_cpu.py, which asks the check alone)
+    for a in bad:
+        assert call(a) == GOL_EINVAL, a
         assert L.gol_last_error()
     torch.cuda.synchronize()
     _compare(buf, {}, "refusals")
     # (each family's base arguments are good: one launch of each, on the same buffers)
-    for kw in (dict(), dict(scan, scan=1), dict(cyc), dict(lst, left=p["left"]), dict(aged), dict(aged, have_prev=1, done=3)):
-        assert call(**kw) == 0, (sorted(kw), L.gol_last_error())
+    assert len(good) == 6
+    for a in good:
+        assert call(a) == 0, (a, L.gol_last_error())
     torch.cuda.synchronize()
     assert _error_word(G) == (0, 0)

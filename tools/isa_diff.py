@@ -53,24 +53,37 @@ def immediates(line):
     return re.sub(r"((?:^|[ ,]|\boffset:))(%s)(?=$|[ ,])" % NUMBER, mask, line), imm
 
 
+def kind_of(a, b):
+    """Two streams -> "equal", "immediates" (they differ only there) or "differs"."""
+    if a == b:
+        return "equal"
+    if len(a) == len(b) and all(x == y or immediates(x)[0] == immediates(y)[0] for x, y in zip(a, b)):
+        return "immediates"
+    return "differs"
+
+
 def compare(a, b):
     """Two streams -> ("equal", 0), ("immediates", lines that differ only there) or ("differs", diff lines)."""
-    if a == b:
-        return "equal", 0
-    if len(a) == len(b) and all(immediates(x)[0] == immediates(y)[0] for x, y in zip(a, b)):
-        return "immediates", sum(x != y for x, y in zip(a, b))
-    return "differs", [d for d in difflib.unified_diff(a, b, "REV", "tree", n=0, lineterm="")][2:]
+    kind = kind_of(a, b)
+    if kind == "equal":
+        return kind, 0
+    if kind == "immediates":
+        return kind, sum(x != y for x, y in zip(a, b))
+    return kind, [d for d in difflib.unified_diff(a, b, "REV", "tree", n=0, lineterm="")][2:]
 
 
 def short_name(demangled):
     """golk::band_step_kernel<8, 2, false> of `void golk::band_step_kernel<8, 2, false, golk::B3S23>(golk::B3S23)`."""
     s = re.sub(r"^void ", "", demangled)
+    anon = "(anonymous namespace)::"  # (its parenthesis is not the parameter list's)
+    s = s.replace(anon, "\0")
     depth = 0
     for i, c in enumerate(s):  # cut the parameter list: the first '(' outside the template arguments
         depth += (c == "<") - (c == ">")
         if c == "(" and depth == 0:
             s = s[:i]
             break
+    s = s.replace("\0", anon)
     m = re.match(r"([^<]*)<(.*)>$", s)
     if not m:
         return s
@@ -138,8 +151,8 @@ def fmt_res(a, b=None):
 
 
 def distance(a, b):
-    kind, _ = compare(a, b)
-    return {"equal": 0, "immediates": 1, "differs": 2 + abs(len(a) - len(b))}[kind]
+    """(no diff is made here: pairing n kernels of one name asks n^2 times)"""
+    return {"equal": 0, "immediates": 1, "differs": 2 + abs(len(a) - len(b))}[kind_of(a, b)]
 
 
 def report(old, new, lines, out=print):
