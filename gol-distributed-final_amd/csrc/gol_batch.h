@@ -208,8 +208,8 @@ GOL_BATCH_HD uint32_t gol_batch_conway_next(uint32_t a0, uint32_t a1, uint32_t b
     const uint32_t t0 = a0 ^ b0 ^ c0, k0 = (a0 & b0) | (c0 & (a0 | b0));
     const uint32_t u = a1 ^ b1 ^ c1, v = (a1 & b1) | (c1 & (a1 | b1));
     const uint32_t g1 = (t0 ^ k0 ^ v) & ~(t0 & k0 & v);  // exactly one of t0, k0, v
-    const uint32_t g2 = (~u & ~v & ~g1) | (~u & v & g1) | (u & ~v & g1);
-    return (t0 | cell) & g2;
+    const uint32_t g2 = (u & v) | ((u ^ v ^ g1) & ~(u & v & g1));  // (u & v) | exactly one of u, v, g1
+    return (t0 | cell) & ~g2;
 #endif
 }
 

@@ -38,19 +38,23 @@ constexpr unsigned TT_XOR3 = 0x96;  // a ^ b ^ c
 constexpr unsigned TT_MAJ = 0xE8;   // majority(a, b, c)
 // The rule tail (tools/rule_search.c, tests/test_rule_circuit_cpu.py): with T = t0 + 2(k0 + u +
 // 2v) the 3x3 sum including the cell, alive' = (T == 3) | (cell & T == 4)
-//   = (t0 | cell) & G2,  G2 = TT_G2(u, v, G1),  G1 = TT_G1(t0, k0, v)  (exactly one of t0, k0, v).
+//   = (t0 | cell) & ~G2,  G2 = TT_G2(u, v, G1),  G1 = TT_G1(t0, k0, v)  (exactly one of t0, k0, v).
 // Three gates instead of the four of t0 ? [S == 1] : cell & [S == 2]: an exhaustive search over
 // 3-gate circuits finds them only when it may use that the centre row's horizontal sum includes
 // the cell (a centre sum of 0 means a dead cell, 3 a live one), which holds in every kernel here.
+// Polarity (here and in the pair tails): every gate answers 0 on a dead neighbourhood, so that no
+// nearly all-ones word sits between the nearly all-zero ones of a settled board; the complements
+// live in the tables of the gates that read them (tools/rule_search_pair.c --hist
+// ranks the choice, tests/test_tail_polarity_cpu.py holds it).
 constexpr unsigned TT_G1 = 0x16;    // exactly one of a, b, c
-constexpr unsigned TT_G2 = 0x29;    // (~a & ~b & ~c) | (~a & b & c) | (a & ~b & c)
-constexpr unsigned TT_OUT = 0xA8;   // (a | b) & c
+constexpr unsigned TT_G2 = 0xD6;    // (a & b) | exactly one of a, b, c
+constexpr unsigned TT_OUT = 0x54;   // (a | b) & ~c
 
 // The pair step's tails (gol_pipe.h pair_tail; tools/rule_search_pair.c)
-constexpr unsigned TT_PG1 = 0x43;   // (p0, x0, cell)
-constexpr unsigned TT_PG2 = 0x25;   // (p1, p2, x1)
-constexpr unsigned TT_PG3 = 0x8D;   // (p2, cell, g1)
-constexpr unsigned TT_POUT = 0x90;  // (g3, g1, g2)
+constexpr unsigned TT_PG1 = 0xBC;   // (p0, x0, cell)
+constexpr unsigned TT_PG2 = 0xDA;   // (p1, p2, x1)
+constexpr unsigned TT_PG3 = 0xE4;   // (p2, cell, g1)
+constexpr unsigned TT_POUT = 0x18;  // (g3, g1, g2)
 
 template <unsigned TT>
 __device__ __forceinline__ uint32_t bitop3(uint32_t a, uint32_t b, uint32_t c)

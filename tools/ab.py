@@ -4,7 +4,9 @@
 
 Runs bench.py once per (rep, library) in a child process whose golhip binding is pointed at that
 library (the product path always loads golhip/libgolhip.so; "lib" = the product library), so
-box-to-box clock differences cancel out of the comparison.  One JSON line per run."""
+box-to-box clock differences cancel out of the comparison; the runs interleave (rep 0 of every
+library, rep 1, ...).  --plain: the plain bench.py line (the acceptance A/B of a change to the hot
+kernel).  One JSON line per run."""
 import argparse
 import json
 import os
@@ -31,13 +33,14 @@ def main():
     ap.add_argument("--libs", required=True)
     ap.add_argument("--bench", default="")
     ap.add_argument("--reps", type=int, default=2)
+    ap.add_argument("--plain", action="store_true", help="bench.py as given, without --full (no parity verdict, no roofline)")
     a = ap.parse_args()
     libs = a.libs.split(",")
     for rep in range(a.reps):
         for lib in libs:
             path = lib if lib == "lib" else os.path.join(ROOT, lib)
             code = CHILD % (ROOT, os.path.join(ROOT, "gol-distributed-final_amd"), lib, path,
-                            shlex.split(a.bench) + ["--full", "--no-cpu-baseline"])
+                            shlex.split(a.bench) + ([] if a.plain else ["--full", "--no-cpu-baseline"]))
             p = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300, cwd=ROOT)
             lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
             # (exit 1 with a line: bench.py's parity check failed -- a diagnostic build that computes

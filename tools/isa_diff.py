@@ -1,6 +1,6 @@
 """Compare the gfx950 device assembly of the kernel units between a git revision and the working tree.
 
-    python tools/isa_diff.py REV [--pattern REGEX] [--lines N]
+    python tools/isa_diff.py REV [--pattern REGEX] [--lines N] [--tables] [--quiet]
 
 Every *.hip unit of csrc/ is compiled to assembly with its Makefile's flags (check_lds_wait.py's
 compile_asm), once from the sources of REV (git show into a temporary directory) and once from the
@@ -10,7 +10,9 @@ first lines of a diff, and the VGPRs, SGPRs, scratch and LDS bytes of the code o
 compared.  Kernels are matched by demangled name without the parameter list and without template
 arguments that are types (a rule policy); where several share such a name, the closest streams
 pair up.  Kernels on one side only are listed with their size.  A refactor of the kernel sources
-should leave the kernels it does not mean to change `equal`.
+should leave the kernels it does not mean to change `equal`.  A v_bitop3 truth table is part of the
+instruction (another table is another function) unless --tables asks to count it as an immediate: a
+change of tables alone then reads `equal but for N immediates`.  --quiet prints one line per kernel.
 """
 import argparse
 import difflib
@@ -25,6 +27,9 @@ from check_lds_wait import CSRC, ROOT, compile_asm, kernels  # noqa: E402
 
 CSRC_REL = os.path.relpath(CSRC, ROOT)
 NUMBER = r"-?(?:0x[0-9a-fA-F]+|\d+)"
+# --tables: a v_bitop3 truth table counts as an immediate (a change of tables that must leave the
+# streams alone); by default another table is another instruction
+TABLES_ARE_IMMEDIATES = False
 
 
 def stream(body):
@@ -50,7 +55,8 @@ def immediates(line):
     def mask(m):
         imm.append(m.group(2))
         return m.group(1) + "#"
-    return re.sub(r"((?:^|[ ,]|\boffset:))(%s)(?=$|[ ,])" % NUMBER, mask, line), imm
+    names = "offset|bitop3" if TABLES_ARE_IMMEDIATES else "offset"
+    return re.sub(r"((?:^|[ ,]|\b(?:%s):))(%s)(?=$|[ ,])" % (names, NUMBER), mask, line), imm
 
 
 def kind_of(a, b):
@@ -191,14 +197,18 @@ def main():
     ap.add_argument("rev")
     ap.add_argument("--pattern", default=r"", help="regex on the mangled kernel name")
     ap.add_argument("--lines", type=int, default=12, help="diff lines shown per differing kernel")
+    ap.add_argument("--tables", action="store_true", help="count v_bitop3 truth tables as immediates")
+    ap.add_argument("--quiet", action="store_true", help="one line per kernel: no instruction lines")
     args = ap.parse_args()
+    global TABLES_ARE_IMMEDIATES
+    TABLES_ARE_IMMEDIATES = args.tables
     with tempfile.TemporaryDirectory() as d:
         csrc, inc = sources_at(args.rev, d)
         compile_asm(os.path.join(d, "rev.s"), csrc, inc, units(csrc))
         compile_asm(os.path.join(d, "tree.s"), units=units(CSRC))
         old = load(open(os.path.join(d, "rev.s")).read(), args.pattern)
         new = load(open(os.path.join(d, "tree.s")).read(), args.pattern)
-    report(old, new, args.lines)
+    report(old, new, args.lines, (lambda s: s.startswith("    ") or print(s)) if args.quiet else print)
     return 0
 
 

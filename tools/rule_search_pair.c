@@ -11,15 +11,31 @@
 //
 // Result: no 3-gate tail exists (over the binary P; nor over the other 4-gate pair encodings
 // (p0, two 2-valued splits of floor/ceil(P/2)); nor with the carry k as a fifth pair signal);
-// 152 4-gate tails exist.  The kernel uses g1 = 0x43(p0, x0, cell), g2 = 0x25(p1, p2, x1),
-// g3 = 0x8D(p2, cell, g1), out = 0x90(g3, g1, g2): g1 and g2 independent, depth 3.
+// 152 4-gate tails exist.  The kernel uses the wiring g1(p0, x0, cell), g2(p1, p2, x1),
+// g3(p2, cell, g1), out(g3, g1, g2): g1 and g2 independent, depth 3 (found as 0x43, 0x25, 0x8D,
+// 0x90; the shipped tables are that wiring's sparsest assignment, see --hist below).
 // Per 32 cells and generation: 2 (row sum) + 4/2 (pair) + 4 (tail) = 8 gates, against 9 for the
 // row-by-row circuit (tools/rule_search.c).
 //   gcc -O3 -march=native -o /tmp/rsp tools/rule_search_pair.c && /tmp/rsp        (~15 min)
+//
+// Polarity (DESIGN.md §4.1b "data polarity"): /tmp/rsp --hist tests/golden/nbhd_hist_4x3.json     (~1 s)
+// For the shipped wiring (g1(p0, x0, cell), g2(p1, p2, x1), g3(p2, cell, g1), out(g3, g1, g2)) it enumerates
+// every assignment of the four truth tables that computes the rule (256^3 tables of g1, g2, g3; out's table
+// follows), weights each gate's output by the histogram of a settled soup (tools/nbhd_hist.py: both tails of
+// every 4 x 3 neighbourhood) and ranks the assignments by the largest share of ones among g1, g2, g3 (out is
+// the next generation under every assignment), then by their sum.  A 3-input table absorbs a complemented
+// input or output for free, so the polarity of every inner signal is a free choice; the kernel takes the
+// assignment whose words are sparsest (SHIPPED below = gol_device.h, checked by
+// tests/test_tail_polarity_cpu.py): no nearly all-ones word between the nearly all-zero ones of the VALU's
+// result stream.  Table entries whose inputs never occur (the don't-cares above) do not change a share, so
+// assignments tie in groups; the tool prints the distinct shares and where SHIPPED stands.
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 typedef uint64_t u64;
+
+static const unsigned SHIPPED[4] = {0xBC, 0xDA, 0xE4, 0x18};  // TT_PG1, TT_PG2, TT_PG3, TT_POUT
 
 static u64 lut3(unsigned tt, u64 a, u64 b, u64 c)
 {
@@ -29,8 +45,11 @@ static u64 lut3(unsigned tt, u64 a, u64 b, u64 c)
     return r;
 }
 
-int main(void)
+static int hist_mode(const char *path);
+
+int main(int argc, char **argv)
 {
+    if (argc == 3 && !strcmp(argv[1], "--hist")) return hist_mode(argv[2]);
     // points: P (3 bits, 0..7), x (2 bits), cell; signals 0 p0, 1 p1, 2 p2, 3 x0, 4 x1, 5 cell
     u64 X[6] = {0}, F = 0, care = 0;
     for (int pt = 0; pt < 64; pt++) {
@@ -116,4 +135,124 @@ int main(void)
                 }
     printf("%ld circuits\n", found);
     return 0;
+}
+
+// ------------------------------------------------------------------ --hist: polarity ranking
+static double share(u64 sig, const double *wt)
+{
+    double s = 0;
+    for (int pt = 0; pt < 64; pt++)
+        if ((sig >> pt) & 1) s += wt[pt];
+    return s;
+}
+
+typedef struct { double mx, sum, f[3]; unsigned t[4]; long n; } Rank;
+
+static int hist_mode(const char *path)
+{
+    // the 4096 counts: the numbers after "counts":[ ; index bit 3 r + c = cell (row y-1+r, column x-1+c)
+    FILE *f = fopen(path, "r");
+    if (!f) { perror(path); return 2; }
+    static char buf[1 << 20];
+    const size_t len = fread(buf, 1, sizeof buf - 1, f);
+    fclose(f);
+    buf[len] = 0;
+    char *q = strstr(buf, "\"counts\"");
+    if (!q || !(q = strchr(q, '['))) { fprintf(stderr, "%s: no counts\n", path); return 2; }
+    static double cnt[4096];
+    double total = 0;
+    for (int i = 0; i < 4096; i++) {
+        q++;
+        cnt[i] = (double)strtoll(q, &q, 10);
+        total += cnt[i];
+        if (*q != (i < 4095 ? ',' : ']')) { fprintf(stderr, "%s: %d counts, expected 4096\n", path, i + 1); return 2; }
+    }
+    // both tails of every neighbourhood -> weights of the points (P, x, cell), as in main()
+    double wt[64] = {0};
+    u64 X[6] = {0}, F = 0, care = 0;
+    for (int i = 0; i < 4096; i++) {
+        int h[4], c[4];
+        for (int r = 0; r < 4; r++) {
+            h[r] = ((i >> (3 * r)) & 1) + ((i >> (3 * r + 1)) & 1) + ((i >> (3 * r + 2)) & 1);
+            c[r] = (i >> (3 * r + 1)) & 1;
+        }
+        const int P = h[1] + h[2];
+        wt[P | (h[0] << 3) | (c[1] << 5)] += cnt[i] / (2 * total);  // row y: above = row y-1
+        wt[P | (h[3] << 3) | (c[2] << 5)] += cnt[i] / (2 * total);  // row y+1: below = row y+2
+    }
+    for (int pt = 0; pt < 64; pt++) {
+        const int P = pt & 7, A = (pt >> 3) & 3, c = (pt >> 5) & 1;
+        const u64 bit = 1ull << pt;
+        if (P & 1) X[0] |= bit;
+        if (P & 2) X[1] |= bit;
+        if (P & 4) X[2] |= bit;
+        if (A & 1) X[3] |= bit;
+        if (A & 2) X[4] |= bit;
+        if (c) X[5] |= bit;
+        if (P + A == 3 || (P + A == 4 && c)) F |= bit;
+        if (P <= 6 && (c ? P >= 1 : P <= 5)) care |= bit;
+        if (!(care & bit) && wt[pt] > 0) { fprintf(stderr, "a don't-care point occurs: %d\n", pt); return 2; }
+    }
+    printf("inputs: p0 %.3f p1 %.3f p2 %.3f x0 %.3f x1 %.3f cell %.3f   out %.3f\n", share(X[0], wt), share(X[1], wt),
+           share(X[2], wt), share(X[3], wt), share(X[4], wt), share(X[5], wt), share(F & care, wt));
+    enum { TOP = 4096 };
+    static Rank top[TOP];
+    int ntop = 0;
+    long valid = 0;
+    Rank ship = {0};
+    int ship_found = 0;
+    for (unsigned t1 = 0; t1 < 256; t1++) {
+        const u64 g1 = lut3(t1, X[0], X[3], X[5]);
+        for (unsigned t2 = 0; t2 < 256; t2++) {
+            const u64 g2 = lut3(t2, X[1], X[2], X[4]);
+            for (unsigned t3 = 0; t3 < 256; t3++) {
+                const u64 g3 = lut3(t3, X[2], X[5], g1);
+                unsigned to = 0;
+                int ok = 1;
+                for (int idx = 0; idx < 8 && ok; idx++) {
+                    const u64 pm = ((idx & 4) ? g3 : ~g3) & ((idx & 2) ? g1 : ~g1) & ((idx & 1) ? g2 : ~g2) & care;
+                    if (!pm) continue;  // (never occurs: the entry stays 0)
+                    if ((F & pm) == pm) to |= 1u << idx;
+                    else if (F & pm) ok = 0;
+                }
+                if (!ok) continue;
+                valid++;
+                Rank r = {0, 0, {share(g1 & care, wt), share(g2 & care, wt), share(g3 & care, wt)}, {t1, t2, t3, to}, 1};
+                for (int k = 0; k < 3; k++) {
+                    r.sum += r.f[k];
+                    if (r.f[k] > r.mx) r.mx = r.f[k];
+                }
+                // (out's never-occurring entries are free: SHIPPED's out table may set them)
+                if (t1 == SHIPPED[0] && t2 == SHIPPED[1] && t3 == SHIPPED[2]) {
+                    const u64 o = lut3(SHIPPED[3], g3, g1, g2);
+                    if (((o ^ F) & care) == 0) { ship = r; ship.t[3] = SHIPPED[3]; ship_found = 1; }
+                }
+                int k = 0;  // distinct (f[0], f[1], f[2]) kept with a count; the list is short
+                while (k < ntop && !(top[k].f[0] == r.f[0] && top[k].f[1] == r.f[1] && top[k].f[2] == r.f[2])) k++;
+                if (k < ntop) top[k].n++;
+                else if (ntop < TOP) top[ntop++] = r;
+                else { fprintf(stderr, "more than %d distinct share triples\n", TOP); return 2; }
+            }
+        }
+    }
+    // selection sort of the distinct triples by (largest share, sum)
+    for (int i = 0; i < ntop; i++)
+        for (int j = i + 1; j < ntop; j++)
+            if (top[j].mx < top[i].mx || (top[j].mx == top[i].mx && top[j].sum < top[i].sum)) {
+                const Rank t = top[i];
+                top[i] = top[j];
+                top[j] = t;
+            }
+    printf("%ld assignments of the wiring compute the rule, %d distinct (g1, g2, g3) shares of ones\n", valid, ntop);
+    printf("rank  max    sum    g1     g2     g3     assignments  first: PG1 PG2 PG3 POUT\n");
+    for (int i = 0; i < ntop; i++)
+        if (i < 8 || i == ntop - 1)
+            printf("%4d  %.3f  %.3f  %.3f  %.3f  %.3f  %11ld  0x%02X 0x%02X 0x%02X 0x%02X\n", i + 1, top[i].mx, top[i].sum,
+                   top[i].f[0], top[i].f[1], top[i].f[2], top[i].n, top[i].t[0], top[i].t[1], top[i].t[2], top[i].t[3]);
+    if (!ship_found) { printf("SHIPPED does not compute the rule\n"); return 1; }
+    int rank = 0;
+    while (!(top[rank].f[0] == ship.f[0] && top[rank].f[1] == ship.f[1] && top[rank].f[2] == ship.f[2])) rank++;
+    printf("shipped 0x%02X 0x%02X 0x%02X 0x%02X: g1 %.3f g2 %.3f g3 %.3f, rank %d%s\n", SHIPPED[0], SHIPPED[1], SHIPPED[2],
+           SHIPPED[3], ship.f[0], ship.f[1], ship.f[2], rank + 1, rank == 0 ? " (top)" : "");
+    return rank == 0 ? 0 : 1;
 }
