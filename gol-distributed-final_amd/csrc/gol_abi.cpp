@@ -90,39 +90,39 @@ extern "C" int gol_next_state_slab(const uint8_t *world, int64_t H, int64_t W, i
         return GOL_OK;                                                                                    \
     } while (0)
 
+// The step entries: each resolves cells_per_lane to words per lane, fills a descriptor
+// (gol_step_launch.h) and answers as gol_step_launch_ok does for a C entry, with its own text.
+// step_launch: the part they share, a pretended device (cus, slots; 0, 0: this one) and the launch.
+static int step_launch(gol_step_launch l, void *stream, int32_t cus, int32_t slots)
+{
+    l.as_cus = cus;
+    l.as_slots = slots;
+    if ((cus || slots) && !gol_step_launch_ok(l, true))
+        return gol_set_error(GOL_EINVAL, "a pretended device (%d CUs, %d resident workgroups) needs the pipelined k, cus %% 8 == 0 and both > 0", cus, slots);
+    const hipError_t e = golk_step(l, (hipStream_t)stream);
+    if (e == hipErrorInvalidValue && cus) {  // the device has less (gol_launch.cpp pipe_device): nothing was launched
+        int dcus = 0;
+        int64_t dslots = 0;
+        const gol_step_geometry g = gol_step_geometry_of(l);
+        if (!golk_pipe_limits(l.family == GOL_FAMILY_BAND, g.contig, l.slots != nullptr, &dcus, &dslots))
+            return gol_set_error(GOL_EHIP, "no device properties");
+        return gol_set_error(GOL_EINVAL, "a pretended device of %d CUs and %d resident workgroups exceeds this one (%d, %lld)", cus,
+                             slots, dcus, (long long)dslots);
+    }
+    if (e != hipSuccess) return gol_set_error(GOL_EHIP, "step launch: %s", hipGetErrorString(e));
+    return GOL_OK;
+}
+
 extern "C" int gol_dev_bits_step(const uint32_t *top, const uint32_t *mid, const uint32_t *bot, uint32_t *dst,
                                  int64_t R, int64_t Wd, int64_t pitch, int64_t row0, int64_t rows, int32_t k,
                                  int32_t cells_per_lane, int32_t strip_rows, uint64_t *count_slots, void *stream)
 {
-    const int dw = cells_per_lane > 0 ? cells_per_lane / 32 : GOL_DEFAULT_DW;
-    if (!top || !mid || !bot || !dst || R <= 0 || Wd <= 0 || pitch < Wd || row0 < 0 || rows < 0 ||
-        row0 + rows > R || (dw != 1 && dw != 2 && dw != 4) || Wd % dw || pitch % dw ||
-        !(k == 1 || k == 2 || k == 4 || k == 8 || (k == 16 && dw <= 2)) || k > R)
+    const int dw = gol_step_dw(GOL_FAMILY_BITS, cells_per_lane);
+    const gol_step_launch l = {GOL_FAMILY_BITS, top, mid, bot, dst, R, Wd, pitch, row0, rows, k, dw, strip_rows, 0, 0, count_slots};
+    if (!gol_step_launch_ok(l, true))
         return gol_set_error(GOL_EINVAL, "bad bits_step arguments (R=%lld Wd=%lld pitch=%lld k=%d dw=%d)",
                              (long long)R, (long long)Wd, (long long)pitch, k, dw);
-    LAUNCH(golk_bits_step(top, mid, bot, dst, R, Wd, pitch, row0, rows, k, dw, strip_rows, count_slots,
-                          (hipStream_t)stream));
-}
-
-// Words per lane of the band kernels for a cells_per_lane (<= 0: the default); 0: not one of theirs.
-static int band_dw(int32_t cells_per_lane)
-{
-    return cells_per_lane == 64 ? 2 : (cells_per_lane == 128 ? 4 : (cells_per_lane <= 0 ? GOL_BAND_DEFAULT_DW : 0));
-}
-
-// cus = slots = 0: this device
-static int pipe_on_check(bool band, bool contig, bool count, bool pipelined, int32_t cus, int32_t slots)
-{
-    if (!cus && !slots) return GOL_OK;
-    int dcus = 0;
-    int64_t dslots = 0;
-    if (!pipelined || cus <= 0 || slots <= 0 || cus % 8)
-        return gol_set_error(GOL_EINVAL, "a pretended device (%d CUs, %d resident workgroups) needs the pipelined k, cus %% 8 == 0 and both > 0", cus, slots);
-    if (!golk_pipe_limits(band, contig, count, &dcus, &dslots)) return gol_set_error(GOL_EHIP, "no device properties");
-    if (cus > dcus || slots > dslots)
-        return gol_set_error(GOL_EINVAL, "a pretended device of %d CUs and %d resident workgroups exceeds this one (%d, %lld)", cus,
-                             slots, dcus, (long long)dslots);
-    return GOL_OK;
+    return step_launch(l, stream, 0, 0);
 }
 
 extern "C" int gol_dev_band_step_on(const uint32_t *top, const uint32_t *mid, const uint32_t *bot, uint32_t *dst,
@@ -130,18 +130,12 @@ extern "C" int gol_dev_band_step_on(const uint32_t *top, const uint32_t *mid, co
                                     int32_t cells_per_lane, int32_t strip_rows, uint64_t *count_slots, void *stream,
                                     int32_t cus, int32_t slots)
 {
-    const int dw = band_dw(cells_per_lane);
-    if (!top || !mid || !bot || !dst || R <= 0 || Wd <= 0 || !dw || Wd % dw || pitch < Wd || pitch % dw ||
-        row0 < 0 || rows < 0 || row0 + rows > R ||
-        !(k == 1 || k == 2 || k == 4 || k == 8 || (k == 16 && dw == 2) || (k == 12 && dw == 4)) ||
-        k > R || (((uintptr_t)mid | (uintptr_t)top | (uintptr_t)bot | (uintptr_t)dst) & (4 * dw - 1)))
+    const gol_step_launch l = {GOL_FAMILY_BAND, top, mid, bot, dst, R, Wd, pitch, row0, rows, k,
+                               gol_step_dw(GOL_FAMILY_BAND, cells_per_lane), strip_rows, 0, 0, count_slots};
+    if (!gol_step_launch_ok(l, true))
         return gol_set_error(GOL_EINVAL, "bad band_step arguments (R=%lld Wd=%lld pitch=%lld k=%d cells_per_lane=%d)",
                              (long long)R, (long long)Wd, (long long)pitch, k, cells_per_lane);
-    const bool contig = top + (int64_t)k * pitch == mid && bot == mid + R * pitch;
-    const int rc = pipe_on_check(true, contig, count_slots != nullptr, k == 12 && dw == 4, cus, slots);
-    if (rc) return rc;
-    LAUNCH(golk_band_step(top, mid, bot, dst, R, Wd, pitch, row0, rows, k, dw, strip_rows, count_slots, nullptr,
-                          (hipStream_t)stream, cus, slots));
+    return step_launch(l, stream, cus, slots);
 }
 
 extern "C" int gol_dev_band_step(const uint32_t *top, const uint32_t *mid, const uint32_t *bot, uint32_t *dst,
@@ -157,23 +151,20 @@ extern "C" int gol_dev_rule_step(const uint32_t *top, const uint32_t *mid, const
                                  int32_t layout, uint32_t birth, uint32_t survive, int32_t cells_per_lane,
                                  int32_t strip_rows, uint64_t *count_slots, void *stream)
 {
-    const int dw = GOLK_RULE_DW;
-    if (!top || !mid || !bot || !dst || R <= 0 || Wd <= 0 || Wd % dw || pitch < Wd || pitch % dw || row0 < 0 ||
-        rows < 0 || row0 + rows > R || !(k == 1 || k == 2 || k == 4 || k == 8) || k > R ||
-        (layout != GOL_LAYOUT_STANDARD && layout != GOL_LAYOUT_BAND) || birth >= 512 || survive >= 512 ||
-        !(cells_per_lane <= 0 || cells_per_lane == 32 * dw) ||
-        (((uintptr_t)mid | (uintptr_t)top | (uintptr_t)bot | (uintptr_t)dst) & (4 * dw - 1)))
+    // (a layout that is neither: no family, which the check refuses)
+    const int family = layout == GOL_LAYOUT_STANDARD ? GOL_FAMILY_RULE_STD : (layout == GOL_LAYOUT_BAND ? GOL_FAMILY_RULE_BAND : -1);
+    const gol_step_launch l = {family, top, mid, bot, dst, R, Wd, pitch, row0, rows, k, gol_step_dw(family, cells_per_lane),
+                               strip_rows, birth, survive, count_slots};
+    if (!gol_step_launch_ok(l, true))
         return gol_set_error(GOL_EINVAL,
                              "bad rule_step arguments (R=%lld Wd=%lld pitch=%lld k=%d layout=%d B=0x%x S=0x%x cells_per_lane=%d)",
                              (long long)R, (long long)Wd, (long long)pitch, k, layout, birth, survive, cells_per_lane);
-    LAUNCH(golk_rule_step(top, mid, bot, dst, R, Wd, pitch, row0, rows, k, layout == GOL_LAYOUT_BAND, birth, survive,
-                          strip_rows, count_slots, (hipStream_t)stream));
+    return step_launch(l, stream, 0, 0);
 }
 
 extern "C" int gol_band_max_k(int32_t cells_per_lane)
 {
-    const int dw = band_dw(cells_per_lane);
-    return dw == 2 ? 16 : (dw == 4 ? 12 : 0);
+    return gol_step_max_k(GOL_FAMILY_BAND, gol_step_dw(GOL_FAMILY_BAND, cells_per_lane), GOL_STEP_MAX_K, true);
 }
 
 extern "C" int gol_dev_band_convert(int32_t to_band, const uint32_t *src, uint32_t *dst, int64_t rows, int64_t Wd,
@@ -229,15 +220,11 @@ extern "C" int gol_dev_bytes_step_k_on(const uint8_t *top, const uint8_t *mid, c
                                        int32_t strip_rows, uint64_t *count_slots, void *stream, int32_t cus,
                                        int32_t slots)
 {
-    if (!top || !mid || !bot || !dst || R <= 0 || W <= 0 || W % 32 || stride < W || stride % 16 || row0 < 0 ||
-        rows < 0 || row0 + rows > R || !(k == 1 || k == 2 || k == 4 || k == 8 || k == 16 || k == 32) || k > R ||
-        (((uintptr_t)mid | (uintptr_t)top | (uintptr_t)bot | (uintptr_t)dst) & 15))
+    const gol_step_launch l = {GOL_FAMILY_BYTES, top, mid, bot, dst, R, W, stride, row0, rows, k, 1, strip_rows, 0, 0, count_slots};
+    if (!gol_step_launch_ok(l, true))
         return gol_set_error(GOL_EINVAL, "bad bytes_step_k arguments (R=%lld W=%lld stride=%lld k=%d)",
                              (long long)R, (long long)W, (long long)stride, k);
-    const int rc = pipe_on_check(false, false, count_slots != nullptr, k == 32, cus, slots);
-    if (rc) return rc;
-    LAUNCH(golk_bytes_blocked(top, mid, bot, dst, R, W, stride, row0, rows, k, strip_rows, count_slots, nullptr,
-                              (hipStream_t)stream, cus, slots));
+    return step_launch(l, stream, cus, slots);
 }
 
 extern "C" int gol_dev_bytes_step_k(const uint8_t *top, const uint8_t *mid, const uint8_t *bot, uint8_t *dst,

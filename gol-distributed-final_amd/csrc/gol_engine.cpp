@@ -159,7 +159,7 @@ static int engine_shards(gol_engine *e, const std::vector<int> &devices)
         return gol_set_error(GOL_EINVAL, "%d shards cannot split %lld rows", e->nranks, (long long)e->H);
     e->min_rows = e->H / e->nranks;  // broker.go:172-206: the smallest shard
     // every exchange carries the rows of the longest launch the engine makes
-    e->kx = pick_k(e->k, INT64_MAX, e->min_rows, e->band_capable ? e->band_dw : e->dw, e->band_capable);
+    e->kx = pick_k(e->band_capable ? GOL_FAMILY_BAND : GOL_FAMILY_BITS, e->k, INT64_MAX, e->min_rows, e->band_capable ? e->band_dw : e->dw);
     e->sh.resize(devices.size());
     for (size_t i = 0; i < devices.size(); ++i) {
         gol_shard &s = e->sh[i];

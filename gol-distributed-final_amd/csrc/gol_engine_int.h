@@ -64,7 +64,7 @@ int xtime_wait(gol_shard &s, hipStream_t st, size_t ev);
 int xtime_waited(gol_shard &s, hipStream_t st, size_t ev);
 int xtime_stop(gol_engine *e, gol_shard &s, hipStream_t st, size_t ev, int shard);
 // gol_step.cpp
-int pick_k(int want, int64_t remaining, int64_t rows, int dw, bool band);
+int pick_k(int family, int want, int64_t remaining, int64_t rows, int dw);
 int rule_step_check(const gol_engine *e);
 int launch_k(gol_engine *e, int k, int64_t count_ci);
 int exact_turn(gol_engine *e);

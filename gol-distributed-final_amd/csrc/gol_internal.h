@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "golhip.h"
+#include "gol_step_launch.h"
 
 struct gol_comm;
 class gol_ipc;
@@ -19,7 +20,7 @@ class gol_ipc;
 #define GOL_DEFAULT_BAND_K 12  // band layout, 4 words per lane: the split pipeline
 #endif
 #define GOL_DEFAULT_BYTES_K 32 // byte board: the byte pipeline (0/255 boards with W % 32 == 0)
-#define GOL_DEFAULT_DW 2       // standard layout: 64 cells per lane
+// (GOL_DEFAULT_DW, the standard layout's words per lane: gol_step_launch.h)
 
 // A step whose launch runs more rounds of workgroups than this overlaps its edge launches with
 // the interior (GOL_STEP_OVERLAP), else it runs as one launch (gol_step.cpp step_mode).
@@ -124,8 +125,8 @@ struct gol_engine {
     bool bytes_binary = false; // BYTES mode: the board holds only 0/255
     int cur = 0, bcur = 0;
     int64_t turn = 0;
-    // the rule (gol_engine_set_rule): 9-bit masks; rule_generic: the rule kernels (golk_rule_step)
-    // step the bit board, with at most GOLK_RULE_MAX_K turns per launch -- else B3/S23 on the Conway kernels
+    // the rule (gol_engine_set_rule): 9-bit masks; rule_generic: the rule kernels (GOL_FAMILY_RULE_*)
+    // step the bit board, with the turns per launch their table has -- else B3/S23 on the Conway kernels
     uint32_t birth = 0x008, survive = 0x00C;
     bool rule_generic = false;
     int k = GOL_DEFAULT_K;

@@ -1,10 +1,13 @@
 // gol_kernels.h -- internal launcher interface of the kernel units (each unit holds its own
-// launchers, gol_launch.cpp the state they share; not part of the C ABI).
+// launchers, gol_launch.cpp the state they share; not part of the C ABI).  The step kernels and
+// the batch kernel each have one launcher that takes a descriptor: golk_step (gol_step_launch.h)
+// and golk_batch_step (gol_batch.h); the headers that hold a descriptor also hold its check.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "gol_edit.h"  // GOL_EDIT_BYTES / _STANDARD / _BAND: how a board's rows are stored (`form`)
+#include "gol_step_launch.h"
 
 #ifndef GOL_COUNT_SLOTS
 #define GOL_COUNT_SLOTS 256
@@ -31,23 +34,12 @@ void golk_release_claims(hipStream_t s);
 void golk_own_stream(hipStream_t s);
 hipError_t golk_reset_claims_device(int device);
 
-int golk_auto_strip(int64_t rows, int64_t ngroups, int k);
-// Standard layout: dw words per lane (1, 2 or 4), k in {1, 2, 4, 8} (and 16 for dw <= 2).
-hipError_t golk_bits_step(const uint32_t *top, const uint32_t *mid, const uint32_t *bot, uint32_t *dst,
-                          int64_t R, int64_t Wd, int64_t pitch, int64_t row0, int64_t rows, int k, int dw,
-                          int strip, uint64_t *slots, hipStream_t s);
-// Band layout (bit b of word w = cell b*Wd + w): dw words per lane (2 or 4), k in {1, 2, 4, 8},
-// 16 for dw = 2, 12 for dw = 4 (the split pipeline); Wd % dw == 0, pitch % dw == 0, 4*dw-byte
-// aligned rows.  err: error word of the launch (NULL = the device's default word).
-// as_cus, as_slots (the pipelined k = 12 at dw = 4 only): schedule the launch as for a device of
-// as_cus CUs holding as_slots resident workgroups of the kernel (gol_strips.h band_strip_plan); 0,
-// 0: this device.  hipErrorInvalidValue unless as_cus % 8 == 0 and neither exceeds this device's.
-#ifndef GOL_BAND_DEFAULT_DW
-#define GOL_BAND_DEFAULT_DW 4
-#endif
-hipError_t golk_band_step(const uint32_t *top, const uint32_t *mid, const uint32_t *bot, uint32_t *dst, int64_t R,
-                          int64_t Wd, int64_t pitch, int64_t row0, int64_t rows, int k, int dw, int strip,
-                          uint64_t *slots, uint32_t *err, hipStream_t s, int as_cus = 0, int64_t as_slots = 0);
+// One launch of a step kernel -- bits_step_kernel, band_step_kernel, their TableRule forms,
+// bytes_blocked_kernel or one of the two split pipelines behind them -- of what the descriptor says
+// (gol_step_launch.h, where the kernel table, every field and the check are).  hipErrorInvalidValue,
+// nothing launched, unless gol_step_launch_ok accepts the descriptor and, for a pretended device
+// (as_cus, as_slots), neither value exceeds this device's; hipSuccess at once for rows == 0.
+hipError_t golk_step(const gol_step_launch &launch, hipStream_t s);
 // This device's CU count and resident workgroups of a pipeline kernel (band: band_pipe_kernel with
 // contiguous ghost rows or not; else bytes_pipe_kernel), with the fused count or not.
 bool golk_pipe_limits(bool band, bool contig, bool count, int *cus, int64_t *slots);
@@ -55,30 +47,15 @@ bool golk_pipe_limits(bool band, bool contig, bool count, int *cus, int64_t *slo
 // queries, and what the units' _launch launches (gol_device.h).
 const void *golk_band_pipe_fn(bool contig, bool count);
 const void *golk_bytes_pipe_fn(bool count);
-int golk_band_useful_words(int k, int dw);
-// Rounds of resident workgroups a step launch over `rows` rows makes (the band pipeline: 1 for
-// its one-round rank-weighted launch; other kernels: 1e9, i.e. many); for the engine's choice of
-// step plan.
-double golk_step_rounds(bool band, int64_t rows, int64_t Wd, int64_t pitch, int k, int dw, int strip);
-// Life-like rules (the step kernels with TableRule; birth / survive: 9-bit masks over the neighbour count, gol_rule.h):
-// k in {1, 2, 4, 8} turns of a standard or band bit board, GOLK_RULE_DW words per lane in both
-// layouts (Wd and pitch multiples of it, rows aligned to 4 bytes x GOLK_RULE_DW); row addressing,
-// strips and count slots as golk_bits_step / golk_band_step.  golk_rule_useful_words: output words
-// of a wave's column group.
-#define GOLK_RULE_DW 2
-#define GOLK_RULE_MAX_K 8
-hipError_t golk_rule_step(const uint32_t *top, const uint32_t *mid, const uint32_t *bot, uint32_t *dst, int64_t R,
-                          int64_t Wd, int64_t pitch, int64_t row0, int64_t rows, int k, bool band, uint32_t birth,
-                          uint32_t survive, int strip, uint64_t *slots, hipStream_t s);
-int golk_rule_useful_words(bool band, int k);
+// Rounds of resident workgroups a step launch of (family, k, dw) over `rows` rows makes (the band
+// pipeline: 1 for its one-round rank-weighted launch; other kernels: 1e9, i.e. many); for the
+// engine's choice of step plan.
+double golk_step_rounds(int family, int64_t rows, int64_t Wd, int64_t pitch, int k, int dw, int strip);
 // Standard <-> band rows (Wd % 32 == 0), out of place.
 hipError_t golk_band_convert(bool to_band, const uint32_t *src, uint32_t *dst, int64_t rows, int64_t Wd,
                              int64_t spitch, int64_t dpitch, hipStream_t s);
 hipError_t golk_bytes_step(const uint8_t *world, int64_t H, int64_t W, int64_t stride, int64_t y0, int64_t y1,
                            uint8_t *out, int64_t out_stride, hipStream_t s);
-hipError_t golk_bytes_blocked(const uint8_t *top, const uint8_t *mid, const uint8_t *bot, uint8_t *dst, int64_t R,
-                              int64_t W, int64_t pitch, int64_t row0, int64_t rows, int k, int strip, uint64_t *slots,
-                              uint32_t *err, hipStream_t s, int as_cus = 0, int64_t as_slots = 0);  // (k = 32: as golk_band_step's)
 hipError_t golk_nonbinary(const uint8_t *bytes, int64_t rows, int64_t W, int64_t stride, uint32_t *flag, hipStream_t s);
 hipError_t golk_random_fill(uint32_t *dst, int64_t rows, int64_t grow0, int64_t W, int64_t pitch, uint64_t seed,
                             hipStream_t s);

@@ -18,14 +18,16 @@
 // and live in git history (commit 297b13e).
 //
 // This unit: the step kernels (bits_step_kernel, band_step_kernel) with their rules, the layout
-// conversion, the blocked and exact byte kernels, and their launchers.  The two split pipelines are
+// conversion, the blocked and exact byte kernels, and their launchers: golk_step, the one launcher
+// of every step kernel, takes a descriptor (gol_step_launch.h: the kernel table, the check, the
+// geometry) and expands the table into its dispatch.  The two split pipelines are
 // units of their own (gol_band_pipe.hip, gol_bytes_pipe.hip; launched through gol_device.h), the
 // board utilities gol_util.hip; the launch state (error word, CU slots, claim counters, the strips
 // of a pipelined launch) is host code, gol_launch.cpp.
 // gol_device.h holds what the units share, gol_pipe.h what only the pipelines share.
 #include <stdlib.h>
 
-#include <algorithm>
+#include <type_traits>
 
 #include "gol_device.h"
 #include "gol_launch.h"
@@ -629,139 +631,82 @@ __global__ void bytes_step_scalar_kernel(BytesArgs a)
 // ------------------------------------------------------------------ launchers
 using namespace golk;
 
-template <int K, int DW>
-static hipError_t launch_bits(const BitsArgs &a, hipStream_t s)
+// The kernel arguments of a step launch, filled in one place: column groups and strips from the
+// launch's geometry (a pipeline's strips come from its plan afterwards), no strip map; the error
+// word and the CU slot masks for the families that have a pipeline (the one-wave kernels wait for
+// no flag and read neither).  A: TableRule::Args (BitsArgs and the masks) or BytesKArgs.
+template <class A>
+static hipError_t fill_args(A &a, const gol_step_launch &l, const gol_step_geometry &g)
 {
-    const int nstrips = (int)((a.rows + a.strip - 1) / a.strip);
-    dim3 grid((a.ngroups + 3) / 4, nstrips);
-    hipLaunchKernelGGL((bits_step_kernel<K, DW>), grid, dim3(256), 0, s, a);
-    return hipGetLastError();
-}
-
-template <int DW>
-static hipError_t launch_bits_k(int k, const BitsArgs &a, hipStream_t s)
-{
-    switch (k) {
-    case 1: return launch_bits<1, DW>(a, s);
-    case 2: return launch_bits<2, DW>(a, s);
-    case 4: return launch_bits<4, DW>(a, s);
-    case 8: return launch_bits<8, DW>(a, s);
-    case 16: if constexpr (DW <= 2) return launch_bits<16, DW>(a, s);
-             return hipErrorInvalidValue;
-    default: return hipErrorInvalidValue;
-    }
-}
-
-// Arguments of a step launch (golk_bits_step, golk_band_step, golk_rule_step): waves of U output
-// words, strips of `strip` rows (<= 0: golk_auto_strip), no strip map, error word or CU slots.
-static BitsArgs step_args(const uint32_t *top, const uint32_t *mid, const uint32_t *bot, uint32_t *dst, int64_t R,
-                          int64_t Wd, int64_t pitch, int64_t row0, int64_t rows, int U, int k, int strip,
-                          uint64_t *slots)
-{
-    BitsArgs a;
-    a.top = top; a.mid = mid; a.bot = bot; a.dst = dst;
-    a.R = R; a.Wd = Wd; a.pitch = pitch; a.row0 = row0; a.rows = rows;
-    a.ngroups = (int)((Wd + U - 1) / U);
-    a.strip = strip > 0 ? std::min(strip, GOL_MAX_STRIP) : golk_auto_strip(rows, a.ngroups, k);
-    a.slots = slots;
+    a.top = static_cast<decltype(a.top)>(l.top); a.mid = static_cast<decltype(a.mid)>(l.mid);
+    a.bot = static_cast<decltype(a.bot)>(l.bot); a.dst = static_cast<decltype(a.dst)>(l.dst);
+    a.R = l.R; a.Wd = g.words; a.pitch = l.pitch; a.row0 = l.row0; a.rows = l.rows;
+    a.ngroups = g.ngroups;
+    a.strip = g.strip;
+    a.slots = l.slots;
     a.sm = StripMap{};
-    a.err = nullptr;  // no flag waits in the step kernels
-    a.cu_slots = nullptr;
-    return a;
-}
-
-hipError_t golk_bits_step(const uint32_t *top, const uint32_t *mid, const uint32_t *bot, uint32_t *dst,
-                          int64_t R, int64_t Wd, int64_t pitch, int64_t row0, int64_t rows, int k, int dw,
-                          int strip, uint64_t *slots, hipStream_t s)
-{
-    if (rows <= 0) return hipSuccess;
-    const BitsArgs a = step_args(top, mid, bot, dst, R, Wd, pitch, row0, rows, 62 * dw, k, strip, slots);
-    switch (dw) {
-    case 1: return launch_bits_k<1>(k, a, s);
-    case 2: return launch_bits_k<2>(k, a, s);
-    case 4: return launch_bits_k<4>(k, a, s);
-    default: return hipErrorInvalidValue;
+    a.err = nullptr;
+    if (l.family == GOL_FAMILY_BAND || l.family == GOL_FAMILY_BYTES) {
+        a.err = err_or_default(l.err);
+        if (!a.err) return hipErrorOutOfMemory;
     }
-}
-
-template <int DW, bool C>
-static hipError_t launch_band(int k, dim3 grid, const BitsArgs &a, hipStream_t s)
-{
-    switch (k) {
-    case 1: hipLaunchKernelGGL((band_step_kernel<1, DW, C>), grid, dim3(256), 0, s, a); break;
-    case 2: hipLaunchKernelGGL((band_step_kernel<2, DW, C>), grid, dim3(256), 0, s, a); break;
-    case 4: hipLaunchKernelGGL((band_step_kernel<4, DW, C>), grid, dim3(256), 0, s, a); break;
-    case 8: hipLaunchKernelGGL((band_step_kernel<8, DW, C>), grid, dim3(256), 0, s, a); break;
-    case 12: if constexpr (DW <= 2) { hipLaunchKernelGGL((band_step_kernel<12, DW, C>), grid, dim3(256), 0, s, a); break; }
-             return hipErrorInvalidValue;
-    case 16: if constexpr (DW <= 2) { hipLaunchKernelGGL((band_step_kernel<16, DW, C>), grid, dim3(256), 0, s, a); break; }
-             return hipErrorInvalidValue;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-}
-
-hipError_t golk_band_step(const uint32_t *top, const uint32_t *mid, const uint32_t *bot, uint32_t *dst, int64_t R,
-                          int64_t Wd, int64_t pitch, int64_t row0, int64_t rows, int k, int dw, int strip,
-                          uint64_t *slots, uint32_t *err, hipStream_t s, int as_cus, int64_t as_slots)
-{
-    if (rows <= 0) return hipSuccess;
-    BitsArgs a = step_args(top, mid, bot, dst, R, Wd, pitch, row0, rows, band_useful_words(k, dw), k, strip, slots);
-    a.err = err_or_default(err);
-    if (!a.err) return hipErrorOutOfMemory;
-    if (GOL_BAND_PLACE) {
+    if constexpr (std::is_same<A, TableRule::Args>::value) {
+        a.birth = l.birth; a.survive = l.survive;
+        a.cu_slots = nullptr;
         int dev = 0;
-        if (hipGetDevice(&dev) == hipSuccess) a.cu_slots = golk_cu_slots(dev);
+        if (GOL_BAND_PLACE && l.family == GOL_FAMILY_BAND && hipGetDevice(&dev) == hipSuccess) a.cu_slots = golk_cu_slots(dev);
     }
-    const bool contig = top + (int64_t)k * pitch == mid && bot == mid + R * pitch;
-    if (dw == 4 && k == GOL_BAND_KW * GOL_BAND_P) {
-        // k = 12 on the band layout: 4 waves x 3 stages (band_pipe_kernel), one workgroup per
-        // (column group, range of rows): band_strip_plan.
-        const bool count = a.slots != nullptr;
+    return hipSuccess;
+}
+
+// One entry of the kernel table (gol_step_launch.h) on `grid`; a pipelined entry is not launched here.
+template <int F, int K, int DW, bool PIPE>
+static void launch_kernel(dim3 grid, bool contig, const TableRule::Args &a, const BytesKArgs &b, hipStream_t s)
+{
+    const BitsArgs &c = a;  // (the B3/S23 kernels take the arguments without the masks)
+    if constexpr (PIPE) return;
+    else if constexpr (F == GOL_FAMILY_BITS) hipLaunchKernelGGL((bits_step_kernel<K, DW>), grid, dim3(256), 0, s, c);
+    else if constexpr (F == GOL_FAMILY_BAND) {
+        if (contig) hipLaunchKernelGGL((band_step_kernel<K, DW, true>), grid, dim3(256), 0, s, c);
+        else hipLaunchKernelGGL((band_step_kernel<K, DW, false>), grid, dim3(256), 0, s, c);
+    } else if constexpr (F == GOL_FAMILY_RULE_STD) hipLaunchKernelGGL((bits_step_kernel<K, DW, TableRule>), grid, dim3(256), 0, s, a);
+    else if constexpr (F == GOL_FAMILY_RULE_BAND) hipLaunchKernelGGL((band_step_kernel<K, DW, false, TableRule>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(bytes_blocked_kernel<K>, grid, dim3(256), 0, s, b);
+}
+
+hipError_t golk_step(const gol_step_launch &l, hipStream_t s)
+{
+    if (!gol_step_launch_ok(l)) return hipErrorInvalidValue;
+    if (l.rows == 0) return hipSuccess;
+    const gol_step_geometry g = gol_step_geometry_of(l);
+    const bool bytes = l.family == GOL_FAMILY_BYTES, count = l.slots != nullptr;
+    TableRule::Args a;
+    BytesKArgs b;
+    const hipError_t e = bytes ? fill_args(b, l, g) : fill_args(a, l, g);
+    if (e != hipSuccess) return e;
+    if (g.pipelined) {
+        // one workgroup of the pipeline's waves per (column group, range of rows): band_strip_plan
+        // (k = 12: 4 waves x 3 stages), bytes_strip_plan (k = 32: 8 waves x 4)
         unsigned nwg = 0;
-        if (!pipe_plan(band_strip_plan, golk_band_pipe_fn(contig, count), 64 * GOL_BAND_P, rows, Wd, pitch, k, strip,
-                       as_cus, as_slots, s, a.strip, a.sm, nwg))
+        if (bytes) {
+            if (!pipe_plan(bytes_strip_plan, golk_bytes_pipe_fn(count), 64 * GOL_BYTES_PIPE_P, l.rows, l.width, l.pitch, l.k,
+                           l.strip_rows, l.as_cus, l.as_slots, s, b.strip, b.sm, nwg))
+                return hipErrorInvalidValue;
+            return golk_bytes_pipe_launch(count, nwg, b, s);
+        }
+        if (!pipe_plan(band_strip_plan, golk_band_pipe_fn(g.contig, count), 64 * GOL_BAND_P, l.rows, l.width, l.pitch, l.k,
+                       l.strip_rows, l.as_cus, l.as_slots, s, a.strip, a.sm, nwg))
             return hipErrorInvalidValue;
-        return golk_band_pipe_launch(contig, count, nwg, a, s);
+        return golk_band_pipe_launch(g.contig, count, nwg, a, s);
     }
-    if (as_cus || as_slots) return hipErrorInvalidValue;
-    dim3 grid((a.ngroups + 3) / 4, (int)((rows + a.strip - 1) / a.strip));
-    if (dw == 2) return contig ? launch_band<2, true>(k, grid, a, s) : launch_band<2, false>(k, grid, a, s);
-    if (dw == 4) return contig ? launch_band<4, true>(k, grid, a, s) : launch_band<4, false>(k, grid, a, s);
-    return hipErrorInvalidValue;
-}
-
-int golk_band_useful_words(int k, int dw) { return band_useful_words(k, dw); }
-
-// Life-like rules: the step kernels with the rule as data, general row addressing.
-template <int K>
-static hipError_t launch_rule(bool band, dim3 grid, const TableRule::Args &a, hipStream_t s)
-{
-    constexpr int DW = GOLK_RULE_DW;
-    if (band) hipLaunchKernelGGL((band_step_kernel<K, DW, false, TableRule>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((bits_step_kernel<K, DW, TableRule>), grid, dim3(256), 0, s, a);
+    const dim3 grid((g.ngroups + 3) / 4, (unsigned)((l.rows + g.strip - 1) / g.strip));
+    switch (gol_step_key(l.family, l.k, l.dw)) {
+#define GOL_STEP_CASE(F, K, DW, FLAGS) \
+    case gol_step_key(GOL_FAMILY_##F, K, DW): launch_kernel<GOL_FAMILY_##F, K, DW, ((FLAGS) & GOL_STEP_PIPELINED) != 0>(grid, g.contig, a, b, s); break;
+    GOL_STEP_KERNELS(GOL_STEP_CASE)
+#undef GOL_STEP_CASE
+    }
     return hipGetLastError();
-}
-
-int golk_rule_useful_words(bool band, int k) { return band ? band_useful_words(k, GOLK_RULE_DW) : 62 * GOLK_RULE_DW; }
-
-hipError_t golk_rule_step(const uint32_t *top, const uint32_t *mid, const uint32_t *bot, uint32_t *dst, int64_t R,
-                          int64_t Wd, int64_t pitch, int64_t row0, int64_t rows, int k, bool band, uint32_t birth,
-                          uint32_t survive, int strip, uint64_t *slots, hipStream_t s)
-{
-    if (rows <= 0) return hipSuccess;
-    if (birth >= 512 || survive >= 512 || Wd % GOLK_RULE_DW || pitch % GOLK_RULE_DW) return hipErrorInvalidValue;
-    const TableRule::Args a{step_args(top, mid, bot, dst, R, Wd, pitch, row0, rows, golk_rule_useful_words(band, k), k,
-                                      strip, slots),
-                            birth, survive};
-    const dim3 grid((a.ngroups + 3) / 4, (unsigned)((rows + a.strip - 1) / a.strip));
-    switch (k) {
-    case 1: return launch_rule<1>(band, grid, a, s);
-    case 2: return launch_rule<2>(band, grid, a, s);
-    case 4: return launch_rule<4>(band, grid, a, s);
-    case 8: return launch_rule<8>(band, grid, a, s);
-    default: return hipErrorInvalidValue;
-    }
 }
 
 hipError_t golk_band_convert(bool to_band, const uint32_t *src, uint32_t *dst, int64_t rows, int64_t Wd,
@@ -799,43 +744,6 @@ hipError_t golk_bytes_step(const uint8_t *world, int64_t H, int64_t W, int64_t s
     } else {
         a.ngroups = 0; a.strip = 0;
         hipLaunchKernelGGL(bytes_step_scalar_kernel, dim3(grid_for((y1 - y0) * W)), dim3(256), 0, s, a);
-    }
-    return hipGetLastError();
-}
-
-hipError_t golk_bytes_blocked(const uint8_t *top, const uint8_t *mid, const uint8_t *bot, uint8_t *dst, int64_t R,
-                              int64_t W, int64_t pitch, int64_t row0, int64_t rows, int k, int strip, uint64_t *slots,
-                              uint32_t *err, hipStream_t s, int as_cus, int64_t as_slots)
-{
-    BytesKArgs a;
-    a.top = top; a.mid = mid; a.bot = bot; a.dst = dst;
-    a.R = R; a.Wd = W / 32; a.pitch = pitch; a.row0 = row0; a.rows = rows;
-    a.ngroups = (int)((a.Wd + 61) / 62);
-    a.strip = strip > 0 ? std::min(strip, GOL_MAX_STRIP) : golk_auto_strip(rows, a.ngroups, k);
-    a.slots = slots;
-    a.err = err_or_default(err);
-    if (rows <= 0) return hipSuccess;
-    if (!a.err) return hipErrorOutOfMemory;
-    a.sm = StripMap{};
-    if (k == 32) {
-        // one workgroup of GOL_BYTES_PIPE_P waves per (column group, strip): bytes_strip_plan
-        const bool count = a.slots != nullptr;
-        unsigned nwg = 0;
-        if (!pipe_plan(bytes_strip_plan, golk_bytes_pipe_fn(count), 64 * GOL_BYTES_PIPE_P, rows, W, pitch, k, strip,
-                       as_cus, as_slots, s, a.strip, a.sm, nwg))
-            return hipErrorInvalidValue;
-        return golk_bytes_pipe_launch(count, nwg, a, s);
-    }
-    if (as_cus || as_slots) return hipErrorInvalidValue;
-    const int nstrips = (int)((rows + a.strip - 1) / a.strip);
-    dim3 grid((a.ngroups + 3) / 4, nstrips);
-    switch (k) {
-    case 1: hipLaunchKernelGGL(bytes_blocked_kernel<1>, grid, dim3(256), 0, s, a); break;
-    case 2: hipLaunchKernelGGL(bytes_blocked_kernel<2>, grid, dim3(256), 0, s, a); break;
-    case 4: hipLaunchKernelGGL(bytes_blocked_kernel<4>, grid, dim3(256), 0, s, a); break;
-    case 8: hipLaunchKernelGGL(bytes_blocked_kernel<8>, grid, dim3(256), 0, s, a); break;
-    case 16: hipLaunchKernelGGL(bytes_blocked_kernel<16>, grid, dim3(256), 0, s, a); break;
-    default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
 }

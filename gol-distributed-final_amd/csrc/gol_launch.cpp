@@ -1,7 +1,7 @@
 // gol_launch.cpp -- the launch state of the kernel units, as host code: the per-device words (error
 // word, CU slot masks), the paired ranks' claim counters per stream with their recovery after a
 // faulted launch, the resident-workgroup cache and the strips of a pipelined launch (gol_strips.h),
-// and the strip heuristics the engine asks for.  A kernel is an opaque handle here (const void *).
+// and the rounds of a launch the engine asks for.  A kernel is an opaque handle here (const void *).
 #include <algorithm>
 #include <map>
 #include <mutex>
@@ -58,26 +58,6 @@ uint32_t *err_or_default(uint32_t *err)
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return nullptr;
     return golk_device_err_word(dev);
-}
-
-int golk_auto_strip(int64_t rows, int64_t ngroups, int k)
-{
-    // aim for >= ~8192 waves (32 per CU) but no longer than 64*k rows: the 2k halo rows then
-    // cost <= 1/32 (measured best on the 2^17 x 2^20 torus: 512 rows at k = 8, 1024 at k = 16)
-    int64_t strip = rows * ngroups / 8192;
-    const int64_t hi = 64 * (int64_t)k;
-    if (strip > hi) strip = hi;
-    int64_t lo = 8 * (int64_t)k;
-    if (lo < 32) lo = 32;
-    // a board too small for ~512 strips of lo rows (the reference's images: 512^2 is one column
-    // group) is latency-bound: a launch lasts one wave's serial walk over strip + 2k rows, so
-    // ~512 short strips win (512^2, k = 8: strip 1-2 -> 2.3 us per turn, 64 -> 5.8;
-    // profiles/r03/r03q_small.jsonl)
-    if (rows * ngroups < lo * 512) lo = std::max<int64_t>(1, rows * ngroups / 512);
-    if (strip < lo) strip = lo;
-    if (strip > rows) strip = rows;
-    if (strip < 1) strip = 1;
-    return (int)strip;
 }
 
 // Workgroups of `kernel` (block threads) resident on the whole device at once (cached).
@@ -196,14 +176,15 @@ hipError_t golk_reset_claims_device(int device)
 }
 
 // The device a pipelined launch is scheduled for: this one (as_cus = as_slots = 0), or a
-// pretended smaller one of as_cus CUs (a multiple of 8) holding as_slots resident workgroups of
-// `kernel`; false: it asks for more than this device has.
+// pretended smaller one of as_cus CUs holding as_slots resident workgroups of `kernel` (what the
+// two must be on any device: gol_step_launch_ok); false: it asks for more than this device has,
+// which is checked here and nowhere else.
 static bool pipe_device(const void *kernel, int block, int as_cus, int64_t as_slots, int &cus, int64_t &slots)
 {
     cus = device_cus();
     slots = resident_workgroups(kernel, block);
     if (!as_cus && !as_slots) return true;
-    if (as_cus <= 0 || as_cus % 8 || as_cus > cus || as_slots <= 0 || as_slots > slots) return false;
+    if (as_cus > cus || as_slots > slots) return false;
     cus = as_cus;
     slots = as_slots;
     return true;
@@ -238,9 +219,9 @@ bool golk_pipe_limits(bool band, bool contig, bool count, int *cus, int64_t *slo
     return *cus > 0 && *slots > 0;
 }
 
-double golk_step_rounds(bool band, int64_t rows, int64_t Wd, int64_t pitch, int k, int dw, int strip)
+double golk_step_rounds(int family, int64_t rows, int64_t Wd, int64_t pitch, int k, int dw, int strip)
 {
-    if (!band || dw != 4 || k != GOL_BAND_KW * GOL_BAND_P || rows <= 0) return 1e9;
+    if (family != GOL_FAMILY_BAND || !gol_step_kernel_of(family, k, dw).pipelined || rows <= 0) return 1e9;
     const int64_t slots = resident_workgroups(golk_band_pipe_fn(true, true), 64 * GOL_BAND_P);
     if (slots <= 0) return 1e9;
     const StripPlan p = band_strip_plan(rows, Wd, pitch, k, strip, device_cus(), slots);  // the launch's own plan

@@ -3,28 +3,25 @@
 // stepping calls with their batched count points, and the whole-board count and hash.
 #include "gol_engine_int.h"
 
-// Turns per launch: the largest supported k <= want, the remaining turns and the smallest
-// shard.  k = 12 is the band layout's (the split pipeline at 4 words per lane, one wave for
-// all 12 turns at 2); k = 16 needs <= 2 words per lane.
-int pick_k(int want, int64_t remaining, int64_t rows, int dw, bool band)
+// Turns per launch: the largest k of (family, dw) in the kernel table (gol_step_launch.h; every
+// kernel, the engine-only one included) that is <= want, the remaining turns and the smallest shard.
+int pick_k(int family, int want, int64_t remaining, int64_t rows, int dw)
 {
-    static const int ks[] = {16, 12, 8, 4, 2, 1};
-    for (int k : ks) {
-        if (k == 16 && dw > 2) continue;
-        if (k == 12 && !band) continue;  // band: the split pipeline (4 words per lane) or one wave (2)
-        if (k <= want && k <= remaining && k <= rows) return k;
-    }
-    return 1;
+    const int k = gol_step_max_k(family, dw, std::min<int64_t>({want, remaining, rows}));
+    return k ? k : 1;
 }
 
-// The bit board's launches under the engine's rule: words per lane of the kernel that runs them
-// and their turns per launch.  The rule kernels run at most GOLK_RULE_MAX_K turns, so under them
-// pick_k never sees a want of 12 or 16; e->kx (the exchanged halo, from the Conway k) stays >= k.
+// The bit board's launches under the engine's rule: the kernel family and the words per lane that
+// run them, and their turns per launch.  The rule families have no k above 8, so under them
+// e->kx (the exchanged halo, from the Conway k) stays >= k.
+static int step_family(const gol_engine *e, bool band)
+{
+    return e->rule_generic ? (band ? GOL_FAMILY_RULE_BAND : GOL_FAMILY_RULE_STD) : (band ? GOL_FAMILY_BAND : GOL_FAMILY_BITS);
+}
 static int step_dw(const gol_engine *e, bool band) { return e->rule_generic ? GOLK_RULE_DW : (band ? e->band_dw : e->dw); }
 static int step_pick_k(const gol_engine *e, int64_t remaining, bool band)
 {
-    const int want = e->rule_generic ? std::min(e->k, GOLK_RULE_MAX_K) : e->k;
-    return pick_k(want, remaining, e->min_rows, step_dw(e, band), band);
+    return pick_k(step_family(e, band), e->k, remaining, e->min_rows, step_dw(e, band));
 }
 
 // Stepping calls under a non-B3/S23 rule: the reference's byte semantics (exactly 0 / exactly
@@ -47,14 +44,9 @@ static int step_launch(gol_engine *e, gol_shard &s, hipStream_t st, int k, int64
         top = mid + (s.R - k) * e->pitch;
         bot = mid;
     }
-    uint32_t *dst = s.bits[1 - e->cur];
-    if (e->rule_generic)
-        HIPCHK(golk_rule_step(top, mid, bot, dst, s.R, e->Wd, e->pitch, row0, rows, k, e->band, e->birth, e->survive, e->strip,
-                              slots, st));
-    else if (e->band)
-        HIPCHK(golk_band_step(top, mid, bot, dst, s.R, e->Wd, e->pitch, row0, rows, k, e->band_dw, e->strip, slots, s.err, st));
-    else
-        HIPCHK(golk_bits_step(top, mid, bot, dst, s.R, e->Wd, e->pitch, row0, rows, k, e->dw, e->strip, slots, st));
+    const gol_step_launch l = {step_family(e, e->band), top, mid, bot, s.bits[1 - e->cur], s.R, e->Wd, e->pitch, row0, rows, k,
+                               step_dw(e, e->band), e->strip, e->birth, e->survive, slots, s.err, 0, 0};
+    HIPCHK(golk_step(l, st));
     return GOL_OK;
 }
 
@@ -68,7 +60,7 @@ static int step_mode(gol_engine *e, const gol_shard &s, int k)
     if (e->step_flags) return e->step_flags;
     if (local_wrap(e)) return GOL_STEP_SERIAL;  // nothing to exchange, nothing to overlap
     if (e->rule_generic) return GOL_STEP_OVERLAP;  // the rule kernels: equal strips, launches of many rounds
-    const double rounds = golk_step_rounds(e->band, s.R, e->Wd, e->pitch, k, e->band ? e->band_dw : e->dw, e->strip);
+    const double rounds = golk_step_rounds(step_family(e, e->band), s.R, e->Wd, e->pitch, k, step_dw(e, e->band), e->strip);
     return rounds > GOL_OVERLAP_ROUNDS ? GOL_STEP_OVERLAP : GOL_STEP_SERIAL;
 }
 
@@ -225,12 +217,12 @@ int advance(gol_engine *e, int64_t n, int64_t ci)
             const uint8_t *mid = s.bytes[e->bcur];
             if (e->bytes_binary && e->W % 32 == 0) {
                 // 0/255 byte board: k turns per launch on the bytes (torus wrap through top/bot)
-                const int k = e->k >= 32 && n >= 32 && e->H >= 32 ? 32 : pick_k(e->k, n, e->H, 1, false);
+                const int k = pick_k(GOL_FAMILY_BYTES, e->k, n, e->H, 1);
                 const bool last = n == k && ci >= 0;
                 if (last) RCCHK(batch_begin(e, ci));
-                HIPCHK(golk_bytes_blocked(mid + (e->H - k) * e->bstride, mid, mid, s.bytes[1 - e->bcur], e->H, e->W,
-                                          e->bstride, 0, e->H, k, e->strip, last ? batch_slots(s, ci) : nullptr, s.err,
-                                          s.stream));
+                const gol_step_launch l = {GOL_FAMILY_BYTES, mid + (e->H - k) * e->bstride, mid, mid, s.bytes[1 - e->bcur], e->H, e->W,
+                                           e->bstride, 0, e->H, k, 1, e->strip, 0, 0, last ? batch_slots(s, ci) : nullptr, s.err, 0, 0};
+                HIPCHK(golk_step(l, s.stream));
                 if (timing_open(e)) {
                     e->tcall_cells[0] += (double)e->H * (double)e->W * k;
                     e->tcall_steps += 1;
@@ -377,19 +369,18 @@ extern "C" int gol_engine_info(gol_engine *e, int32_t *k, int32_t *cells_per_lan
     if (!e) return gol_set_error(GOL_EINVAL, "engine is NULL");
     const bool bits = e->mode == GOL_MODE_BITS;
     const bool band = bits && e->band_capable;
+    const bool blocked = e->mode == GOL_MODE_BYTES && e->bytes_binary && e->W % 32 == 0;  // the 0/255 byte board
+    const int family = bits ? step_family(e, band) : (blocked ? GOL_FAMILY_BYTES : GOL_FAMILY_BITS);
     const int dw = bits ? step_dw(e, band) : e->dw;
-    // the k of the next launch, as advance() picks it
-    int kk = 1;  // the exact one-turn kernel: a board before its exact first turn, a byte board of W % 32 != 0 or non-0/255 bytes
-    if (bits) kk = step_pick_k(e, e->k, band);
-    else if (e->mode == GOL_MODE_BYTES && e->bytes_binary && e->W % 32 == 0)
-        kk = e->k >= 32 && e->H >= 32 ? 32 : pick_k(e->k, e->k, e->H, 1, false);
+    // the k of the next launch, as advance() picks it; 1: the exact one-turn kernel (a board before
+    // its exact first turn, a byte board of W % 32 != 0 or non-0/255 bytes)
+    const int kk = bits ? step_pick_k(e, e->k, band) : (blocked ? pick_k(family, e->k, e->k, e->H, 1) : 1);
     if (k) *k = kk;
     if (cells_per_lane) *cells_per_lane = 32 * dw;
-    if (strip_rows) {
-        const int64_t u = bits && e->rule_generic ? golk_rule_useful_words(band, kk)
-                                                  : (band ? golk_band_useful_words(kk, dw) : 62 * dw);
-        const int64_t ng = (e->Wd + u - 1) / u;
-        *strip_rows = e->strip > 0 ? e->strip : golk_auto_strip(e->min_rows, ng, kk);
+    if (strip_rows) {  // of a one-wave kernel over the smallest shard, as the launch computes it
+        gol_step_geometry g;
+        gol_step_strips(gol_step_kernel_of(family, kk, blocked ? 1 : dw), e->Wd, e->min_rows, kk, e->strip, g);
+        *strip_rows = g.strip;
     }
     if (bit_mode) *bit_mode = bits ? (band ? 2 : 1) : 0;
     return GOL_OK;

@@ -44,6 +44,8 @@ GOL_RULE_GENERIC = 1  # gol_engine_set_rule flag: B3/S23 on the rule kernels too
 GOL_PASTE_COPY, GOL_PASTE_OR, GOL_PASTE_XOR, GOL_PASTE_ANDNOT = 0, 1, 2, 3
 GOL_STRIP_KERNEL_BAND, GOL_STRIP_KERNEL_BYTES = 0, 1
 STRIP_KERNELS = {"band": GOL_STRIP_KERNEL_BAND, "bytes": GOL_STRIP_KERNEL_BYTES}
+# GOL_FAMILY_*: the step kernels' families (gol_step_check_host)
+STEP_FAMILIES = {"bits": 0, "band": 1, "rule_std": 2, "rule_band": 3, "bytes": 4}
 # gol_strip_info.mode (GOL_STRIPS_*)
 STRIP_MODES = {0: "small", 1: "explicit", 2: "plain", 3: "round_tiled", 4: "tail", 5: "ranked_static",
                6: "ranked_paired"}
@@ -196,6 +198,8 @@ SIGNATURES = [
     ("gol_batch_verdict_host", ctypes.c_int, [_i64, _i64, _i64]),
     ("gol_batch_step_check_host", ctypes.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i32, _i64, _i32, _i32, ctypes.c_uint32,
                                                  ctypes.c_uint32, _vp, _i32, _i64, _vp, _vp, _i64, _vp, _vp]),
+    ("gol_step_check_host", ctypes.c_int, [_i32, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i32, _i32, ctypes.c_uint32,
+                                           ctypes.c_uint32, _i32, _i32, _i32, _vp]),
     ("gol_halo_plan", ctypes.c_int, [_i64, _i32, _i32, _i32, _P(gol_halo_op), _i32, _P(_i32)]),
     ("gol_step_plan", ctypes.c_int, [_i64, _i32, _i32, _i32, _P(gol_launch), _i32, _P(_i32)]),
     ("gol_view_plan", ctypes.c_int, [_i64, _i32, _i32, _i64, _i64, _P(gol_view_run), _i32, _P(_i32)]),

@@ -733,6 +733,32 @@ int gol_batch_step_check_host(const uint64_t *boards, const uint64_t *prev, cons
                               int64_t W, int32_t turns, int64_t turn0, int32_t have_prev, int32_t write_prev, uint32_t birth,
                               uint32_t survive, const uint32_t *rules, int32_t scan, int64_t done, const int32_t *list,
                               const int32_t *count, int64_t slots, const int64_t *left, const int64_t *born);
+/* The argument check of the step launches (a host function, no GPU needed; the
+ * function of csrc/gol_step_launch.h that every launch of a step kernel passes,
+ * from gol_dev_bits_step, _band_step(_on), _rule_step, _bytes_step_k(_on) and from
+ * the engine).  family: the kernels of gol_dev_bits_step, gol_dev_band_step,
+ * gol_dev_rule_step in the standard and in the band layout, gol_dev_bytes_step_k.
+ * The arguments are those entries' (width and pitch: Wd and pitch in words, for
+ * BYTES W and stride in bytes; cus, slots: those of the _on entries, else 0)
+ * with words_per_lane in place of cells_per_lane: cells_per_lane / 32, the
+ * default resolved (64 cells; band 128), 1 for BYTES.  as_entry != 0: as the C
+ * entries answer; 0: as the engine's launches are checked, which also have the
+ * band kernel of k = 12 at 2 words per lane.  GOL_OK where the launch would be
+ * made, GOL_EINVAL where it is refused (what only a device can refuse -- cus or
+ * slots above its own -- is not looked at).  geometry (may be NULL) receives,
+ * for a launch that passes: [0] the output words of a wave's column group, [1]
+ * the column groups of a row, [2] 1 where the ghost rows are contiguous with
+ * the shard (top + k rows == mid and bot == mid + R rows), [3] 1 for a
+ * pipelined kernel.  Launches nothing and reads no memory: of a pointer only
+ * its value counts.  No version bump: probe by symbol. */
+#define GOL_FAMILY_BITS 0
+#define GOL_FAMILY_BAND 1
+#define GOL_FAMILY_RULE_STD 2
+#define GOL_FAMILY_RULE_BAND 3
+#define GOL_FAMILY_BYTES 4
+int gol_step_check_host(int32_t family, const void *top, const void *mid, const void *bot, const void *dst, int64_t R,
+                        int64_t width, int64_t pitch, int64_t row0, int64_t rows, int32_t k, int32_t words_per_lane,
+                        uint32_t birth, uint32_t survive, int32_t cus, int32_t slots, int32_t as_entry, int32_t *geometry);
 
 /* ---------------------------------------------------------------- plans
  * The schedule of a sharded step as data (host functions, no GPU needed).  The

@@ -11,7 +11,10 @@ tests/rule_ref.py.  This module holds what that comparison needs and no GPU:
 * expected(): rows [y0, y0 + R) of a torus after k turns;
 * CASES: the generated case table, with the memory picture of every case (which allocations,
   where top / mid / bot / dst point into them, what they hold before the launch);
-* check_args(): the argument rules of include/golhip.h, restated.
+* check_args(): the argument rules of include/golhip.h, restated;
+* TABLE: the step kernels as csrc/gol_step_launch.h lists them, the engine-only one and the two
+  pipelines included; refusals(): calls one change away from a good one, per family and clause of
+  the launch check, shared by the CPU and GPU tests of the refusals.
 
 tests/test_step_ref_cpu.py checks the helpers against the oracle and asserts the table's coverage.
 """
@@ -97,15 +100,42 @@ def stepped(seed: int, H: int, Wd: int, rule: str, k: int) -> np.ndarray:
     return t
 
 
-# ------------------------------------------------------------------ the instantiations
-def _instantiations():
-    out = [("bits", k, dw) for dw in (1, 2, 4) for k in (1, 2, 4, 8, 16) if not (k == 16 and dw == 4)]
-    out += [("band", k, 2) for k in (1, 2, 4, 8, 16)] + [("band", k, 4) for k in (1, 2, 4, 8)]
-    out += [(kind, k, RULE_DW) for kind in ("rule_std", "rule_band") for k in (1, 2, 4, 8)]
-    return tuple(out)
+# ------------------------------------------------------------------ the kernel table
+FAMILIES = ("bits", "band", "rule_std", "rule_band", "bytes")  # GOL_FAMILY_* 0..4 (include/golhip.h)
 
 
-INSTANTIATIONS = _instantiations()
+def _table():
+    """(family, k, words per lane) -> flags, as GOL_STEP_KERNELS of csrc/gol_step_launch.h states it:
+    "pipelined" (a split pipeline), "engine_only" (the engine launches it, gol_dev_band_step refuses it)."""
+    t = {("bits", k, dw): () for dw in (1, 2, 4) for k in (1, 2, 4, 8, 16) if not (k == 16 and dw == 4)}
+    t.update({("band", k, 2): () for k in (1, 2, 4, 8, 16)})
+    t.update({("band", k, 4): () for k in (1, 2, 4, 8)})
+    t[("band", 12, 2)] = ("engine_only",)
+    t[("band", 12, 4)] = ("pipelined",)
+    t.update({(kind, k, RULE_DW): () for kind in ("rule_std", "rule_band") for k in (1, 2, 4, 8)})
+    t.update({("bytes", k, 1): () for k in (1, 2, 4, 8, 16)})
+    t[("bytes", 32, 1)] = ("pipelined",)
+    return t
+
+
+TABLE = _table()
+# The instantiations of bits_step_kernel and band_step_kernel: the table's one-wave kernels of the
+# bit families.  PUBLIC: those a gol_dev_* entry launches (the case table below); ENGINE_ONLY: the
+# rest, reached through the engine alone (tests/test_gpu_engine.py).
+INSTANTIATIONS = tuple(i for i, f in TABLE.items() if i[0] != "bytes" and "pipelined" not in f)
+ENGINE_ONLY = tuple(i for i in INSTANTIATIONS if "engine_only" in TABLE[i])
+PUBLIC = tuple(i for i in INSTANTIATIONS if i not in ENGINE_ONLY)
+
+
+def words_per_lane(family: str, cells_per_lane: int) -> int:
+    """The words per lane a gol_dev_* entry makes of its cells_per_lane (include/golhip.h); 0: none."""
+    if family == "bits":
+        return cells_per_lane // 32 if cells_per_lane > 0 else 2
+    if family == "band":
+        return {64: 2, 128: 4}.get(cells_per_lane, 4 if cells_per_lane <= 0 else 0)
+    if family == "bytes":
+        return 1
+    return RULE_DW if cells_per_lane <= 0 or cells_per_lane == 32 * RULE_DW else 0
 
 
 def inst_id(inst) -> str:
@@ -120,7 +150,7 @@ def is_band(kind: str) -> bool:
 def useful_words(inst) -> int:
     """Output words of one wave: 62 lanes (standard), 64 less ceil(k / dw) halo lanes a side (band)."""
     kind, k, dw = inst
-    return (64 - 2 * -(-k // dw)) * dw if is_band(kind) else 62 * dw
+    return (64 - 2 * -(-k // dw)) * dw if is_band(kind) else 62 * dw  # (bytes: dw = 1, 62 words of 32 cells)
 
 
 def widths(inst) -> dict:
@@ -196,7 +226,7 @@ class Case:
         return ptr
 
     def contiguous(self, bases: dict) -> bool:
-        """The launcher's predicate (golk_band_step) on word addresses: bases = allocation -> word address."""
+        """The launch geometry's predicate (gol_step_geometry_of) on word addresses: bases = allocation -> word address."""
         a = {n: bases[al] + off for n, (al, off) in self.pointers().items()}
         return a["top"] + self.k * self.pitch == a["mid"] and a["bot"] == a["mid"] + self.R * self.pitch
 
@@ -284,7 +314,7 @@ def _cases_of(index: int, inst):
     return out
 
 
-CASES = tuple(c for i, inst in enumerate(INSTANTIATIONS) for c in _cases_of(i, inst))
+CASES = tuple(c for i, inst in enumerate(PUBLIC) for c in _cases_of(i, inst))
 
 
 def cases_of(inst):
@@ -309,3 +339,83 @@ def check_args(c: Case) -> None:
         assert c.dw == RULE_DW and c.k in (1, 2, 4, 8)
         assert all(0 <= m < 512 for m in RR.masks(c.rule))
     assert c.strip >= 0
+
+
+# ------------------------------------------------------------------ refusals
+P = 0x10000  # a pointer's value, aligned; a refused call reads nothing through it
+_GPU = dict(top=P, mid=P, bot=P, dst=P, R=20, Wd=8, pitch=16, row0=0, rows=20, k=4)
+GOOD = {  # name -> (family, a good call in the C entry's arguments; Wd, pitch: W, stride for bytes)
+    "bits": ("bits", dict(_GPU, cells_per_lane=128)),
+    "band": ("band", dict(_GPU, cells_per_lane=128)),
+    "rule_std": ("rule_std", dict(_GPU, cells_per_lane=64, layout=1, birth=0x008, survive=0x00C)),
+    "rule_band": ("rule_band", dict(_GPU, cells_per_lane=64, layout=2, birth=0x008, survive=0x00C)),
+    "twin_band": ("band", dict(top=P, mid=P, bot=P, dst=P, R=24, Wd=128, pitch=128, row0=0, rows=24, k=12, cells_per_lane=128)),
+    "twin_bytes": ("bytes", dict(top=P, mid=P, bot=P, dst=P, R=32, Wd=64, pitch=64, row0=0, rows=32, k=32)),
+}
+# The clause classes of the launch check (gol_step_launch_ok) and the families that have them.
+CLAUSES = {c: FAMILIES for c in ("null", "kernel", "k>R", "board", "unit", "rows", "pretend")}
+CLAUSES["align"] = ("band", "rule_std", "rule_band", "bytes")  # (the bits entry has no alignment clause)
+CLAUSES["mask"] = ("rule_std", "rule_band")
+
+
+def refusals():
+    """[(good, change, clause, via)]: GOOD[good] with `change` applied is refused under `clause`.  via: "entry" the
+    plain gol_dev_* entry can be given it, "on" the _on entries (cus, slots) alone, "check" only gol_step_check_host."""
+    R = _GPU["R"]
+    out = []
+    for g in ("bits", "band"):  # the shape tests/test_gpu_step_kernels.py launches: 4 words per lane, k = 4
+        out += [(g, c, "unit", "entry") for c in (dict(Wd=6), dict(Wd=2), dict(pitch=18), dict(cells_per_lane=64, Wd=6, pitch=7))]
+        out += [(g, c, "k>R", "entry") for c in (dict(k=8, R=7, rows=7), dict(k=4, R=3, rows=3))]
+        out += [(g, dict(k=16), "kernel", "entry")]  # no k = 16 at 128 cells per lane
+        out += [(g, c, "rows", "entry") for c in (dict(row0=1), dict(row0=R, rows=1), dict(row0=5, rows=R - 4))]
+        out += [(g, dict(top=0), "null", "entry"), (g, dict(pitch=4), "board", "entry"), (g, dict(Wd=0), "board", "entry")]
+    out += [("bits", dict(cells_per_lane=96), "kernel", "entry"), ("bits", dict(k=12), "kernel", "entry")]
+    for g in ("rule_std", "rule_band"):
+        out += [(g, dict(birth=512), "mask", "entry"), (g, dict(survive=512), "mask", "entry")]
+        out += [(g, dict(layout=7), "kernel", "entry"), (g, dict(cells_per_lane=128), "kernel", "entry"), (g, dict(k=16), "kernel", "entry")]
+        out += [(g, dict(Wd=7), "unit", "entry"), (g, dict(pitch=17), "unit", "entry"), (g, dict(k=8, R=7, rows=7), "k>R", "entry")]
+        out += [(g, dict(row0=1), "rows", "entry"), (g, dict(dst=0), "null", "entry"), (g, dict(pitch=4), "board", "entry")]
+        out += [(g, dict(mid=P + 4), "align", "entry")]
+    b = "twin_band"
+    out += [(b, dict(**{n: 0}), "null", "entry") for n in ("top", "mid", "bot", "dst")]
+    out += [(b, dict(row0=1), "rows", "entry"), (b, dict(rows=25), "rows", "entry")]
+    out += [(b, dict(k=3), "kernel", "entry"), (b, dict(k=16), "kernel", "entry"), (b, dict(k=12, cells_per_lane=64), "kernel", "entry")]
+    out += [(b, dict(k=12, R=8, rows=8), "k>R", "entry")]
+    out += [(b, dict(cells_per_lane=c), "kernel", "entry") for c in (32, 96, 256)]
+    out += [(b, dict(mid=P + 4), "align", "entry"), (b, dict(top=P + 8), "align", "entry"), (b, dict(dst=P + 2), "align", "entry")]
+    out += [(b, dict(pitch=124), "board", "entry"), (b, dict(Wd=130, pitch=130), "unit", "entry")]
+    b = "twin_bytes"
+    out += [(b, dict(**{n: 0}), "null", "entry") for n in ("top", "mid", "bot", "dst")]
+    out += [(b, dict(row0=1), "rows", "entry"), (b, dict(rows=33), "rows", "entry")]
+    out += [(b, dict(k=3), "kernel", "entry"), (b, dict(k=12), "kernel", "entry"), (b, dict(k=64), "kernel", "entry")]
+    out += [(b, dict(k=32, R=16, rows=16), "k>R", "entry")]
+    out += [(b, dict(mid=P + 4), "align", "entry"), (b, dict(bot=P + 8), "align", "entry"), (b, dict(dst=P + 1), "align", "entry")]
+    out += [(b, dict(pitch=48), "board", "entry"), (b, dict(pitch=72), "unit", "entry"), (b, dict(Wd=48), "unit", "entry")]
+    # a pretended device: one of the two left 0, CUs not in eights, a negative count, a k that is not pipelined
+    for b, k in (("twin_band", 8), ("twin_bytes", 16)):
+        out += [(b, dict(cus=c, slots=n), "pretend", "on") for c, n in ((8, 0), (0, 8), (12, 12), (-8, 8))]
+        out += [(b, dict(k=k, cus=8, slots=8), "pretend", "on")]
+    out += [(g, dict(cus=8, slots=8), "pretend", "check") for g in ("bits", "rule_std", "rule_band")]
+    return out
+
+
+def twin_refusals():
+    """The refusals of the twin entries (tests/test_abi_cpu.py): [(family, change)]."""
+    return [(GOOD[g][0], c) for g, c, _, via in refusals() if g.startswith("twin_") and via == "entry"]
+
+
+def refusal_args(good: str, change: dict) -> dict:
+    """The call: family, the arguments of gol_step_check_host by name (words_per_lane resolved), and the entry's own."""
+    family, a = GOOD[good]
+    a = dict(dict(cells_per_lane=0, birth=0, survive=0, cus=0, slots=0), **a)
+    a.update(change)
+    if "layout" in a and a["layout"] not in (1, 2):
+        family = None  # a layout that is neither: no family
+    return dict(a, family=family, words_per_lane=words_per_lane(family or "rule_std", a["cells_per_lane"]))
+
+
+def check_refusal_coverage(entries=None):
+    """Every (family, clause class) pair the check has is hit at least once."""
+    hit = {(GOOD[g][0], clause) for g, _, clause, _ in (entries or refusals())}
+    want = {(f, c) for c, fams in CLAUSES.items() for f in fams}
+    assert hit == want, (sorted(want - hit), sorted(hit - want))

@@ -110,22 +110,10 @@ def test_no_gpu_calls_fail_cleanly(G):
         G.next_state_slab(np.zeros((16, 16), np.uint8), 5, 2)  # bad bounds: EINVAL before any HIP call
 
 
-P = 0x10000  # a pointer's value, aligned; a refused call reads nothing through it
-BAND_OK = dict(top=P, mid=P, bot=P, dst=P, R=24, Wd=128, pitch=128, row0=0, rows=24, k=12, cells_per_lane=128)
-BYTES_OK = dict(top=P, mid=P, bot=P, dst=P, R=32, Wd=64, pitch=64, row0=0, rows=32, k=32)
-TWIN_REFUSALS = [
-    ("band", dict(top=0)), ("band", dict(mid=0)), ("band", dict(bot=0)), ("band", dict(dst=0)),
-    ("band", dict(row0=1)), ("band", dict(rows=25)),
-    ("band", dict(k=3)), ("band", dict(k=16)), ("band", dict(k=12, cells_per_lane=64)), ("band", dict(k=12, R=8, rows=8)),
-    ("band", dict(cells_per_lane=32)), ("band", dict(cells_per_lane=96)), ("band", dict(cells_per_lane=256)),
-    ("band", dict(mid=P + 4)), ("band", dict(top=P + 8)), ("band", dict(dst=P + 2)),
-    ("band", dict(pitch=124)), ("band", dict(Wd=130, pitch=130)),
-    ("bytes", dict(top=0)), ("bytes", dict(mid=0)), ("bytes", dict(bot=0)), ("bytes", dict(dst=0)),
-    ("bytes", dict(row0=1)), ("bytes", dict(rows=33)),
-    ("bytes", dict(k=3)), ("bytes", dict(k=12)), ("bytes", dict(k=64)), ("bytes", dict(k=32, R=16, rows=16)),
-    ("bytes", dict(mid=P + 4)), ("bytes", dict(bot=P + 8)), ("bytes", dict(dst=P + 1)),
-    ("bytes", dict(pitch=48)), ("bytes", dict(pitch=72)), ("bytes", dict(Wd=48)),
-]
+import step_ref as S  # the shared refusal list (S.refusals): the twins' part of it
+
+BAND_OK, BYTES_OK = S.GOOD["twin_band"][1], S.GOOD["twin_bytes"][1]
+TWIN_REFUSALS = S.twin_refusals()
 
 
 def test_step_twins_refuse_alike(G):

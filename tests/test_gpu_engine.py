@@ -183,6 +183,28 @@ def test_band_layout_vs_bit_oracle(golhip, k, cpl, shape):
         assert e.alive_count() == O.popcount_words(O.bits_run(ref, 3))
 
 
+@pytest.mark.parametrize("W", [1024, 3072])
+@pytest.mark.parametrize("H,shards", [(12, 1), (13, 1), (40, 1), (40, 2)])
+def test_engine_only_band_kernel_at_its_edges(golhip, H, shards, W):
+    """band_step_kernel<12, 2, C>: k = 12 in one wave at 64 cells per lane, which the engine launches and
+    gol_dev_band_step refuses (csrc/gol_step_launch.h, GOL_STEP_ENGINE_ONLY), so the table of
+    tests/test_gpu_step_kernels.py cannot reach it.  R == k, one row over, and several strips of 5 rows
+    with a tail; the wave's 104 output words span the 32-word row of W = 1024 three times and straddle
+    the 96 words of W = 3072; one shard reads its ghost rows as the torus wrap (C = false), two shards
+    theirs contiguous with the shard (C = true).  Two launches of 12 turns, each with the fused count."""
+    seed = 500 + H + W
+    words = O.random_words(seed, 0, H, W // 64)
+    ref, counts = O.bits_run(words, 24, with_counts=True)
+    kw = dict(shards=2, same_device=True, transport="loopback") if shards == 2 else {}
+    with golhip.Engine(H, W, device=0, turns_per_launch=12, cells_per_lane=64, layout="band", strip_rows=5, **kw) as e:
+        e.load_random(seed)
+        info = e.info()
+        assert (info["layout"], info["cells_per_lane"], info["turns_per_launch"]) == ("band", 64, 12)
+        assert e.step_counted(24, 12).tolist() == [counts[11], counts[23]]
+        assert e.hash() == O.hash_words(ref)
+        assert np.array_equal(e.store_bytes(), O.unpack(ref))
+
+
 def test_band_layout_standard_agree(golhip):
     """layout=band and layout=standard engines agree on a board loaded from bytes, on the alive
     list (row-major), the PGM bytes and the counts."""

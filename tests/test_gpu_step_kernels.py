@@ -108,7 +108,7 @@ def _check(c, before, after, slots):
         assert int(slots.sum().item()) == S.COUNT_SEED[1] + S.popcount(want), c.id
 
 
-@pytest.mark.parametrize("inst", S.INSTANTIATIONS, ids=S.inst_id)
+@pytest.mark.parametrize("inst", S.PUBLIC, ids=S.inst_id)
 def test_instantiation_at_its_edges(G, inst):
     cases = S.cases_of(inst)
     assert cases
@@ -162,39 +162,38 @@ def test_chained_launches_see_each_other(G, kind, k, dw):
 
 
 # ------------------------------------------------------------------ refusals
-@pytest.mark.parametrize("kind", ["bits", "band"])
+def _call_entry(G, kind, ptr, a, slots, stream):
+    """The entry of `kind` with the arguments a (S.refusal_args: cells_per_lane, layout and masks as given)."""
+    lib = G.lib()
+    p = [None if a[n] == 0 else ptr[n] + (a[n] - S.P) for n in ("top", "mid", "bot", "dst")]
+    head = (*p, a["R"], a["Wd"], a["pitch"], a["row0"], a["rows"], a["k"])
+    if kind in ("bits", "band"):
+        return getattr(lib, f"gol_dev_{kind}_step")(*head, a["cells_per_lane"], 0, slots, stream)
+    return lib.gol_dev_rule_step(*head, a["layout"], a["birth"], a["survive"], a["cells_per_lane"], 0, slots, stream)
+
+
+@pytest.mark.parametrize("kind", ["bits", "band", "rule_std", "rule_band"])
 def test_refusals_launch_nothing(G, kind):
     import torch
-    dw, k, R, Wd, pitch, g = 4, 4, 20, 8, 16, S.GUARD
+    good = S.refusal_args(kind, {})
+    k, R, Wd, pitch, g = good["k"], good["R"], good["Wd"], good["pitch"], S.GUARD
+    assert (k, R, Wd, pitch) == (4, 20, 8, 16)
     src = _dev(np.full((R + 2 * g, pitch), 0xFFFFFFFF, dtype=np.uint32))  # all alive: a launch would write zeros
     dst = _dev(np.full((R + 2 * g, pitch), S.SENT, dtype=np.uint32))
     slots = _slots(G)
     mid = src.data_ptr() + 4 * g * pitch
     ptr = {"top": mid + 4 * (R - k) * pitch, "mid": mid, "bot": mid, "dst": dst.data_ptr() + 4 * g * pitch}
     st = torch.cuda.current_stream().cuda_stream
-    good = dict(k=k, dw=dw, R=R, Wd=Wd, pitch=pitch, row0=0, rows=R)
-    bad = [
-        dict(Wd=6),               # Wd % dw != 0
-        dict(Wd=2),
-        dict(pitch=18),           # pitch % dw != 0
-        dict(dw=2, Wd=6, pitch=7),
-        dict(k=8, R=7, rows=7),   # k > R
-        dict(k=4, R=3, rows=3),
-        dict(k=16),               # no k = 16 at 128 cells per lane
-        dict(row0=1),             # row0 + rows > R
-        dict(row0=R, rows=1),
-        dict(row0=5, rows=R - 4),
-    ]
+    bad = [b for name, b, _, via in S.refusals() if name == kind and via == "entry"]
+    assert len(bad) >= 12
     for b in bad:
-        a = dict(good, **b)
-        rc = _call(G, kind, a["k"], a["dw"], ptr, a["R"], a["Wd"], a["pitch"], a["row0"], a["rows"], 0, S.CONWAY,
-                   slots.data_ptr(), st)
+        rc = _call_entry(G, kind, ptr, S.refusal_args(kind, b), slots.data_ptr(), st)
         assert rc == G._lib.GOL_EINVAL, (kind, b)
     torch.cuda.synchronize()
     assert _error_word(G) == (0, 0)
     assert bool((_host(dst) == S.SENT).all()) and int(slots.sum().item()) == S.COUNT_SEED[1]
     # and the call they were derived from is a good one
-    assert _call(G, kind, k, dw, ptr, R, Wd, pitch, 0, R, 0, S.CONWAY, slots.data_ptr(), st) == 0
+    assert _call_entry(G, kind, ptr, good, slots.data_ptr(), st) == 0
     torch.cuda.synchronize()
     assert _error_word(G) == (0, 0)
     out = _host(dst)

@@ -72,14 +72,26 @@ def test_stepped_is_expected_and_shared():
 
 # ------------------------------------------------------------------ the case table
 def test_every_instantiation_is_listed():
-    want = {("bits", k, dw) for k in (1, 2, 4, 8, 16) for dw in (1, 2, 4)} - {("bits", 16, 4)}
-    want |= {("band", k, 2) for k in (1, 2, 4, 8, 16)} | {("band", k, 4) for k in (1, 2, 4, 8)}
-    want |= {(kind, k, S.RULE_DW) for kind in ("rule_std", "rule_band") for k in (1, 2, 4, 8)}
-    assert set(S.INSTANTIATIONS) == want and len(S.INSTANTIATIONS) == len(want) == 31
-    assert {c.inst for c in S.CASES} == want
+    """step_ref's table is the library's: what gol_step_check_host (the kernel table of
+    csrc/gol_step_launch.h) answers for every (family, k, words per lane), no hand-kept second list."""
+    import golhip
+    check, fam = golhip.lib().gol_step_check_host, golhip._lib.STEP_FAMILIES
+    P = S.P
+
+    def is_kernel(f, k, dw, as_entry):
+        W = 128 if f != "bytes" else 4096  # a multiple of every unit; R = 64 rows >= every k
+        return check(fam[f], P, P, P, P, 64, W, W, 0, 64, k, dw, 0, 0, 0, 0, as_entry, None) == 0
+    every = [(f, k, dw) for f in S.FAMILIES for k in range(1, 34) for dw in (1, 2, 3, 4)]
+    listed = {i for i in every if is_kernel(*i, 0)}
+    offered = {i for i in every if is_kernel(*i, 1)}
+    assert listed == set(S.TABLE) and listed - offered == set(S.ENGINE_ONLY) == {("band", 12, 2)}
+    want = {i for i in listed if i[0] != "bytes" and "pipelined" not in S.TABLE[i]}
+    assert set(S.INSTANTIATIONS) == want and len(S.INSTANTIATIONS) == len(want) == 32
+    assert set(S.PUBLIC) == want & offered and len(S.PUBLIC) == 31
+    assert {c.inst for c in S.CASES} == set(S.PUBLIC)
     assert len({c.id for c in S.CASES}) == len(S.CASES)
     # the rule kernels' words per lane, from the source
-    h = os.path.join(os.path.dirname(__file__), "..", "gol-distributed-final_amd", "csrc", "gol_kernels.h")
+    h = os.path.join(os.path.dirname(__file__), "..", "gol-distributed-final_amd", "csrc", "gol_step_launch.h")
     with open(h) as f:
         assert int(re.search(r"#define GOLK_RULE_DW (\d+)", f.read()).group(1)) == S.RULE_DW
 
@@ -95,7 +107,7 @@ def test_width_classes_are_the_column_group_edges():
         assert c.Wd == {"one-lane": c.dw, "under-group": U - c.dw, "exact-group": U, "one-lane-over": U + c.dw}[c.wclass]
 
 
-@pytest.mark.parametrize("inst", S.INSTANTIATIONS, ids=S.inst_id)
+@pytest.mark.parametrize("inst", S.PUBLIC, ids=S.inst_id)
 def test_coverage_of_an_instantiation(inst):
     cases = S.cases_of(inst)
     rules = S.RULES if inst[0].startswith("rule") else (S.CONWAY,)
