@@ -14,8 +14,9 @@
 //    consecutive cells make a pattern word.
 // Bounds.  Lane t < T of the paste's geometry (the 4-byte form of byte rows included) masks its unit
 // to the rectangle -- gol_copy_mask: gol_edit_word / gol_edit_bytes4 without a pattern under COPY --
-// and ORs gol_copy_occ of it into a column-occupancy word per lane; gol_copy_cols turns the set
-// bits of that word back into the smallest and largest rectangle column among them.
+// and ORs gol_copy_occ of it into a column-occupancy word per lane (gol_copy_occ_unit, one lane and
+// row of it, is what kernel and host both call); gol_copy_cols turns the set bits of that word back
+// into the smallest and largest rectangle column among them.
 #pragma once
 #include "gol_edit.h"
 
@@ -63,6 +64,15 @@ GOL_EDIT_HD uint32_t gol_copy_occ(const gol_edit_geom &g, uint32_t v)
     uint32_t o = 0;
     for (int i = 0; i < 4; ++i) o |= (uint32_t)(((v >> (8 * i)) & 0xffu) != 0) << i;
     return o;
+}
+
+// Pass 1 of the bounds for one lane and row, as the kernels and gol_bounds_host both run it: unit u
+// (gol_edit_unit of the lane) of the board row at `brow` (gol_edit_row) loaded, masked to the
+// rectangle (mask: gol_copy_mask of the lane) and turned into occupancy bits.
+GOL_EDIT_HD uint32_t gol_copy_occ_unit(int32_t form, const gol_edit_geom &g, int64_t u, uint32_t mask, const void *brow)
+{
+    if (form == GOL_EDIT_BYTES) return ((const uint8_t *)brow)[u] != 0;
+    return gol_copy_occ(g, ((const uint32_t *)brow)[u] & mask);
 }
 
 GOL_EDIT_HD int gol_copy_ctz(uint32_t v)  // v != 0

@@ -110,13 +110,7 @@ __global__ __launch_bounds__(COPY_BLOCK) void bounds_rows_kernel(const BoundsArg
     uint32_t n = 0, col = 0;
     int64_t first = -1, last = -1;  // wave-uniform: the wave's first and last row with an alive cell
     for (int64_t r = blockIdx.y; r < a.rows; r += gridDim.y) {
-        uint32_t v = 0;
-        if (active) {
-            if (FORM == GOL_EDIT_BYTES) v = ((const uint8_t *)a.src)[(a.row + r) * a.pitch + u];
-            else if (FORM == GOL_EDIT_BYTES4) v = ((const uint32_t *)((const uint8_t *)a.src + (a.row + r) * a.pitch))[u] & mask;
-            else v = ((const uint32_t *)a.src)[(a.row + r) * a.pitch + u] & mask;
-        }
-        const uint32_t o = FORM == GOL_EDIT_BYTES ? (uint32_t)(v != 0) : gol_copy_occ(a.g, v);
+        const uint32_t o = active ? gol_copy_occ_unit(FORM, a.g, u, mask, gol_edit_row(FORM, a.src, a.pitch, a.row + r)) : 0u;
         col |= o;
         n += (uint32_t)__popc(o);
         if (__ballot(o != 0)) {  // (every lane of the wave takes part)
@@ -155,77 +149,55 @@ __global__ __launch_bounds__(COPY_BLOCK) void bounds_cols_kernel(const gol_edit_
     }
 }
 
-bool rows_ok(int form, const void *src, int64_t pitch, int64_t W, int64_t row, int64_t rows)
-{
-    return form >= GOL_EDIT_BYTES && form <= GOL_EDIT_BAND && src && row >= 0 && rows >= 0 && W >= 1 &&
-           pitch >= (form == GOL_EDIT_BYTES ? W : W / 32);
-}
-
 }  // namespace
 
-hipError_t golk_copy(int form, const void *src, int64_t pitch, int64_t W, int64_t x0, int64_t w, int64_t row, int64_t rows,
-                     int64_t prow, uint64_t *pattern, int64_t pstride, uint64_t *alive, hipStream_t s)
+hipError_t golk_copy(const gol_region &r, uint64_t *pattern, int64_t pstride, uint64_t *alive, hipStream_t s)
 {
     CopyArgs a{};
-    if (!rows_ok(form, src, pitch, W, row, rows) || prow < 0 || !pattern || !alive || pstride < (w + 63) / 64 ||
-        !gol_edit_geom_init(a.g, form, W, x0, w, GOL_EDIT_COPY))
+    if (!pattern || !alive || !gol_region_ok(r, GOL_EDIT_COPY, false, &a.g) || !gol_region_stride_ok(r.w, pstride))
         return hipErrorInvalidValue;
-    if (rows == 0) return hipSuccess;
-    a.src = src;
-    a.pitch = pitch;
-    a.row = row;
-    a.rows = rows;
-    a.prow = prow;
-    a.lanes = form == GOL_EDIT_BAND ? a.g.T : form == GOL_EDIT_STANDARD ? (w + 31) / 32 : w;
+    if (r.rows == 0) return hipSuccess;
+    a.src = r.base;
+    a.pitch = r.pitch;
+    a.row = r.row;
+    a.rows = r.rows;
+    a.prow = r.at;
+    a.lanes = r.layout == GOL_EDIT_BAND ? a.g.T : r.layout == GOL_EDIT_STANDARD ? (r.w + 31) / 32 : r.w;
     a.pattern = (uint32_t *)pattern;
     a.pstride = pstride;
     a.alive = (u64 *)alive;
     dim3 grid;
-    if (!gol_edit_grid(a.lanes, rows, &grid)) return hipErrorInvalidValue;
-    if (form == GOL_EDIT_BAND) copy_kernel<GOL_EDIT_BAND><<<grid, COPY_BLOCK, 0, s>>>(a);
-    else if (form == GOL_EDIT_STANDARD) copy_kernel<GOL_EDIT_STANDARD><<<grid, COPY_BLOCK, 0, s>>>(a);
+    if (!gol_edit_grid(a.lanes, r.rows, &grid)) return hipErrorInvalidValue;
+    if (r.layout == GOL_EDIT_BAND) copy_kernel<GOL_EDIT_BAND><<<grid, COPY_BLOCK, 0, s>>>(a);
+    else if (r.layout == GOL_EDIT_STANDARD) copy_kernel<GOL_EDIT_STANDARD><<<grid, COPY_BLOCK, 0, s>>>(a);
     else copy_kernel<GOL_EDIT_BYTES><<<grid, COPY_BLOCK, 0, s>>>(a);
     return hipGetLastError();
 }
 
-hipError_t golk_bounds_rows(int form, const void *src, int64_t pitch, int64_t W, int64_t x0, int64_t w, int64_t row,
-                            int64_t rows, int64_t vrow, uint32_t *occ, uint64_t *hdr, hipStream_t s)
+hipError_t golk_bounds_rows(const gol_region &r, uint32_t *occ, uint64_t *hdr, hipStream_t s)
 {
     BoundsArgs a{};
-    if (!rows_ok(form, src, pitch, W, row, rows) || vrow < 0 || !occ || !hdr) return hipErrorInvalidValue;
-    const int f = GOL_EDIT_FORM(form, W, pitch, src);  // byte rows as aligned 4-byte words where the board allows it
-    if (!gol_edit_geom_init(a.g, f, W, x0, w, GOL_EDIT_COPY)) return hipErrorInvalidValue;
-    if (rows == 0) return hipSuccess;
-    a.src = src;
-    a.pitch = pitch;
-    a.row = row;
-    a.rows = rows;
-    a.vrow = vrow;
+    if (!occ || !hdr || !gol_region_ok(r, GOL_EDIT_COPY, true, &a.g)) return hipErrorInvalidValue;
+    if (r.rows == 0) return hipSuccess;
+    a.src = r.base;
+    a.pitch = r.pitch;
+    a.row = r.row;
+    a.rows = r.rows;
+    a.vrow = r.at;
     a.occ = occ;
     a.hdr = (u64 *)hdr;
     dim3 grid;
-    if (!gol_edit_grid(a.g.T, rows, &grid)) return hipErrorInvalidValue;
-    if (f == GOL_EDIT_BYTES4) bounds_rows_kernel<GOL_EDIT_BYTES4><<<grid, COPY_BLOCK, 0, s>>>(a);
-    else if (f == GOL_EDIT_BYTES) bounds_rows_kernel<GOL_EDIT_BYTES><<<grid, COPY_BLOCK, 0, s>>>(a);
+    if (!gol_edit_grid(a.g.T, r.rows, &grid)) return hipErrorInvalidValue;
+    if (a.g.layout == GOL_EDIT_BYTES4) bounds_rows_kernel<GOL_EDIT_BYTES4><<<grid, COPY_BLOCK, 0, s>>>(a);
+    else if (a.g.layout == GOL_EDIT_BYTES) bounds_rows_kernel<GOL_EDIT_BYTES><<<grid, COPY_BLOCK, 0, s>>>(a);
     else bounds_rows_kernel<GOL_EDIT_STANDARD><<<grid, COPY_BLOCK, 0, s>>>(a);
     return hipGetLastError();
 }
 
-int64_t golk_bounds_lanes(int form, const void *src, int64_t pitch, int64_t W, int64_t x0, int64_t w)
+hipError_t golk_bounds_cols(const gol_region &r, const uint32_t *occ, uint64_t *hdr, hipStream_t s)
 {
     gol_edit_geom g;
-    if (form < GOL_EDIT_BYTES || form > GOL_EDIT_BAND || !gol_edit_geom_init(g, GOL_EDIT_FORM(form, W, pitch, src), W, x0, w, GOL_EDIT_COPY))
-        return -1;
-    return g.T;
-}
-
-hipError_t golk_bounds_cols(int form, const void *src, int64_t pitch, int64_t W, int64_t x0, int64_t w, const uint32_t *occ,
-                            uint64_t *hdr, hipStream_t s)
-{
-    gol_edit_geom g;
-    if (form < GOL_EDIT_BYTES || form > GOL_EDIT_BAND || !occ || !hdr ||
-        !gol_edit_geom_init(g, GOL_EDIT_FORM(form, W, pitch, src), W, x0, w, GOL_EDIT_COPY))
-        return hipErrorInvalidValue;
+    if (!occ || !hdr || !gol_region_ok(r, GOL_EDIT_COPY, true, &g)) return hipErrorInvalidValue;
     dim3 grid;
     if (!gol_edit_grid(g.T, 1, &grid)) return hipErrorInvalidValue;
     bounds_cols_kernel<<<grid, COPY_BLOCK, 0, s>>>(g, occ, (u64 *)hdr);

@@ -1,5 +1,6 @@
 // gol_copy_host.cpp -- gol_copy_host and gol_bounds_host (include/golhip.h): the region-read
-// kernels' mapping (gol_copy.h) applied to a host buffer, lane by lane and row by row as the kernels
+// kernels' check (gol_region_ok, gol_edit.h) and mapping (gol_copy.h; the bounds' pass 1 is
+// gol_copy_occ_unit itself) applied to a host buffer, lane by lane and row by row as the kernels
 // do.  No HIP header: a stand-alone program links this file and gol_edit_host.cpp alone
 // (copy_check.cpp).
 #include <stdint.h>
@@ -12,18 +13,12 @@
 
 int gol_set_error(int code, const char *fmt, ...);
 
-static bool rows_ok(int32_t layout, const void *board, int64_t pitch, int64_t W, int64_t row, int64_t rows)
-{
-    return layout >= GOL_EDIT_BYTES && layout <= GOL_EDIT_BAND && board && row >= 0 && rows >= 0 && W >= 1 &&
-           pitch >= (layout == GOL_EDIT_BYTES ? W : W / 32);
-}
-
 extern "C" int gol_copy_host(int32_t layout, const void *board, int64_t pitch, int64_t W, int64_t row, int64_t rows,
                              int64_t prow, int64_t x0, int64_t w, uint64_t *pattern, int64_t stride, int64_t *alive)
 {
+    const gol_region reg{layout, const_cast<void *>(board), pitch, W, x0, w, row, rows, prow};
     gol_edit_geom g;
-    if (!rows_ok(layout, board, pitch, W, row, rows) || prow < 0 || !pattern ||
-        !gol_edit_geom_init(g, layout, W, x0, w, GOL_EDIT_COPY) || stride < (w + 63) / 64)
+    if (!pattern || !gol_region_ok(reg, GOL_EDIT_COPY, false, &g) || !gol_region_stride_ok(w, stride))
         return gol_set_error(GOL_EINVAL, "bad host copy (layout %d, W %lld, pitch %lld, x0 %lld, w %lld, rows %lld, stride %lld)",
                              layout, (long long)W, (long long)pitch, (long long)x0, (long long)w, (long long)rows,
                              (long long)stride);
@@ -71,27 +66,25 @@ extern "C" int gol_bounds_host(int32_t layout, const void *board, int64_t pitch,
                                int64_t x0, int64_t w, int64_t *cmin, int64_t *cmax, int64_t *rmin, int64_t *rmax,
                                int64_t *alive)
 {
+    const gol_region reg{layout, const_cast<void *>(board), pitch, W, x0, w, row, rows, 0};
     gol_edit_geom g;
-    const int32_t form = layout < GOL_EDIT_BYTES || layout > GOL_EDIT_BAND ? -1 : GOL_EDIT_FORM(layout, W, pitch, board);
-    if (!rows_ok(layout, board, pitch, W, row, rows) || !gol_edit_geom_init(g, form, W, x0, w, GOL_EDIT_COPY))
+    if (!gol_region_ok(reg, GOL_EDIT_COPY, true, &g))
         return gol_set_error(GOL_EINVAL, "bad host bounds (layout %d, W %lld, pitch %lld, x0 %lld, w %lld, rows %lld)", layout,
                              (long long)W, (long long)pitch, (long long)x0, (long long)w, (long long)rows);
     std::vector<uint32_t> occ((size_t)g.T, 0u);
     int64_t n = 0, r0 = rows, r1 = -1, c0 = w, c1 = -1;
-    for (int64_t r = 0; r < rows; ++r)
-        for (int64_t t = 0; t < g.T; ++t) {  // pass 1
-            const int64_t u = gol_edit_unit(g, t);
-            uint32_t v;
-            if (form == GOL_EDIT_BYTES) v = ((const uint8_t *)board)[(row + r) * pitch + u];
-            else if (form == GOL_EDIT_BYTES4) v = ((const uint32_t *)((const uint8_t *)board + (row + r) * pitch))[u] & gol_copy_mask(g, t);
-            else v = ((const uint32_t *)board)[(row + r) * pitch + u] & gol_copy_mask(g, t);
-            const uint32_t o = form == GOL_EDIT_BYTES ? (uint32_t)(v != 0) : gol_copy_occ(g, v);
+    for (int64_t t = 0; t < g.T; ++t) {  // pass 1: a lane keeps its unit and mask over the rows, as in the kernel
+        const int64_t u = gol_edit_unit(g, t);
+        const uint32_t mask = gol_copy_mask(g, t);
+        for (int64_t r = 0; r < rows; ++r) {
+            const uint32_t o = gol_copy_occ_unit(g.layout, g, u, mask, gol_edit_row(g.layout, board, pitch, row + r));
             if (!o) continue;
             occ[(size_t)t] |= o;
             n += __builtin_popcount(o);
             if (r < r0) r0 = r;
-            r1 = r;
+            if (r > r1) r1 = r;
         }
+    }
     for (int64_t t = 0; t < g.T; ++t) {  // pass 2
         if (!occ[(size_t)t]) continue;
         int64_t a, b;

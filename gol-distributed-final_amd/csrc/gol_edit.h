@@ -16,8 +16,10 @@
 //    a word) would name the first word twice, so T = min(n, Wd) and lane 0 also applies the cells
 //    that wrapped, from c = W - x0 % 32;
 //  - byte rows: T = w, lane t owns byte (x0 + t) mod W; or, where the rows are 4-byte aligned (W % 4
-//    == 0, pitch % 4 == 0, an aligned buffer: GOL_EDIT_BYTES4, chosen by the callers), the standard
+//    == 0, pitch % 4 == 0, an aligned buffer: GOL_EDIT_BYTES4, chosen by gol_region_ok), the standard
 //    form with 4 cells per aligned 4-byte word.
+// Below the mapping: gol_region, what a launch of any region kernel or a call of a host twin is
+// given, its one check, and the paste's step of one unit, which kernel and twin both call.
 #pragma once
 #include <stdint.h>
 
@@ -37,7 +39,7 @@
 #define GOL_EDIT_STANDARD 1
 #define GOL_EDIT_BAND 2
 #define GOL_EDIT_BYTES4 3  // (internal) byte rows as aligned 4-byte words, 4 cells each
-// GOL_EDIT_BYTES4 for byte rows that allow it, else the layout itself.
+// GOL_EDIT_BYTES4 for byte rows that allow it, else the layout itself (for gol_region_ok alone).
 #define GOL_EDIT_FORM(layout, W, pitch, base) \
     ((layout) == GOL_EDIT_BYTES && (W) % 4 == 0 && (pitch) % 4 == 0 && (uintptr_t)(base) % 4 == 0 ? GOL_EDIT_BYTES4 : (layout))
 
@@ -184,6 +186,64 @@ GOL_EDIT_HD int gol_edit_flips4(uint32_t a, uint32_t b)
     int n = 0;
     for (int i = 0; i < 4; ++i) n += (((a >> (8 * i)) & 0xffu) != 0) != (((b >> (8 * i)) & 0xffu) != 0);
     return n;
+}
+
+// ------------------------------------------------------------------ a region launch and its check
+// What every region kernel (view, paste, copy, bounds: gol_kernels.h) and every host twin
+// (gol_paste_host, gol_copy_host, gol_bounds_host) is given: a rectangle of a run of board rows.
+struct gol_region {
+    int32_t layout;     // how the rows are stored: GOL_EDIT_BYTES / _STANDARD / _BAND
+    void *base;         // row 0 of the rows (a shard's rows; only the paste writes through it)
+    int64_t pitch;      // units from a row to the next: words, bytes of a byte board
+    int64_t W;          // cells per board row
+    int64_t x0, w;      // cell c of a rectangle row, 0 <= c < w <= W, is board column (x0 + c) mod W
+    int64_t row, rows;  // board rows [row, row + rows) ..
+    int64_t at;         // .. are the pattern's, the rectangle's or the viewport's rows [at, at + rows)
+};
+
+// The one rule of a valid region: the layout 0..2, a base, row, rows, at >= 0, the geometry
+// (gol_edit_geom_init: the columns, the layout's width rule, op) and a pitch of at least the
+// layout's units per row.  words4: byte rows take their 4-byte form where GOL_EDIT_FORM allows it;
+// g->layout is the form chosen.  false: *g holds nothing of use.
+GOL_EDIT_HD bool gol_region_ok(const gol_region &r, int32_t op, bool words4, gol_edit_geom *g)
+{
+    if (r.layout < GOL_EDIT_BYTES || r.layout > GOL_EDIT_BAND || !r.base || r.row < 0 || r.rows < 0 || r.at < 0) return false;
+    const int32_t form = words4 ? GOL_EDIT_FORM(r.layout, r.W, r.pitch, r.base) : r.layout;
+    return gol_edit_geom_init(*g, form, r.W, r.x0, r.w, op) && r.pitch >= (r.layout == GOL_EDIT_BYTES ? r.W : g->units);
+}
+
+// A pattern buffer of `stride` words per row holds rows of w cells.
+GOL_EDIT_HD bool gol_region_stride_ok(int64_t w, int64_t stride) { return stride >= (w + 63) / 64; }
+
+// Row r of the rows at `base` in form `form` (a pitch counts bytes for both byte forms, else words).
+GOL_EDIT_HD void *gol_edit_row(int32_t form, const void *base, int64_t pitch, int64_t r)
+{
+    if (form == GOL_EDIT_BYTES || form == GOL_EDIT_BYTES4) return (uint8_t *)base + r * pitch;
+    return (uint32_t *)base + r * pitch;
+}
+
+// One lane's step of a paste, as the kernels and gol_paste_host both run it: the unit lane t owns
+// (t < g.T; u = gol_edit_unit(g, t), which a kernel lane keeps over its rows) of the board row at
+// `brow` (gol_edit_row) read, the pattern row `prow` (NULL: ones) applied, the unit stored if it
+// changed.  Returns the cells whose alive state flipped.
+GOL_EDIT_HD uint32_t gol_edit_paste_unit(int32_t form, const gol_edit_geom &g, int64_t t, int64_t u, void *brow, const uint64_t *prow)
+{
+    if (form == GOL_EDIT_BYTES4) {
+        uint32_t *p = (uint32_t *)brow + u;
+        const uint32_t old = *p, v = gol_edit_bytes4(g, t, prow, old);
+        if (v != old) *p = v;
+        return (uint32_t)gol_edit_flips4(old, v);
+    }
+    if (form == GOL_EDIT_BYTES) {
+        uint8_t *p = (uint8_t *)brow + u;
+        const uint8_t old = *p, v = gol_edit_byte(old, gol_edit_pbit(prow, t), g.op);
+        if (v != old) *p = v;
+        return (old != 0) != (v != 0);
+    }
+    uint32_t *p = (uint32_t *)brow + u;
+    const uint32_t old = *p, v = gol_edit_word(g, t, prow, old);
+    if (v != old) *p = v;
+    return (uint32_t)__builtin_popcount(old ^ v);
 }
 
 #if defined(__HIPCC__)

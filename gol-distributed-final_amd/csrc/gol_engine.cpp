@@ -72,13 +72,10 @@ static void shard_release(gol_shard &s)
     if (s.host_word) (void)hipHostFree(s.host_word);
     if (s.staging) (void)hipFree(s.staging);
     if (s.host_staging) (void)hipHostFree(s.host_staging);
-    if (s.view_frame) (void)hipFree(s.view_frame);
-    if (s.view_pix) (void)hipFree(s.view_pix);
-    if (s.view_host) (void)hipHostFree(s.view_host);
-    if (s.edit_dev) (void)hipFree(s.edit_dev);
-    if (s.edit_host) (void)hipHostFree(s.edit_host);
-    if (s.read_dev) (void)hipFree(s.read_dev);
-    if (s.read_host) (void)hipHostFree(s.read_host);
+    for (gol_scratch *b : {&s.view, &s.edit, &s.read}) {
+        if (b->dev) (void)hipFree(b->dev);
+        if (b->host) (void)hipHostFree(b->host);
+    }
     for (auto ev : s.tev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : {s.ev_start, s.ev_edge, s.ev_halo})
         if (ev) (void)hipEventDestroy(ev);

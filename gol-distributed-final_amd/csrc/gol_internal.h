@@ -39,6 +39,12 @@ class gol_ipc;
 // of a timed stepping call; within one call the pool grows instead, gol_timing.cpp timing_event).
 #define GOL_TIMING_EVENTS 512
 
+// A device buffer and its pinned host copy of `cap` uint64 words each, grown on demand.
+struct gol_scratch {
+    uint64_t *dev = nullptr, *host = nullptr;
+    int64_t cap = 0;
+};
+
 // One row shard: rows [y0, y1) of the board on one GPU.
 struct gol_shard {
     int device = 0;
@@ -67,21 +73,9 @@ struct gol_shard {
     uint8_t *staging = nullptr;       // device byte rows for chunked copies
     uint8_t *host_staging = nullptr;  // pinned host rows
     int64_t stage_rows = 0;
-    // viewport frames (gol_engine_view): grown on demand, view_cap elements each
-    uint32_t *view_frame = nullptr;   // device counts of this shard's rows
-    uint8_t *view_pix = nullptr;      // device pixels (one shard: the whole frame)
-    uint32_t *view_host = nullptr;    // pinned host copy of either
-    int64_t view_cap = 0;
-    // board edits (gol_engine_paste): word 0 the changed-cells counter, then edit_cap pattern words; grown on demand
-    uint64_t *edit_dev = nullptr;     // device
-    uint64_t *edit_host = nullptr;    // pinned host: the staged pattern rows, the counter's readback
-    int64_t edit_cap = 0;
-    // region reads (gol_engine_copy, _bounds): 8 header words (READ_HDR of gol_frames.cpp: the alive
-    // counter, the bounds' row and column extremes), then read_cap words (the staged pattern rows; the
-    // bounds' column occupancy); grown on demand
-    uint64_t *read_dev = nullptr;     // device
-    uint64_t *read_host = nullptr;    // pinned host copy
-    int64_t read_cap = 0;
+    // scratch of the region queries (gol_frames.cpp, where each one's words are laid out): the viewport
+    // frames', the paste's and the reads' (copy, bounds); a cut has the last two live on one stream
+    gol_scratch view, edit, read;
     ncclComm_t nccl = nullptr;
     // timing (gol_engine_set_timing): events on `stream` around the timed launches
     std::vector<hipEvent_t> tev;

@@ -1,12 +1,13 @@
 // gol_kernels.h -- internal launcher interface of the kernel units (each unit holds its own
 // launchers, gol_launch.cpp the state they share; not part of the C ABI).  The step kernels and
 // the batch kernel each have one launcher that takes a descriptor: golk_step (gol_step_launch.h)
-// and golk_batch_step (gol_batch.h); the headers that hold a descriptor also hold its check.
+// and golk_batch_step (gol_batch.h); the region kernels share one, gol_region (gol_edit.h); the
+// headers that hold a descriptor also hold its check.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "gol_edit.h"  // GOL_EDIT_BYTES / _STANDARD / _BAND: how a board's rows are stored (`form`)
+#include "gol_edit.h"  // gol_region; GOL_EDIT_BYTES / _STANDARD / _BAND: how a board's rows are stored
 #include "gol_step_launch.h"
 
 #ifndef GOL_COUNT_SLOTS
@@ -80,47 +81,33 @@ hipError_t golk_row_counts(bool bits_mode, const void *board, const void *prev, 
 hipError_t golk_alive_list(bool bits_mode, const void *board, const void *prev, int64_t rows, int64_t width_units,
                            int64_t pitch, const int64_t *offs, int32_t *xy, int64_t cap, int64_t y0, hipStream_t s);
 
-// Viewport frames (gol_view.hip).  golk_view_counts adds to `frame` (out_w uint32 per pixel row,
-// dense) the alive cells of source rows [row, row + rows) of `src` (row 0 of a shard's rows), which
-// are viewport rows [vrow, vrow + rows): viewport cell (c, v) is board column (x0 + c) mod W and
-// belongs to pixel (c / scale, v / scale), 0 <= c < out_w * scale <= W.  form: byte rows (alive =
-// a byte != 0; pitch in bytes), standard bit rows (W % 32 == 0) or band bit rows (W % 1024 == 0),
-// pitch in words: GOL_EDIT_BYTES / _STANDARD / _BAND (gol_edit.h).  Reads only the words the
-// viewport covers.  1 <= scale <= 4096.
-hipError_t golk_view_counts(int form, const void *src, int64_t pitch, int64_t W, int64_t x0, int32_t scale,
-                            int32_t out_w, int64_t row, int64_t rows, int64_t vrow, uint32_t *frame, hipStream_t s);
+// The region kernels: a rectangle of the running board read or edited in place.  Every launcher takes
+// a gol_region (gol_edit.h, where its fields, its one check gol_region_ok and the column mapping
+// are): hipErrorInvalidValue, nothing launched, unless the check accepts it; hipSuccess at once for
+// rows == 0.  Counters and headers are device words the caller zeroes.
+// gol_view.hip: adds to `frame` (w / scale uint32 per pixel row, dense) the alive cells of the
+// region's rows, which are viewport rows [at, at + rows); viewport cell (c, v) belongs to pixel
+// (c / scale, v / scale), 1 <= scale <= 4096, w a multiple of scale.
+hipError_t golk_view_counts(const gol_region &r, int32_t scale, uint32_t *frame, hipStream_t s);
 // pixels[i] = ceil(255 * frame[i] / scale^2) for i < n; both buffers hold n rounded up to 4
 // elements, 16-byte aligned.
 hipError_t golk_view_pixels(const uint32_t *frame, int64_t n, int32_t scale, uint8_t *pixels, hipStream_t s);
-
-// Board edits (gol_edit.hip).  golk_paste applies pattern rows [prow, prow + rows) (pstride uint64
-// words per row, bit c % 64 of word c / 64 = cell c; pattern NULL: all ones) to rows [row, row + rows)
-// of `dst` (row 0 of a shard's rows) at board columns (x0 + c) mod W, 0 <= c < w <= W, under op
-// (GOL_PASTE_*), in place; form as the views' (GOL_EDIT_BYTES / _STANDARD / _BAND; pitch in bytes
-// or words).  Adds the number of cells whose state changed to *changed (a device counter).  Writes
-// only units the rectangle covers; one lane per unit and row (gol_edit.h).
-hipError_t golk_paste(int form, void *dst, int64_t pitch, int64_t W, int64_t x0, int64_t w, int64_t row, int64_t rows,
-                      int64_t prow, const uint64_t *pattern, int64_t pstride, int32_t op, uint64_t *changed,
+// gol_edit.hip: pattern rows [at, at + rows) (pstride uint64 words per row; pattern NULL: all ones)
+// applied to the region under op (GOL_PASTE_*); *changed += the cells whose state changed.
+hipError_t golk_paste(const gol_region &r, const uint64_t *pattern, int64_t pstride, int32_t op, uint64_t *changed,
                       hipStream_t s);
-
-// Region reads (gol_copy.hip; form, src, pitch, W, x0, w, row, rows as golk_paste; nothing is written
-// to the board).  golk_copy gathers the rectangle's cells of rows [row, row + rows) into pattern rows
-// [prow, prow + rows) (pstride uint64 words per row, bit c % 64 of word c / 64 = cell c): it writes
-// every 32-bit half that holds a cell c < w, bits at c >= w zero, and no other half -- the caller
-// clears the pattern first -- and adds the alive cells gathered to *alive (a device counter).
-hipError_t golk_copy(int form, const void *src, int64_t pitch, int64_t W, int64_t x0, int64_t w, int64_t row, int64_t rows,
-                     int64_t prow, uint64_t *pattern, int64_t pstride, uint64_t *alive, hipStream_t s);
-// The bounding box of the rectangle's alive cells in two passes.  hdr: 5 device words, zeroed by
-// the caller: [0] += alive cells, [1] = max of ~r and [2] = max of r over the rows r (rows of the
-// rectangle: vrow + the row's offset from `row`) that hold one, [3] = max of ~c and [4] = max of c
-// over the rectangle's columns that hold one.  golk_bounds_rows (once per run of rows) fills [0 .. 2]
-// and ORs the columns seen into occ, golk_bounds_lanes(..) zeroed uint32 words; golk_bounds_cols
-// (once, after them, with the same form, src and pitch) turns occ into [3] and [4].
-hipError_t golk_bounds_rows(int form, const void *src, int64_t pitch, int64_t W, int64_t x0, int64_t w, int64_t row,
-                            int64_t rows, int64_t vrow, uint32_t *occ, uint64_t *hdr, hipStream_t s);
-int64_t golk_bounds_lanes(int form, const void *src, int64_t pitch, int64_t W, int64_t x0, int64_t w);
-hipError_t golk_bounds_cols(int form, const void *src, int64_t pitch, int64_t W, int64_t x0, int64_t w, const uint32_t *occ,
-                            uint64_t *hdr, hipStream_t s);
+// gol_copy.hip (nothing is written to the board).  golk_copy gathers the region into pattern rows
+// [at, at + rows): it writes every 32-bit half that holds a cell c < w, bits at c >= w zero, and no
+// other half -- the caller clears the pattern first; *alive += the alive cells gathered.
+hipError_t golk_copy(const gol_region &r, uint64_t *pattern, int64_t pstride, uint64_t *alive, hipStream_t s);
+// The bounding box of the region's alive cells.  hdr, 5 words: [0] += alive cells, [1] = max of ~v and
+// [2] = max of v over the rectangle rows v (at + the row's offset from `row`) that hold one, [3] = max
+// of ~c and [4] = max of c over the columns that hold one.  golk_bounds_rows (once per run of rows)
+// fills [0 .. 2] and ORs the columns seen into occ: T uint32 words, T the geom.T of gol_region_ok(r,
+// GOL_EDIT_COPY, true, .); golk_bounds_cols (once, after them, on a region of the same rows) turns
+// occ into [3] and [4].
+hipError_t golk_bounds_rows(const gol_region &r, uint32_t *occ, uint64_t *hdr, hipStream_t s);
+hipError_t golk_bounds_cols(const gol_region &r, const uint32_t *occ, uint64_t *hdr, hipStream_t s);
 
 // Batches of small boards: n tori of H x W cells (1 <= H, W <= 512, n <= 2^20), board i at boards + i*H*Ww, Ww =
 // ceil(W / 64) uint64 words per row, the bits at c >= W of a row zero.

@@ -250,70 +250,53 @@ hipError_t launch_bits(const ViewArgs &a, int np, dim3 grid, hipStream_t s)
 
 }  // namespace
 
-hipError_t golk_view_counts(int form, const void *src, int64_t pitch, int64_t W, int64_t x0, int32_t scale,
-                            int32_t out_w, int64_t row, int64_t rows, int64_t vrow, uint32_t *frame, hipStream_t s)
+hipError_t golk_view_counts(const gol_region &r, int32_t scale, uint32_t *frame, hipStream_t s)
 {
-    if (!src || !frame || form < GOL_EDIT_BYTES || form > GOL_EDIT_BAND || W < 1 || x0 < 0 || x0 >= W || scale < 1 ||
-        scale > 4096 || out_w < 1 || (int64_t)out_w * scale > W || row < 0 || rows < 0 || vrow < 0)
+    gol_edit_geom g;  // of the viewport's cells: r.w = out_w * scale of them from column r.x0
+    if (!frame || scale < 1 || scale > 4096 || r.w % scale != 0 || !gol_region_ok(r, GOL_EDIT_COPY, true, &g))
         return hipErrorInvalidValue;
-    if (form != GOL_EDIT_BYTES && W % 32 != 0) return hipErrorInvalidValue;
-    if (form == GOL_EDIT_BAND && W % 1024 != 0) return hipErrorInvalidValue;
-    if (rows == 0) return hipSuccess;
+    if (r.rows == 0) return hipSuccess;
     ViewArgs a{};
-    a.src = src;
-    a.pitch = pitch;
-    a.C = (int64_t)out_w * scale;
-    a.row = row;
-    a.rows = rows;
-    a.vrow = vrow;
+    a.src = r.base;
+    a.pitch = r.pitch;
+    a.units = g.units;
+    a.first = g.first;
+    a.bit0 = g.bit0;
+    a.C = r.w;
+    a.row = r.row;
+    a.rows = r.rows;
+    a.vrow = r.at;
     a.frame = frame;
     a.scale = (uint32_t)scale;
-    a.out_w = (uint32_t)out_w;
+    a.out_w = (uint32_t)(r.w / scale);
     a.nsub = (uint32_t)((scale + VIEW_ROWS - 1) / VIEW_ROWS);
-    // byte rows as aligned 4-byte words where the board allows it
-    const bool bytes4 = form == GOL_EDIT_BYTES && W % 4 == 0 && pitch % 4 == 0 && (uintptr_t)src % 4 == 0;
-    if (form == GOL_EDIT_BYTES && pitch < W) return hipErrorInvalidValue;
-    if (bytes4) {
-        a.units = W / 4;
-        a.first = x0 / 4;
-        a.bit0 = (uint32_t)(x0 % 4);
-        a.T = (a.bit0 + a.C + 3) / 4;  // <= W / 4 + 1
-        a.nslots = (2 + a.scale) / a.scale + 1;  // pixels 4 consecutive cells can touch
-    } else if (form == GOL_EDIT_BYTES) {
-        a.units = W;
-        a.first = x0;
-        a.T = a.C;
+    // the view's own: a lane per unit the viewport touches -- past the geometry's clamp to the units of a
+    // row, the first word again for the cells that wrapped (g.wrap_c) -- and the pixels (slots) of a unit
+    a.T = g.T + (g.wrap_c >= 0);
+    if (g.layout == GOL_EDIT_BYTES) {
         a.nslots = 1;
-    } else if (form == GOL_EDIT_STANDARD) {
-        a.units = W / 32;
-        a.first = x0 / 32;
-        a.bit0 = (uint32_t)(x0 % 32);
-        a.T = (a.bit0 + a.C + 31) / 32;  // <= Wd + 1: the first word again, for the cells that wrapped
-        a.nslots = (30 + a.scale) / a.scale + 1;  // pixels 32 consecutive cells can touch
-    } else {
-        a.units = W / 32;
-        a.first = x0 % a.units;
-        a.bit0 = (uint32_t)(x0 / a.units);
-        a.T = a.C < a.units ? a.C : a.units;
+    } else if (g.layout == GOL_EDIT_BAND) {
         a.nslots = (uint32_t)((a.C + a.units - 1) / a.units);  // <= 32 bits of a word
         a.qW = (uint32_t)(a.units / scale);
         a.rW = (uint32_t)(a.units % scale);
+    } else {
+        const uint32_t cells = g.layout == GOL_EDIT_STANDARD ? 32 : 4;
+        a.nslots = (cells - 2 + a.scale) / a.scale + 1;  // pixels `cells` consecutive cells can touch
     }
-    if (form != GOL_EDIT_BYTES && pitch < a.units) return hipErrorInvalidValue;
     // one workgroup per pixel row of the run and VIEW_ROWS rows of its boxes
-    const int64_t j0 = vrow / scale, j1 = (vrow + rows - 1) / scale;
+    const int64_t j0 = r.at / scale, j1 = (r.at + r.rows - 1) / scale;
     const int64_t groups = (j1 - j0 + 1) * a.nsub;
     const int64_t nxb = (a.T + VIEW_BLOCK - 1) / VIEW_BLOCK;
     if (groups > INT32_MAX) return hipErrorInvalidValue;
     const dim3 grid((unsigned)groups, (unsigned)(nxb < 65535 ? nxb : 65535));
     const int most = scale < VIEW_ROWS ? scale : VIEW_ROWS;  // rows a workgroup adds at most
-    if (form == GOL_EDIT_BYTES) {
-        if (bytes4) view_bytes4_kernel<<<grid, VIEW_BLOCK, 0, s>>>(a);
+    if (r.layout == GOL_EDIT_BYTES) {
+        if (g.layout == GOL_EDIT_BYTES4) view_bytes4_kernel<<<grid, VIEW_BLOCK, 0, s>>>(a);
         else view_bytes_kernel<<<grid, VIEW_BLOCK, 0, s>>>(a);
         return hipGetLastError();
     }
     const int np = most == 1 ? 1 : (most <= 15 ? 4 : 8);
-    return form == GOL_EDIT_BAND ? launch_bits<true>(a, np, grid, s) : launch_bits<false>(a, np, grid, s);
+    return r.layout == GOL_EDIT_BAND ? launch_bits<true>(a, np, grid, s) : launch_bits<false>(a, np, grid, s);
 }
 
 hipError_t golk_view_pixels(const uint32_t *frame, int64_t n, int32_t scale, uint8_t *pixels, hipStream_t s)

@@ -12,7 +12,8 @@ import subprocess
 import numpy as np
 import pytest
 
-from test_edit_cpu import CASES as PASTE_SHAPES, board_cells, to_layout
+import region_ref as RR
+from test_edit_cpu import CASES as PASTE_SHAPES, EDGES, board_cells, to_layout
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 COPY_CHECK = os.path.join(ROOT, "gol-distributed-final_amd", "build", "asan", "copy_check")
@@ -52,13 +53,13 @@ def np_bounds(sub):
     return int(xs.min()), int(xs.max()), int(ys.min()), int(ys.max()), len(ys)
 
 
-def cases(binary_bytes=False):
+def cases(binary_bytes=False, shapes=SHAPES, pads=(0, 3)):
     """(args of gol_copy_host, buffer, the board's cells): every shape with a plain and a padded pitch
     (bytes: the one-byte and the 4-byte lane form) and a dense and a wider pattern stride."""
     rng = np.random.default_rng(17)
-    for i, (layout, W, x0, w, kind) in enumerate(SHAPES):
+    for i, (layout, W, x0, w, kind) in enumerate(shapes):
         units = W if layout == 0 else W // 32
-        for pad in (0, 3) if kind == "random" or layout == 0 else (0,):
+        for pad in pads if kind == "random" or layout == 0 else (0,):
             cells = board_cells(11 + i % 4, BROWS, W).copy()
             xs = (x0 + np.arange(w)) % W
             if kind == "empty":  # alive all around the rectangle, nothing inside
@@ -98,9 +99,14 @@ def check_pattern(args, flat, want):
 
 
 def test_copy_host_matches_numpy(G):
+    assert {(0, False), (0, True)} <= run_copy_cases(G, cases())  # byte rows that allow aligned 4-byte words, and not
+
+
+def run_copy_cases(G, cs):
+    """gol_copy_host on each case against numpy; returns the (layout, rows 4-byte aligned) pairs seen."""
     L = G.lib()
     forms = set()
-    for args, buf, cells in cases():
+    for args, buf, cells in cs:
         layout, W, pitch, brows, row, rows, prow, x0, w, stride = args
         before = buf.copy()
         pat = pattern_block(args)
@@ -112,13 +118,31 @@ def test_copy_host_matches_numpy(G):
         assert alive.value == np.count_nonzero(want), args
         assert np.array_equal(buf, before)  # a read
         forms.add((layout, pitch % 4 == 0 and W % 4 == 0))
-    assert {(0, False), (0, True)} <= forms  # byte rows that allow aligned 4-byte words, and not
+    return forms
 
 
 def test_bounds_host_matches_numpy(G):
     L = G.lib()
+    assert run_bounds_cases(G, cases()) >= 8
+    args, buf, _ = list(cases())[-1]
+    layout, W, pitch, brows, row, rows, prow, x0, w, stride = args
+    assert L.gol_bounds_host(layout, buf.ctypes.data, pitch, W, row, rows, x0, w, None, None, None, None, None) == 0
+
+
+def test_copy_and_bounds_host_at_the_geometry_edges(G):
+    """test_edit_cpu.EDGES at a dense pitch, on the random board and with one alive cell at each
+    corner of the rectangle: the copy's one-byte form and the bounds' 4-byte form of the 8-cell rows."""
+    shapes = [(layout, W, x0, w, kind) for layout, W, x0, w in EDGES for kind in ("random", "corners")]
+    assert all(buf.ctypes.data % 4 == 0 for _, buf, _ in cases(shapes=shapes, pads=(0,)))
+    assert {(0, True), (0, False)} <= run_copy_cases(G, cases(shapes=shapes, pads=(0,)))  # W = 8 and W = 7
+    run_bounds_cases(G, cases(shapes=shapes, pads=(0,)))
+
+
+def run_bounds_cases(G, cs):
+    """gol_bounds_host on each case against numpy; returns how many rectangles held no alive cell."""
+    L = G.lib()
     n_empty = 0
-    for args, buf, cells in cases():
+    for args, buf, cells in cs:
         layout, W, pitch, brows, row, rows, prow, x0, w, stride = args
         v = [ctypes.c_int64(-7) for _ in range(5)]
         rc = L.gol_bounds_host(layout, buf.ctypes.data, pitch, W, row, rows, x0, w, *(ctypes.byref(x) for x in v))
@@ -130,8 +154,7 @@ def test_bounds_host_matches_numpy(G):
             assert got[0] > got[1] and got[2] > got[3] and got[4] == 0, args
         else:
             assert got == want, args
-    assert n_empty >= 8
-    assert L.gol_bounds_host(layout, buf.ctypes.data, pitch, W, row, rows, x0, w, None, None, None, None, None) == 0
+    return n_empty
 
 
 def test_copy_then_paste_is_the_identity(G):
@@ -150,25 +173,32 @@ def test_copy_then_paste_is_the_identity(G):
 
 
 def test_copy_host_argument_errors(G):
+    """The refusals every twin shares (region_ref.REFUSED), then those of the copy's own arguments."""
     L, E = G.lib(), G._lib
-    buf = np.zeros((2, 32), np.uint32)
-    pat = np.full((2, 2), 5, np.uint64)
+    buf, pat = RR.buffers()
+    assert RR.bounds(L, buf) == 0
+    for kw in RR.REFUSED:
+        assert "at" in kw or RR.bounds(L, buf, **kw) == E.GOL_EINVAL, kw
+        assert RR.copy(L, buf, pat, **kw) == E.GOL_EINVAL, kw
+    for kw in (dict(stride=0), dict(w=65, stride=1), dict(pattern=False)):
+        assert RR.copy(L, buf, pat, **kw) == E.GOL_EINVAL, kw
+    assert (pat == 5).all() and not buf.any()
+    assert RR.copy(L, buf, pat, stride=2) == 0 and pat.tolist() == [[0, 5], [0, 5]]  # words past ceil(w / 64) stay
 
-    def copy(layout=2, pitch=32, W=1024, row=0, rows=2, prow=0, x0=0, w=10, stride=1, board=buf.ctypes.data, p=pat.ctypes.data):
-        return L.gol_copy_host(layout, board, pitch, W, row, rows, prow, x0, w, p, stride, None)
 
-    def bounds(layout=2, pitch=32, W=1024, row=0, rows=2, x0=0, w=10, board=buf.ctypes.data):
-        return L.gol_bounds_host(layout, board, pitch, W, row, rows, x0, w, None, None, None, None, None)
-    bad = [dict(layout=3), dict(layout=-1), dict(pitch=31), dict(W=1000), dict(layout=1, W=100), dict(row=-1), dict(rows=-1),
-           dict(x0=1024), dict(x0=-1), dict(w=0), dict(w=1025), dict(board=None)]
-    assert bounds() == 0
-    for kw in bad:
-        assert bounds(**kw) == E.GOL_EINVAL, kw
-        assert copy(**kw) == E.GOL_EINVAL, kw
-    for kw in (dict(prow=-1), dict(stride=0), dict(w=65, stride=1), dict(p=None)):
-        assert copy(**kw) == E.GOL_EINVAL, kw
-    assert (pat == 5).all()
-    assert copy(stride=2) == 0 and pat.tolist() == [[0, 5], [0, 5]]  # words past ceil(w / 64) stay
+def test_every_twin_refuses_the_same_regions(G):
+    """One list for gol_paste_host, gol_copy_host and gol_bounds_host: each call of region_ref.ACCEPTED
+    succeeds, each row of REFUSED is GOL_EINVAL from all three, and board and pattern are untouched."""
+    L, E = G.lib(), G._lib
+    for twin in (RR.paste, RR.copy, RR.bounds):
+        for kw in RR.ACCEPTED:
+            assert twin(L, *RR.buffers(), **kw) == 0, (twin.__name__, kw, L.gol_last_error())
+        buf, pat = RR.buffers()
+        for kw in RR.REFUSED:
+            if twin is RR.bounds and "at" in kw:
+                continue  # (its signature has no such argument)
+            assert twin(L, buf, pat, **kw) == E.GOL_EINVAL, (twin.__name__, kw)
+        assert not buf.any() and (pat == 5).all(), twin.__name__
 
 
 def test_copy_abi_edges(G):

@@ -12,6 +12,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import region_ref as RR
 from oracle import oracle as O
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -211,18 +212,25 @@ SHAPES = [
     (0, 50, [(49, 50), (3, 5), (0, 50)]),
 ]
 CASES = [(layout, W, x0, w) for layout, W, xs in SHAPES for x0, w in xs]
+# The smallest shapes at which the unit step the kernels share with the host (gol_edit_paste_unit, the
+# bounds' gol_copy_occ_unit) can go wrong, each at a dense pitch: standard rows of 2 words with the
+# full width from the middle of a word (wrap_c: lane 0 also takes the cells that wrapped); byte rows
+# of 2 aligned 4-byte words, the same wrap in the 4-byte form; byte rows of 7 bytes, one per lane;
+# band rows with the carry into the next band and the wrap from bit 31 to bit 0.
+EDGES = [(1, 64, 33, 64), (0, 8, 3, 8), (0, 7, 5, 7), (2, 1024, 1023, 34)]
 
 
-def paste_cases(G):
+def paste_cases(G, cases=CASES, pad=None):
     """Every shape x op x {pattern, NULL pattern}: (args of gol_paste_host, buffer, pattern words or
-    None, expected buffer cells, expected written mask, expected changed)."""
+    None, expected buffer cells, expected written mask, expected changed).  pad: the units a row
+    has past its last one (None: 0 and 3 in turn)."""
     rng = np.random.default_rng(7)
-    for layout, W, x0, w in CASES:
+    for layout, W, x0, w in cases:
         units = W if layout == 0 else W // 32
         for i, op in enumerate(OPS):
             for null in (False, True):
                 brows, row, rows, prow = 5, 1, 3, 2
-                pitch = units + (0 if (i + null) % 2 else 3)
+                pitch = units + ((0 if (i + null) % 2 else 3) if pad is None else pad)
                 cells = board_cells(11 + i, brows, W)
                 buf = to_layout(layout, cells, pitch, rng)
                 p_all = np.ones((prow + rows, w), bool) if null else rng.random((prow + rows, w)) < 0.5
@@ -243,10 +251,11 @@ def check_result(layout, W, before, after, cells, want, written):
     return int(np.count_nonzero(want != cells))
 
 
-def test_paste_host_matches_numpy(G):
+def run_paste_cases(G, cases):
+    """gol_paste_host on each case against numpy; returns how many ran."""
     L = G.lib()
     n = 0
-    for args, buf, words, cells, want, written in paste_cases(G):
+    for args, buf, words, cells, want, written in cases:
         layout, W, pitch, brows, row, rows, prow, x0, w, stride, op = args
         after = buf.copy()
         changed = ctypes.c_int64(-1)
@@ -255,22 +264,30 @@ def test_paste_host_matches_numpy(G):
         assert rc == 0, (args, L.gol_last_error())
         assert changed.value == check_result(layout, W, buf, after, cells, want, written), args
         n += 1
-    assert n == len(CASES) * 8
+    return n
+
+
+def test_paste_host_matches_numpy(G):
+    assert run_paste_cases(G, paste_cases(G)) == len(CASES) * 8
+
+
+def test_paste_host_at_the_geometry_edges(G):
+    """EDGES under ops 0..3, with a pattern and without: the byte rows of 8 cells take the 4-byte
+    form (W, the dense pitch and the buffer are 4-byte aligned), those of 7 the one-byte form."""
+    cases = list(paste_cases(G, EDGES, pad=0))
+    assert all(buf.ctypes.data % 4 == 0 for _, buf, *_ in cases)
+    assert run_paste_cases(G, cases) == len(EDGES) * 8
 
 
 def test_paste_host_argument_errors(G):
+    """The refusals every twin shares (region_ref.REFUSED), then those of the paste's own arguments."""
     L, E = G.lib(), G._lib
-    buf = np.zeros((2, 32), np.uint32)
+    buf, _ = RR.buffers()
     pat = np.zeros((2, 1), np.uint64)
-
-    def call(layout=2, pitch=32, W=1024, row=0, rows=2, prow=0, x0=0, w=10, stride=1, op=0, board=buf.ctypes.data):
-        return L.gol_paste_host(layout, board, pitch, W, row, rows, prow, x0, w, pat.ctypes.data, stride, op, None)
-    assert call() == 0
-    for bad in (dict(layout=3), dict(layout=-1), dict(pitch=31), dict(W=1000), dict(layout=1, W=100), dict(row=-1),
-                dict(rows=-1), dict(prow=-1), dict(x0=1024), dict(x0=-1), dict(w=0), dict(w=1025), dict(stride=0),
-                dict(op=4), dict(op=-1), dict(board=None)):
-        assert call(**bad) == E.GOL_EINVAL, bad
-    assert not buf.any()
+    assert RR.paste(L, buf, pat) == 0
+    for bad in RR.REFUSED + [dict(stride=0), dict(op=4), dict(op=-1)]:
+        assert RR.paste(L, buf, pat, **bad) == E.GOL_EINVAL, bad
+    assert not buf.any() and not pat.any()
 
 
 def test_paste_abi_edges(G):
