@@ -11,6 +11,7 @@
 
 #include "gol_batch.h"
 #include "gol_engine_int.h"
+#include "gol_island.h"
 #include "gol_rule.h"
 
 // ------------------------------------------------------------------ errors
@@ -289,6 +290,18 @@ extern "C" int gol_dev_batch_step(uint64_t *boards, uint64_t *prev, int64_t *set
         return gol_set_error(GOL_EINVAL, "bad batch_step arguments (n %lld, %lld x %lld, %d turns, scan %d, done %lld, slots %lld, or a pointer)",
                              (long long)n, (long long)H, (long long)W, turns, scan, (long long)done, (long long)slots);
     if (e != hipSuccess) return gol_set_error(GOL_EHIP, "batch_step: %s", hipGetErrorString(e));
+    return GOL_OK;
+}
+
+extern "C" int gol_dev_batch_islands(const uint64_t *boards, int64_t n, int64_t H, int64_t W, int32_t reach, int64_t cap,
+                                     int64_t *count, gol_island *islands, uint64_t *fingerprint, void *stream)
+{
+    const gol_island_launch l = {boards, n, H, W, reach, cap, count, islands, fingerprint};
+    const hipError_t e = golk_batch_islands(l, (hipStream_t)stream);
+    if (e == hipErrorInvalidValue)  // gol_island_launch_ok said no: nothing was launched
+        return gol_set_error(GOL_EINVAL, "bad batch_islands arguments (n %lld, %lld x %lld, reach %d, cap %lld, or a pointer)",
+                             (long long)n, (long long)H, (long long)W, reach, (long long)cap);
+    if (e != hipSuccess) return gol_set_error(GOL_EHIP, "batch_islands: %s", hipGetErrorString(e));
     return GOL_OK;
 }
 

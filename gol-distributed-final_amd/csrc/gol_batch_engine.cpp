@@ -1,8 +1,9 @@
 // gol_batch_engine.cpp -- batches of small boards (include/golhip.h): the handle, the argument
 // checks, the rules per board, the split of a stepping call into launches (one gol_batch_launch per call,
-// gol_batch.h), the retiring call's lists and readbacks, the soup search's driver, and the strided copies.
-// The kernels are gol_batch.hip (the step kernel) and gol_batch_pass.hip (the rest), the host twin
-// gol_batch_host.cpp.
+// gol_batch.h), the retiring call's lists and readbacks, the soup search's driver, the strided copies, and the
+// island census's chunks and scratch (gol_batch_islands).
+// The kernels are gol_batch.hip (the step kernel), gol_batch_pass.hip (the rest) and gol_island.hip (the census),
+// the host twins gol_batch_host.cpp and gol_island_host.cpp.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -12,6 +13,7 @@
 
 #include "gol_batch.h"
 #include "gol_engine_int.h"
+#include "gol_island.h"
 
 // A launch is bounded to about this many cell-updates (and GOL_BATCH_MAX_TURNS turns), as the
 // broker's chunks are: no launch runs long, whatever the batch.
@@ -19,6 +21,8 @@
 #define GOL_BATCH_MAX_TURNS 4096
 // Strided loads and stores are staged through a dense host block of at most this many bytes.
 #define GOL_BATCH_STAGE_BYTES ((int64_t)64 << 20)
+// The island census cuts its range into chunks whose device scratch (counts, fingerprints, records) is at most this.
+#define GOL_ISLAND_SCRATCH_BYTES ((int64_t)256 << 20)
 
 struct gol_batch {
     int64_t n = 0, H = 0, W = 0, Ww = 0;
@@ -47,6 +51,9 @@ struct gol_batch {
     int64_t *tab = nullptr;
     int64_t tab_cap = 0;
     int32_t *scounts = nullptr;
+    // islands (on demand, grown and reused): per chunk of boards the counts, the fingerprints and the records
+    unsigned char *isl = nullptr;
+    int64_t isl_bytes = 0;
 };
 
 namespace {
@@ -316,7 +323,7 @@ extern "C" void gol_batch_destroy(gol_batch *b)
     {
         OnDevice dev(b->device);
         if (b->stream) (void)hipStreamSynchronize(b->stream);
-        void *const device[] = {b->boards, b->prev, b->aux, b->drules, b->lists, b->left, b->slists, b->sages, b->tab};
+        void *const device[] = {b->boards, b->prev, b->aux, b->drules, b->lists, b->left, b->slists, b->sages, b->tab, b->isl};
         for (void *p : device)
             if (p) (void)hipFree(p);
         for (void *p : {(void *)b->hcounts, (void *)b->scounts})
@@ -550,6 +557,62 @@ extern "C" int gol_batch_run_cycles(gol_batch *b, int64_t turns, int64_t *found,
             const int64_t at = *std::lower_bound(ends.begin(), ends.end(), d);
             made[i] = at + gol_batch_turns_left(d, turns - at);
         }
+    }
+    return GOL_OK;
+}
+
+// The census of boards [i0, i1) in chunks of at most `per` boards, one launch each: the chunk's counts and fingerprints
+// come back whole, of its records the first min(dcap, the chunk's largest count) of every board in one strided copy to
+// a host block, from which a board's own records go to the caller's.  No board holds more than H W islands, so the
+// device never keeps more records per board than that, whatever cap says.
+extern "C" int gol_batch_islands(gol_batch *b, int64_t i0, int64_t i1, int32_t reach, int64_t cap, int64_t *count,
+                                 gol_island *islands, uint64_t *fingerprint)
+{
+    if (!b || !count || i0 < 0 || i0 > i1 || i1 > b->n || reach < 1 || reach > GOL_ISLAND_MAX_REACH || cap < 0 ||
+        (cap > 0 && !islands))
+        return gol_set_error(GOL_EINVAL, "bad batch islands (boards [%lld, %lld) of %lld, reach %d in 1..2, cap %lld, or NULL)",
+                             (long long)i0, (long long)i1, b ? (long long)b->n : 0LL, reach, (long long)cap);
+    if (i0 == i1) return GOL_OK;
+    OnDevice dev(b->device);
+    HIPCHK(dev.err);
+    const int64_t dcap = std::min(cap, b->H * b->W), rec = (int64_t)sizeof(gol_island);
+    const int64_t each = 2 * (int64_t)sizeof(int64_t) + dcap * rec;  // bytes of a board's scratch
+    const int64_t per = std::min(i1 - i0, std::max<int64_t>(1, GOL_ISLAND_SCRATCH_BYTES / each));
+    if (b->isl_bytes < per * each) {
+        if (b->isl) HIPCHK(hipFree(b->isl));
+        b->isl = nullptr;
+        b->isl_bytes = 0;
+        HIPCHK(hipMalloc(&b->isl, (size_t)(per * each)));
+        b->isl_bytes = per * each;
+    }
+    int64_t *dcount = (int64_t *)b->isl;
+    uint64_t *dfp = (uint64_t *)(b->isl + per * 8);
+    gol_island *drec = (gol_island *)(b->isl + per * 16);
+    std::vector<gol_island> stage;
+    for (int64_t c0 = i0; c0 < i1; c0 += per) {
+        const int64_t m = std::min(per, i1 - c0);
+        const gol_island_launch l = {b->boards + c0 * b->H * b->Ww, m, b->H, b->W, reach, dcap, dcount, dcap ? drec : nullptr, dfp};
+        HIPCHK(golk_batch_islands(l, b->stream));
+        HIPCHK(hipMemcpyAsync(count + (c0 - i0), dcount, (size_t)m * sizeof(int64_t), hipMemcpyDeviceToHost, b->stream));
+        if (fingerprint)
+            HIPCHK(hipMemcpyAsync(fingerprint + (c0 - i0), dfp, (size_t)m * sizeof(uint64_t), hipMemcpyDeviceToHost, b->stream));
+        HIPCHK(hipStreamSynchronize(b->stream));
+        int64_t most = 0;
+        for (int64_t i = c0; i < c0 + m; ++i) {
+            if (count[i - i0] < 0) return gol_set_error(GOL_EHIP, "batch islands: board %lld reached the census's trip bound", (long long)i);
+            most = std::max(most, std::min(count[i - i0], dcap));
+        }
+        if (most == 0) continue;
+        try {
+            stage.resize((size_t)(m * most));
+        } catch (const std::exception &) {
+            return gol_set_error(GOL_ENOMEM, "batch islands: %lld records of %lld boards", (long long)most, (long long)m);
+        }
+        HIPCHK(hipMemcpy2DAsync(stage.data(), (size_t)(most * rec), drec, (size_t)(dcap * rec), (size_t)(most * rec), (size_t)m,
+                                hipMemcpyDeviceToHost, b->stream));
+        HIPCHK(hipStreamSynchronize(b->stream));
+        for (int64_t i = c0; i < c0 + m; ++i)
+            memcpy(islands + (i - i0) * cap, stage.data() + (i - c0) * most, (size_t)(std::min(count[i - i0], dcap) * rec));
     }
     return GOL_OK;
 }

@@ -1,0 +1,158 @@
+// gol_island.h -- the island census of a small torus (include/golhip.h, "the island census of a batch", where link,
+// island, window code, term, record, order and fingerprint are defined): what the kernel (gol_island.hip, one row per
+// lane) and the host twin (gol_island_host.cpp) share, so the code the GPU runs is tested on the CPU.  No HIP header.
+//
+// A row is the NW words of gol_batch.h (gol_batch_row: nwr words in use, the last cell's bit tb, the tail mask; the
+// padding zero).  Here:
+//   - the record (gol_island, from golhip.h) and the term of a cell's window code;
+//   - the rotations of a row on its W-cell ring by one cell either way, as words, on the L / R formulas of gol_batch.h
+//     with the column wrap of a row that ends inside a word (two cells: the rotation twice, which is right on rings of
+//     one and two cells as well);
+//   - one dilation step of a row of the flood: M' = board & the OR of the (2 reach + 1)^2 shifted neighbours of M, from
+//     the OR of the 2 reach + 1 rows of M round it;
+//   - the window row: a board row turned so that the 2 reach + 1 cells round cell x are bits x .. x + 2 reach of NW + 1
+//     words (the ring unrolled past its end), so a cell's part of the code is a shift and a mask;
+//   - the hash of the cells of M in one row;
+//   - the descriptor of one launch with the one check of what makes it valid.
+#pragma once
+#include <stdint.h>
+
+#include "gol_batch.h"
+#include "golhip.h"
+
+#define GOL_ISLAND_MAX_REACH 2
+
+static_assert(sizeof(gol_island) == 24, "the record is 24 bytes");
+
+GOL_BATCH_HD uint64_t gol_island_term(uint64_t code, int32_t reach) { return gol_batch_splitmix64(code ^ ((uint64_t)reach << 32)); }
+
+// One launch of the census, as gol_dev_batch_islands takes it; the pointers are device memory.
+struct gol_island_launch {
+    const uint64_t *boards;  // n boards of H rows of ceil(W / 64) words
+    int64_t n, H, W;
+    int32_t reach;
+    int64_t cap;            // records per board in `islands`
+    int64_t *count;         // n
+    gol_island *islands;    // n cap, or NULL with cap == 0
+    uint64_t *fingerprint;  // n, or NULL
+};
+
+// What makes a launch valid; everything else is refused and nothing is launched.
+GOL_BATCH_HD bool gol_island_launch_ok(const gol_island_launch &l)
+{
+    if (!l.boards || !l.count || !gol_batch_shape_ok(l.n, l.H, l.W)) return false;
+    if (l.reach < 1 || l.reach > GOL_ISLAND_MAX_REACH || l.cap < 0) return false;
+    return l.cap == 0 || l.islands != nullptr;
+}
+
+// The mask of word j of a row (uniform in a kernel).
+GOL_BATCH_HD uint32_t gol_island_keep(const gol_batch_row &g, int j) { return j < g.nwr - 1 ? ~0u : (j == g.nwr - 1 ? g.tail : 0u); }
+
+// o[x] = c[(x - 1) mod W]: every cell moves one column up (L of gol_batch.h, masked).  o is not c.
+template <int NW>
+GOL_BATCH_HD void gol_island_rot_up(const uint32_t (&c)[NW], const gol_batch_row &g, uint32_t (&o)[NW])
+{
+    uint32_t last = c[0];  // word nwr - 1, picked without a variable register index
+    GOL_BATCH_UNROLL
+    for (int j = 1; j < NW; ++j) last = j == g.nwr - 1 ? c[j] : last;
+    const uint32_t wl = (last >> g.tb) & 1u;  // cell W - 1, to the left of cell 0
+    GOL_BATCH_UNROLL
+    for (int j = 0; j < NW; ++j) o[j] = ((c[j] << 1) | (j > 0 ? c[j > 0 ? j - 1 : 0] >> 31 : wl)) & gol_island_keep(g, j);
+}
+
+// o[x] = c[(x + 1) mod W]: every cell moves one column down (R of gol_batch.h).  o is not c.
+template <int NW>
+GOL_BATCH_HD void gol_island_rot_down(const uint32_t (&c)[NW], const gol_batch_row &g, uint32_t (&o)[NW])
+{
+    const uint32_t wr = (c[0] & 1u) << g.tb;  // cell 0, to the right of cell W - 1
+    GOL_BATCH_UNROLL
+    for (int j = 0; j < NW; ++j)
+        o[j] = (c[j] >> 1) | (j + 1 < NW ? c[j + 1 < NW ? j + 1 : j] << 31 : 0u) | (j == g.nwr - 1 ? wr : 0u);
+}
+
+// One dilation step of a row: v is the OR of the rows (y + dy) mod H, |dy| <= REACH, of M; out = board & the OR of v
+// rotated by every |dx| <= REACH.
+template <int NW, int REACH>
+GOL_BATCH_HD void gol_island_dilate(const uint32_t (&board)[NW], const uint32_t (&v)[NW], const gol_batch_row &g,
+                                    uint32_t (&out)[NW])
+{
+    uint32_t acc[NW], a[NW], t[NW];  // (one direction after the other: fewer rows alive at a time)
+    GOL_BATCH_UNROLL
+    for (int j = 0; j < NW; ++j) acc[j] = a[j] = v[j];
+    GOL_BATCH_UNROLL
+    for (int k = 0; k < REACH; ++k) {
+        gol_island_rot_up<NW>(a, g, t);
+        GOL_BATCH_UNROLL
+        for (int j = 0; j < NW; ++j) acc[j] |= a[j] = t[j];
+    }
+    GOL_BATCH_UNROLL
+    for (int j = 0; j < NW; ++j) a[j] = v[j];
+    GOL_BATCH_UNROLL
+    for (int k = 0; k < REACH; ++k) {
+        gol_island_rot_down<NW>(a, g, t);
+        GOL_BATCH_UNROLL
+        for (int j = 0; j < NW; ++j) acc[j] |= a[j] = t[j];
+    }
+    GOL_BATCH_UNROLL
+    for (int j = 0; j < NW; ++j) out[j] = board[j] & acc[j];
+}
+
+// The window row of a board row c: bit i of e, 0 <= i < W + 2 REACH, is cell (i - REACH) mod W, so the cells x - REACH
+// .. x + REACH of the ring are bits x .. x + 2 REACH.  The row rotated up by REACH, and its first 2 REACH cells again
+// from bit W on; a ring of fewer than 4 cells is repeated five times (W + 2 REACH <= 5 W), all in word 0.
+template <int NW, int REACH>
+GOL_BATCH_HD void gol_island_window_row(const uint32_t (&c)[NW], const gol_batch_row &g, int32_t W, uint32_t (&e)[NW + 1])
+{
+    uint32_t p[NW], t[NW];
+    GOL_BATCH_UNROLL
+    for (int j = 0; j < NW; ++j) p[j] = c[j];
+    GOL_BATCH_UNROLL
+    for (int k = 0; k < REACH; ++k) {
+        gol_island_rot_up<NW>(p, g, t);
+        GOL_BATCH_UNROLL
+        for (int j = 0; j < NW; ++j) p[j] = t[j];
+    }
+    if (W < 4) {  // (uniform)
+        e[0] = p[0] | p[0] << W | p[0] << 2 * W | p[0] << 3 * W | p[0] << 4 * W;
+        GOL_BATCH_UNROLL
+        for (int j = 1; j <= NW; ++j) e[j] = 0u;
+        return;
+    }
+    const uint32_t low = p[0] & ((1u << 2 * REACH) - 1u);
+    const int32_t ws = W / 32, bs = W % 32;  // where bit W lies
+    GOL_BATCH_UNROLL
+    for (int j = 0; j <= NW; ++j) {
+        uint32_t v = j < NW ? p[j < NW ? j : 0] : 0u;
+        v |= j == ws ? low << bs : 0u;
+        v |= j == ws + 1 && bs > 0 ? low >> (32 - bs) : 0u;
+        e[j] = v;
+    }
+}
+
+// The 2 REACH + 1 cells of a window row from bit b < 32 of word lo on (hi: the word after it).  A funnel shift in 32-bit
+// operations: written through a 64-bit word, the two words of a lane's register array are read as one, overlapping the
+// next pair, and the array leaves the registers.
+template <int REACH>
+GOL_BATCH_HD uint32_t gol_island_field(uint32_t lo, uint32_t hi, uint32_t b)
+{
+    return ((lo >> b) | ((hi << 1) << (31u - b))) & ((1u << (2 * REACH + 1)) - 1u);
+}
+
+// The sum of the terms of the cells of m, one row of an island: e[dy + REACH] is the window row of board row (y + dy) mod H.
+template <int NW, int REACH>
+GOL_BATCH_HD uint64_t gol_island_row_hash(const uint32_t (&m)[NW], const uint32_t (&e)[2 * REACH + 1][NW + 1])
+{
+    uint64_t h = 0;
+    GOL_BATCH_UNROLL
+    for (int j = 0; j < NW; ++j) {
+        for (uint32_t left = m[j]; left; left &= left - 1u) {  // (at most 32 trips)
+            const uint32_t b = (uint32_t)__builtin_ctz(left);
+            uint64_t code = 0;
+            GOL_BATCH_UNROLL
+            for (int d = 0; d < 2 * REACH + 1; ++d)
+                code |= (uint64_t)gol_island_field<REACH>(e[d][j], e[d][j + 1], b) << (d * (2 * REACH + 1));
+            h += gol_island_term(code, REACH);
+        }
+    }
+    return h;
+}

@@ -14,7 +14,37 @@ import ctypes
 
 import numpy as np
 
-from ._lib import GOL_EINVAL, GolError, format_rule, lib, parse_rule
+from ._lib import GOL_EINVAL, GolError, format_rule, lib, parse_rle, parse_rule
+
+# gol_island (include/golhip.h): the record of an island, 24 bytes
+ISLAND_DTYPE = np.dtype([("y", "<i4"), ("x", "<i4"), ("cells", "<i4"), ("rows", "<u2"), ("cols", "<u2"), ("hash", "<u8")])
+
+
+def island(pattern, reach: int = 1, library=None):
+    """The record of a lone pattern (a 2-D array of cells, non-zero = alive, or RLE text) as the island census
+    gives it: a numpy record of ISLAND_DTYPE whose cells, rows, cols and hash are those of the same pattern
+    anywhere on any torus where nothing else lies within `reach` of it, so a caller can name what a tally of
+    Batch.islands finds.  Computed on the host (gol_batch_islands_host) on a torus padded by 2 reach cells; no GPU
+    needed.  GolError(GOL_EINVAL) when the pattern is empty, is not one island at this reach, or does not fit a
+    512 x 512 torus."""
+    L = library or lib()
+    cells = parse_rle(pattern, L)[0] if isinstance(pattern, (str, bytes, bytearray)) else np.asarray(pattern) != 0
+    if cells.ndim != 2 or not cells.any():
+        raise GolError(GOL_EINVAL, f"a pattern is a 2-D array with at least one alive cell, got shape {cells.shape}")
+    ys, xs = np.nonzero(cells)
+    cells = cells[ys.min():ys.max() + 1, xs.min():xs.max() + 1]
+    h, w = cells.shape
+    board = np.zeros((h + 2 * reach, w + 2 * reach), dtype=np.uint8)
+    board[:h, :w] = cells
+    words = Batch.pack(board)
+    count, out = ctypes.c_int64(), np.zeros(1, dtype=ISLAND_DTYPE)
+    rc = L.gol_batch_islands_host(board.shape[0], board.shape[1], reach, words.ctypes.data, words.shape[1], 1,
+                                  ctypes.byref(count), out.ctypes.data, None)
+    if rc:
+        raise GolError(rc, L.gol_last_error().decode(errors="replace"))
+    if count.value != 1:
+        raise GolError(GOL_EINVAL, f"the pattern is {count.value} islands at reach {reach}, not one")
+    return out[0]
 
 
 class Batch:
@@ -247,6 +277,28 @@ class Batch:
         out = np.zeros(self.n, dtype=np.uint64)
         self._check(self._L.gol_batch_hashes(self._h, out.ctypes.data, self.n))
         return out
+
+    def islands(self, reach: int = 1, cap: int = 64, first: int = 0, count: int | None = None, fingerprints: bool = False):
+        """The island census of boards [first, first + count) (default: all from `first`), labelled on the GPU
+        where the boards lie; boards, turn and rules stay.  An island is a connected group of alive cells: two
+        cells are linked when they are within `reach` (1: the 8-connected islands; 2: everything that shares a
+        neighbour cell) of each other on the torus.  Returns (counts, islands): counts int64[count], the full
+        number of islands per board; islands a zero-initialised structured array of shape (count, cap) and
+        ISLAND_DTYPE whose first min(counts[i], cap) records of row i are board i's islands ordered by their
+        first cell (y, x) in row-major order, with cells (the population), rows and cols (the distinct rows and
+        columns occupied) and hash (the sum of the cells' window terms, gol_batch_islands in golhip.h).
+        cells, rows, cols and hash do not change under a torus translation of the board; they do under
+        rotation and reflection.  fingerprints=True appends uint64[count]: per board the wrapping sum of the
+        hashes of all its islands, those past `cap` included."""
+        count = self.n - first if count is None else count
+        m = max(int(count), 0)
+        counts = np.zeros(m, dtype=np.int64)
+        recs = np.zeros((m, max(int(cap), 0)), dtype=ISLAND_DTYPE)
+        fps = np.zeros(m, dtype=np.uint64) if fingerprints else None
+        self._check(self._L.gol_batch_islands(self._h, first, first + count, reach, cap, counts.ctypes.data,
+                                              recs.ctypes.data if cap > 0 else None,
+                                              fps.ctypes.data if fingerprints else None))
+        return (counts, recs, fps) if fingerprints else (counts, recs)
 
     def info(self) -> dict:
         n, H, W = (ctypes.c_int64() for _ in range(3))

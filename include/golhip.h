@@ -733,6 +733,66 @@ int gol_batch_step_check_host(const uint64_t *boards, const uint64_t *prev, cons
                               int64_t W, int32_t turns, int64_t turn0, int32_t have_prev, int32_t write_prev, uint32_t birth,
                               uint32_t survive, const uint32_t *rules, int32_t scan, int64_t done, const int32_t *list,
                               const int32_t *count, int64_t slots, const int64_t *left, const int64_t *born);
+/* The island census of a batch: per board its islands, the connected groups of
+ * alive cells, each with a fingerprint that no torus translation changes,
+ * labelled on the GPU in one launch on the boards where they lie (the kernel
+ * is csrc/gol_island.hip, the functions it shares with the host twin
+ * csrc/gol_island.h).  No version bump: probe by symbol.
+ * Board i of a batch is an H x W torus; reach is 1 or 2.
+ *  - Link: two alive cells are linked when one is at ((y + dy) mod H, (x + dx)
+ *    mod W) of the other for some |dy|, |dx| <= reach.
+ *  - Island: a class of the transitive closure of the link.  reach 1 gives the
+ *    8-connected islands; reach 2 joins everything that shares a neighbour cell.
+ *  - Window code of an alive cell (y, x): the sum over dy, dx in [-reach, reach]
+ *    of alive((y + dy) mod H, (x + dx) mod W) << ((dy + reach) (2 reach + 1) + (dx
+ *    + reach)).  The formula holds as written on tori narrower than the window,
+ *    where a cell may appear in it more than once.
+ *  - Term of a cell: splitmix64(code ^ ((uint64_t)reach << 32)), the splitmix64
+ *    of the soup words (gol_batch_soup_host).
+ *  - Record of an island (gol_island, 24 bytes): (y, x) its first cell in
+ *    row-major order, cells its population, rows and cols the numbers of
+ *    distinct rows and columns it occupies, hash the wrapping sum of its cells'
+ *    terms.
+ *  - Order: a board's records are ordered by (y, x) ascending.
+ *  - Fingerprint of a board: the wrapping sum of all its islands' hash.
+ * Every cell in the window of a cell is linked to it, so it belongs to the
+ * cell's own island: cells, rows, cols, hash and the fingerprint do not change
+ * under any torus translation of the board (y and x do).  They do change under
+ * rotation and reflection: orientation is not factored out.
+ *
+ * gol_batch_islands: boards [i0, i1) of the batch.  count[i - i0] is always the
+ * full number of islands of board i.  islands may be NULL when cap == 0;
+ * otherwise it has (i1 - i0) cap records, the first min(count, cap) records of
+ * board i are written at islands + (i - i0) cap and the rest are not touched.
+ * fingerprint may be NULL; otherwise fingerprint[i - i0] covers all islands of
+ * the board, those past cap included.  The boards, the turn and the rules
+ * stay; the call blocks.  The device scratch for counts and records lives in
+ * the handle, grown and reused, and the range is cut into chunks so that it
+ * stays at or below 256 MiB.  GOL_EINVAL before any GPU work, outputs
+ * untouched: a NULL handle or count, a bad range, reach outside 1..2, cap < 0,
+ * or cap > 0 with NULL islands.
+ * gol_batch_islands_host: the same census of one board in host memory (a host
+ * function, no GPU needed) with the rotation, dilation and term functions the
+ * kernel runs; rows of row_stride >= ceil(W / 64) words, the padding bits and
+ * the words between the rows are not read.  The outputs and the refusals are
+ * those of one board of gol_batch_islands (and a NULL `words` or a short row
+ * stride).
+ * gol_batch_islands_check_host: the argument check of gol_dev_batch_islands (a
+ * host function: the function of csrc/gol_island.h that every launch passes),
+ * its arguments without the stream.  GOL_OK where that call would launch,
+ * GOL_EINVAL where it refuses; reads no memory. */
+typedef struct gol_island {
+    int32_t y, x;        /* the island's first cell in row-major order */
+    int32_t cells;       /* its population */
+    uint16_t rows, cols; /* the distinct rows and columns it occupies */
+    uint64_t hash;       /* the wrapping sum of its cells' terms */
+} gol_island;
+int gol_batch_islands(gol_batch *b, int64_t i0, int64_t i1, int32_t reach, int64_t cap, int64_t *count, gol_island *islands,
+                      uint64_t *fingerprint);
+int gol_batch_islands_host(int64_t H, int64_t W, int32_t reach, const uint64_t *words, int64_t row_stride, int64_t cap,
+                           int64_t *count, gol_island *islands, uint64_t *fingerprint);
+int gol_batch_islands_check_host(const uint64_t *boards, int64_t n, int64_t H, int64_t W, int32_t reach, int64_t cap,
+                                 const int64_t *count, const gol_island *islands, const uint64_t *fingerprint);
 /* The argument check of the step launches (a host function, no GPU needed; the
  * function of csrc/gol_step_launch.h that every launch of a step kernel passes,
  * from gol_dev_bits_step, _band_step(_on), _rule_step, _bytes_step_k(_on) and from
@@ -1088,6 +1148,16 @@ int gol_dev_batch_step(uint64_t *boards, uint64_t *prev, int64_t *settled, int64
                        int64_t turn0, int32_t have_prev, int32_t write_prev, uint32_t birth, uint32_t survive,
                        const uint32_t *rules, int32_t scan, int64_t done, const int32_t *list, const int32_t *count,
                        int64_t slots, int64_t *left, const int64_t *born, void *stream);
+/* One launch of the island census (gol_batch_islands, above, where islands,
+ * records and fingerprints are defined) on caller device memory: boards as for
+ * gol_dev_batch_step, only read; count int64_t[n]; islands n cap records (may be
+ * NULL when cap == 0), board b's first min(count[b], cap) at islands + b cap, the
+ * rest not touched; fingerprint uint64_t[n] or NULL.  Not checked: that the
+ * pointers are device memory of the stated sizes.  GOL_EINVAL, nothing
+ * launched: NULL boards or count, n, H, W out of range, reach outside 1..2, cap <
+ * 0, or cap > 0 with NULL islands.  No version bump: probe by symbol. */
+int gol_dev_batch_islands(const uint64_t *boards, int64_t n, int64_t H, int64_t W, int32_t reach, int64_t cap, int64_t *count,
+                          gol_island *islands, uint64_t *fingerprint, void *stream);
 /* Read and clear the error word of `device` (-1 = current) that the gol_dev_*
  * launchers' kernels report into (*flags = 0: no fault; nonzero: a pipeline
  * wave timed out waiting for its neighbour, so the launch's output is not

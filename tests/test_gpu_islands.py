@@ -1,0 +1,184 @@
+"""The island census on the GPU: every instantiation of batch_islands_kernel<NW, REACH> (csrc/gol_island.hip) on
+caller memory through gol_dev_batch_islands, against the reference of tests/island_ref.py (a plain-Python flood
+fill written from include/golhip.h), every compared field bit for bit.  The case table is island_ref's (its
+coverage is asserted in tests/test_island_ref_cpu.py).  Every buffer of a launch lies between two margins of
+sentinel bytes; the records are filled with 0xA5 before the launch, so a record written past min(count, cap)
+shows; the boards are compared byte for byte after the call.  Then the same census through golhip.Batch: on
+settled soups against the reference, under random torus translations, and of named patterns."""
+import ctypes
+
+import numpy as np
+import pytest
+
+import island_ref as I
+
+pytestmark = pytest.mark.gpu
+
+GOL_EINVAL = -1
+MARGIN = 64  # int64 words before and after every buffer
+FILL = 0xA5
+
+
+@pytest.fixture(scope="module")
+def G():
+    import torch
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    import golhip
+    golhip.lib()
+    torch.cuda.set_device(0)
+    return golhip
+
+
+def _device(host_bytes, fill=0x5A):
+    """A device buffer holding host_bytes (uint8) between two margins of `fill` bytes: (tensor, pointer, padded host)."""
+    import torch
+    m = np.full(MARGIN * 8, fill, dtype=np.uint8)
+    padded = np.concatenate([m, host_bytes, m])
+    t = torch.from_numpy(padded.copy()).cuda()
+    return t, t.data_ptr() + MARGIN * 8, padded
+
+
+def _launch(G, cells, reach, cap, with_fp=True):
+    """One launch on caller memory; returns (rc, count, records[n, cap], fingerprint) after checking that the
+    boards and every margin are as before."""
+    import torch
+    n, H, W = cells.shape
+    words = G.Batch.pack(cells.astype(np.uint8))
+    tb, pb, hb = _device(words.view(np.uint8).ravel())
+    tc, pc, hc = _device(np.full(n * 8, FILL, dtype=np.uint8))
+    tr, pr, hr = _device(np.full(n * cap * 24, FILL, dtype=np.uint8), fill=FILL)
+    tf, pf, hf = _device(np.full(n * 8, FILL, dtype=np.uint8))
+    rc = G.lib().gol_dev_batch_islands(pb, n, H, W, reach, cap, pc, pr if cap else None, pf if with_fp else None,
+                                       torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    got = [t.cpu().numpy() for t in (tb, tc, tr, tf)]
+    assert np.array_equal(got[0], hb), "the boards or their margins changed"
+    lo, hi = MARGIN * 8, -MARGIN * 8
+    for g, h, name in ((got[1], hc, "count"), (got[2], hr, "islands"), (got[3], hf, "fingerprint")):
+        assert np.array_equal(g[:lo], h[:lo]) and np.array_equal(g[hi:], h[hi:]), f"a margin of {name} changed"
+    count = got[1][lo:hi].view(np.int64)
+    recs = got[2][lo:hi].view(I.DTYPE).reshape(n, cap)
+    fp = got[3][lo:hi].view(np.uint64)
+    return rc, count, recs, fp
+
+
+def _check_case(G, c, reach):
+    want = I.want(c, reach)
+    rc, count, recs, fp = _launch(G, c.cells, reach, c.cap)
+    assert rc == 0, (c.id, G.lib().gol_last_error())
+    untouched = np.frombuffer(bytes([FILL]) * 24, dtype=I.DTYPE)[0]
+    for i, (wrecs, wfp) in enumerate(want):
+        where = (c.id, reach, i)
+        assert int(count[i]) == len(wrecs), (where, int(count[i]), len(wrecs))
+        assert int(fp[i]) == wfp, (where, hex(int(fp[i])), hex(wfp))
+        k = min(len(wrecs), c.cap)
+        assert np.array_equal(recs[i, :k], wrecs[:k]), (where, recs[i, :3], wrecs[:3])
+        assert np.all(recs[i, k:] == untouched), (where, "a record past min(count, cap) was written")
+
+
+@pytest.mark.parametrize("c", I.CASES, ids=lambda c: c.id)
+def test_case(G, c):
+    for reach in c.reaches:
+        _check_case(G, c, reach)
+
+
+def test_null_fingerprint(G):
+    c = next(c for c in I.CASES if c.id == "five-cap20")
+    rc, count, recs, fp = _launch(G, c.cells, 1, c.cap, with_fp=False)
+    assert rc == 0 and count.tolist() == [0, 1, 4, 9, 2]
+    assert fp.tobytes() == bytes([FILL]) * fp.nbytes
+
+
+def test_refusals_launch_nothing(G):
+    import torch
+    c = next(c for c in I.CASES if c.id == "five-cap3")
+    n, H, W = c.cells.shape
+    words = G.Batch.pack(c.cells.astype(np.uint8))
+    tb, pb, _ = _device(words.view(np.uint8).ravel())
+    tc, pc, hc = _device(np.full(n * 8, FILL, dtype=np.uint8))
+    tr, pr, hr = _device(np.full(n * 3 * 24, FILL, dtype=np.uint8))
+    s = torch.cuda.current_stream().cuda_stream
+    f = G.lib().gol_dev_batch_islands
+    bad = [f(None, n, H, W, 1, 3, pc, pr, None, s), f(pb, n, H, W, 1, 3, None, pr, None, s), f(pb, n, H, W, 1, 3, pc, None, None, s),
+           f(pb, 0, H, W, 1, 3, pc, pr, None, s), f(pb, n, 0, W, 1, 3, pc, pr, None, s), f(pb, n, H, 513, 1, 3, pc, pr, None, s),
+           f(pb, n, H, W, 0, 3, pc, pr, None, s), f(pb, n, H, W, 3, 3, pc, pr, None, s), f(pb, n, H, W, 1, -1, pc, pr, None, s)]
+    torch.cuda.synchronize()
+    assert bad == [GOL_EINVAL] * len(bad)
+    assert np.array_equal(tc.cpu().numpy(), hc) and np.array_equal(tr.cpu().numpy(), hr)
+
+
+# ------------------------------------------------------------------------------------------------ through Batch
+@pytest.fixture(scope="module")
+def soups(G):
+    """The settled soups: (cells uint8[n, side, side], reference per reach), made once."""
+    S = I.SOUPS
+    with G.Batch(S["n"], S["side"], S["side"], device=0) as b:
+        b.load_soups(S["seed"])
+        b.run_cycles(S["turns"])
+        cells = b.store()
+        got = {reach: b.islands(reach=reach, cap=S["cap"], fingerprints=True) for reach in (1, 2)}
+        assert np.array_equal(b.store(), cells) and b.turn == S["turns"]
+    want = {reach: [I.census(c, reach) for c in cells] for reach in (1, 2)}
+    return cells, got, want
+
+
+def test_batch_islands_on_settled_soups(G, soups):
+    cells, got, want = soups
+    assert cells.any()
+    for reach in (1, 2):
+        counts, recs, fps = got[reach]
+        assert recs.dtype == G.ISLAND_DTYPE and recs.shape == (len(cells), I.SOUPS["cap"])
+        for i, (wrecs, wfp) in enumerate(want[reach]):
+            k = len(wrecs)
+            assert int(counts[i]) == k <= I.SOUPS["cap"] and int(fps[i]) == wfp, (reach, i)
+            assert np.array_equal(recs[i, :k], wrecs), (reach, i)
+            assert not recs[i, k:].tobytes().strip(b"\0"), (reach, i)  # zero-initialised
+
+
+def test_batch_islands_under_translation(G, soups):
+    cells, got, _ = soups
+    rng = np.random.default_rng(9)
+    rolled = np.stack([np.roll(c, tuple(int(v) for v in rng.integers(0, c.shape)), axis=(0, 1)) for c in cells])
+    with G.Batch(len(cells), cells.shape[1], cells.shape[2], device=0) as b:
+        b.load(rolled)
+        for reach in (1, 2):
+            counts, recs, fps = b.islands(reach=reach, cap=I.SOUPS["cap"], fingerprints=True)
+            c0, r0, f0 = got[reach]
+            assert np.array_equal(counts, c0) and np.array_equal(fps, f0)
+            for i in range(len(cells)):
+                assert I.key(recs[i, :counts[i]]) == I.key(r0[i, :c0[i]]), (reach, i)
+
+
+def test_batch_islands_ranges_and_refusals(G, soups):
+    cells, got, _ = soups
+    with G.Batch(len(cells), cells.shape[1], cells.shape[2], device=0) as b:
+        b.load(cells)
+        counts, recs = b.islands(reach=1, cap=5, first=7, count=3)
+        assert np.array_equal(counts, got[1][0][7:10]) and np.array_equal(recs, got[1][1][7:10, :5])
+        counts, recs = b.islands(cap=0)
+        assert np.array_equal(counts, got[1][0]) and recs.shape == (len(cells), 0)
+        for bad in (dict(reach=0), dict(reach=3), dict(cap=-1), dict(first=-1), dict(first=1, count=len(cells))):
+            with pytest.raises(G.GolError):
+                b.islands(**bad)
+        out = ctypes.c_int64(77)
+        assert G.lib().gol_batch_islands(b._h, 0, 1, 1, 4, ctypes.byref(out), None, None) == GOL_EINVAL and out.value == 77
+        assert G.lib().gol_batch_islands(None, 0, 1, 1, 0, ctypes.byref(out), None, None) == GOL_EINVAL
+
+
+def test_named_patterns_are_found_again(G):
+    """A board holding a block, a blinker and a beehive: each is found under the record golhip.island gives it."""
+    pats = {"block": "x = 2, y = 2\n2o$2o!", "blinker": "x = 3, y = 1\n3o!", "beehive": "x = 4, y = 3\nb2o$o2bo$b2o!"}
+    board = np.zeros((1, 40, 70), dtype=np.uint8)
+    for (y, x), text in zip(((38, 68), (10, 30), (20, 62)), pats.values()):  # the block over the corner, the beehive over bit 63|64
+        p = G.parse_rle(text)[0]
+        for dy, dx in np.argwhere(p):
+            board[0, (y + dy) % 40, (x + dx) % 70] = 1
+    with G.Batch(1, 40, 70, device=0) as b:
+        b.load(board)
+        for reach in (1, 2):
+            counts, recs = b.islands(reach=reach)
+            assert counts.tolist() == [3]
+            names = {(int(r["cells"]), int(r["rows"]), int(r["cols"]), int(r["hash"])): k
+                     for k, r in ((k, G.island(t, reach)) for k, t in pats.items())}
+            assert sorted(names[k] for k in I.key(recs[0, :3])) == ["beehive", "blinker", "block"]
