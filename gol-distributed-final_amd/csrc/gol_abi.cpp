@@ -305,6 +305,33 @@ extern "C" int gol_dev_batch_islands(const uint64_t *boards, int64_t n, int64_t 
     return GOL_OK;
 }
 
+extern "C" int gol_dev_batch_islands_tally(const uint64_t *boards, int64_t n, int64_t H, int64_t W, int32_t reach,
+                                           const int32_t *pairs, const int32_t *pair_count, int64_t max_pairs, const int64_t *found,
+                                           int64_t owner0, int64_t *count, uint64_t *fingerprint, gol_island_kind *table,
+                                           int32_t table_log2, int64_t *dropped, void *stream)
+{
+    const gol_island_launch l = {boards, n, H, W, reach, 0, count, nullptr, fingerprint, table, table_log2, dropped, owner0, pairs,
+                                 pair_count, max_pairs, found};
+    // (a NULL table would be the plain launch, which is not this entry's)
+    const hipError_t e = table ? golk_batch_islands(l, (hipStream_t)stream) : hipErrorInvalidValue;
+    if (e == hipErrorInvalidValue)  // gol_island_launch_ok said no: nothing was launched
+        return gol_set_error(GOL_EINVAL,
+                             "bad batch_islands_tally arguments (n %lld, %lld x %lld, reach %d, table 2^%d, owner0 %lld, %lld pairs, or a "
+                             "pointer)",
+                             (long long)n, (long long)H, (long long)W, reach, table_log2, (long long)owner0, (long long)max_pairs);
+    if (e != hipSuccess) return gol_set_error(GOL_EHIP, "batch_islands_tally: %s", hipGetErrorString(e));
+    return GOL_OK;
+}
+
+extern "C" int gol_dev_island_table_clear(gol_island_kind *table, int32_t table_log2, int64_t *dropped, void *stream)
+{
+    const hipError_t e = golk_island_table_clear(table, table_log2, dropped, (hipStream_t)stream);
+    if (e == hipErrorInvalidValue)
+        return gol_set_error(GOL_EINVAL, "bad island_table_clear arguments (table 2^%d in 4..24, or a pointer)", table_log2);
+    if (e != hipSuccess) return gol_set_error(GOL_EHIP, "island_table_clear: %s", hipGetErrorString(e));
+    return GOL_OK;
+}
+
 extern "C" int gol_dev_error(int32_t device, uint32_t *flags)
 {
     if (!flags) return gol_set_error(GOL_EINVAL, "flags is NULL");

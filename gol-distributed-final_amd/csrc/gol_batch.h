@@ -84,10 +84,10 @@ GOL_BATCH_HD uint64_t gol_batch_soup_word(uint64_t seed, uint64_t i, int64_t Ww,
 }
 
 // The census of a board: its alive cells, and its hash (oracle_hash_words) the sum over its H Ww words of this term of
-// word i.  The kernels sum the terms over a wave's lanes (gol_batch_pass.hip), gol_batch_census over a dense host board.
+// word i.  The kernels sum the terms over a wave's lanes (gol_batch_pass.hip), gol_batch_board_census over a dense host board.
 GOL_BATCH_HD uint64_t gol_batch_hash_term(uint64_t word, uint64_t i) { return gol_batch_splitmix64(word ^ gol_batch_splitmix64(i)); }
 
-GOL_BATCH_HD void gol_batch_census(const uint64_t *board, int64_t words, uint64_t *alive, uint64_t *hash)
+GOL_BATCH_HD void gol_batch_board_census(const uint64_t *board, int64_t words, uint64_t *alive, uint64_t *hash)
 {
     *alive = *hash = 0;
     for (int64_t i = 0; i < words; ++i) {

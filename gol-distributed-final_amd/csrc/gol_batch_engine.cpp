@@ -1,7 +1,8 @@
 // gol_batch_engine.cpp -- batches of small boards (include/golhip.h): the handle, the argument
 // checks, the rules per board, the split of a stepping call into launches (one gol_batch_launch per call,
 // gol_batch.h), the retiring call's lists and readbacks, the soup search's driver, the strided copies, and the
-// island census's chunks and scratch (gol_batch_islands).
+// island census's chunks and scratch (gol_batch_islands), and the kind table of a tally (gol_batch_census,
+// gol_batch_islands_tally): its size, its clearing, its one read-back and the sort on the host.
 // The kernels are gol_batch.hip (the step kernel), gol_batch_pass.hip (the rest) and gol_island.hip (the census),
 // the host twins gol_batch_host.cpp and gol_island_host.cpp.
 #include <hip/hip_runtime.h>
@@ -45,7 +46,8 @@ struct gol_batch {
     int64_t *left = nullptr;
     int32_t *hcounts = nullptr;  // pinned host memory: the two counts read back after every launch
     // search (on demand): the active list (n), the harvest list (2 n), the soup per slot (n) and the four counts; born and
-    // the found age per slot (2 n); the result tables found, period, alive, hash (4 tab_cap words); four pinned counts
+    // the found age per slot (2 n); the result tables found, period, alive, hash, islands, fingerprint (6 tab_cap words);
+    // four pinned counts
     int32_t *slists = nullptr;
     int64_t *sages = nullptr;
     int64_t *tab = nullptr;
@@ -54,6 +56,9 @@ struct gol_batch {
     // islands (on demand, grown and reused): per chunk of boards the counts, the fingerprints and the records
     unsigned char *isl = nullptr;
     int64_t isl_bytes = 0;
+    // the tally of kinds (on demand, grown and reused): the table of kind_slots slots, then the counter `dropped`
+    gol_island_kind *kind = nullptr;
+    int64_t kind_slots = 0;
 };
 
 namespace {
@@ -219,11 +224,82 @@ int run_cycles(gol_batch *b, int64_t turns, int64_t *out, std::vector<int64_t> &
     return GOL_OK;
 }
 
+// The kind table of one tally call: log2 from kinds_cap (the smallest power of two >= 2 max(kinds_cap, 512), at most 2^24).
+struct Tally {
+    int32_t reach = 1, log2 = 0;
+    gol_island_kind *table = nullptr;
+    int64_t *dropped = nullptr;
+};
+
+bool tally_args_ok(int32_t reach, const gol_island_kind *kinds, int64_t kinds_cap, const int64_t *n_kinds)
+{
+    return reach >= 1 && reach <= GOL_ISLAND_MAX_REACH && kinds_cap >= 0 && kinds_cap <= ((int64_t)1 << 23) && n_kinds &&
+           (kinds_cap == 0 || kinds);
+}
+
+// The handle's table sized for kinds_cap and set to empty, `dropped` to 0.
+int tally_begin(gol_batch *b, int32_t reach, int64_t kinds_cap, Tally *t)
+{
+    t->reach = reach;
+    t->log2 = 10;
+    while (((int64_t)1 << t->log2) < 2 * kinds_cap) t->log2 += 1;
+    const int64_t slots = (int64_t)1 << t->log2;
+    if (b->kind_slots < slots) {
+        if (b->kind) HIPCHK(hipFree(b->kind));
+        b->kind = nullptr;
+        b->kind_slots = 0;
+        HIPCHK(hipMalloc(&b->kind, (size_t)(slots + 1) * sizeof(gol_island_kind)));
+        b->kind_slots = slots;
+    }
+    t->table = b->kind;
+    t->dropped = (int64_t *)(b->kind + slots);
+    HIPCHK(golk_island_table_clear(t->table, t->log2, t->dropped, b->stream));
+    return GOL_OK;
+}
+
+// The one read-back of a tally: `dropped`, and unless it is set the table, its kinds unpacked and sorted.
+int tally_end(gol_batch *b, const Tally &t, const char *what, gol_island_kind *kinds, int64_t kinds_cap, int64_t *n_kinds)
+{
+    const int64_t slots = (int64_t)1 << t.log2;
+    int64_t dropped = 0;
+    HIPCHK(hipMemcpyAsync(&dropped, t.dropped, sizeof dropped, hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    *n_kinds = -1;
+    if (dropped != 0)
+        return gol_set_error(GOL_ENOMEM, "batch %s: the table of %lld kinds that kinds_cap %lld asks for is full, %lld islands not tallied",
+                             what, (long long)slots, (long long)kinds_cap, (long long)dropped);
+    std::vector<gol_island_kind> all;
+    try {
+        all.resize((size_t)slots);
+    } catch (const std::exception &) {
+        return gol_set_error(GOL_ENOMEM, "batch %s: a table of %lld kinds", what, (long long)slots);
+    }
+    HIPCHK(hipMemcpyAsync(all.data(), t.table, (size_t)slots * sizeof(gol_island_kind), hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    size_t kept = 0;
+    for (const gol_island_kind &k : all) {
+        if (k.hash == 0) continue;
+        const gol_island_slot &d = reinterpret_cast<const gol_island_slot &>(k);  // (the device layout: the shape packed)
+        const uint64_t shape = d.shape;
+        all[kept] = k;
+        all[kept].cells = (int32_t)(shape >> 32), all[kept].rows = (uint16_t)(shape >> 16), all[kept].cols = (uint16_t)shape;
+        kept += 1;
+    }
+    all.resize(kept);
+    std::sort(all.begin(), all.end(), gol_island_kind_before);
+    if (kept) memcpy(kinds, all.data(), (size_t)std::min<int64_t>((int64_t)kept, kinds_cap) * sizeof(gol_island_kind));
+    *n_kinds = (int64_t)kept;
+    return GOL_OK;
+}
+
 // gol_batch_search on st->slots = min(n, total) slots in launches of st->launch_turns turns: the first fill, then per
 // launch the aged step over the active list, the restock pass, the harvest and the refill of the slots it names, and a
 // blocking read of the counts, until no slot is active.  The tables live on the device and are copied out once.
+// tally (gol_batch_census; else NULL): after the harvest, the listed TALLY census of the same harvest list, on the
+// snapshots, into the tables islands and fingerprint and the kind table.
 int search(gol_batch *b, uint64_t seed, int64_t first, int64_t total, int64_t horizon, int64_t *found, int64_t *period,
-           uint64_t *alive, uint64_t *hash, gol_batch_search_stats *st)
+           uint64_t *alive, uint64_t *hash, gol_batch_search_stats *st, const Tally *tally, int64_t *islands,
+           uint64_t *fingerprint)
 {
     const int64_t n = b->n, m = st->slots;
     const int L = (int)st->launch_turns;
@@ -236,7 +312,7 @@ int search(gol_batch *b, uint64_t seed, int64_t first, int64_t total, int64_t ho
         if (b->tab) HIPCHK(hipFree(b->tab));
         b->tab = nullptr;
         b->tab_cap = 0;
-        HIPCHK(hipMalloc(&b->tab, (size_t)(4 * total) * sizeof(int64_t)));
+        HIPCHK(hipMalloc(&b->tab, (size_t)(6 * total) * sizeof(int64_t)));
         b->tab_cap = total;
     }
     int32_t *active = b->slists, *harvest = b->slists + n, *soup = b->slists + 3 * n, *counts = b->slists + 4 * n;
@@ -244,7 +320,9 @@ int search(gol_batch *b, uint64_t seed, int64_t first, int64_t total, int64_t ho
     int64_t *tfound = b->tab, *tperiod = b->tab + total;
     uint64_t *talive = (uint64_t *)(b->tab + 2 * total), *thash = (uint64_t *)(b->tab + 3 * total);
     HIPCHK(hipMemsetAsync(tfound, 0xff, (size_t)(2 * total) * sizeof(int64_t), b->stream));
-    HIPCHK(hipMemsetAsync(talive, 0, (size_t)(2 * total) * sizeof(uint64_t), b->stream));
+    int64_t *tislands = b->tab + 4 * total;
+    uint64_t *tfp = (uint64_t *)(b->tab + 5 * total);
+    HIPCHK(hipMemsetAsync(talive, 0, (size_t)((tally ? 4 : 2) * total) * sizeof(uint64_t), b->stream));
     HIPCHK(golk_batch_soups(b->boards, m, b->H, b->W, seed, first, b->stream));
     HIPCHK(golk_batch_search_init(active, counts, soup, born, age, m, b->stream));
     // the aged launch: the cycle scan of the listed slots in their own ages from turn 0, the snapshot always written
@@ -261,6 +339,11 @@ int search(gol_batch *b, uint64_t seed, int64_t first, int64_t total, int64_t ho
         st->board_turns += in * L;
         HIPCHK(golk_batch_restock(active, counts, age, born, soup, n, done, horizon, total, tfound, tperiod, harvest, b->stream));
         HIPCHK(golk_batch_harvest(b->prev, harvest, counts, n, b->H, b->W, total, tfound, talive, thash, in, b->stream));
+        if (tally) {
+            const gol_island_launch il = {b->prev, n, b->H, b->W, tally->reach, 0, tislands, nullptr, tfp, tally->table, tally->log2,
+                                          tally->dropped, first, harvest, counts + 1, in, tfound};
+            HIPCHK(golk_batch_islands(il, b->stream));
+        }
         HIPCHK(golk_batch_refill(b->boards, harvest, counts, soup, n, b->H, b->W, seed, first, total, in, b->stream));
         HIPCHK(hipMemcpyAsync(host, counts, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, b->stream));
         HIPCHK(hipStreamSynchronize(b->stream));
@@ -275,8 +358,55 @@ int search(gol_batch *b, uint64_t seed, int64_t first, int64_t total, int64_t ho
     if (period) HIPCHK(hipMemcpyAsync(period, tperiod, bytes, hipMemcpyDeviceToHost, b->stream));
     if (alive) HIPCHK(hipMemcpyAsync(alive, talive, bytes, hipMemcpyDeviceToHost, b->stream));
     if (hash) HIPCHK(hipMemcpyAsync(hash, thash, bytes, hipMemcpyDeviceToHost, b->stream));
+    if (tally && islands) HIPCHK(hipMemcpyAsync(islands, tislands, bytes, hipMemcpyDeviceToHost, b->stream));
+    if (tally && fingerprint) HIPCHK(hipMemcpyAsync(fingerprint, tfp, bytes, hipMemcpyDeviceToHost, b->stream));
     HIPCHK(hipStreamSynchronize(b->stream));
     return GOL_OK;
+}
+
+// gol_batch_search and gol_batch_census (tally_kinds: its kinds_cap, n_kinds and kinds; census == false: none).
+int search_call(gol_batch *b, uint64_t seed, int64_t first, int64_t total, int64_t horizon, int64_t *found, int64_t *period,
+                uint64_t *alive, uint64_t *hash, gol_batch_search_stats *stats, bool census, int32_t reach, int64_t *islands,
+                uint64_t *fingerprint, gol_island_kind *kinds, int64_t kinds_cap, int64_t *n_kinds)
+{
+    const char *what = census ? "census" : "search";
+    if (!b || !found || first < 0 || total < 0 || horizon < 0 || first > ((int64_t)1 << 40) || total > ((int64_t)1 << 26) ||
+        first + total > ((int64_t)1 << 40))
+        return gol_set_error(GOL_EINVAL, "bad batch %s (soups [%lld, +%lld) in 0..2^40, at most 2^26, horizon %lld, or NULL)", what,
+                             (long long)first, (long long)total, (long long)horizon);
+    if (census && !tally_args_ok(reach, kinds, kinds_cap, n_kinds))
+        return gol_set_error(GOL_EINVAL, "bad batch census (reach %d in 1..2, kinds_cap %lld in 0..2^23, or NULL)", reach,
+                             (long long)kinds_cap);
+    if (!b->rules.empty()) return gol_set_error(GOL_ESTATE, "batch %s: the boards of the batch have different rules", what);
+    OnDevice dev(b->device);
+    HIPCHK(dev.err);
+    const int64_t m = std::min(b->n, total);
+    // every launch makes L turns (no longer than the horizon), so ages are multiples of L
+    const int64_t L = std::max<int64_t>(1, std::min<int64_t>(b->auto_tpl ? auto_turns(std::max<int64_t>(m, 1), b->H, b->W) : b->tpl,
+                                                             horizon));
+    gol_batch_search_stats st{};
+    st.slots = m;
+    st.launch_turns = L;
+    Tally tally;
+    int tallied = GOL_OK;  // (a full table: the per-soup outputs stand, the call ends as after a search, and then says so)
+    if (total > 0 && horizon > 0) {
+        int rc = census ? tally_begin(b, reach, kinds_cap, &tally) : GOL_OK;
+        if (!rc) rc = search(b, seed, first, total, horizon, found, period, alive, hash, &st, census ? &tally : nullptr, islands, fingerprint);
+        if (rc) return rc;
+        if (census) tallied = tally_end(b, tally, what, kinds, kinds_cap, n_kinds);
+    } else {  // nothing to run
+        gol_batch_no_results(total, found, period, alive, hash);
+        for (int64_t g = 0; census && g < total; ++g) {
+            if (islands) islands[g] = 0;
+            if (fingerprint) fingerprint[g] = 0;
+        }
+        if (census) *n_kinds = 0;
+    }
+    HIPCHK(hipMemsetAsync(b->boards, 0, (size_t)(b->n * b->H * b->Ww) * sizeof(uint64_t), b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    b->turn = 0;
+    if (stats) *stats = st;
+    return tallied;
 }
 
 // gol_batch_load_words (load) and gol_batch_store_words: boards [i0, i1) between the caller's rows, row_stride and
@@ -323,7 +453,7 @@ extern "C" void gol_batch_destroy(gol_batch *b)
     {
         OnDevice dev(b->device);
         if (b->stream) (void)hipStreamSynchronize(b->stream);
-        void *const device[] = {b->boards, b->prev, b->aux, b->drules, b->lists, b->left, b->slists, b->sages, b->tab, b->isl};
+        void *const device[] = {b->boards, b->prev, b->aux, b->drules, b->lists, b->left, b->slists, b->sages, b->tab, b->isl, b->kind};
         for (void *p : device)
             if (p) (void)hipFree(p);
         for (void *p : {(void *)b->hcounts, (void *)b->scounts})
@@ -490,31 +620,17 @@ extern "C" int gol_batch_load_soups(gol_batch *b, uint64_t seed, int64_t first)
 extern "C" int gol_batch_search(gol_batch *b, uint64_t seed, int64_t first, int64_t total, int64_t horizon, int64_t *found,
                                 int64_t *period, uint64_t *alive, uint64_t *hash, gol_batch_search_stats *stats)
 {
-    if (!b || !found || first < 0 || total < 0 || horizon < 0 || first > ((int64_t)1 << 40) || total > ((int64_t)1 << 26) ||
-        first + total > ((int64_t)1 << 40))
-        return gol_set_error(GOL_EINVAL, "bad batch search (soups [%lld, +%lld) in 0..2^40, at most 2^26, horizon %lld, or NULL)",
-                             (long long)first, (long long)total, (long long)horizon);
-    if (!b->rules.empty()) return gol_set_error(GOL_ESTATE, "batch search: the boards of the batch have different rules");
-    OnDevice dev(b->device);
-    HIPCHK(dev.err);
-    const int64_t m = std::min(b->n, total);
-    // every launch makes L turns (no longer than the horizon), so ages are multiples of L
-    const int64_t L = std::max<int64_t>(1, std::min<int64_t>(b->auto_tpl ? auto_turns(std::max<int64_t>(m, 1), b->H, b->W) : b->tpl,
-                                                             horizon));
-    gol_batch_search_stats st{};
-    st.slots = m;
-    st.launch_turns = L;
-    if (total > 0 && horizon > 0) {
-        const int rc = search(b, seed, first, total, horizon, found, period, alive, hash, &st);
-        if (rc) return rc;
-    } else {  // nothing to run
-        gol_batch_no_results(total, found, period, alive, hash);
-    }
-    HIPCHK(hipMemsetAsync(b->boards, 0, (size_t)(b->n * b->H * b->Ww) * sizeof(uint64_t), b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
-    b->turn = 0;
-    if (stats) *stats = st;
-    return GOL_OK;
+    return search_call(b, seed, first, total, horizon, found, period, alive, hash, stats, false, 0, nullptr, nullptr, nullptr, 0,
+                       nullptr);
+}
+
+extern "C" int gol_batch_census(gol_batch *b, uint64_t seed, int64_t first, int64_t total, int64_t horizon, int32_t reach,
+                                int64_t *found, int64_t *period, uint64_t *alive, uint64_t *hash, int64_t *islands,
+                                uint64_t *fingerprint, gol_island_kind *kinds, int64_t kinds_cap, int64_t *n_kinds,
+                                gol_batch_search_stats *stats)
+{
+    return search_call(b, seed, first, total, horizon, found, period, alive, hash, stats, true, reach, islands, fingerprint, kinds,
+                       kinds_cap, n_kinds);
 }
 
 extern "C" int gol_batch_step(gol_batch *b, int64_t turns, int64_t *settled)
@@ -615,6 +731,50 @@ extern "C" int gol_batch_islands(gol_batch *b, int64_t i0, int64_t i1, int32_t r
             memcpy(islands + (i - i0) * cap, stage.data() + (i - c0) * most, (size_t)(std::min(count[i - i0], dcap) * rec));
     }
     return GOL_OK;
+}
+
+// The tally of boards [i0, i1) as they stand: the chunks of gol_batch_islands (counts and fingerprints alone in the
+// scratch), each one dense TALLY launch with owner = the board's index, then the table's one read-back.
+extern "C" int gol_batch_islands_tally(gol_batch *b, int64_t i0, int64_t i1, int32_t reach, int64_t *count, uint64_t *fingerprint,
+                                       gol_island_kind *kinds, int64_t kinds_cap, int64_t *n_kinds)
+{
+    if (!b || !count || i0 < 0 || i0 > i1 || i1 > b->n || !tally_args_ok(reach, kinds, kinds_cap, n_kinds))
+        return gol_set_error(GOL_EINVAL,
+                             "bad batch islands_tally (boards [%lld, %lld) of %lld, reach %d in 1..2, kinds_cap %lld in 0..2^23, or NULL)",
+                             (long long)i0, (long long)i1, b ? (long long)b->n : 0LL, reach, (long long)kinds_cap);
+    if (i0 == i1) {
+        *n_kinds = 0;
+        return GOL_OK;
+    }
+    OnDevice dev(b->device);
+    HIPCHK(dev.err);
+    const int64_t each = 2 * (int64_t)sizeof(int64_t);  // bytes of a board's scratch
+    const int64_t per = std::min(i1 - i0, std::max<int64_t>(1, GOL_ISLAND_SCRATCH_BYTES / each));
+    if (b->isl_bytes < per * each) {
+        if (b->isl) HIPCHK(hipFree(b->isl));
+        b->isl = nullptr;
+        b->isl_bytes = 0;
+        HIPCHK(hipMalloc(&b->isl, (size_t)(per * each)));
+        b->isl_bytes = per * each;
+    }
+    int64_t *dcount = (int64_t *)b->isl;
+    uint64_t *dfp = (uint64_t *)(b->isl + per * 8);
+    Tally t;
+    const int rc = tally_begin(b, reach, kinds_cap, &t);
+    if (rc) return rc;
+    for (int64_t c0 = i0; c0 < i1; c0 += per) {
+        const int64_t m = std::min(per, i1 - c0);
+        const gol_island_launch l = {b->boards + c0 * b->H * b->Ww, m, b->H, b->W, reach, 0, dcount, nullptr, dfp, t.table, t.log2,
+                                     t.dropped, c0};
+        HIPCHK(golk_batch_islands(l, b->stream));
+        HIPCHK(hipMemcpyAsync(count + (c0 - i0), dcount, (size_t)m * sizeof(int64_t), hipMemcpyDeviceToHost, b->stream));
+        if (fingerprint)
+            HIPCHK(hipMemcpyAsync(fingerprint + (c0 - i0), dfp, (size_t)m * sizeof(uint64_t), hipMemcpyDeviceToHost, b->stream));
+        HIPCHK(hipStreamSynchronize(b->stream));
+        for (int64_t i = c0; i < c0 + m; ++i)
+            if (count[i - i0] < 0) return gol_set_error(GOL_EHIP, "batch islands_tally: board %lld reached the census's trip bound", (long long)i);
+    }
+    return tally_end(b, t, "islands_tally", kinds, kinds_cap, n_kinds);
 }
 
 extern "C" int gol_batch_alive_counts(gol_batch *b, uint64_t *counts, int64_t cap) { return reduce(b, false, counts, cap); }

@@ -4,10 +4,12 @@
 // board with that turn and the mark functions the kernel and the engine use; and gol_batch_run_cycles_host: the
 // retiring scheme of gol_batch_run_cycles on one board, with the remainder function the retire pass runs; and gol_batch_soup_host and
 // gol_batch_search_host: a soup from the fill kernels' word function, and the scheme of gol_batch_search; and
+// gol_batch_census_host: that scheme with the island census of every kept s(found) (gol_island_host.cpp) and their tally; and
 // gol_batch_step_check_host: the check every launch of the step kernel passes (gol_batch_launch_ok).  No HIP
-// header: a stand-alone program links this file alone (batch_check.cpp).
+// header: a stand-alone program links this file and gol_island_host.cpp (batch_check.cpp, tally_check.cpp).
 #include <stdint.h>
 
+#include <functional>
 #include <vector>
 
 #include "gol_batch.h"
@@ -173,11 +175,14 @@ extern "C" int gol_batch_soup_host(int64_t H, int64_t W, uint64_t seed, int64_t 
     return GOL_OK;
 }
 
+namespace {
+
 // gol_batch_search on host memory: the slots, the launches, the restock pass in the list's order and the census of the
-// kept snapshot, as the kernels and the driver of gol_batch_engine.cpp have them
-extern "C" int gol_batch_search_host(int64_t H, int64_t W, uint32_t birth, uint32_t survive, uint64_t seed, int64_t first,
-                                     int64_t total, int64_t slots, int64_t launch, int64_t horizon, int64_t *found,
-                                     int64_t *period, uint64_t *alive, uint64_t *hash)
+// kept snapshot, as the kernels and the driver of gol_batch_engine.cpp have them.  harvested (may be empty) sees every
+// found soup's number and its s(found), dense, in the harvest's order.
+int search_host(int64_t H, int64_t W, uint32_t birth, uint32_t survive, uint64_t seed, int64_t first, int64_t total, int64_t slots,
+                int64_t launch, int64_t horizon, int64_t *found, int64_t *period, uint64_t *alive, uint64_t *hash,
+                const std::function<int(int64_t, const uint64_t *)> &harvested)
 {
     // (no rows of the caller's: the result arrays stand in for them)
     if (!args_ok(H, W, birth, survive, found, found, (W + 63) / 64) || first < 0 || total < 0 || horizon < 0 ||
@@ -233,11 +238,13 @@ extern "C" int gol_batch_search_host(int64_t H, int64_t W, uint32_t birth, uint3
             }
             if (v == GOL_BATCH_FOUND) {  // the harvest: s(found) is the snapshot
                 uint64_t a, h;
-                gol_batch_census(s.snap.data(), bw, &a, &h);
+                gol_batch_board_census(s.snap.data(), bw, &a, &h);
                 found[s.soup] = s.found;
                 if (period) period[s.soup] = gol_batch_period(s.found);
                 if (alive) alive[s.soup] = a;
                 if (hash) hash[s.soup] = h;
+                const int rc = harvested ? harvested(s.soup, s.snap.data()) : GOL_OK;
+                if (rc) return rc;
             }
             if (next < total) {
                 const int rc = fill(s, next++, done);
@@ -246,6 +253,52 @@ extern "C" int gol_batch_search_host(int64_t H, int64_t W, uint32_t birth, uint3
             }
         }
         active.swap(stay);
+    }
+    return GOL_OK;
+}
+
+}  // namespace
+
+extern "C" int gol_batch_search_host(int64_t H, int64_t W, uint32_t birth, uint32_t survive, uint64_t seed, int64_t first,
+                                     int64_t total, int64_t slots, int64_t launch, int64_t horizon, int64_t *found,
+                                     int64_t *period, uint64_t *alive, uint64_t *hash)
+{
+    return search_host(H, W, birth, survive, seed, first, total, slots, launch, horizon, found, period, alive, hash, nullptr);
+}
+
+extern "C" int gol_batch_census_host(int64_t H, int64_t W, uint32_t birth, uint32_t survive, uint64_t seed, int64_t first,
+                                     int64_t total, int64_t slots, int64_t launch, int64_t horizon, int32_t reach, int64_t *found,
+                                     int64_t *period, uint64_t *alive, uint64_t *hash, int64_t *islands, uint64_t *fingerprint,
+                                     gol_island_kind *kinds, int64_t kinds_cap, int64_t *n_kinds)
+{
+    if (reach < 1 || reach > 2 || kinds_cap < 0 || !n_kinds || (kinds_cap > 0 && !kinds))
+        return gol_set_error(GOL_EINVAL, "bad host batch census (reach %d in 1..2, kinds_cap %lld, or NULL)", reach,
+                             (long long)kinds_cap);
+    // every record of every found soup, then the tally; the outputs are written once nothing can fail
+    std::vector<gol_island> records, mine;
+    std::vector<int64_t> owners, counts;
+    std::vector<uint64_t> fps;
+    const int64_t Ww = (W + 63) / 64;
+    auto harvested = [&](int64_t soup, const uint64_t *snap) -> int {
+        int64_t count = 0;
+        uint64_t fp = 0;
+        mine.resize((size_t)(H * W));
+        const int rc = gol_batch_islands_host(H, W, reach, snap, Ww, H * W, &count, mine.data(), &fp);
+        if (rc) return rc;
+        if (count < 0) return gol_set_error(GOL_EINVAL, "host batch census: soup %lld reached the census's trip bound", (long long)soup);
+        records.insert(records.end(), mine.begin(), mine.begin() + count);
+        owners.insert(owners.end(), (size_t)count, first + soup);
+        counts[(size_t)soup] = count;
+        fps[(size_t)soup] = fp;
+        return GOL_OK;
+    };
+    if (total > 0 && total <= ((int64_t)1 << 26)) counts.assign((size_t)total, 0), fps.assign((size_t)total, 0);
+    int rc = search_host(H, W, birth, survive, seed, first, total, slots, launch, horizon, found, period, alive, hash, harvested);
+    if (!rc) rc = gol_island_tally_host(records.data(), owners.data(), (int64_t)records.size(), kinds, kinds_cap, n_kinds);
+    if (rc) return rc;
+    for (int64_t g = 0; g < total; ++g) {
+        if (islands) islands[g] = counts[(size_t)g];
+        if (fingerprint) fingerprint[g] = fps[(size_t)g];
     }
     return GOL_OK;
 }

@@ -13,7 +13,8 @@
 //   - the window row: a board row turned so that the 2 reach + 1 cells round cell x are bits x .. x + 2 reach of NW + 1
 //     words (the ring unrolled past its end), so a cell's part of the code is a shift and a mask;
 //   - the hash of the cells of M in one row;
-//   - the descriptor of one launch with the one check of what makes it valid.
+//   - the descriptor of one launch, plain or TALLY, with the one check of what makes it valid;
+//   - the kind table of a tally: the packed shape, the empty slot, the home slot and the probe step.
 #pragma once
 #include <stdint.h>
 
@@ -22,19 +23,56 @@
 
 #define GOL_ISLAND_MAX_REACH 2
 
+#define GOL_ISLAND_TALLY_MIN_LOG2 4
+#define GOL_ISLAND_TALLY_MAX_LOG2 24
+#define GOL_ISLAND_TALLY_BUFFER 64  // records a workgroup gathers before wave 0 inserts them, one lane each
+
 static_assert(sizeof(gol_island) == 24, "the record is 24 bytes");
+static_assert(sizeof(gol_island_kind) == 32, "a kind, and a slot of the device table, is 32 bytes");
+
+// A slot of the device table as the kernel sees it: four 64-bit words, the last the packed shape.
+struct gol_island_slot {
+    uint64_t hash, count, first, shape;
+};
+static_assert(sizeof(gol_island_slot) == sizeof(gol_island_kind), "a slot has the bytes of a kind");
+#define GOL_ISLAND_SLOT_EMPTY {0u, 0u, (uint64_t)INT64_MAX, ~(uint64_t)0}
+
+GOL_BATCH_HD uint64_t gol_island_shape_pack(int32_t cells, uint32_t rows, uint32_t cols)
+{
+    return (uint64_t)(uint32_t)cells << 32 | (uint64_t)(rows & 0xffffu) << 16 | (uint64_t)(cols & 0xffffu);
+}
+// The tag a hash is tallied under: 0 is the empty slot's.
+GOL_BATCH_HD uint64_t gol_island_tally_tag(uint64_t hash) { return hash ? hash : 1u; }
+// The home slot of a tag in a table of 2^log2 slots, and the slot a probe visits after `slot`.
+GOL_BATCH_HD uint64_t gol_island_tally_home(uint64_t tag, int32_t log2) { return gol_batch_splitmix64(tag) >> (64 - log2); }
+// The order of a tally: count descending, then hash ascending.
+GOL_BATCH_HD bool gol_island_kind_before(const gol_island_kind &a, const gol_island_kind &b)
+{
+    return a.count != b.count ? a.count > b.count : a.hash < b.hash;
+}
+GOL_BATCH_HD uint64_t gol_island_tally_next(uint64_t slot, int32_t log2) { return (slot + 1u) & (((uint64_t)1 << log2) - 1u); }
 
 GOL_BATCH_HD uint64_t gol_island_term(uint64_t code, int32_t reach) { return gol_batch_splitmix64(code ^ ((uint64_t)reach << 32)); }
 
-// One launch of the census, as gol_dev_batch_islands takes it; the pointers are device memory.
+// One launch of the census, as gol_dev_batch_islands (table NULL: plain, the fields after fingerprint 0) or
+// gol_dev_batch_islands_tally (table not NULL: TALLY, cap 0) takes it; the pointers are device memory.
 struct gol_island_launch {
     const uint64_t *boards;  // n boards of H rows of ceil(W / 64) words
     int64_t n, H, W;
     int32_t reach;
     int64_t cap;            // records per board in `islands`
-    int64_t *count;         // n
+    int64_t *count;         // n (listed: indexed by soup)
     gol_island *islands;    // n cap, or NULL with cap == 0
-    uint64_t *fingerprint;  // n, or NULL
+    uint64_t *fingerprint;  // as count, or NULL
+    // TALLY
+    gol_island_kind *table;     // 2^table_log2 slots (gol_island_slot)
+    int32_t table_log2;
+    int64_t *dropped;           // one counter
+    int64_t owner0;             // the owner of board 0 (listed: of soup 0)
+    const int32_t *pairs;       // NULL: dense; else (slot, soup) pairs, the harvest list of the restock pass
+    const int32_t *pair_count;  // the pairs in the list (device memory)
+    int64_t max_pairs;          // the workgroups of a listed launch
+    const int64_t *found;       // listed: by soup, < 0: the soup expired
 };
 
 // What makes a launch valid; everything else is refused and nothing is launched.
@@ -42,7 +80,12 @@ GOL_BATCH_HD bool gol_island_launch_ok(const gol_island_launch &l)
 {
     if (!l.boards || !l.count || !gol_batch_shape_ok(l.n, l.H, l.W)) return false;
     if (l.reach < 1 || l.reach > GOL_ISLAND_MAX_REACH || l.cap < 0) return false;
-    return l.cap == 0 || l.islands != nullptr;
+    if (!l.pairs && (l.pair_count || l.found || l.max_pairs != 0)) return false;
+    if (!l.table)  // plain
+        return (l.cap == 0 || l.islands != nullptr) && !l.dropped && !l.pairs && l.table_log2 == 0 && l.owner0 == 0;
+    if (l.cap != 0 || l.islands || !l.dropped || l.owner0 < 0 || l.owner0 > ((int64_t)1 << 40)) return false;
+    if (l.table_log2 < GOL_ISLAND_TALLY_MIN_LOG2 || l.table_log2 > GOL_ISLAND_TALLY_MAX_LOG2) return false;
+    return !l.pairs || (l.pair_count && l.found && l.max_pairs >= 1 && l.max_pairs <= l.n);
 }
 
 // The mask of word j of a row (uniform in a kernel).

@@ -1,7 +1,7 @@
 // gol_island.hip -- the island census of a batch of small tori in one launch (include/golhip.h, "the island census of
 // a batch"; the row functions are gol_island.h).
 //
-// batch_islands_kernel<NW, REACH>: one board per workgroup of ceil(H / 64) waves, one row per lane, NW = 1, 2, 4, 8 or
+// batch_islands_kernel<NW, REACH, TALLY>: one board per workgroup of ceil(H / 64) waves, one row per lane, NW = 1, 2, 4, 8 or
 // 16 words of it in registers, as in the step kernel (gol_batch.hip).  The board is read once and stays resident: a
 // lane holds its row's remaining cells and the window rows (gol_island_window_row) of the 2 REACH + 1 board rows (y +
 // dy) mod H round it, read straight from memory; they are constant, so the fingerprint needs no lane exchange.  (At
@@ -20,16 +20,33 @@
 //     seed's candidates through LDS under one barrier; thread 0 writes the record (if it is within cap) and sums the
 //     fingerprint;
 //   - M leaves the remaining cells.
-// Synchronisation is __syncthreads() alone: no atomic, no flag between workgroups, no spin loop.  Every barrier is
-// reached by every wave: every loop that holds one ends on a value all waves read from LDS after the same barrier.
+// Synchronisation is __syncthreads() alone: no flag between workgroups, no spin loop, and in the plain instantiations
+// (TALLY = false) no atomic.  Every barrier is reached by every wave: every loop that holds one ends on a value all waves
+// read from LDS after the same barrier.
 // The DPP moves run with all lanes active, outside divergent branches; no register array is indexed by a variable.
 // Both loops carry a hard trip bound of H W (an island has at most H W cells, a board at most H W islands, and every
 // flood step but the last adds a cell): it cannot be reached, and a board that hit it would report count = -1.
 //
-// This unit holds the kernel, the dispatch over its ten instantiations and its one entry, golk_batch_islands, which
-// launches what a gol_island_launch describes once gol_island_launch_ok accepts it.
+// TALLY = true (include/golhip.h, "the tally of island kinds"): no record array; every finished island goes into a
+// table of kinds in global memory instead, under its owner.  The board is board blockIdx.x (dense), or the slot of pair
+// blockIdx.x of a device list of (slot, soup) pairs whose length is in device memory (listed: one uniform scalar branch,
+// not another instantiation); a workgroup past the length, or whose soup expired, leaves before its first barrier.
+// Thread 0 gathers the records in LDS, GOL_ISLAND_TALLY_BUFFER of them; wave 0, in which thread 0 runs, inserts a full
+// buffer, and the remainder at the board's end, one lane per record, the equal hashes of a buffer merged first so that
+// one lane inserts for all of them (tally_flush; DESIGN.md 4.24 has what that bought): a probe from the kind's home
+// slot with a 64-bit compare-and-swap on the tag where it reads 0, an atomic add on the count, an atomic minimum on
+// the first owner and on the packed shape only where a load shows the new value is lower.  Every field is a
+// commutative reduction, so no workgroup waits for another and the table's contents do not depend on the order; a
+// full table is counted in `dropped`.  The buffer is wave 0's alone and an insertion holds no barrier, so the barriers
+// are those of the plain form.
+//
+// This unit holds the kernel, the dispatch over its twenty instantiations, the kernel that empties a table, and its
+// entries: golk_batch_islands, which launches what a gol_island_launch describes once gol_island_launch_ok accepts it,
+// and golk_island_table_clear.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <algorithm>
 
 #include "gol_device.h"
 #include "gol_island.h"
@@ -44,6 +61,13 @@ struct IslandArgs {
     int64_t *count;
     gol_island *islands;
     uint64_t *fingerprint;
+    // TALLY
+    gol_island_slot *table;
+    int32_t log2;
+    unsigned long long *dropped;
+    int64_t owner0, n;
+    const int32_t *pairs, *pair_count;
+    const int64_t *found;
 };
 
 constexpr uint32_t NO_SEED = ~0u;
@@ -66,7 +90,47 @@ __device__ __forceinline__ void posted_row(const uint32_t (&edge)[GOL_BATCH_MAX_
     for (int j = 0; j < NW; ++j) t[j] = edge[ww][slot][j];
 }
 
-template <int NW, int REACH>
+// `add` islands of one kind and one owner, `shape` their smallest, into the table (a lane of wave 0; the others run
+// beside it or are masked off).
+__device__ __forceinline__ void tally_insert(const IslandArgs &a, uint64_t hash, uint64_t shape, uint64_t owner, uint64_t add)
+{
+    typedef unsigned long long u64;
+    const uint64_t tag = gol_island_tally_tag(hash), slots = (uint64_t)1 << a.log2;
+    uint64_t at = gol_island_tally_home(tag, a.log2);
+    for (uint64_t tries = 0; tries < slots; ++tries, at = gol_island_tally_next(at, a.log2)) {
+        gol_island_slot *p = a.table + at;
+        uint64_t seen = __hip_atomic_load(&p->hash, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (seen == 0) seen = atomicCAS((u64 *)&p->hash, (u64)0, (u64)tag);  // (the value before: 0 where this lane claimed it)
+        if (seen != 0 && seen != tag) continue;
+        atomicAdd((u64 *)&p->count, (u64)add);
+        if (__hip_atomic_load(&p->first, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > owner) atomicMin((u64 *)&p->first, (u64)owner);
+        if (__hip_atomic_load(&p->shape, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > shape) atomicMin((u64 *)&p->shape, (u64)shape);
+        return;
+    }
+    atomicAdd(a.dropped, (u64)add);  // every slot holds another kind
+}
+
+// The n gathered records into the table, lane l < n holding record l (all of wave 0; n is uniform).  Equal hashes are
+// merged first: every lane counts its hash among the n and takes their smallest shape (broadcast reads of LDS), and
+// the first lane of a kind inserts for all of them.  A board's commonest kinds come several to a buffer, and every
+// atomic on a kind goes to one slot's cache line, whatever the workgroup: the merge takes that many off it.
+__device__ __forceinline__ void tally_flush(const IslandArgs &a, const uint64_t (*kept)[2], int lane, int n, uint64_t owner)
+{
+    const bool on = lane < n;
+    const uint64_t hash = kept[on ? lane : 0][0];
+    uint64_t shape = kept[on ? lane : 0][1], same = 0;
+    bool leader = on;
+    for (int j = 0; j < n; ++j) {
+        const uint64_t h = kept[j][0], s = kept[j][1];
+        if (h != hash) continue;
+        same += 1;
+        shape = min(shape, s);
+        leader = leader && j >= lane;
+    }
+    if (leader) tally_insert(a, hash, shape, owner, same);
+}
+
+template <int NW, int REACH, bool TALLY>
 __global__ __launch_bounds__(512) void batch_islands_kernel(const IslandArgs a)
 {
     // [buffer][wave][lane 0, lane 1, the last lane but one, the last lane][word]
@@ -78,8 +142,29 @@ __global__ __launch_bounds__(512) void batch_islands_kernel(const IslandArgs a)
     __shared__ uint64_t part_hash[2][GOL_BATCH_MAX_WAVES];
     __shared__ uint64_t fingerprint;  // the sum of the records' hashes so far
 
+    uint64_t(*kept)[2] = nullptr;  // TALLY: the records gathered for wave 0, hash and packed shape
+    if constexpr (TALLY) {
+        __shared__ uint64_t kept_records[GOL_ISLAND_TALLY_BUFFER][2];
+        kept = kept_records;
+    }
+
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t board = blockIdx.x;
+    int64_t board = blockIdx.x, out = blockIdx.x;  // the board read, and the place of its count and fingerprint
+    if constexpr (TALLY) {
+        if (a.pairs) {  // (uniform: every exit below is the whole workgroup's, before its first barrier)
+            if ((int64_t)blockIdx.x >= (int64_t)*a.pair_count) return;
+            const int32_t slot = a.pairs[2 * blockIdx.x], soup = a.pairs[2 * blockIdx.x + 1];
+            if (slot < 0 || slot >= a.n || soup < 0) return;
+            if (a.found[soup] < 0) {  // expired: the slot holds no s(found)
+                if (threadIdx.x == 0) {
+                    a.count[soup] = 0;
+                    if (a.fingerprint) a.fingerprint[soup] = 0;
+                }
+                return;
+            }
+            board = slot, out = soup;
+        }
+    }
     const int H = a.H;
     const int y = wave * 64 + lane;
     const int last = min(63, H - 1 - wave * 64);  // the wave's last lane with a row (>= 0)
@@ -264,23 +349,52 @@ __global__ __launch_bounds__(512) void batch_islands_kernel(const IslandArgs a)
             r.rows = (uint16_t)nrows;
             r.cols = (uint16_t)ncols;
             fingerprint += r.hash;
-            if (k < a.cap) a.islands[board * a.cap + k] = r;
+            if constexpr (TALLY) {
+                kept[k % GOL_ISLAND_TALLY_BUFFER][0] = r.hash;
+                kept[k % GOL_ISLAND_TALLY_BUFFER][1] = gol_island_shape_pack(r.cells, nrows, ncols);
+            } else {
+                if (k < a.cap) a.islands[board * a.cap + k] = r;
+            }
+        }
+        if constexpr (TALLY) {
+            if (wave == 0 && k % GOL_ISLAND_TALLY_BUFFER == GOL_ISLAND_TALLY_BUFFER - 1) {  // full: thread 0's writes, in this wave's order
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                tally_flush(a, kept, lane, GOL_ISLAND_TALLY_BUFFER, (uint64_t)(a.owner0 + out));
+            }
         }
         seed = lowest(par);
         par ^= 1;
         ++k;
     }
-    if (threadIdx.x == 0) {
-        a.count[board] = over ? -1 : k;
-        if (a.fingerprint) a.fingerprint[board] = fingerprint;
+    if constexpr (TALLY) {
+        if (wave == 0 && !over) {  // the remainder
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            tally_flush(a, kept, lane, k % GOL_ISLAND_TALLY_BUFFER, (uint64_t)(a.owner0 + out));
+        }
     }
+    if (threadIdx.x == 0) {
+        a.count[out] = over ? -1 : k;
+        if (a.fingerprint) a.fingerprint[out] = fingerprint;
+    }
+}
+
+__global__ __launch_bounds__(256) void island_table_clear_kernel(gol_island_slot *table, int64_t slots, unsigned long long *dropped)
+{
+    const gol_island_slot empty = GOL_ISLAND_SLOT_EMPTY;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < slots; i += (int64_t)gridDim.x * 256) table[i] = empty;
+    if (blockIdx.x == 0 && threadIdx.x == 0) *dropped = 0;
 }
 
 template <int NW>
 hipError_t launch(int reach, const IslandArgs &a, dim3 grid, dim3 block, hipStream_t s)
 {
-    if (reach == 1) batch_islands_kernel<NW, 1><<<grid, block, 0, s>>>(a);
-    else batch_islands_kernel<NW, 2><<<grid, block, 0, s>>>(a);
+    if (a.table) {
+        if (reach == 1) batch_islands_kernel<NW, 1, true><<<grid, block, 0, s>>>(a);
+        else batch_islands_kernel<NW, 2, true><<<grid, block, 0, s>>>(a);
+    } else {
+        if (reach == 1) batch_islands_kernel<NW, 1, false><<<grid, block, 0, s>>>(a);
+        else batch_islands_kernel<NW, 2, false><<<grid, block, 0, s>>>(a);
+    }
     return hipGetLastError();
 }
 
@@ -292,8 +406,9 @@ hipError_t golk_batch_islands(const gol_island_launch &l, hipStream_t s)
     const gol_batch_row g = gol_batch_row_init(l.W);
     const int wpb = (int)((l.H + 63) / 64);
     const IslandArgs a = {l.boards, g, (int32_t)l.H, (int32_t)l.W, (int32_t)((l.W + 63) / 64), wpb, l.cap, l.count, l.islands,
-                          l.fingerprint};
-    const dim3 grid((unsigned)l.n), block((unsigned)(wpb * 64));
+                          l.fingerprint, (gol_island_slot *)l.table, l.table_log2, (unsigned long long *)l.dropped, l.owner0, l.n,
+                          l.pairs, l.pair_count, l.found};
+    const dim3 grid((unsigned)(l.pairs ? l.max_pairs : l.n)), block((unsigned)(wpb * 64));
     switch (g.nw) {
     case 1: return launch<1>(l.reach, a, grid, block, s);
     case 2: return launch<2>(l.reach, a, grid, block, s);
@@ -301,4 +416,14 @@ hipError_t golk_batch_islands(const gol_island_launch &l, hipStream_t s)
     case 8: return launch<8>(l.reach, a, grid, block, s);
     default: return launch<16>(l.reach, a, grid, block, s);
     }
+}
+
+hipError_t golk_island_table_clear(gol_island_kind *table, int32_t table_log2, int64_t *dropped, hipStream_t s)
+{
+    if (!table || !dropped || table_log2 < GOL_ISLAND_TALLY_MIN_LOG2 || table_log2 > GOL_ISLAND_TALLY_MAX_LOG2)
+        return hipErrorInvalidValue;
+    const int64_t slots = (int64_t)1 << table_log2;
+    island_table_clear_kernel<<<(unsigned)std::min<int64_t>((slots + 255) / 256, 4096), 256, 0, s>>>((gol_island_slot *)table, slots,
+                                                                                                  (unsigned long long *)dropped);
+    return hipGetLastError();
 }

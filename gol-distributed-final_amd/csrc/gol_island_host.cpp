@@ -3,8 +3,10 @@
 // instantiation the kernel picks for the width and the reach, row by row as the lanes do; and
 // gol_batch_islands_check_host: the check every launch of the kernel passes (gol_island_launch_ok).  The flood visits
 // only the rows round the island so far (the rows a step can change lie within `reach` of them), which is what keeps a
-// large sparse board cheap; the rest is the kernel's scheme.  No HIP header: a stand-alone program links this file
-// alone (island_check.cpp).
+// large sparse board cheap; the rest is the kernel's scheme.  And the tally of island kinds: gol_island_tally_host, the
+// definition by a sort and a merge, gol_island_tally_home_host and gol_batch_islands_tally_check_host, the table's home
+// function and the check of a TALLY launch.  No HIP header: a stand-alone program links this file alone
+// (island_check.cpp).
 #include <stdint.h>
 
 #include <algorithm>
@@ -140,4 +142,57 @@ extern "C" int gol_batch_islands_check_host(const uint64_t *boards, int64_t n, i
     const gol_island_launch l = {boards, n, H, W, reach, cap, const_cast<int64_t *>(count), const_cast<gol_island *>(islands),
                                  const_cast<uint64_t *>(fingerprint)};
     return gol_island_launch_ok(l) ? GOL_OK : GOL_EINVAL;
+}
+
+extern "C" int gol_island_tally_host(const gol_island *records, const int64_t *owners, int64_t n, gol_island_kind *kinds,
+                                     int64_t kinds_cap, int64_t *n_kinds)
+{
+    if (n < 0 || (n > 0 && (!records || !owners)) || kinds_cap < 0 || !n_kinds || (kinds_cap > 0 && !kinds))
+        return gol_set_error(GOL_EINVAL, "bad host island tally (%lld records, kinds_cap %lld, or NULL)", (long long)n,
+                             (long long)kinds_cap);
+    std::vector<gol_island_kind> all;
+    try {
+        all.reserve((size_t)n);
+        for (int64_t i = 0; i < n; ++i)
+            all.push_back({gol_island_tally_tag(records[i].hash), 1, owners[i], records[i].cells, records[i].rows, records[i].cols});
+    } catch (const std::exception &) {
+        return gol_set_error(GOL_ENOMEM, "host island tally: %lld records", (long long)n);
+    }
+    std::sort(all.begin(), all.end(), [](const gol_island_kind &a, const gol_island_kind &b) { return a.hash < b.hash; });
+    size_t kept = 0;  // the merge, in place: all[0 .. kept) the kinds so far
+    for (size_t i = 0; i < all.size(); ++i) {
+        if (kept == 0 || all[kept - 1].hash != all[i].hash) {
+            all[kept++] = all[i];
+            continue;
+        }
+        gol_island_kind &k = all[kept - 1];
+        k.count += 1;
+        k.first = std::min(k.first, all[i].first);
+        if (gol_island_shape_pack(all[i].cells, all[i].rows, all[i].cols) < gol_island_shape_pack(k.cells, k.rows, k.cols))
+            k.cells = all[i].cells, k.rows = all[i].rows, k.cols = all[i].cols;
+    }
+    all.resize(kept);
+    std::sort(all.begin(), all.end(), gol_island_kind_before);
+    for (size_t i = 0; i < kept && (int64_t)i < kinds_cap; ++i) kinds[i] = all[i];
+    *n_kinds = (int64_t)kept;
+    return GOL_OK;
+}
+
+extern "C" int64_t gol_island_tally_home_host(uint64_t hash, int32_t table_log2)
+{
+    if (table_log2 < GOL_ISLAND_TALLY_MIN_LOG2 || table_log2 > GOL_ISLAND_TALLY_MAX_LOG2) return -1;
+    return (int64_t)gol_island_tally_home(gol_island_tally_tag(hash), table_log2);
+}
+
+extern "C" int gol_batch_islands_tally_check_host(const uint64_t *boards, int64_t n, int64_t H, int64_t W, int32_t reach,
+                                                  const int32_t *pairs, const int32_t *pair_count, int64_t max_pairs,
+                                                  const int64_t *found, int64_t owner0, const int64_t *count,
+                                                  const uint64_t *fingerprint, const gol_island_kind *table, int32_t table_log2,
+                                                  const int64_t *dropped)
+{
+    // (the check reads the pointers' values alone; a NULL table is the plain launch, which this entry does not make)
+    const gol_island_launch l = {boards, n, H, W, reach, 0, const_cast<int64_t *>(count), nullptr, const_cast<uint64_t *>(fingerprint),
+                                 const_cast<gol_island_kind *>(table), table_log2, const_cast<int64_t *>(dropped), owner0, pairs,
+                                 pair_count, max_pairs, found};
+    return table && gol_island_launch_ok(l) ? GOL_OK : GOL_EINVAL;
 }

@@ -123,6 +123,9 @@ hipError_t golk_batch_step(const gol_batch_launch &launch, hipStream_t s);
 // gol_dev_batch_islands, include/golhip.h).  hipErrorInvalidValue, nothing launched, unless gol_island_launch_ok accepts it.
 struct gol_island_launch;
 hipError_t golk_batch_islands(const gol_island_launch &launch, hipStream_t s);
+// Every slot of a kind table of 2^table_log2 slots empty, *dropped = 0 (gol_dev_island_table_clear).
+struct gol_island_kind;
+hipError_t golk_island_table_clear(gol_island_kind *table, int32_t table_log2, int64_t *dropped, hipStream_t s);
 // The small kernels (gol_batch_pass.hip).
 // list[i] = i for i < n, counts = {n, 0}
 hipError_t golk_batch_iota(int32_t *list, int32_t *counts, int64_t n, hipStream_t s);

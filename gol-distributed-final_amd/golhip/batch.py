@@ -14,10 +14,12 @@ import ctypes
 
 import numpy as np
 
-from ._lib import GOL_EINVAL, GolError, format_rule, lib, parse_rle, parse_rule
+from ._lib import GOL_EINVAL, GOL_ENOMEM, GolError, format_rule, lib, parse_rle, parse_rule
 
 # gol_island (include/golhip.h): the record of an island, 24 bytes
 ISLAND_DTYPE = np.dtype([("y", "<i4"), ("x", "<i4"), ("cells", "<i4"), ("rows", "<u2"), ("cols", "<u2"), ("hash", "<u8")])
+# gol_island_kind (include/golhip.h): one kind of a tally, 32 bytes
+ISLAND_KIND_DTYPE = np.dtype([("hash", "<u8"), ("count", "<i8"), ("first", "<i8"), ("cells", "<i4"), ("rows", "<u2"), ("cols", "<u2")])
 
 
 def island(pattern, reach: int = 1, library=None):
@@ -181,6 +183,34 @@ class Batch:
         d["occupancy"] = d["board_turns"] / d["full_turns"] if d["full_turns"] else 0.0
         return found, period, alive, hashes, d
 
+    def census(self, seed: int, total: int, horizon: int, first: int = 0, reach: int = 1, kinds: int = 4096,
+               stats: bool = False) -> dict:
+        """search() with the island census of every soup's state at `found` taken inside the search, and the tally
+        of the kinds of island the soups turned into, built on the GPU: nothing per island comes back.  Returns a
+        dict: found, period, alive, hash as search() returns them; islands (int64) and fingerprint (uint64), the
+        island count and fingerprint of each soup's state at `found` at `reach` (0, 0 for a soup not found);
+        n_kinds, the number of distinct kinds (a kind is an island's hash); kinds, a structured array of
+        ISLAND_KIND_DTYPE with the first min(n_kinds, kinds) of them, ordered by count descending, then hash: per
+        kind its hash, count, first (the lowest soup number that holds one: Batch.soup re-makes it) and the
+        smallest (cells, rows, cols) among its islands; with stats=True also stats, the dict of search().
+        GolError(GOL_ENOMEM) when the kind table that `kinds` sizes (at least 1024 slots) is full."""
+        m, cap = max(int(total), 0), max(int(kinds), 0)
+        out = {"found": np.full(m, -1, dtype=np.int64), "period": np.full(m, -1, dtype=np.int64),
+               "alive": np.zeros(m, dtype=np.uint64), "hash": np.zeros(m, dtype=np.uint64),
+               "islands": np.zeros(m, dtype=np.int64), "fingerprint": np.zeros(m, dtype=np.uint64)}
+        table = np.zeros(cap, dtype=ISLAND_KIND_DTYPE)
+        n_kinds, st = ctypes.c_int64(), (ctypes.c_int64 * 5)()
+        self._check(self._L.gol_batch_census(self._h, seed, first, total, horizon, reach, *[a.ctypes.data for a in out.values()],
+                                             table.ctypes.data if kinds > 0 else None, kinds, ctypes.byref(n_kinds),
+                                             ctypes.addressof(st) if stats else None))
+        out["n_kinds"] = n_kinds.value
+        out["kinds"] = table[:min(n_kinds.value, cap)]
+        if stats:
+            d = dict(zip(("launches", "slots", "launch_turns", "board_turns", "full_turns"), (int(v) for v in st)))
+            d["occupancy"] = d["board_turns"] / d["full_turns"] if d["full_turns"] else 0.0
+            out["stats"] = d
+        return out
+
     # -- the rule
     def set_rule(self, rule) -> None:
         """The rule of every later turn: "B36/S23" or a (birth, survive) pair of 9-bit masks.  The
@@ -299,6 +329,27 @@ class Batch:
                                               recs.ctypes.data if cap > 0 else None,
                                               fps.ctypes.data if fingerprints else None))
         return (counts, recs, fps) if fingerprints else (counts, recs)
+
+    def islands_tally(self, reach: int = 1, kinds: int = 4096, first: int = 0, count: int | None = None):
+        """The tally of the island kinds of boards [first, first + count) as they stand (default: all from `first`),
+        built on the GPU; boards, turn and rules stay.  Returns (counts, fingerprints, kinds): per board the number
+        of islands (int64) and the fingerprint (uint64) as islands() gives them, and the kinds as census() returns
+        them, all of them up to `kinds`, `first` being the lowest board index that holds one.  When the kind table
+        is full GolError(GOL_ENOMEM) is raised; its `counts` and `fingerprints` attributes hold the per-board
+        outputs, which are right."""
+        count = self.n - first if count is None else count
+        m, cap = max(int(count), 0), max(int(kinds), 0)
+        counts, fps = np.zeros(m, dtype=np.int64), np.zeros(m, dtype=np.uint64)
+        table = np.zeros(cap, dtype=ISLAND_KIND_DTYPE)
+        n_kinds = ctypes.c_int64()
+        rc = self._L.gol_batch_islands_tally(self._h, first, first + count, reach, counts.ctypes.data, fps.ctypes.data,
+                                             table.ctypes.data if kinds > 0 else None, kinds, ctypes.byref(n_kinds))
+        if rc == GOL_ENOMEM:
+            e = GolError(rc, self._L.gol_last_error().decode(errors="replace"))
+            e.counts, e.fingerprints = counts, fps
+            raise e
+        self._check(rc)
+        return counts, fps, table[:min(n_kinds.value, cap)]
 
     def info(self) -> dict:
         n, H, W = (ctypes.c_int64() for _ in range(3))

@@ -793,6 +793,99 @@ int gol_batch_islands_host(int64_t H, int64_t W, int32_t reach, const uint64_t *
                            int64_t *count, gol_island *islands, uint64_t *fingerprint);
 int gol_batch_islands_check_host(const uint64_t *boards, int64_t n, int64_t H, int64_t W, int32_t reach, int64_t cap,
                                  const int64_t *count, const gol_island *islands, const uint64_t *fingerprint);
+/* The tally of island kinds: what a census of many boards adds up to, built on
+ * the GPU so that nothing per island crosses the bus (the kernel is the TALLY
+ * form of csrc/gol_island.hip).  No version bump: probe by symbol.
+ *  - Kind of an island: its hash, as gol_island.hash is defined above.  Islands
+ *    with equal hash nearly always have equal shape, but different islands
+ *    with the same multiset of window codes exist: they count as one kind.
+ *  - Tally over a set of (owner, island) pairs, an owner being a soup number or
+ *    a board index: one gol_island_kind (32 bytes) per distinct kind, with
+ *    count the islands of the kind, first the lowest owner that holds one, and
+ *    (cells, rows, cols) the smallest such triple, compared in that order,
+ *    among the kind's islands.  Every field is an order-independent reduction
+ *    (a sum, a minimum, a minimum of cells << 32 | rows << 16 | cols), so the
+ *    tally is a function of the set of pairs alone.
+ *  - Order of a tally: count descending, then hash ascending.
+ *  - Device table: an open-addressing array of 2^log2 slots of 32 bytes, 4 <=
+ *    log2 <= 24.  A slot is four 64-bit words: hash (the tag, claimed by a
+ *    compare-and-swap from 0), count, first, and the shape packed as cells << 32
+ *    | rows << 16 | cols in one word (so its minimum is one 64-bit atomic; a
+ *    gol_island_kind has the same bytes but for this word, which
+ *    gol_batch_census and gol_batch_islands_tally unpack on the host).  An
+ *    empty slot is {0, 0, INT64_MAX, all ones}.  An island whose hash is 0 is
+ *    tallied under hash 1 (one hash in 2^64; no field is spent on it).  An
+ *    island's home slot is gol_island_tally_home_host(hash, log2) < 2^log2 and
+ *    a probe goes on to the next slot, round the table.  Which slot a kind
+ *    ends in depends on the order of insertion: no public output depends on
+ *    it, every one is sorted on the host after one read-back.
+ *  - Full table: an island whose probe has visited all 2^log2 slots without
+ *    finding its kind or an empty slot is not tallied, and the device counter
+ *    `dropped` grows by one.
+ *
+ * gol_batch_census: gol_batch_search (above) with the census of every soup's
+ * s(found) taken inside the search's harvest, one more launch per round over
+ * the same harvest list.  found, period, alive, hash and stats are exactly those
+ * of gol_batch_search for the same arguments (period, alive, hash, islands,
+ * fingerprint and stats may each be NULL).  islands[g - first] and fingerprint[g
+ * - first] are the island count and the fingerprint of s(found) at `reach`, 0
+ * and 0 for a soup not found.  The tally is over the pairs (g, island of
+ * s(found) of soup g): *n_kinds is the number of distinct kinds, and `kinds`
+ * receives the first min(*n_kinds, kinds_cap) of them in the tally's order;
+ * `first` holds the soup number g (first included), so gol_batch_soup_host
+ * re-makes an example.  Nothing depends on the number of slots, on
+ * turns_per_launch or on which slot a soup ran in.  The kind table lives in
+ * the handle: the smallest power of two >= 2 max(kinds_cap, 512) slots, at most
+ * 2^24.  `dropped` is read once, at the end: if it is not 0 the call returns
+ * GOL_ENOMEM with a message naming kinds_cap, the per-soup outputs written and
+ * valid, `kinds` untouched and *n_kinds = -1.  Refused before any GPU work, the
+ * batch and the outputs untouched: as gol_batch_search, and GOL_EINVAL for
+ * reach outside 1..2, kinds_cap < 0 or > 2^23, a NULL n_kinds, kinds_cap > 0 with
+ * NULL kinds.
+ * gol_batch_islands_tally: the tally of boards [i0, i1) as they stand, owner =
+ * the board's index: count[i - i0] and fingerprint[i - i0] (may be NULL) as
+ * gol_batch_islands gives them, kinds, kinds_cap, *n_kinds, the table's size and
+ * GOL_ENOMEM as for gol_batch_census.  The range is cut into chunks by the rule
+ * of gol_batch_islands; no record is kept on the device.  The boards, the turn
+ * and the rules stay.  GOL_EINVAL as gol_batch_islands and as above.
+ * gol_island_tally_host: the definition on host memory (a host function, no
+ * GPU needed): the tally of the pairs (owners[i], records[i]), i < n, by a sort
+ * and a merge; outputs as above.  GOL_EINVAL: n < 0, NULL records or owners
+ * with n > 0, kinds_cap < 0, NULL n_kinds, kinds_cap > 0 with NULL kinds.
+ * gol_batch_census_host: gol_batch_search_host, gol_batch_islands_host on every
+ * soup's s(found) and gol_island_tally_host (a host function); arguments,
+ * outputs and refusals as those three (no table, so no GOL_ENOMEM for a small
+ * kinds_cap).
+ * gol_island_tally_home_host: the home slot of a hash in a table of 2^log2
+ * slots (the function of csrc/gol_island.h the kernel runs); -1 for log2
+ * outside 4..24.
+ * gol_batch_islands_tally_check_host: the argument check of
+ * gol_dev_batch_islands_tally (below; a host function), its arguments without
+ * the stream: GOL_OK where that call would launch, GOL_EINVAL where it refuses;
+ * reads no memory. */
+typedef struct gol_island_kind {
+    uint64_t hash;       /* the kind */
+    int64_t count;       /* islands of this kind */
+    int64_t first;       /* the lowest owner (soup number, or board index) that holds one */
+    int32_t cells;       /* the smallest (cells, rows, cols), compared in that order, among them */
+    uint16_t rows, cols;
+} gol_island_kind;
+int gol_batch_census(gol_batch *b, uint64_t seed, int64_t first, int64_t total, int64_t horizon, int32_t reach, int64_t *found,
+                     int64_t *period, uint64_t *alive, uint64_t *hash, int64_t *islands, uint64_t *fingerprint,
+                     gol_island_kind *kinds, int64_t kinds_cap, int64_t *n_kinds, gol_batch_search_stats *stats);
+int gol_batch_islands_tally(gol_batch *b, int64_t i0, int64_t i1, int32_t reach, int64_t *count, uint64_t *fingerprint,
+                            gol_island_kind *kinds, int64_t kinds_cap, int64_t *n_kinds);
+int gol_island_tally_host(const gol_island *records, const int64_t *owners, int64_t n, gol_island_kind *kinds, int64_t kinds_cap,
+                          int64_t *n_kinds);
+int gol_batch_census_host(int64_t H, int64_t W, uint32_t birth, uint32_t survive, uint64_t seed, int64_t first, int64_t total,
+                          int64_t slots, int64_t launch, int64_t horizon, int32_t reach, int64_t *found, int64_t *period,
+                          uint64_t *alive, uint64_t *hash, int64_t *islands, uint64_t *fingerprint, gol_island_kind *kinds,
+                          int64_t kinds_cap, int64_t *n_kinds);
+int64_t gol_island_tally_home_host(uint64_t hash, int32_t table_log2);
+int gol_batch_islands_tally_check_host(const uint64_t *boards, int64_t n, int64_t H, int64_t W, int32_t reach, const int32_t *pairs,
+                                       const int32_t *pair_count, int64_t max_pairs, const int64_t *found, int64_t owner0,
+                                       const int64_t *count, const uint64_t *fingerprint, const gol_island_kind *table,
+                                       int32_t table_log2, const int64_t *dropped);
 /* The argument check of the step launches (a host function, no GPU needed; the
  * function of csrc/gol_step_launch.h that every launch of a step kernel passes,
  * from gol_dev_bits_step, _band_step(_on), _rule_step, _bytes_step_k(_on) and from
@@ -1158,6 +1251,34 @@ int gol_dev_batch_step(uint64_t *boards, uint64_t *prev, int64_t *settled, int64
  * 0, or cap > 0 with NULL islands.  No version bump: probe by symbol. */
 int gol_dev_batch_islands(const uint64_t *boards, int64_t n, int64_t H, int64_t W, int32_t reach, int64_t cap, int64_t *count,
                           gol_island *islands, uint64_t *fingerprint, void *stream);
+/* One launch of the census in its TALLY form (the tally of island kinds, above)
+ * on caller device memory: every island of the boards it visits goes into
+ * `table` (2^table_log2 slots in the device layout, 4 <= table_log2 <= 24) under
+ * its owner, and *dropped counts those a full table turned away.  The call adds
+ * to the table and to *dropped; it clears neither (gol_dev_island_table_clear
+ * sets a table to empty and *dropped to 0).  No record array is written.
+ *  - pairs == NULL (pair_count, found NULL, max_pairs 0): dense.  Board i of n
+ *    has the owner owner0 + i; count[i] and fingerprint[i] are written.
+ *  - otherwise: listed.  pairs is the harvest list of gol_dev_batch_restock,
+ *    (slot, soup) pairs, its length *pair_count in device memory; max_pairs (1 ..
+ *    n) workgroups run and the first min(*pair_count, max_pairs) of them work.
+ *    The board is slot `slot` of `boards` (the search's snapshots, which hold
+ *    s(found)), the owner owner0 + soup, and count[soup], fingerprint[soup] are
+ *    written.  A pair whose found[soup] < 0 (the soup expired) gets 0 and 0, its
+ *    board is not read and nothing of it is tallied; a pair with a slot
+ *    outside 0 .. n - 1 or a soup < 0 is passed over.  Entries of count and
+ *    fingerprint that no pair names are not written.
+ * fingerprint may be NULL.  Not checked: that the pointers are device memory
+ * of the stated sizes (count, fingerprint and found hold every soup listed).
+ * GOL_EINVAL, nothing launched: NULL boards, count, table or dropped, n, H, W out
+ * of range, reach outside 1..2, table_log2 outside 4..24, owner0 outside 0..2^40,
+ * a combination that is neither mode, max_pairs outside 1..n with pairs.  No
+ * version bump: probe by symbol. */
+int gol_dev_batch_islands_tally(const uint64_t *boards, int64_t n, int64_t H, int64_t W, int32_t reach, const int32_t *pairs,
+                                const int32_t *pair_count, int64_t max_pairs, const int64_t *found, int64_t owner0,
+                                int64_t *count, uint64_t *fingerprint, gol_island_kind *table, int32_t table_log2,
+                                int64_t *dropped, void *stream);
+int gol_dev_island_table_clear(gol_island_kind *table, int32_t table_log2, int64_t *dropped, void *stream);
 /* Read and clear the error word of `device` (-1 = current) that the gol_dev_*
  * launchers' kernels report into (*flags = 0: no fault; nonzero: a pipeline
  * wave timed out waiting for its neighbour, so the launch's output is not
