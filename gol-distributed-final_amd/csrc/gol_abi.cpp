@@ -293,15 +293,41 @@ extern "C" int gol_dev_batch_step(uint64_t *boards, uint64_t *prev, int64_t *set
     return GOL_OK;
 }
 
+extern "C" int gol_dev_batch_islands_sym(const uint64_t *boards, int64_t n, int64_t H, int64_t W, int32_t reach, int32_t symmetry,
+                                         int64_t cap, int64_t *count, gol_island *islands, uint64_t *fingerprint, void *stream)
+{
+    const gol_island_launch l = {boards, n, H, W, reach, symmetry, cap, count, islands, fingerprint};
+    const hipError_t e = golk_batch_islands(l, (hipStream_t)stream);
+    if (e == hipErrorInvalidValue)  // gol_island_launch_ok said no: nothing was launched
+        return gol_set_error(GOL_EINVAL,
+                             "bad batch_islands arguments (n %lld, %lld x %lld, reach %d, symmetry %d, cap %lld, or a pointer)",
+                             (long long)n, (long long)H, (long long)W, reach, symmetry, (long long)cap);
+    if (e != hipSuccess) return gol_set_error(GOL_EHIP, "batch_islands: %s", hipGetErrorString(e));
+    return GOL_OK;
+}
+
 extern "C" int gol_dev_batch_islands(const uint64_t *boards, int64_t n, int64_t H, int64_t W, int32_t reach, int64_t cap,
                                      int64_t *count, gol_island *islands, uint64_t *fingerprint, void *stream)
 {
-    const gol_island_launch l = {boards, n, H, W, reach, cap, count, islands, fingerprint};
-    const hipError_t e = golk_batch_islands(l, (hipStream_t)stream);
+    return gol_dev_batch_islands_sym(boards, n, H, W, reach, GOL_ISLAND_FIXED, cap, count, islands, fingerprint, stream);
+}
+
+extern "C" int gol_dev_batch_islands_tally_sym(const uint64_t *boards, int64_t n, int64_t H, int64_t W, int32_t reach,
+                                               int32_t symmetry, const int32_t *pairs, const int32_t *pair_count, int64_t max_pairs,
+                                               const int64_t *found, int64_t owner0, int64_t *count, uint64_t *fingerprint,
+                                               gol_island_kind *table, int32_t table_log2, int64_t *dropped, void *stream)
+{
+    const gol_island_launch l = {boards, n, H, W, reach, symmetry, 0, count, nullptr, fingerprint, table, table_log2, dropped, owner0,
+                                 pairs, pair_count, max_pairs, found};
+    // (a NULL table would be the plain launch, which is not this entry's)
+    const hipError_t e = table ? golk_batch_islands(l, (hipStream_t)stream) : hipErrorInvalidValue;
     if (e == hipErrorInvalidValue)  // gol_island_launch_ok said no: nothing was launched
-        return gol_set_error(GOL_EINVAL, "bad batch_islands arguments (n %lld, %lld x %lld, reach %d, cap %lld, or a pointer)",
-                             (long long)n, (long long)H, (long long)W, reach, (long long)cap);
-    if (e != hipSuccess) return gol_set_error(GOL_EHIP, "batch_islands: %s", hipGetErrorString(e));
+        return gol_set_error(GOL_EINVAL,
+                             "bad batch_islands_tally arguments (n %lld, %lld x %lld, reach %d, symmetry %d, table 2^%d, owner0 %lld, %lld "
+                             "pairs, or a pointer)",
+                             (long long)n, (long long)H, (long long)W, reach, symmetry, table_log2, (long long)owner0,
+                             (long long)max_pairs);
+    if (e != hipSuccess) return gol_set_error(GOL_EHIP, "batch_islands_tally: %s", hipGetErrorString(e));
     return GOL_OK;
 }
 
@@ -310,17 +336,8 @@ extern "C" int gol_dev_batch_islands_tally(const uint64_t *boards, int64_t n, in
                                            int64_t owner0, int64_t *count, uint64_t *fingerprint, gol_island_kind *table,
                                            int32_t table_log2, int64_t *dropped, void *stream)
 {
-    const gol_island_launch l = {boards, n, H, W, reach, 0, count, nullptr, fingerprint, table, table_log2, dropped, owner0, pairs,
-                                 pair_count, max_pairs, found};
-    // (a NULL table would be the plain launch, which is not this entry's)
-    const hipError_t e = table ? golk_batch_islands(l, (hipStream_t)stream) : hipErrorInvalidValue;
-    if (e == hipErrorInvalidValue)  // gol_island_launch_ok said no: nothing was launched
-        return gol_set_error(GOL_EINVAL,
-                             "bad batch_islands_tally arguments (n %lld, %lld x %lld, reach %d, table 2^%d, owner0 %lld, %lld pairs, or a "
-                             "pointer)",
-                             (long long)n, (long long)H, (long long)W, reach, table_log2, (long long)owner0, (long long)max_pairs);
-    if (e != hipSuccess) return gol_set_error(GOL_EHIP, "batch_islands_tally: %s", hipGetErrorString(e));
-    return GOL_OK;
+    return gol_dev_batch_islands_tally_sym(boards, n, H, W, reach, GOL_ISLAND_FIXED, pairs, pair_count, max_pairs, found, owner0, count,
+                                           fingerprint, table, table_log2, dropped, stream);
 }
 
 extern "C" int gol_dev_island_table_clear(gol_island_kind *table, int32_t table_log2, int64_t *dropped, void *stream)

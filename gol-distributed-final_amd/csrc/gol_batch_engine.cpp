@@ -226,21 +226,24 @@ int run_cycles(gol_batch *b, int64_t turns, int64_t *out, std::vector<int64_t> &
 
 // The kind table of one tally call: log2 from kinds_cap (the smallest power of two >= 2 max(kinds_cap, 512), at most 2^24).
 struct Tally {
-    int32_t reach = 1, log2 = 0;
+    int32_t reach = 1, symmetry = GOL_ISLAND_FIXED, log2 = 0;
     gol_island_kind *table = nullptr;
     int64_t *dropped = nullptr;
 };
 
-bool tally_args_ok(int32_t reach, const gol_island_kind *kinds, int64_t kinds_cap, const int64_t *n_kinds)
+bool symmetry_ok(int32_t symmetry) { return symmetry == GOL_ISLAND_FIXED || symmetry == GOL_ISLAND_FREE; }
+
+bool tally_args_ok(int32_t reach, int32_t symmetry, const gol_island_kind *kinds, int64_t kinds_cap, const int64_t *n_kinds)
 {
-    return reach >= 1 && reach <= GOL_ISLAND_MAX_REACH && kinds_cap >= 0 && kinds_cap <= ((int64_t)1 << 23) && n_kinds &&
+    return reach >= 1 && reach <= GOL_ISLAND_MAX_REACH && symmetry_ok(symmetry) && kinds_cap >= 0 && kinds_cap <= ((int64_t)1 << 23) && n_kinds &&
            (kinds_cap == 0 || kinds);
 }
 
 // The handle's table sized for kinds_cap and set to empty, `dropped` to 0.
-int tally_begin(gol_batch *b, int32_t reach, int64_t kinds_cap, Tally *t)
+int tally_begin(gol_batch *b, int32_t reach, int32_t symmetry, int64_t kinds_cap, Tally *t)
 {
     t->reach = reach;
+    t->symmetry = symmetry;
     t->log2 = 10;
     while (((int64_t)1 << t->log2) < 2 * kinds_cap) t->log2 += 1;
     const int64_t slots = (int64_t)1 << t->log2;
@@ -340,8 +343,8 @@ int search(gol_batch *b, uint64_t seed, int64_t first, int64_t total, int64_t ho
         HIPCHK(golk_batch_restock(active, counts, age, born, soup, n, done, horizon, total, tfound, tperiod, harvest, b->stream));
         HIPCHK(golk_batch_harvest(b->prev, harvest, counts, n, b->H, b->W, total, tfound, talive, thash, in, b->stream));
         if (tally) {
-            const gol_island_launch il = {b->prev, n, b->H, b->W, tally->reach, 0, tislands, nullptr, tfp, tally->table, tally->log2,
-                                          tally->dropped, first, harvest, counts + 1, in, tfound};
+            const gol_island_launch il = {b->prev, n, b->H, b->W, tally->reach, tally->symmetry, 0, tislands, nullptr, tfp, tally->table,
+                                          tally->log2, tally->dropped, first, harvest, counts + 1, in, tfound};
             HIPCHK(golk_batch_islands(il, b->stream));
         }
         HIPCHK(golk_batch_refill(b->boards, harvest, counts, soup, n, b->H, b->W, seed, first, total, in, b->stream));
@@ -366,17 +369,17 @@ int search(gol_batch *b, uint64_t seed, int64_t first, int64_t total, int64_t ho
 
 // gol_batch_search and gol_batch_census (tally_kinds: its kinds_cap, n_kinds and kinds; census == false: none).
 int search_call(gol_batch *b, uint64_t seed, int64_t first, int64_t total, int64_t horizon, int64_t *found, int64_t *period,
-                uint64_t *alive, uint64_t *hash, gol_batch_search_stats *stats, bool census, int32_t reach, int64_t *islands,
-                uint64_t *fingerprint, gol_island_kind *kinds, int64_t kinds_cap, int64_t *n_kinds)
+                uint64_t *alive, uint64_t *hash, gol_batch_search_stats *stats, bool census, int32_t reach, int32_t symmetry,
+                int64_t *islands, uint64_t *fingerprint, gol_island_kind *kinds, int64_t kinds_cap, int64_t *n_kinds)
 {
     const char *what = census ? "census" : "search";
     if (!b || !found || first < 0 || total < 0 || horizon < 0 || first > ((int64_t)1 << 40) || total > ((int64_t)1 << 26) ||
         first + total > ((int64_t)1 << 40))
         return gol_set_error(GOL_EINVAL, "bad batch %s (soups [%lld, +%lld) in 0..2^40, at most 2^26, horizon %lld, or NULL)", what,
                              (long long)first, (long long)total, (long long)horizon);
-    if (census && !tally_args_ok(reach, kinds, kinds_cap, n_kinds))
-        return gol_set_error(GOL_EINVAL, "bad batch census (reach %d in 1..2, kinds_cap %lld in 0..2^23, or NULL)", reach,
-                             (long long)kinds_cap);
+    if (census && !tally_args_ok(reach, symmetry, kinds, kinds_cap, n_kinds))
+        return gol_set_error(GOL_EINVAL, "bad batch census (reach %d in 1..2, symmetry %d in 0..1, kinds_cap %lld in 0..2^23, or NULL)",
+                             reach, symmetry, (long long)kinds_cap);
     if (!b->rules.empty()) return gol_set_error(GOL_ESTATE, "batch %s: the boards of the batch have different rules", what);
     OnDevice dev(b->device);
     HIPCHK(dev.err);
@@ -390,7 +393,7 @@ int search_call(gol_batch *b, uint64_t seed, int64_t first, int64_t total, int64
     Tally tally;
     int tallied = GOL_OK;  // (a full table: the per-soup outputs stand, the call ends as after a search, and then says so)
     if (total > 0 && horizon > 0) {
-        int rc = census ? tally_begin(b, reach, kinds_cap, &tally) : GOL_OK;
+        int rc = census ? tally_begin(b, reach, symmetry, kinds_cap, &tally) : GOL_OK;
         if (!rc) rc = search(b, seed, first, total, horizon, found, period, alive, hash, &st, census ? &tally : nullptr, islands, fingerprint);
         if (rc) return rc;
         if (census) tallied = tally_end(b, tally, what, kinds, kinds_cap, n_kinds);
@@ -620,8 +623,17 @@ extern "C" int gol_batch_load_soups(gol_batch *b, uint64_t seed, int64_t first)
 extern "C" int gol_batch_search(gol_batch *b, uint64_t seed, int64_t first, int64_t total, int64_t horizon, int64_t *found,
                                 int64_t *period, uint64_t *alive, uint64_t *hash, gol_batch_search_stats *stats)
 {
-    return search_call(b, seed, first, total, horizon, found, period, alive, hash, stats, false, 0, nullptr, nullptr, nullptr, 0,
+    return search_call(b, seed, first, total, horizon, found, period, alive, hash, stats, false, 0, 0, nullptr, nullptr, nullptr, 0,
                        nullptr);
+}
+
+extern "C" int gol_batch_census_sym(gol_batch *b, uint64_t seed, int64_t first, int64_t total, int64_t horizon, int32_t reach,
+                                    int32_t symmetry, int64_t *found, int64_t *period, uint64_t *alive, uint64_t *hash,
+                                    int64_t *islands, uint64_t *fingerprint, gol_island_kind *kinds, int64_t kinds_cap,
+                                    int64_t *n_kinds, gol_batch_search_stats *stats)
+{
+    return search_call(b, seed, first, total, horizon, found, period, alive, hash, stats, true, reach, symmetry, islands, fingerprint,
+                       kinds, kinds_cap, n_kinds);
 }
 
 extern "C" int gol_batch_census(gol_batch *b, uint64_t seed, int64_t first, int64_t total, int64_t horizon, int32_t reach,
@@ -629,8 +641,8 @@ extern "C" int gol_batch_census(gol_batch *b, uint64_t seed, int64_t first, int6
                                 uint64_t *fingerprint, gol_island_kind *kinds, int64_t kinds_cap, int64_t *n_kinds,
                                 gol_batch_search_stats *stats)
 {
-    return search_call(b, seed, first, total, horizon, found, period, alive, hash, stats, true, reach, islands, fingerprint, kinds,
-                       kinds_cap, n_kinds);
+    return gol_batch_census_sym(b, seed, first, total, horizon, reach, GOL_ISLAND_FIXED, found, period, alive, hash, islands,
+                                fingerprint, kinds, kinds_cap, n_kinds, stats);
 }
 
 extern "C" int gol_batch_step(gol_batch *b, int64_t turns, int64_t *settled)
@@ -681,13 +693,14 @@ extern "C" int gol_batch_run_cycles(gol_batch *b, int64_t turns, int64_t *found,
 // come back whole, of its records the first min(dcap, the chunk's largest count) of every board in one strided copy to
 // a host block, from which a board's own records go to the caller's.  No board holds more than H W islands, so the
 // device never keeps more records per board than that, whatever cap says.
-extern "C" int gol_batch_islands(gol_batch *b, int64_t i0, int64_t i1, int32_t reach, int64_t cap, int64_t *count,
-                                 gol_island *islands, uint64_t *fingerprint)
+extern "C" int gol_batch_islands_sym(gol_batch *b, int64_t i0, int64_t i1, int32_t reach, int32_t symmetry, int64_t cap,
+                                     int64_t *count, gol_island *islands, uint64_t *fingerprint)
 {
-    if (!b || !count || i0 < 0 || i0 > i1 || i1 > b->n || reach < 1 || reach > GOL_ISLAND_MAX_REACH || cap < 0 ||
-        (cap > 0 && !islands))
-        return gol_set_error(GOL_EINVAL, "bad batch islands (boards [%lld, %lld) of %lld, reach %d in 1..2, cap %lld, or NULL)",
-                             (long long)i0, (long long)i1, b ? (long long)b->n : 0LL, reach, (long long)cap);
+    if (!b || !count || i0 < 0 || i0 > i1 || i1 > b->n || reach < 1 || reach > GOL_ISLAND_MAX_REACH || !symmetry_ok(symmetry) ||
+        cap < 0 || (cap > 0 && !islands))
+        return gol_set_error(GOL_EINVAL,
+                             "bad batch islands (boards [%lld, %lld) of %lld, reach %d in 1..2, symmetry %d in 0..1, cap %lld, or NULL)",
+                             (long long)i0, (long long)i1, b ? (long long)b->n : 0LL, reach, symmetry, (long long)cap);
     if (i0 == i1) return GOL_OK;
     OnDevice dev(b->device);
     HIPCHK(dev.err);
@@ -707,7 +720,8 @@ extern "C" int gol_batch_islands(gol_batch *b, int64_t i0, int64_t i1, int32_t r
     std::vector<gol_island> stage;
     for (int64_t c0 = i0; c0 < i1; c0 += per) {
         const int64_t m = std::min(per, i1 - c0);
-        const gol_island_launch l = {b->boards + c0 * b->H * b->Ww, m, b->H, b->W, reach, dcap, dcount, dcap ? drec : nullptr, dfp};
+        const gol_island_launch l = {b->boards + c0 * b->H * b->Ww, m, b->H, b->W, reach, symmetry, dcap, dcount, dcap ? drec : nullptr,
+                                     dfp};
         HIPCHK(golk_batch_islands(l, b->stream));
         HIPCHK(hipMemcpyAsync(count + (c0 - i0), dcount, (size_t)m * sizeof(int64_t), hipMemcpyDeviceToHost, b->stream));
         if (fingerprint)
@@ -733,15 +747,22 @@ extern "C" int gol_batch_islands(gol_batch *b, int64_t i0, int64_t i1, int32_t r
     return GOL_OK;
 }
 
+extern "C" int gol_batch_islands(gol_batch *b, int64_t i0, int64_t i1, int32_t reach, int64_t cap, int64_t *count,
+                                 gol_island *islands, uint64_t *fingerprint)
+{
+    return gol_batch_islands_sym(b, i0, i1, reach, GOL_ISLAND_FIXED, cap, count, islands, fingerprint);
+}
+
 // The tally of boards [i0, i1) as they stand: the chunks of gol_batch_islands (counts and fingerprints alone in the
 // scratch), each one dense TALLY launch with owner = the board's index, then the table's one read-back.
-extern "C" int gol_batch_islands_tally(gol_batch *b, int64_t i0, int64_t i1, int32_t reach, int64_t *count, uint64_t *fingerprint,
-                                       gol_island_kind *kinds, int64_t kinds_cap, int64_t *n_kinds)
+extern "C" int gol_batch_islands_tally_sym(gol_batch *b, int64_t i0, int64_t i1, int32_t reach, int32_t symmetry, int64_t *count,
+                                           uint64_t *fingerprint, gol_island_kind *kinds, int64_t kinds_cap, int64_t *n_kinds)
 {
-    if (!b || !count || i0 < 0 || i0 > i1 || i1 > b->n || !tally_args_ok(reach, kinds, kinds_cap, n_kinds))
+    if (!b || !count || i0 < 0 || i0 > i1 || i1 > b->n || !tally_args_ok(reach, symmetry, kinds, kinds_cap, n_kinds))
         return gol_set_error(GOL_EINVAL,
-                             "bad batch islands_tally (boards [%lld, %lld) of %lld, reach %d in 1..2, kinds_cap %lld in 0..2^23, or NULL)",
-                             (long long)i0, (long long)i1, b ? (long long)b->n : 0LL, reach, (long long)kinds_cap);
+                             "bad batch islands_tally (boards [%lld, %lld) of %lld, reach %d in 1..2, symmetry %d in 0..1, kinds_cap "
+                             "%lld in 0..2^23, or NULL)",
+                             (long long)i0, (long long)i1, b ? (long long)b->n : 0LL, reach, symmetry, (long long)kinds_cap);
     if (i0 == i1) {
         *n_kinds = 0;
         return GOL_OK;
@@ -760,12 +781,12 @@ extern "C" int gol_batch_islands_tally(gol_batch *b, int64_t i0, int64_t i1, int
     int64_t *dcount = (int64_t *)b->isl;
     uint64_t *dfp = (uint64_t *)(b->isl + per * 8);
     Tally t;
-    const int rc = tally_begin(b, reach, kinds_cap, &t);
+    const int rc = tally_begin(b, reach, symmetry, kinds_cap, &t);
     if (rc) return rc;
     for (int64_t c0 = i0; c0 < i1; c0 += per) {
         const int64_t m = std::min(per, i1 - c0);
-        const gol_island_launch l = {b->boards + c0 * b->H * b->Ww, m, b->H, b->W, reach, 0, dcount, nullptr, dfp, t.table, t.log2,
-                                     t.dropped, c0};
+        const gol_island_launch l = {b->boards + c0 * b->H * b->Ww, m, b->H, b->W, reach, symmetry, 0, dcount, nullptr, dfp, t.table,
+                                     t.log2, t.dropped, c0};
         HIPCHK(golk_batch_islands(l, b->stream));
         HIPCHK(hipMemcpyAsync(count + (c0 - i0), dcount, (size_t)m * sizeof(int64_t), hipMemcpyDeviceToHost, b->stream));
         if (fingerprint)
@@ -775,6 +796,12 @@ extern "C" int gol_batch_islands_tally(gol_batch *b, int64_t i0, int64_t i1, int
             if (count[i - i0] < 0) return gol_set_error(GOL_EHIP, "batch islands_tally: board %lld reached the census's trip bound", (long long)i);
     }
     return tally_end(b, t, "islands_tally", kinds, kinds_cap, n_kinds);
+}
+
+extern "C" int gol_batch_islands_tally(gol_batch *b, int64_t i0, int64_t i1, int32_t reach, int64_t *count, uint64_t *fingerprint,
+                                       gol_island_kind *kinds, int64_t kinds_cap, int64_t *n_kinds)
+{
+    return gol_batch_islands_tally_sym(b, i0, i1, reach, GOL_ISLAND_FIXED, count, fingerprint, kinds, kinds_cap, n_kinds);
 }
 
 extern "C" int gol_batch_alive_counts(gol_batch *b, uint64_t *counts, int64_t cap) { return reduce(b, false, counts, cap); }

@@ -266,14 +266,16 @@ extern "C" int gol_batch_search_host(int64_t H, int64_t W, uint32_t birth, uint3
     return search_host(H, W, birth, survive, seed, first, total, slots, launch, horizon, found, period, alive, hash, nullptr);
 }
 
-extern "C" int gol_batch_census_host(int64_t H, int64_t W, uint32_t birth, uint32_t survive, uint64_t seed, int64_t first,
-                                     int64_t total, int64_t slots, int64_t launch, int64_t horizon, int32_t reach, int64_t *found,
-                                     int64_t *period, uint64_t *alive, uint64_t *hash, int64_t *islands, uint64_t *fingerprint,
-                                     gol_island_kind *kinds, int64_t kinds_cap, int64_t *n_kinds)
+extern "C" int gol_batch_census_sym_host(int64_t H, int64_t W, uint32_t birth, uint32_t survive, uint64_t seed, int64_t first,
+                                         int64_t total, int64_t slots, int64_t launch, int64_t horizon, int32_t reach,
+                                         int32_t symmetry, int64_t *found, int64_t *period, uint64_t *alive, uint64_t *hash,
+                                         int64_t *islands, uint64_t *fingerprint, gol_island_kind *kinds, int64_t kinds_cap,
+                                         int64_t *n_kinds)
 {
-    if (reach < 1 || reach > 2 || kinds_cap < 0 || !n_kinds || (kinds_cap > 0 && !kinds))
-        return gol_set_error(GOL_EINVAL, "bad host batch census (reach %d in 1..2, kinds_cap %lld, or NULL)", reach,
-                             (long long)kinds_cap);
+    if (reach < 1 || reach > 2 || (symmetry != GOL_ISLAND_FIXED && symmetry != GOL_ISLAND_FREE) || kinds_cap < 0 || !n_kinds ||
+        (kinds_cap > 0 && !kinds))
+        return gol_set_error(GOL_EINVAL, "bad host batch census (reach %d in 1..2, symmetry %d in 0..1, kinds_cap %lld, or NULL)", reach,
+                             symmetry, (long long)kinds_cap);
     // every record of every found soup, then the tally; the outputs are written once nothing can fail
     std::vector<gol_island> records, mine;
     std::vector<int64_t> owners, counts;
@@ -283,7 +285,7 @@ extern "C" int gol_batch_census_host(int64_t H, int64_t W, uint32_t birth, uint3
         int64_t count = 0;
         uint64_t fp = 0;
         mine.resize((size_t)(H * W));
-        const int rc = gol_batch_islands_host(H, W, reach, snap, Ww, H * W, &count, mine.data(), &fp);
+        const int rc = gol_batch_islands_sym_host(H, W, reach, symmetry, snap, Ww, H * W, &count, mine.data(), &fp);
         if (rc) return rc;
         if (count < 0) return gol_set_error(GOL_EINVAL, "host batch census: soup %lld reached the census's trip bound", (long long)soup);
         records.insert(records.end(), mine.begin(), mine.begin() + count);
@@ -301,6 +303,15 @@ extern "C" int gol_batch_census_host(int64_t H, int64_t W, uint32_t birth, uint3
         if (fingerprint) fingerprint[g] = fps[(size_t)g];
     }
     return GOL_OK;
+}
+
+extern "C" int gol_batch_census_host(int64_t H, int64_t W, uint32_t birth, uint32_t survive, uint64_t seed, int64_t first,
+                                     int64_t total, int64_t slots, int64_t launch, int64_t horizon, int32_t reach, int64_t *found,
+                                     int64_t *period, uint64_t *alive, uint64_t *hash, int64_t *islands, uint64_t *fingerprint,
+                                     gol_island_kind *kinds, int64_t kinds_cap, int64_t *n_kinds)
+{
+    return gol_batch_census_sym_host(H, W, birth, survive, seed, first, total, slots, launch, horizon, reach, GOL_ISLAND_FIXED, found,
+                                     period, alive, hash, islands, fingerprint, kinds, kinds_cap, n_kinds);
 }
 
 extern "C" int gol_batch_step_check_host(const uint64_t *boards, const uint64_t *prev, const int64_t *settled, int64_t n, int64_t H,

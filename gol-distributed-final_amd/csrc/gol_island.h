@@ -12,7 +12,8 @@
 //     the OR of the 2 reach + 1 rows of M round it;
 //   - the window row: a board row turned so that the 2 reach + 1 cells round cell x are bits x .. x + 2 reach of NW + 1
 //     words (the ring unrolled past its end), so a cell's part of the code is a shift and a mask;
-//   - the hash of the cells of M in one row;
+//   - the hash of the cells of M in one row, and its FREE form: a code in the eight orientations of the square
+//     (gol_island_orient), the eight sums of a row and their minimum, the free hash;
 //   - the descriptor of one launch, plain or TALLY, with the one check of what makes it valid;
 //   - the kind table of a tally: the packed shape, the empty slot, the home slot and the probe step.
 #pragma once
@@ -60,6 +61,7 @@ struct gol_island_launch {
     const uint64_t *boards;  // n boards of H rows of ceil(W / 64) words
     int64_t n, H, W;
     int32_t reach;
+    int32_t symmetry;       // GOL_ISLAND_FIXED or GOL_ISLAND_FREE: the hash of the records, the fingerprint and the table's tag
     int64_t cap;            // records per board in `islands`
     int64_t *count;         // n (listed: indexed by soup)
     gol_island *islands;    // n cap, or NULL with cap == 0
@@ -80,6 +82,7 @@ GOL_BATCH_HD bool gol_island_launch_ok(const gol_island_launch &l)
 {
     if (!l.boards || !l.count || !gol_batch_shape_ok(l.n, l.H, l.W)) return false;
     if (l.reach < 1 || l.reach > GOL_ISLAND_MAX_REACH || l.cap < 0) return false;
+    if (l.symmetry != GOL_ISLAND_FIXED && l.symmetry != GOL_ISLAND_FREE) return false;
     if (!l.pairs && (l.pair_count || l.found || l.max_pairs != 0)) return false;
     if (!l.table)  // plain
         return (l.cap == 0 || l.islands != nullptr) && !l.dropped && !l.pairs && l.table_log2 == 0 && l.owner0 == 0;
@@ -198,4 +201,123 @@ GOL_BATCH_HD uint64_t gol_island_row_hash(const uint32_t (&m)[NW], const uint32_
         }
     }
     return h;
+}
+
+// ---------------------------------------------------------------------------------------------- the FREE form
+// (include/golhip.h, "island kinds free of orientation": orientation s = t | fy << 1 | fx << 2.)
+// A code is 2 REACH + 1 fields of 2 REACH + 1 bits, the bit of (dy, dx) at (dy + REACH) (2 REACH + 1) + (dx + REACH).  The
+// three generators as delta swaps, their masks constants of REACH: the rows flipped (the fields reordered), the
+// columns flipped (every field's bits reversed), the transpose (the bit of (i, i + d) and that of (i + d, i) lie d
+// (K - 1) apart).
+template <int REACH>
+struct gol_island_sym {
+    static constexpr int K = 2 * REACH + 1;
+    static constexpr uint64_t row(int i) { return (((uint64_t)1 << K) - 1u) << (i * K); }
+    static constexpr uint64_t col(int j)
+    {
+        uint64_t m = 0;
+        for (int i = 0; i < K; ++i) m |= (uint64_t)1 << (i * K + j);
+        return m;
+    }
+    static constexpr uint64_t diag(int d)  // the bits (i, i + d)
+    {
+        uint64_t m = 0;
+        for (int i = 0; i + d < K; ++i) m |= (uint64_t)1 << (i * K + i + d);
+        return m;
+    }
+};
+
+template <int REACH>
+GOL_BATCH_HD uint64_t gol_island_flip_rows(uint64_t c)
+{
+    typedef gol_island_sym<REACH> S;
+    uint64_t r = c & S::row(REACH);
+    GOL_BATCH_UNROLL
+    for (int i = 0; i < REACH; ++i) {
+        const int sh = (S::K - 1 - 2 * i) * S::K;
+        r |= (c & S::row(i)) << sh | ((c >> sh) & S::row(i));
+    }
+    return r;
+}
+
+template <int REACH>
+GOL_BATCH_HD uint64_t gol_island_flip_cols(uint64_t c)
+{
+    typedef gol_island_sym<REACH> S;
+    uint64_t r = c & S::col(REACH);
+    GOL_BATCH_UNROLL
+    for (int j = 0; j < REACH; ++j) {
+        const int sh = S::K - 1 - 2 * j;
+        r |= (c & S::col(j)) << sh | ((c >> sh) & S::col(j));
+    }
+    return r;
+}
+
+template <int REACH>
+GOL_BATCH_HD uint64_t gol_island_transpose(uint64_t c)
+{
+    typedef gol_island_sym<REACH> S;
+    uint64_t r = c & S::diag(0);
+    GOL_BATCH_UNROLL
+    for (int d = 1; d < S::K; ++d) {
+        const int sh = d * (S::K - 1);
+        r |= (c & S::diag(d)) << sh | ((c >> sh) & S::diag(d));
+    }
+    return r;
+}
+
+// o[s] = orient(c, REACH, s), all eight: the flips first, then the transpose (one row flip, two column flips, four
+// transposes).
+template <int REACH>
+GOL_BATCH_HD void gol_island_orient_all(uint64_t c, uint64_t (&o)[8])
+{
+    o[0] = c;
+    o[2] = gol_island_flip_rows<REACH>(c);
+    o[4] = gol_island_flip_cols<REACH>(c);
+    o[6] = gol_island_flip_cols<REACH>(o[2]);
+    GOL_BATCH_UNROLL
+    for (int s = 0; s < 8; s += 2) o[s + 1] = gol_island_transpose<REACH>(o[s]);
+}
+
+// orient(code, reach, s) of golhip.h; 0 for an s outside 0..7 or a reach outside 1..GOL_ISLAND_MAX_REACH.
+GOL_BATCH_HD uint64_t gol_island_orient(uint64_t code, int32_t reach, int32_t s)
+{
+    if (s < 0 || s > 7 || reach < 1 || reach > GOL_ISLAND_MAX_REACH) return 0;
+    uint64_t o[8];
+    if (reach == 1) gol_island_orient_all<1>(code, o);
+    else gol_island_orient_all<2>(code, o);
+    uint64_t r = o[0];
+    GOL_BATCH_UNROLL
+    for (int i = 1; i < 8; ++i) r = i == s ? o[i] : r;
+    return r;
+}
+
+// gol_island_row_hash in the eight orientations: h[s] the sum of term(orient(code, REACH, s)) over the cells of m.
+template <int NW, int REACH>
+GOL_BATCH_HD void gol_island_row_hash_free(const uint32_t (&m)[NW], const uint32_t (&e)[2 * REACH + 1][NW + 1], uint64_t (&h)[8])
+{
+    GOL_BATCH_UNROLL
+    for (int s = 0; s < 8; ++s) h[s] = 0;
+    GOL_BATCH_UNROLL
+    for (int j = 0; j < NW; ++j) {
+        for (uint32_t left = m[j]; left; left &= left - 1u) {  // (at most 32 trips)
+            const uint32_t b = (uint32_t)__builtin_ctz(left);
+            uint64_t code = 0, o[8];
+            GOL_BATCH_UNROLL
+            for (int d = 0; d < 2 * REACH + 1; ++d)
+                code |= (uint64_t)gol_island_field<REACH>(e[d][j], e[d][j + 1], b) << (d * (2 * REACH + 1));
+            gol_island_orient_all<REACH>(code, o);
+            GOL_BATCH_UNROLL
+            for (int s = 0; s < 8; ++s) h[s] += gol_island_term(o[s], REACH);
+        }
+    }
+}
+
+// The free hash: the smallest of an island's eight sums.
+GOL_BATCH_HD uint64_t gol_island_free_hash(const uint64_t (&h)[8])
+{
+    uint64_t r = h[0];
+    GOL_BATCH_UNROLL
+    for (int s = 1; s < 8; ++s) r = h[s] < r ? h[s] : r;
+    return r;
 }

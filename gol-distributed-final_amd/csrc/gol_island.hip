@@ -1,7 +1,7 @@
 // gol_island.hip -- the island census of a batch of small tori in one launch (include/golhip.h, "the island census of
 // a batch"; the row functions are gol_island.h).
 //
-// batch_islands_kernel<NW, REACH, TALLY>: one board per workgroup of ceil(H / 64) waves, one row per lane, NW = 1, 2, 4, 8 or
+// batch_islands_kernel<NW, REACH, TALLY, FREE>: one board per workgroup of ceil(H / 64) waves, one row per lane, NW = 1, 2, 4, 8 or
 // 16 words of it in registers, as in the step kernel (gol_batch.hip).  The board is read once and stays resident: a
 // lane holds its row's remaining cells and the window rows (gol_island_window_row) of the 2 REACH + 1 board rows (y +
 // dy) mod H round it, read straight from memory; they are constant, so the fingerprint needs no lane exchange.  (At
@@ -40,7 +40,14 @@
 // full table is counted in `dropped`.  The buffer is wave 0's alone and an insertion holds no barrier, so the barriers
 // are those of the plain form.
 //
-// This unit holds the kernel, the dispatch over its twenty instantiations, the kernel that empties a table, and its
+// FREE = true (include/golhip.h, "island kinds free of orientation"): the hash of an island is the smallest of its
+// sums in the eight orientations of the square.  A lane that holds cells of M accumulates eight sums
+// (gol_island_row_hash_free: per cell the code in its eight orientations, gol_island_orient_all, and eight terms), the
+// uniform loop over the holding lanes reads all eight, the waves post eight parts each, and thread 0 adds them and
+// takes the minimum (gol_island_free_hash) before it writes the record, the fingerprint and the gathered record.
+// Nothing after that differs: no barrier, atomic or loop is added, and the table sees a hash as before.
+//
+// This unit holds the kernel, the dispatch over its forty instantiations, the kernel that empties a table, and its
 // entries: golk_batch_islands, which launches what a gol_island_launch describes once gol_island_launch_ok accepts it,
 // and golk_island_table_clear.
 #include <hip/hip_runtime.h>
@@ -130,16 +137,17 @@ __device__ __forceinline__ void tally_flush(const IslandArgs &a, const uint64_t 
     if (leader) tally_insert(a, hash, shape, owner, same);
 }
 
-template <int NW, int REACH, bool TALLY>
+template <int NW, int REACH, bool TALLY, bool FREE>
 __global__ __launch_bounds__(512) void batch_islands_kernel(const IslandArgs a)
 {
+    constexpr int NS = FREE ? 8 : 1;  // the sums of an island: one per orientation
     // [buffer][wave][lane 0, lane 1, the last lane but one, the last lane][word]
     __shared__ uint32_t edge[2][GOL_BATCH_MAX_WAVES][4][NW];
     __shared__ uint32_t changed[2][GOL_BATCH_MAX_WAVES];
     __shared__ uint32_t cand[2][GOL_BATCH_MAX_WAVES];
     __shared__ uint32_t part_cells[2][GOL_BATCH_MAX_WAVES], part_rows[2][GOL_BATCH_MAX_WAVES];
     __shared__ uint32_t part_cols[2][GOL_BATCH_MAX_WAVES][NW];
-    __shared__ uint64_t part_hash[2][GOL_BATCH_MAX_WAVES];
+    __shared__ uint64_t part_hash[2][GOL_BATCH_MAX_WAVES][NS];
     __shared__ uint64_t fingerprint;  // the sum of the records' hashes so far
 
     uint64_t(*kept)[2] = nullptr;  // TALLY: the records gathered for wave 0, hash and packed shape
@@ -304,21 +312,28 @@ __global__ __launch_bounds__(512) void batch_islands_kernel(const IslandArgs a)
             any |= m[j];
             pop += (uint32_t)__popc(m[j]);
         }
-        uint64_t h = 0;
+        uint64_t h[NS];
+#pragma unroll
+        for (int s = 0; s < NS; ++s) h[s] = 0;
         if (any) {
             if (!RESIDENT) load_windows(win);
-            h = gol_island_row_hash<NW, REACH>(m, win);
+            if constexpr (FREE) gol_island_row_hash_free<NW, REACH>(m, win, h);
+            else h[0] = gol_island_row_hash<NW, REACH>(m, win);
         }
         const uint64_t holds = __ballot(any != 0);
         uint32_t cells = 0, cols[NW];
-        uint64_t hash = 0;
+        uint64_t hash[NS];
+#pragma unroll
+        for (int s = 0; s < NS; ++s) hash[s] = 0;
 #pragma unroll
         for (int j = 0; j < NW; ++j) cols[j] = 0u;
         for (uint64_t left = holds; left; left &= left - 1) {  // (uniform in the wave; at most 64 trips)
             const int l = __builtin_amdgcn_readfirstlane(__builtin_ctzll(left));
             cells += (uint32_t)__builtin_amdgcn_readlane((int)pop, l);
-            hash += (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)h, l) |
-                    (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(h >> 32), l) << 32;
+#pragma unroll
+            for (int s = 0; s < NS; ++s)
+                hash[s] += (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)h[s], l) |
+                           (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(h[s] >> 32), l) << 32;
 #pragma unroll
             for (int j = 0; j < NW; ++j) cols[j] |= (uint32_t)__builtin_amdgcn_readlane((int)m[j], l);
         }
@@ -326,7 +341,8 @@ __global__ __launch_bounds__(512) void batch_islands_kernel(const IslandArgs a)
         if (lane == 0) {
             part_cells[par][wave] = cells;
             part_rows[par][wave] = (uint32_t)__popcll(holds);
-            part_hash[par][wave] = hash;
+#pragma unroll
+            for (int s = 0; s < NS; ++s) part_hash[par][wave][s] = hash[s];
 #pragma unroll
             for (int j = 0; j < NW; ++j) part_cols[par][wave][j] = cols[j];
             cand[par][wave] = c;
@@ -335,11 +351,17 @@ __global__ __launch_bounds__(512) void batch_islands_kernel(const IslandArgs a)
         if (threadIdx.x == 0) {
             gol_island r = {sy, sx, 0, 0, 0, 0};
             uint32_t nrows = 0, ncols = 0;
+            uint64_t sums[NS];
+#pragma unroll
+            for (int s = 0; s < NS; ++s) sums[s] = 0;
             for (int i = 0; i < a.wpb; ++i) {
                 r.cells += (int32_t)part_cells[par][i];
                 nrows += part_rows[par][i];
-                r.hash += part_hash[par][i];
+#pragma unroll
+                for (int s = 0; s < NS; ++s) sums[s] += part_hash[par][i][s];
             }
+            if constexpr (FREE) r.hash = gol_island_free_hash(sums);  // the smallest of the eight orientations' sums
+            else r.hash = sums[0];
 #pragma unroll
             for (int j = 0; j < NW; ++j) {
                 uint32_t w = 0;
@@ -385,17 +407,23 @@ __global__ __launch_bounds__(256) void island_table_clear_kernel(gol_island_slot
     if (blockIdx.x == 0 && threadIdx.x == 0) *dropped = 0;
 }
 
-template <int NW>
-hipError_t launch(int reach, const IslandArgs &a, dim3 grid, dim3 block, hipStream_t s)
+template <int NW, bool FREE>
+hipError_t launch_of(int reach, const IslandArgs &a, dim3 grid, dim3 block, hipStream_t s)
 {
     if (a.table) {
-        if (reach == 1) batch_islands_kernel<NW, 1, true><<<grid, block, 0, s>>>(a);
-        else batch_islands_kernel<NW, 2, true><<<grid, block, 0, s>>>(a);
+        if (reach == 1) batch_islands_kernel<NW, 1, true, FREE><<<grid, block, 0, s>>>(a);
+        else batch_islands_kernel<NW, 2, true, FREE><<<grid, block, 0, s>>>(a);
     } else {
-        if (reach == 1) batch_islands_kernel<NW, 1, false><<<grid, block, 0, s>>>(a);
-        else batch_islands_kernel<NW, 2, false><<<grid, block, 0, s>>>(a);
+        if (reach == 1) batch_islands_kernel<NW, 1, false, FREE><<<grid, block, 0, s>>>(a);
+        else batch_islands_kernel<NW, 2, false, FREE><<<grid, block, 0, s>>>(a);
     }
     return hipGetLastError();
+}
+
+template <int NW>
+hipError_t launch(int reach, int symmetry, const IslandArgs &a, dim3 grid, dim3 block, hipStream_t s)
+{
+    return symmetry == GOL_ISLAND_FREE ? launch_of<NW, true>(reach, a, grid, block, s) : launch_of<NW, false>(reach, a, grid, block, s);
 }
 
 }  // namespace
@@ -410,11 +438,11 @@ hipError_t golk_batch_islands(const gol_island_launch &l, hipStream_t s)
                           l.pairs, l.pair_count, l.found};
     const dim3 grid((unsigned)(l.pairs ? l.max_pairs : l.n)), block((unsigned)(wpb * 64));
     switch (g.nw) {
-    case 1: return launch<1>(l.reach, a, grid, block, s);
-    case 2: return launch<2>(l.reach, a, grid, block, s);
-    case 4: return launch<4>(l.reach, a, grid, block, s);
-    case 8: return launch<8>(l.reach, a, grid, block, s);
-    default: return launch<16>(l.reach, a, grid, block, s);
+    case 1: return launch<1>(l.reach, l.symmetry, a, grid, block, s);
+    case 2: return launch<2>(l.reach, l.symmetry, a, grid, block, s);
+    case 4: return launch<4>(l.reach, l.symmetry, a, grid, block, s);
+    case 8: return launch<8>(l.reach, l.symmetry, a, grid, block, s);
+    default: return launch<16>(l.reach, l.symmetry, a, grid, block, s);
     }
 }
 

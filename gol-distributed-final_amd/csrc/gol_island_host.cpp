@@ -3,7 +3,9 @@
 // instantiation the kernel picks for the width and the reach, row by row as the lanes do; and
 // gol_batch_islands_check_host: the check every launch of the kernel passes (gol_island_launch_ok).  The flood visits
 // only the rows round the island so far (the rows a step can change lie within `reach` of them), which is what keeps a
-// large sparse board cheap; the rest is the kernel's scheme.  And the tally of island kinds: gol_island_tally_host, the
+// large sparse board cheap; the rest is the kernel's scheme.  symmetry (the _sym entries; the others are their
+// GOL_ISLAND_FIXED calls) selects the hash: FREE sums an island's rows in the eight orientations
+// (gol_island_row_hash_free) and keeps the smallest sum, as the kernel does; gol_island_orient_host is orient().  And the tally of island kinds: gol_island_tally_host, the
 // definition by a sort and a merge, gol_island_tally_home_host and gol_batch_islands_tally_check_host, the table's home
 // function and the check of a TALLY launch.  No HIP header: a stand-alone program links this file alone
 // (island_check.cpp).
@@ -20,8 +22,8 @@ int gol_set_error(int code, const char *fmt, ...);
 namespace {
 
 template <int NW, int REACH>
-void islands_host(int64_t H, int64_t W, const uint64_t *words, int64_t stride, int64_t cap, int64_t *count, gol_island *islands,
-                  uint64_t *fingerprint)
+void islands_host(int32_t symmetry, int64_t H, int64_t W, const uint64_t *words, int64_t stride, int64_t cap, int64_t *count,
+                  gol_island *islands, uint64_t *fingerprint)
 {
     const gol_batch_row g = gol_batch_row_init(W);
     auto row_of = [H](int64_t y) { return (size_t)(((y % H) + H) % H); };
@@ -82,6 +84,7 @@ void islands_host(int64_t H, int64_t W, const uint64_t *words, int64_t stride, i
         // the record, and M off the remaining cells
         gol_island r = {(int32_t)sy, sx, 0, 0, 0, 0};
         uint32_t cols[NW] = {0u};
+        uint64_t sums[8] = {0u};  // FREE: the island's sums in the eight orientations
         for (int64_t i = 0; i < len; ++i) {
             const size_t y = row_of(top + i);
             uint32_t mm[NW], e[2 * REACH + 1][NW + 1], any = 0u;
@@ -97,8 +100,15 @@ void islands_host(int64_t H, int64_t W, const uint64_t *words, int64_t stride, i
             r.rows += 1;
             for (int d = 0; d < 2 * REACH + 1; ++d)
                 for (int j = 0; j <= NW; ++j) e[d][j] = win[row_of((int64_t)y + d - REACH) * (NW + 1) + j];
-            r.hash += gol_island_row_hash<NW, REACH>(mm, e);
+            if (symmetry == GOL_ISLAND_FREE) {
+                uint64_t h[8];
+                gol_island_row_hash_free<NW, REACH>(mm, e, h);
+                for (int s = 0; s < 8; ++s) sums[s] += h[s];
+            } else {
+                r.hash += gol_island_row_hash<NW, REACH>(mm, e);
+            }
         }
+        if (symmetry == GOL_ISLAND_FREE) r.hash = gol_island_free_hash(sums);
         for (int j = 0; j < NW; ++j) r.cols += (uint16_t)__builtin_popcount(cols[j]);
         fp += r.hash;
         if (k < cap) islands[k] = r;
@@ -108,41 +118,58 @@ void islands_host(int64_t H, int64_t W, const uint64_t *words, int64_t stride, i
 }
 
 template <int NW>
-void islands_host_of(int32_t reach, int64_t H, int64_t W, const uint64_t *words, int64_t stride, int64_t cap, int64_t *count,
-                     gol_island *islands, uint64_t *fingerprint)
+void islands_host_of(int32_t reach, int32_t symmetry, int64_t H, int64_t W, const uint64_t *words, int64_t stride, int64_t cap,
+                     int64_t *count, gol_island *islands, uint64_t *fingerprint)
 {
-    if (reach == 1) islands_host<NW, 1>(H, W, words, stride, cap, count, islands, fingerprint);
-    else islands_host<NW, 2>(H, W, words, stride, cap, count, islands, fingerprint);
+    if (reach == 1) islands_host<NW, 1>(symmetry, H, W, words, stride, cap, count, islands, fingerprint);
+    else islands_host<NW, 2>(symmetry, H, W, words, stride, cap, count, islands, fingerprint);
 }
 
 }  // namespace
 
+extern "C" int gol_batch_islands_sym_host(int64_t H, int64_t W, int32_t reach, int32_t symmetry, const uint64_t *words,
+                                          int64_t row_stride, int64_t cap, int64_t *count, gol_island *islands,
+                                          uint64_t *fingerprint)
+{
+    // (the check of a launch of one board, and the rows to read)
+    const gol_island_launch l = {words, 1, H, W, reach, symmetry, cap, count, islands, fingerprint};
+    if (!gol_island_launch_ok(l) || row_stride < (W + 63) / 64)
+        return gol_set_error(GOL_EINVAL,
+                             "bad host batch islands (H %lld, W %lld, reach %d, symmetry %d, row stride %lld, cap %lld, or NULL)",
+                             (long long)H, (long long)W, reach, symmetry, (long long)row_stride, (long long)cap);
+    switch (gol_batch_row_init(W).nw) {
+    case 1: islands_host_of<1>(reach, symmetry, H, W, words, row_stride, cap, count, islands, fingerprint); break;
+    case 2: islands_host_of<2>(reach, symmetry, H, W, words, row_stride, cap, count, islands, fingerprint); break;
+    case 4: islands_host_of<4>(reach, symmetry, H, W, words, row_stride, cap, count, islands, fingerprint); break;
+    case 8: islands_host_of<8>(reach, symmetry, H, W, words, row_stride, cap, count, islands, fingerprint); break;
+    default: islands_host_of<16>(reach, symmetry, H, W, words, row_stride, cap, count, islands, fingerprint); break;
+    }
+    return GOL_OK;
+}
+
 extern "C" int gol_batch_islands_host(int64_t H, int64_t W, int32_t reach, const uint64_t *words, int64_t row_stride, int64_t cap,
                                       int64_t *count, gol_island *islands, uint64_t *fingerprint)
 {
-    // (the check of a launch of one board, and the rows to read)
-    const gol_island_launch l = {words, 1, H, W, reach, cap, count, islands, fingerprint};
-    if (!gol_island_launch_ok(l) || row_stride < (W + 63) / 64)
-        return gol_set_error(GOL_EINVAL, "bad host batch islands (H %lld, W %lld, reach %d, row stride %lld, cap %lld, or NULL)",
-                             (long long)H, (long long)W, reach, (long long)row_stride, (long long)cap);
-    switch (gol_batch_row_init(W).nw) {
-    case 1: islands_host_of<1>(reach, H, W, words, row_stride, cap, count, islands, fingerprint); break;
-    case 2: islands_host_of<2>(reach, H, W, words, row_stride, cap, count, islands, fingerprint); break;
-    case 4: islands_host_of<4>(reach, H, W, words, row_stride, cap, count, islands, fingerprint); break;
-    case 8: islands_host_of<8>(reach, H, W, words, row_stride, cap, count, islands, fingerprint); break;
-    default: islands_host_of<16>(reach, H, W, words, row_stride, cap, count, islands, fingerprint); break;
-    }
-    return GOL_OK;
+    return gol_batch_islands_sym_host(H, W, reach, GOL_ISLAND_FIXED, words, row_stride, cap, count, islands, fingerprint);
+}
+
+extern "C" int gol_batch_islands_sym_check_host(const uint64_t *boards, int64_t n, int64_t H, int64_t W, int32_t reach,
+                                                int32_t symmetry, int64_t cap, const int64_t *count, const gol_island *islands,
+                                                const uint64_t *fingerprint)
+{
+    // (the check reads the pointers' values alone)
+    const gol_island_launch l = {boards, n, H, W, reach, symmetry, cap, const_cast<int64_t *>(count),
+                                 const_cast<gol_island *>(islands), const_cast<uint64_t *>(fingerprint)};
+    return gol_island_launch_ok(l) ? GOL_OK : GOL_EINVAL;
 }
 
 extern "C" int gol_batch_islands_check_host(const uint64_t *boards, int64_t n, int64_t H, int64_t W, int32_t reach, int64_t cap,
                                             const int64_t *count, const gol_island *islands, const uint64_t *fingerprint)
 {
-    // (the check reads the pointers' values alone)
-    const gol_island_launch l = {boards, n, H, W, reach, cap, const_cast<int64_t *>(count), const_cast<gol_island *>(islands),
-                                 const_cast<uint64_t *>(fingerprint)};
-    return gol_island_launch_ok(l) ? GOL_OK : GOL_EINVAL;
+    return gol_batch_islands_sym_check_host(boards, n, H, W, reach, GOL_ISLAND_FIXED, cap, count, islands, fingerprint);
 }
+
+extern "C" uint64_t gol_island_orient_host(uint64_t code, int32_t reach, int32_t s) { return gol_island_orient(code, reach, s); }
 
 extern "C" int gol_island_tally_host(const gol_island *records, const int64_t *owners, int64_t n, gol_island_kind *kinds,
                                      int64_t kinds_cap, int64_t *n_kinds)
@@ -184,15 +211,25 @@ extern "C" int64_t gol_island_tally_home_host(uint64_t hash, int32_t table_log2)
     return (int64_t)gol_island_tally_home(gol_island_tally_tag(hash), table_log2);
 }
 
+extern "C" int gol_batch_islands_tally_sym_check_host(const uint64_t *boards, int64_t n, int64_t H, int64_t W, int32_t reach,
+                                                      int32_t symmetry, const int32_t *pairs, const int32_t *pair_count,
+                                                      int64_t max_pairs, const int64_t *found, int64_t owner0, const int64_t *count,
+                                                      const uint64_t *fingerprint, const gol_island_kind *table,
+                                                      int32_t table_log2, const int64_t *dropped)
+{
+    // (the check reads the pointers' values alone; a NULL table is the plain launch, which this entry does not make)
+    const gol_island_launch l = {boards, n, H, W, reach, symmetry, 0, const_cast<int64_t *>(count), nullptr,
+                                 const_cast<uint64_t *>(fingerprint), const_cast<gol_island_kind *>(table), table_log2,
+                                 const_cast<int64_t *>(dropped), owner0, pairs, pair_count, max_pairs, found};
+    return table && gol_island_launch_ok(l) ? GOL_OK : GOL_EINVAL;
+}
+
 extern "C" int gol_batch_islands_tally_check_host(const uint64_t *boards, int64_t n, int64_t H, int64_t W, int32_t reach,
                                                   const int32_t *pairs, const int32_t *pair_count, int64_t max_pairs,
                                                   const int64_t *found, int64_t owner0, const int64_t *count,
                                                   const uint64_t *fingerprint, const gol_island_kind *table, int32_t table_log2,
                                                   const int64_t *dropped)
 {
-    // (the check reads the pointers' values alone; a NULL table is the plain launch, which this entry does not make)
-    const gol_island_launch l = {boards, n, H, W, reach, 0, const_cast<int64_t *>(count), nullptr, const_cast<uint64_t *>(fingerprint),
-                                 const_cast<gol_island_kind *>(table), table_log2, const_cast<int64_t *>(dropped), owner0, pairs,
-                                 pair_count, max_pairs, found};
-    return table && gol_island_launch_ok(l) ? GOL_OK : GOL_EINVAL;
+    return gol_batch_islands_tally_sym_check_host(boards, n, H, W, reach, GOL_ISLAND_FIXED, pairs, pair_count, max_pairs, found, owner0,
+                                                  count, fingerprint, table, table_log2, dropped);
 }

@@ -12,6 +12,7 @@
 * ``Engine.copy`` / ``Engine.cut`` / ``Engine.bounds`` / ``Engine.to_rle`` / ``Operations.copy`` / ``Operations.bounds``  exact reads of a region of the running board in place (gol_engine_copy, gol_engine_bounds)
 * ``Batch``                many small boards (<= 512 x 512) stepped in one launch, resident in their workgroups, with a settle scan (gol_batch_*)
 * ``Batch.islands`` / ``island`` / ``ISLAND_DTYPE``  the island census of every board of a batch, labelled on the GPU: per island a translation-invariant record (gol_batch_islands), and the record of a lone pattern to name it by
+* ``symmetry=ISLAND_FREE`` (``ISLAND_FIXED`` the default) on ``Batch.islands``, ``Batch.islands_tally``, ``Batch.census`` and ``island``  the free hash: the smallest of an island's hashes in the eight orientations of the square, computed in the kernel, so a tally holds one line per object however it is turned or mirrored (the _sym entries)
 * ``Batch.census`` / ``Batch.islands_tally`` / ``ISLAND_KIND_DTYPE``  the tally of island kinds (kind -> occurrences, with an example soup) of a streamed soup search or of the boards as they stand, built on the GPU inside the search's harvest (gol_batch_census, gol_batch_islands_tally)
 * ``distributor``          controller mirror (gol/gol.go + gol/distributor.go) over the broker API
 * ``next_state_slab`` / ``partition_rows``  worker.go:15-70 / broker.go:135-206
@@ -20,7 +21,7 @@ Everything runs through libgolhip.so (hipcc, gfx950); there is no CPU fallback.
 """
 from ._lib import (GolError, device_count, format_rle, format_rule, halo_plan, lib, parse_rle, parse_rule,  # noqa: F401
                    step_plan, strip_plan, view_plan)
-from .batch import ISLAND_DTYPE, ISLAND_KIND_DTYPE, Batch, island  # noqa: F401
+from .batch import ISLAND_DTYPE, ISLAND_FIXED, ISLAND_FREE, ISLAND_KIND_DTYPE, Batch, island  # noqa: F401
 from .broker import Operations  # noqa: F401
 from .engine import Engine, next_state_slab, partition_rows  # noqa: F401
 from .pgm import read_pgm, write_pgm_bytes  # noqa: F401

@@ -209,6 +209,18 @@ SIGNATURES = [
     ("gol_island_tally_home_host", _i64, [_u64, _i32]),
     ("gol_batch_islands_tally_check_host", ctypes.c_int, [_vp, _i64, _i64, _i64, _i32, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i32,
                                                           _vp]),
+    # the _sym siblings: symmetry (GOL_ISLAND_FIXED / GOL_ISLAND_FREE) after reach
+    ("gol_batch_islands_sym", ctypes.c_int, [_vp, _i64, _i64, _i32, _i32, _i64, _vp, _vp, _vp]),
+    ("gol_batch_islands_tally_sym", ctypes.c_int, [_vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _i64, _vp]),
+    ("gol_batch_census_sym", ctypes.c_int, [_vp, _u64, _i64, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp,
+                                            _vp]),
+    ("gol_batch_islands_sym_host", ctypes.c_int, [_i64, _i64, _i32, _i32, _vp, _i64, _i64, _vp, _vp, _vp]),
+    ("gol_batch_census_sym_host", ctypes.c_int, [_i64, _i64, ctypes.c_uint32, ctypes.c_uint32, _u64, _i64, _i64, _i64, _i64, _i64,
+                                                 _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    ("gol_batch_islands_sym_check_host", ctypes.c_int, [_vp, _i64, _i64, _i64, _i32, _i32, _i64, _vp, _vp, _vp]),
+    ("gol_batch_islands_tally_sym_check_host", ctypes.c_int, [_vp, _i64, _i64, _i64, _i32, _i32, _vp, _vp, _i64, _vp, _i64, _vp, _vp,
+                                                              _vp, _i32, _vp]),
+    ("gol_island_orient_host", _u64, [_u64, _i32, _i32]),
     ("gol_step_check_host", ctypes.c_int, [_i32, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i32, _i32, ctypes.c_uint32,
                                            ctypes.c_uint32, _i32, _i32, _i32, _vp]),
     ("gol_halo_plan", ctypes.c_int, [_i64, _i32, _i32, _i32, _P(gol_halo_op), _i32, _P(_i32)]),
@@ -246,6 +258,9 @@ SIGNATURES = [
     ("gol_dev_batch_islands_tally", ctypes.c_int, [_vp, _i64, _i64, _i64, _i32, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i32, _vp,
                                                    _vp]),
     ("gol_dev_island_table_clear", ctypes.c_int, [_vp, _i32, _vp, _vp]),
+    ("gol_dev_batch_islands_sym", ctypes.c_int, [_vp, _i64, _i64, _i64, _i32, _i32, _i64, _vp, _vp, _vp, _vp]),
+    ("gol_dev_batch_islands_tally_sym", ctypes.c_int, [_vp, _i64, _i64, _i64, _i32, _i32, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp,
+                                                       _i32, _vp, _vp]),
     ("gol_dev_error", ctypes.c_int, [_i32, _P(ctypes.c_uint32)]),
     ("gol_broker_create", ctypes.c_int, [_P(gol_config), _P(_vp)]),
     ("gol_broker_destroy", None, [_vp]),

@@ -20,15 +20,19 @@ from ._lib import GOL_EINVAL, GOL_ENOMEM, GolError, format_rule, lib, parse_rle,
 ISLAND_DTYPE = np.dtype([("y", "<i4"), ("x", "<i4"), ("cells", "<i4"), ("rows", "<u2"), ("cols", "<u2"), ("hash", "<u8")])
 # gol_island_kind (include/golhip.h): one kind of a tally, 32 bytes
 ISLAND_KIND_DTYPE = np.dtype([("hash", "<u8"), ("count", "<i8"), ("first", "<i8"), ("cells", "<i4"), ("rows", "<u2"), ("cols", "<u2")])
+# GOL_ISLAND_FIXED, GOL_ISLAND_FREE (include/golhip.h): the hash of an island as it lies, or the smallest of its hashes in
+# the eight orientations of the square, which no rotation or reflection changes
+ISLAND_FIXED, ISLAND_FREE = 0, 1
 
 
-def island(pattern, reach: int = 1, library=None):
+def island(pattern, reach: int = 1, library=None, symmetry: int = ISLAND_FIXED):
     """The record of a lone pattern (a 2-D array of cells, non-zero = alive, or RLE text) as the island census
     gives it: a numpy record of ISLAND_DTYPE whose cells, rows, cols and hash are those of the same pattern
     anywhere on any torus where nothing else lies within `reach` of it, so a caller can name what a tally of
     Batch.islands finds.  Computed on the host (gol_batch_islands_host) on a torus padded by 2 reach cells; no GPU
-    needed.  GolError(GOL_EINVAL) when the pattern is empty, is not one island at this reach, or does not fit a
-    512 x 512 torus."""
+    needed.  symmetry=ISLAND_FREE gives the free hash, the same for the pattern turned or mirrored.
+    GolError(GOL_EINVAL) when the pattern is empty, is not one island at this reach, or does not fit a 512 x 512
+    torus."""
     L = library or lib()
     cells = parse_rle(pattern, L)[0] if isinstance(pattern, (str, bytes, bytearray)) else np.asarray(pattern) != 0
     if cells.ndim != 2 or not cells.any():
@@ -40,8 +44,8 @@ def island(pattern, reach: int = 1, library=None):
     board[:h, :w] = cells
     words = Batch.pack(board)
     count, out = ctypes.c_int64(), np.zeros(1, dtype=ISLAND_DTYPE)
-    rc = L.gol_batch_islands_host(board.shape[0], board.shape[1], reach, words.ctypes.data, words.shape[1], 1,
-                                  ctypes.byref(count), out.ctypes.data, None)
+    rc = L.gol_batch_islands_sym_host(board.shape[0], board.shape[1], reach, symmetry, words.ctypes.data, words.shape[1], 1,
+                                      ctypes.byref(count), out.ctypes.data, None)
     if rc:
         raise GolError(rc, L.gol_last_error().decode(errors="replace"))
     if count.value != 1:
@@ -184,7 +188,7 @@ class Batch:
         return found, period, alive, hashes, d
 
     def census(self, seed: int, total: int, horizon: int, first: int = 0, reach: int = 1, kinds: int = 4096,
-               stats: bool = False) -> dict:
+               stats: bool = False, symmetry: int = ISLAND_FIXED) -> dict:
         """search() with the island census of every soup's state at `found` taken inside the search, and the tally
         of the kinds of island the soups turned into, built on the GPU: nothing per island comes back.  Returns a
         dict: found, period, alive, hash as search() returns them; islands (int64) and fingerprint (uint64), the
@@ -193,6 +197,8 @@ class Batch:
         ISLAND_KIND_DTYPE with the first min(n_kinds, kinds) of them, ordered by count descending, then hash: per
         kind its hash, count, first (the lowest soup number that holds one: Batch.soup re-makes it) and the
         smallest (cells, rows, cols) among its islands; with stats=True also stats, the dict of search().
+        symmetry=ISLAND_FREE: fingerprint and the kinds' hash are the free ones, so an object is one kind however it is
+        turned or mirrored (islands() has the definition).
         GolError(GOL_ENOMEM) when the kind table that `kinds` sizes (at least 1024 slots) is full."""
         m, cap = max(int(total), 0), max(int(kinds), 0)
         out = {"found": np.full(m, -1, dtype=np.int64), "period": np.full(m, -1, dtype=np.int64),
@@ -200,9 +206,12 @@ class Batch:
                "islands": np.zeros(m, dtype=np.int64), "fingerprint": np.zeros(m, dtype=np.uint64)}
         table = np.zeros(cap, dtype=ISLAND_KIND_DTYPE)
         n_kinds, st = ctypes.c_int64(), (ctypes.c_int64 * 5)()
-        self._check(self._L.gol_batch_census(self._h, seed, first, total, horizon, reach, *[a.ctypes.data for a in out.values()],
-                                             table.ctypes.data if kinds > 0 else None, kinds, ctypes.byref(n_kinds),
-                                             ctypes.addressof(st) if stats else None))
+        rest = [*[a.ctypes.data for a in out.values()], table.ctypes.data if kinds > 0 else None, kinds, ctypes.byref(n_kinds),
+                ctypes.addressof(st) if stats else None]
+        if symmetry == ISLAND_FIXED:
+            self._check(self._L.gol_batch_census(self._h, seed, first, total, horizon, reach, *rest))
+        else:
+            self._check(self._L.gol_batch_census_sym(self._h, seed, first, total, horizon, reach, symmetry, *rest))
         out["n_kinds"] = n_kinds.value
         out["kinds"] = table[:min(n_kinds.value, cap)]
         if stats:
@@ -308,7 +317,8 @@ class Batch:
         self._check(self._L.gol_batch_hashes(self._h, out.ctypes.data, self.n))
         return out
 
-    def islands(self, reach: int = 1, cap: int = 64, first: int = 0, count: int | None = None, fingerprints: bool = False):
+    def islands(self, reach: int = 1, cap: int = 64, first: int = 0, count: int | None = None, fingerprints: bool = False,
+                symmetry: int = ISLAND_FIXED):
         """The island census of boards [first, first + count) (default: all from `first`), labelled on the GPU
         where the boards lie; boards, turn and rules stay.  An island is a connected group of alive cells: two
         cells are linked when they are within `reach` (1: the 8-connected islands; 2: everything that shares a
@@ -319,31 +329,40 @@ class Batch:
         columns occupied) and hash (the sum of the cells' window terms, gol_batch_islands in golhip.h).
         cells, rows, cols and hash do not change under a torus translation of the board; they do under
         rotation and reflection.  fingerprints=True appends uint64[count]: per board the wrapping sum of the
-        hashes of all its islands, those past `cap` included."""
+        hashes of all its islands, those past `cap` included.  symmetry=ISLAND_FREE: hash is the free hash, the
+        smallest of the island's hashes in the eight orientations of the square ("island kinds free of orientation"
+        in golhip.h), which no rotation or reflection changes, and the fingerprint their sum; y, x, rows and cols
+        still describe the island as it lies."""
         count = self.n - first if count is None else count
         m = max(int(count), 0)
         counts = np.zeros(m, dtype=np.int64)
         recs = np.zeros((m, max(int(cap), 0)), dtype=ISLAND_DTYPE)
         fps = np.zeros(m, dtype=np.uint64) if fingerprints else None
-        self._check(self._L.gol_batch_islands(self._h, first, first + count, reach, cap, counts.ctypes.data,
-                                              recs.ctypes.data if cap > 0 else None,
-                                              fps.ctypes.data if fingerprints else None))
+        rest = [cap, counts.ctypes.data, recs.ctypes.data if cap > 0 else None, fps.ctypes.data if fingerprints else None]
+        if symmetry == ISLAND_FIXED:
+            self._check(self._L.gol_batch_islands(self._h, first, first + count, reach, *rest))
+        else:
+            self._check(self._L.gol_batch_islands_sym(self._h, first, first + count, reach, symmetry, *rest))
         return (counts, recs, fps) if fingerprints else (counts, recs)
 
-    def islands_tally(self, reach: int = 1, kinds: int = 4096, first: int = 0, count: int | None = None):
+    def islands_tally(self, reach: int = 1, kinds: int = 4096, first: int = 0, count: int | None = None,
+                      symmetry: int = ISLAND_FIXED):
         """The tally of the island kinds of boards [first, first + count) as they stand (default: all from `first`),
         built on the GPU; boards, turn and rules stay.  Returns (counts, fingerprints, kinds): per board the number
         of islands (int64) and the fingerprint (uint64) as islands() gives them, and the kinds as census() returns
         them, all of them up to `kinds`, `first` being the lowest board index that holds one.  When the kind table
         is full GolError(GOL_ENOMEM) is raised; its `counts` and `fingerprints` attributes hold the per-board
-        outputs, which are right."""
+        outputs, which are right.  symmetry=ISLAND_FREE: the fingerprints and the kinds' hash are the free ones."""
         count = self.n - first if count is None else count
         m, cap = max(int(count), 0), max(int(kinds), 0)
         counts, fps = np.zeros(m, dtype=np.int64), np.zeros(m, dtype=np.uint64)
         table = np.zeros(cap, dtype=ISLAND_KIND_DTYPE)
         n_kinds = ctypes.c_int64()
-        rc = self._L.gol_batch_islands_tally(self._h, first, first + count, reach, counts.ctypes.data, fps.ctypes.data,
-                                             table.ctypes.data if kinds > 0 else None, kinds, ctypes.byref(n_kinds))
+        rest = [counts.ctypes.data, fps.ctypes.data, table.ctypes.data if kinds > 0 else None, kinds, ctypes.byref(n_kinds)]
+        if symmetry == ISLAND_FIXED:
+            rc = self._L.gol_batch_islands_tally(self._h, first, first + count, reach, *rest)
+        else:
+            rc = self._L.gol_batch_islands_tally_sym(self._h, first, first + count, reach, symmetry, *rest)
         if rc == GOL_ENOMEM:
             e = GolError(rc, self._L.gol_last_error().decode(errors="replace"))
             e.counts, e.fingerprints = counts, fps

@@ -757,8 +757,10 @@ int gol_batch_step_check_host(const uint64_t *boards, const uint64_t *prev, cons
  *  - Fingerprint of a board: the wrapping sum of all its islands' hash.
  * Every cell in the window of a cell is linked to it, so it belongs to the
  * cell's own island: cells, rows, cols, hash and the fingerprint do not change
- * under any torus translation of the board (y and x do).  They do change under
- * rotation and reflection: orientation is not factored out.
+ * under any torus translation of the board (y and x do).  hash and the
+ * fingerprint do change under rotation and reflection; the free hash ("island
+ * kinds free of orientation", below: the _sym entries with GOL_ISLAND_FREE) does
+ * not.
  *
  * gol_batch_islands: boards [i0, i1) of the batch.  count[i - i0] is always the
  * full number of islands of board i.  islands may be NULL when cap == 0;
@@ -886,6 +888,69 @@ int gol_batch_islands_tally_check_host(const uint64_t *boards, int64_t n, int64_
                                        const int32_t *pair_count, int64_t max_pairs, const int64_t *found, int64_t owner0,
                                        const int64_t *count, const uint64_t *fingerprint, const gol_island_kind *table,
                                        int32_t table_log2, const int64_t *dropped);
+/* Island kinds free of orientation: a hash that no rotation or reflection of
+ * an island changes, so that a tally holds one line per object however it is
+ * turned (the FREE form of the kernel of csrc/gol_island.hip).  No version
+ * bump: probe by symbol.  reach, window code and term are those of the island
+ * census above.
+ *  - Orientations: the eight symmetries of the square are numbered s = 0..7
+ *    with t = s & 1 (transpose), fy = (s >> 1) & 1 (rows flipped), fx = (s >> 2)
+ *    & 1 (columns flipped).
+ *  - The code in orientation s: for a window code c, orient(c, reach, s) is the
+ *    code whose bit at (dy, dx) is the bit of c at (dy', dx'), where (a, b) = t ?
+ *    (dx, dy) : (dy, dx), dy' = fy ? -a : a, dx' = fx ? -b : b.  orient(c, reach,
+ *    0) == c.
+ *  - The hash of an island in orientation s: the wrapping sum of
+ *    term(orient(code, reach, s)) over its cells.  Its free hash is the smallest
+ *    of the eight, compared as unsigned 64-bit numbers.
+ *  - Free fingerprint of a board: the wrapping sum of its islands' free hashes.
+ * The eight maps are the whole group, and the window of a cell holds only
+ * cells of its own island, so the eight sums of an island are the hashes
+ * (symmetry 0) of its eight images, and the set of eight is the same for every
+ * image: the minimum does not change under translation, rotation or
+ * reflection.  The window formula holds as written on tori narrower than the
+ * window, so this is true on every torus, and between an H x W board and its W
+ * x H transpose.  Phase is not factored out: an oscillator whose phases are not
+ * images of each other has one kind per phase.
+ * symmetry selects the hash: GOL_ISLAND_FIXED (the hash of the island census
+ * above) or GOL_ISLAND_FREE; every other value is refused.  With
+ * GOL_ISLAND_FREE gol_island.hash, the fingerprint, gol_island_kind.hash and the
+ * table's tag are the free ones; y, x, cells, rows and cols (they describe the
+ * island as it lies), the order of records, the rule that hash 0 is tallied
+ * under 1, the tally's reductions and order and both struct layouts stay.
+ *
+ * Every _sym entry is the entry of the same name without _sym, with symmetry
+ * after reach: with GOL_ISLAND_FIXED it is that entry (which is this call),
+ * outputs and refusals alike; and GOL_EINVAL before any GPU work, outputs
+ * untouched, for a symmetry outside 0..1.  (gol_island_tally_host takes records,
+ * so it tallies either kind of hash.)
+ * gol_island_orient_host: orient(code, reach, s) (a host function: the function
+ * of csrc/gol_island.h the kernel runs); 0 for an s outside 0..7 or a reach
+ * outside 1..2. */
+#define GOL_ISLAND_FIXED 0
+#define GOL_ISLAND_FREE 1
+int gol_batch_islands_sym(gol_batch *b, int64_t i0, int64_t i1, int32_t reach, int32_t symmetry, int64_t cap, int64_t *count,
+                          gol_island *islands, uint64_t *fingerprint);
+int gol_batch_islands_tally_sym(gol_batch *b, int64_t i0, int64_t i1, int32_t reach, int32_t symmetry, int64_t *count,
+                                uint64_t *fingerprint, gol_island_kind *kinds, int64_t kinds_cap, int64_t *n_kinds);
+int gol_batch_census_sym(gol_batch *b, uint64_t seed, int64_t first, int64_t total, int64_t horizon, int32_t reach,
+                         int32_t symmetry, int64_t *found, int64_t *period, uint64_t *alive, uint64_t *hash, int64_t *islands,
+                         uint64_t *fingerprint, gol_island_kind *kinds, int64_t kinds_cap, int64_t *n_kinds,
+                         gol_batch_search_stats *stats);
+int gol_batch_islands_sym_host(int64_t H, int64_t W, int32_t reach, int32_t symmetry, const uint64_t *words, int64_t row_stride,
+                               int64_t cap, int64_t *count, gol_island *islands, uint64_t *fingerprint);
+int gol_batch_census_sym_host(int64_t H, int64_t W, uint32_t birth, uint32_t survive, uint64_t seed, int64_t first, int64_t total,
+                              int64_t slots, int64_t launch, int64_t horizon, int32_t reach, int32_t symmetry, int64_t *found,
+                              int64_t *period, uint64_t *alive, uint64_t *hash, int64_t *islands, uint64_t *fingerprint,
+                              gol_island_kind *kinds, int64_t kinds_cap, int64_t *n_kinds);
+int gol_batch_islands_sym_check_host(const uint64_t *boards, int64_t n, int64_t H, int64_t W, int32_t reach, int32_t symmetry,
+                                     int64_t cap, const int64_t *count, const gol_island *islands, const uint64_t *fingerprint);
+int gol_batch_islands_tally_sym_check_host(const uint64_t *boards, int64_t n, int64_t H, int64_t W, int32_t reach,
+                                           int32_t symmetry, const int32_t *pairs, const int32_t *pair_count, int64_t max_pairs,
+                                           const int64_t *found, int64_t owner0, const int64_t *count,
+                                           const uint64_t *fingerprint, const gol_island_kind *table, int32_t table_log2,
+                                           const int64_t *dropped);
+uint64_t gol_island_orient_host(uint64_t code, int32_t reach, int32_t s);
 /* The argument check of the step launches (a host function, no GPU needed; the
  * function of csrc/gol_step_launch.h that every launch of a step kernel passes,
  * from gol_dev_bits_step, _band_step(_on), _rule_step, _bytes_step_k(_on) and from
@@ -1279,6 +1344,18 @@ int gol_dev_batch_islands_tally(const uint64_t *boards, int64_t n, int64_t H, in
                                 int64_t *count, uint64_t *fingerprint, gol_island_kind *table, int32_t table_log2,
                                 int64_t *dropped, void *stream);
 int gol_dev_island_table_clear(gol_island_kind *table, int32_t table_log2, int64_t *dropped, void *stream);
+/* The two launches above with the hash that symmetry selects ("island kinds
+ * free of orientation", above): GOL_ISLAND_FIXED is the entry without _sym,
+ * GOL_ISLAND_FREE writes free hashes and free fingerprints and tags the table
+ * with free hashes.  Arguments, outputs and refusals as those entries', and
+ * GOL_EINVAL, nothing launched, for a symmetry outside 0..1.  No version bump:
+ * probe by symbol. */
+int gol_dev_batch_islands_sym(const uint64_t *boards, int64_t n, int64_t H, int64_t W, int32_t reach, int32_t symmetry, int64_t cap,
+                              int64_t *count, gol_island *islands, uint64_t *fingerprint, void *stream);
+int gol_dev_batch_islands_tally_sym(const uint64_t *boards, int64_t n, int64_t H, int64_t W, int32_t reach, int32_t symmetry,
+                                    const int32_t *pairs, const int32_t *pair_count, int64_t max_pairs, const int64_t *found,
+                                    int64_t owner0, int64_t *count, uint64_t *fingerprint, gol_island_kind *table,
+                                    int32_t table_log2, int64_t *dropped, void *stream);
 /* Read and clear the error word of `device` (-1 = current) that the gol_dev_*
  * launchers' kernels report into (*flags = 0: no fault; nonzero: a pipeline
  * wave timed out waiting for its neighbour, so the launch's output is not
