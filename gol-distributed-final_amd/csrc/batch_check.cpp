@@ -16,34 +16,8 @@
 // against a scan of every soup written here, over shapes, rules, slot counts and launch lengths; its splitmix64 is its own.
 // `batch_check launch FILE`: gol_batch_launch_ok (gol_batch.h) and its export gol_batch_step_check_host on the launches of
 // a file that tests/test_batch_ref_cpu.py writes: the case table's launches and the refusal list, each with its answer.
-#include <stdarg.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <string.h>
-
-#include <vector>
-
+#include "check_common.h"
 #include "gol_batch.h"
-#include "golhip.h"
-
-static char g_msg[512];
-int gol_set_error(int code, const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_msg, sizeof g_msg, fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-static uint64_t g_state = 0x9E3779B97F4A7C15ULL;
-static uint64_t rnd()
-{
-    g_state ^= g_state << 13;
-    g_state ^= g_state >> 7;
-    g_state ^= g_state << 17;
-    return g_state;
-}
 
 static int cell(const uint64_t *b, int64_t stride, int64_t y, int64_t x) { return (int)(b[y * stride + x / 64] >> (x % 64) & 1); }
 
@@ -68,7 +42,7 @@ static int check(int64_t H, int64_t W, int64_t pad, uint32_t birth, uint32_t sur
 {
     const int64_t Ww = (W + 63) / 64, stride = Ww + pad;
     const size_t words = (size_t)((H - 1) * stride + Ww);
-    const uint64_t gap = 0xA5A5A5A5A5A5A5A5ULL;
+    const uint64_t gap = GAP;
     uint64_t *a = new uint64_t[words], *b = new uint64_t[words], *want = new uint64_t[words];
     for (size_t i = 0; i < words; ++i) a[i] = rnd() & rnd();  // (the padding bits of a row set, too)
     int bad = 0;
@@ -99,23 +73,33 @@ static int check(int64_t H, int64_t W, int64_t pad, uint32_t birth, uint32_t sur
     return bad;
 }
 
-// one call of gol_batch_cycles_host on a board of exact size (row r of `rows` at (y0, x0), 'O' alive, or
-// random cells when rows is NULL; the padding bits set), out of place or in place
-static int check_cycles(int64_t H, int64_t W, int64_t pad, uint32_t birth, uint32_t survive, const char *const *rows, int nrows,
-                        int64_t y0, int64_t x0, int64_t turns, bool in_place)
+// A board of exact size for check_cycles and check_run (delete[]): row r of `rows` at (y0, x0), 'O' alive, or random
+// cells when rows is NULL; the padding bits and the words between the rows GAP
+static uint64_t *pattern_board(int64_t H, int64_t W, int64_t stride, const char *const *rows, int nrows, int64_t y0, int64_t x0)
 {
-    const int64_t Ww = (W + 63) / 64, stride = Ww + pad;
+    const int64_t Ww = (W + 63) / 64;
     const size_t words = (size_t)((H - 1) * stride + Ww);
-    const uint64_t gap = 0xA5A5A5A5A5A5A5A5ULL, tail = W % 64 ? ((uint64_t)1 << (W % 64)) - 1 : ~(uint64_t)0;
-    uint64_t *a = new uint64_t[words], *b = new uint64_t[words];
+    const uint64_t tail = tail_of(W);
+    uint64_t *a = new uint64_t[words];
     for (size_t i = 0; i < words; ++i) a[i] = rows ? 0 : rnd() & rnd();
     for (int r = 0; r < nrows; ++r)
         for (int64_t c = 0; rows[r][c]; ++c)
             if (rows[r][c] == 'O') a[((y0 + r) % H) * stride + ((x0 + c) % W) / 64] |= (uint64_t)1 << (((x0 + c) % W) % 64);
     for (int64_t y = 0; y < H; ++y) {
-        a[y * stride + Ww - 1] = (a[y * stride + Ww - 1] & tail) | (gap & ~tail);  // padding bits set: never read
-        for (int64_t w = Ww; w < stride && y + 1 < H; ++w) a[y * stride + w] = gap;
+        a[y * stride + Ww - 1] = (a[y * stride + Ww - 1] & tail) | (GAP & ~tail);  // padding bits set: never read
+        for (int64_t w = Ww; w < stride && y + 1 < H; ++w) a[y * stride + w] = GAP;
     }
+    return a;
+}
+
+// one call of gol_batch_cycles_host on a board of exact size (pattern_board), out of place or in place
+static int check_cycles(int64_t H, int64_t W, int64_t pad, uint32_t birth, uint32_t survive, const char *const *rows, int nrows,
+                        int64_t y0, int64_t x0, int64_t turns, bool in_place)
+{
+    const int64_t Ww = (W + 63) / 64, stride = Ww + pad;
+    const size_t words = (size_t)((H - 1) * stride + Ww);
+    const uint64_t gap = GAP, tail = tail_of(W);
+    uint64_t *a = pattern_board(H, W, stride, rows, nrows, y0, x0), *b = new uint64_t[words];
     // the scan, naively: every state kept, the marks 0, 1, 3, 7, ... a list
     std::vector<std::vector<uint64_t>> st(1, std::vector<uint64_t>(a, a + words));
     for (int64_t y = 0; y < H; ++y) st[0][y * stride + Ww - 1] &= tail;
@@ -215,16 +199,8 @@ static int check_run(int64_t H, int64_t W, int64_t pad, uint32_t birth, uint32_t
 {
     const int64_t Ww = (W + 63) / 64, stride = Ww + pad;
     const size_t words = (size_t)((H - 1) * stride + Ww);
-    const uint64_t gap = 0xA5A5A5A5A5A5A5A5ULL, tail = W % 64 ? ((uint64_t)1 << (W % 64)) - 1 : ~(uint64_t)0;
-    uint64_t *a = new uint64_t[words], *b = new uint64_t[words], *want = new uint64_t[words];
-    for (size_t i = 0; i < words; ++i) a[i] = rows ? 0 : rnd() & rnd();
-    for (int r = 0; r < nrows; ++r)
-        for (int64_t c = 0; rows[r][c]; ++c)
-            if (rows[r][c] == 'O') a[(r % H) * stride + (c % W) / 64] |= (uint64_t)1 << ((c % W) % 64);
-    for (int64_t y = 0; y < H; ++y) {
-        a[y * stride + Ww - 1] = (a[y * stride + Ww - 1] & tail) | (gap & ~tail);  // padding bits set: never read
-        for (int64_t w = Ww; w < stride && y + 1 < H; ++w) a[y * stride + w] = gap;
-    }
+    const uint64_t gap = GAP;
+    uint64_t *a = pattern_board(H, W, stride, rows, nrows, 0, 0), *b = new uint64_t[words], *want = new uint64_t[words];
     for (size_t i = 0; i < words; ++i) want[i] = b[i] = gap;
     int64_t wf = 77, wp = 77, found = 77, period = 77, made = 77;
     int rc = gol_batch_cycles_host(H, W, birth, survive, a, want, stride, turns, &wf, &wp);
@@ -297,21 +273,13 @@ static int main_run()
     return bad ? 1 : 0;
 }
 
-static uint64_t mix(uint64_t x)  // splitmix64, written out here
-{
-    uint64_t z = x + 0x9E3779B97F4A7C15ULL;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-    return z ^ (z >> 31);
-}
-
 // one call of gol_batch_search_host on result arrays of exact size, against a scan of every soup written here: all states
 // kept, the marks a list, the census of the state at the found turn
 static int check_search(int64_t H, int64_t W, uint32_t birth, uint32_t survive, uint64_t seed, int64_t first, int64_t total,
                         int64_t slots, int64_t launch, int64_t horizon, int nulls)
 {
     const int64_t Ww = (W + 63) / 64, bw = H * Ww;
-    const uint64_t tail = W % 64 ? ((uint64_t)1 << (W % 64)) - 1 : ~(uint64_t)0;
+    const uint64_t tail = tail_of(W);
     int64_t *found = new int64_t[(size_t)total], *period = new int64_t[(size_t)total];
     uint64_t *alive = new uint64_t[(size_t)total], *hash = new uint64_t[(size_t)total];
     for (int64_t g = 0; g < total; ++g) found[g] = period[g] = 77, alive[g] = hash[g] = 77;

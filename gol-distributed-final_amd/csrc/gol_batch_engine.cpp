@@ -1,8 +1,8 @@
 // gol_batch_engine.cpp -- batches of small boards (include/golhip.h): the handle, the argument
 // checks, the rules per board, the split of a stepping call into launches (one gol_batch_launch per call,
-// gol_batch.h), the retiring call's lists and readbacks, the soup search's driver, the strided copies, and the
-// island census's chunks and scratch (gol_batch_islands), and the kind table of a tally (gol_batch_census,
-// gol_batch_islands_tally): its size, its clearing, its one read-back and the sort on the host.
+// gol_batch.h), the retiring call's lists and readbacks, the soup search's driver (with the census launch that
+// gol_batch_census adds to its harvest) and the strided copies.  The handle itself is gol_batch_int.h's; the island
+// census, the tally's kind table and their entries are gol_batch_census.cpp.
 // The kernels are gol_batch.hip (the step kernel), gol_batch_pass.hip (the rest) and gol_island.hip (the census),
 // the host twins gol_batch_host.cpp and gol_island_host.cpp.
 #include <hip/hip_runtime.h>
@@ -12,9 +12,7 @@
 #include <new>
 #include <vector>
 
-#include "gol_batch.h"
-#include "gol_engine_int.h"
-#include "gol_island.h"
+#include "gol_batch_int.h"
 
 // A launch is bounded to about this many cell-updates (and GOL_BATCH_MAX_TURNS turns), as the
 // broker's chunks are: no launch runs long, whatever the batch.
@@ -22,70 +20,8 @@
 #define GOL_BATCH_MAX_TURNS 4096
 // Strided loads and stores are staged through a dense host block of at most this many bytes.
 #define GOL_BATCH_STAGE_BYTES ((int64_t)64 << 20)
-// The island census cuts its range into chunks whose device scratch (counts, fingerprints, records) is at most this.
-#define GOL_ISLAND_SCRATCH_BYTES ((int64_t)256 << 20)
-
-struct gol_batch {
-    int64_t n = 0, H = 0, W = 0, Ww = 0;
-    int device = 0;
-    int tpl = 1;  // turns per launch at most
-    bool auto_tpl = false;  // the automatic length: run_cycles sizes each launch by the boards still in it
-    int wpb = 1, bpw = 1, nw = 1;
-    uint32_t birth = GOL_RULE_BIRTH_CONWAY, survive = GOL_RULE_SURVIVE_CONWAY;
-    // empty: every board under birth / survive; else n pairs (birth, survive), not all equal
-    std::vector<uint32_t> rules;
-    uint32_t *drules = nullptr;  // the device copy of `rules` (on demand), stale while rules_dirty
-    bool rules_dirty = false;
-    int64_t turn = 0;
-    hipStream_t stream = nullptr;
-    uint64_t *boards = nullptr;
-    uint64_t *prev = nullptr;  // state(start - 1) between the launches of a scanning call (on demand)
-    uint64_t *aux = nullptr;   // n words: the settle turns, the counts, the hashes (on demand)
-    // run_cycles (on demand): the active list, the finish list (n entries each) and the two counts; the turns left per board
-    int32_t *lists = nullptr;
-    int64_t *left = nullptr;
-    int32_t *hcounts = nullptr;  // pinned host memory: the two counts read back after every launch
-    // search (on demand): the active list (n), the harvest list (2 n), the soup per slot (n) and the four counts; born and
-    // the found age per slot (2 n); the result tables found, period, alive, hash, islands, fingerprint (6 tab_cap words);
-    // four pinned counts
-    int32_t *slists = nullptr;
-    int64_t *sages = nullptr;
-    int64_t *tab = nullptr;
-    int64_t tab_cap = 0;
-    int32_t *scounts = nullptr;
-    // islands (on demand, grown and reused): per chunk of boards the counts, the fingerprints and the records
-    unsigned char *isl = nullptr;
-    int64_t isl_bytes = 0;
-    // the tally of kinds (on demand, grown and reused): the table of kind_slots slots, then the counter `dropped`
-    gol_island_kind *kind = nullptr;
-    int64_t kind_slots = 0;
-};
 
 namespace {
-
-// The batch's device for the length of a call.
-struct OnDevice {
-    int before = -1;
-    hipError_t err;
-    explicit OnDevice(int device)
-    {
-        err = hipGetDevice(&before);
-        if (err == hipSuccess && before != device) err = hipSetDevice(device);
-    }
-    ~OnDevice()
-    {
-        if (before >= 0) (void)hipSetDevice(before);
-    }
-};
-
-// An on-demand device buffer of the batch (prev, aux, lists, left, slists, sages, drules): allocated at its first use,
-// freed by gol_batch_destroy.
-template <class T>
-int need(T *&p, int64_t count)
-{
-    if (!p) HIPCHK(hipMalloc(&p, (size_t)count * sizeof(T)));
-    return GOL_OK;
-}
 
 int auto_turns(int64_t boards, int64_t H, int64_t W)
 {
@@ -224,100 +160,22 @@ int run_cycles(gol_batch *b, int64_t turns, int64_t *out, std::vector<int64_t> &
     return GOL_OK;
 }
 
-// The kind table of one tally call: log2 from kinds_cap (the smallest power of two >= 2 max(kinds_cap, 512), at most 2^24).
-struct Tally {
-    int32_t reach = 1, symmetry = GOL_ISLAND_FIXED, log2 = 0;
-    gol_island_kind *table = nullptr;
-    int64_t *dropped = nullptr;
-};
-
-bool symmetry_ok(int32_t symmetry) { return symmetry == GOL_ISLAND_FIXED || symmetry == GOL_ISLAND_FREE; }
-
-bool tally_args_ok(int32_t reach, int32_t symmetry, const gol_island_kind *kinds, int64_t kinds_cap, const int64_t *n_kinds)
-{
-    return reach >= 1 && reach <= GOL_ISLAND_MAX_REACH && symmetry_ok(symmetry) && kinds_cap >= 0 && kinds_cap <= ((int64_t)1 << 23) && n_kinds &&
-           (kinds_cap == 0 || kinds);
-}
-
-// The handle's table sized for kinds_cap and set to empty, `dropped` to 0.
-int tally_begin(gol_batch *b, int32_t reach, int32_t symmetry, int64_t kinds_cap, Tally *t)
-{
-    t->reach = reach;
-    t->symmetry = symmetry;
-    t->log2 = 10;
-    while (((int64_t)1 << t->log2) < 2 * kinds_cap) t->log2 += 1;
-    const int64_t slots = (int64_t)1 << t->log2;
-    if (b->kind_slots < slots) {
-        if (b->kind) HIPCHK(hipFree(b->kind));
-        b->kind = nullptr;
-        b->kind_slots = 0;
-        HIPCHK(hipMalloc(&b->kind, (size_t)(slots + 1) * sizeof(gol_island_kind)));
-        b->kind_slots = slots;
-    }
-    t->table = b->kind;
-    t->dropped = (int64_t *)(b->kind + slots);
-    HIPCHK(golk_island_table_clear(t->table, t->log2, t->dropped, b->stream));
-    return GOL_OK;
-}
-
-// The one read-back of a tally: `dropped`, and unless it is set the table, its kinds unpacked and sorted.
-int tally_end(gol_batch *b, const Tally &t, const char *what, gol_island_kind *kinds, int64_t kinds_cap, int64_t *n_kinds)
-{
-    const int64_t slots = (int64_t)1 << t.log2;
-    int64_t dropped = 0;
-    HIPCHK(hipMemcpyAsync(&dropped, t.dropped, sizeof dropped, hipMemcpyDeviceToHost, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
-    *n_kinds = -1;
-    if (dropped != 0)
-        return gol_set_error(GOL_ENOMEM, "batch %s: the table of %lld kinds that kinds_cap %lld asks for is full, %lld islands not tallied",
-                             what, (long long)slots, (long long)kinds_cap, (long long)dropped);
-    std::vector<gol_island_kind> all;
-    try {
-        all.resize((size_t)slots);
-    } catch (const std::exception &) {
-        return gol_set_error(GOL_ENOMEM, "batch %s: a table of %lld kinds", what, (long long)slots);
-    }
-    HIPCHK(hipMemcpyAsync(all.data(), t.table, (size_t)slots * sizeof(gol_island_kind), hipMemcpyDeviceToHost, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
-    size_t kept = 0;
-    for (const gol_island_kind &k : all) {
-        if (k.hash == 0) continue;
-        const gol_island_slot &d = reinterpret_cast<const gol_island_slot &>(k);  // (the device layout: the shape packed)
-        const uint64_t shape = d.shape;
-        all[kept] = k;
-        all[kept].cells = (int32_t)(shape >> 32), all[kept].rows = (uint16_t)(shape >> 16), all[kept].cols = (uint16_t)shape;
-        kept += 1;
-    }
-    all.resize(kept);
-    std::sort(all.begin(), all.end(), gol_island_kind_before);
-    if (kept) memcpy(kinds, all.data(), (size_t)std::min<int64_t>((int64_t)kept, kinds_cap) * sizeof(gol_island_kind));
-    *n_kinds = (int64_t)kept;
-    return GOL_OK;
-}
-
 // gol_batch_search on st->slots = min(n, total) slots in launches of st->launch_turns turns: the first fill, then per
 // launch the aged step over the active list, the restock pass, the harvest and the refill of the slots it names, and a
 // blocking read of the counts, until no slot is active.  The tables live on the device and are copied out once.
 // tally (gol_batch_census; else NULL): after the harvest, the listed TALLY census of the same harvest list, on the
 // snapshots, into the tables islands and fingerprint and the kind table.
-int search(gol_batch *b, uint64_t seed, int64_t first, int64_t total, int64_t horizon, int64_t *found, int64_t *period,
-           uint64_t *alive, uint64_t *hash, gol_batch_search_stats *st, const Tally *tally, int64_t *islands,
-           uint64_t *fingerprint)
+int search(gol_batch *b, uint64_t seed, int64_t first, int64_t total, int64_t horizon, const gol_batch_soup_out &out,
+           gol_batch_search_stats *st, const gol_batch_tally *tally)
 {
     const int64_t n = b->n, m = st->slots;
     const int L = (int)st->launch_turns;
     int rc = need(b->prev, n * b->H * b->Ww);
     if (!rc) rc = need(b->slists, 4 * n + 4);
     if (!rc) rc = need(b->sages, 2 * n);
+    if (!rc) rc = grow(b->tab, b->tab_words, 6 * total);
     if (rc) return rc;
     if (!b->scounts) HIPCHK(hipHostMalloc(&b->scounts, 4 * sizeof(int32_t), hipHostMallocDefault));
-    if (b->tab_cap < total) {
-        if (b->tab) HIPCHK(hipFree(b->tab));
-        b->tab = nullptr;
-        b->tab_cap = 0;
-        HIPCHK(hipMalloc(&b->tab, (size_t)(6 * total) * sizeof(int64_t)));
-        b->tab_cap = total;
-    }
     int32_t *active = b->slists, *harvest = b->slists + n, *soup = b->slists + 3 * n, *counts = b->slists + 4 * n;
     int64_t *born = b->sages, *age = b->sages + n;
     int64_t *tfound = b->tab, *tperiod = b->tab + total;
@@ -357,59 +215,14 @@ int search(gol_batch *b, uint64_t seed, int64_t first, int64_t total, int64_t ho
     }
     st->full_turns = st->launches * m * L;
     const size_t bytes = (size_t)total * sizeof(int64_t);
-    HIPCHK(hipMemcpyAsync(found, tfound, bytes, hipMemcpyDeviceToHost, b->stream));
-    if (period) HIPCHK(hipMemcpyAsync(period, tperiod, bytes, hipMemcpyDeviceToHost, b->stream));
-    if (alive) HIPCHK(hipMemcpyAsync(alive, talive, bytes, hipMemcpyDeviceToHost, b->stream));
-    if (hash) HIPCHK(hipMemcpyAsync(hash, thash, bytes, hipMemcpyDeviceToHost, b->stream));
-    if (tally && islands) HIPCHK(hipMemcpyAsync(islands, tislands, bytes, hipMemcpyDeviceToHost, b->stream));
-    if (tally && fingerprint) HIPCHK(hipMemcpyAsync(fingerprint, tfp, bytes, hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipMemcpyAsync(out.found, tfound, bytes, hipMemcpyDeviceToHost, b->stream));
+    if (out.period) HIPCHK(hipMemcpyAsync(out.period, tperiod, bytes, hipMemcpyDeviceToHost, b->stream));
+    if (out.alive) HIPCHK(hipMemcpyAsync(out.alive, talive, bytes, hipMemcpyDeviceToHost, b->stream));
+    if (out.hash) HIPCHK(hipMemcpyAsync(out.hash, thash, bytes, hipMemcpyDeviceToHost, b->stream));
+    if (tally && out.islands) HIPCHK(hipMemcpyAsync(out.islands, tislands, bytes, hipMemcpyDeviceToHost, b->stream));
+    if (tally && out.fingerprint) HIPCHK(hipMemcpyAsync(out.fingerprint, tfp, bytes, hipMemcpyDeviceToHost, b->stream));
     HIPCHK(hipStreamSynchronize(b->stream));
     return GOL_OK;
-}
-
-// gol_batch_search and gol_batch_census (tally_kinds: its kinds_cap, n_kinds and kinds; census == false: none).
-int search_call(gol_batch *b, uint64_t seed, int64_t first, int64_t total, int64_t horizon, int64_t *found, int64_t *period,
-                uint64_t *alive, uint64_t *hash, gol_batch_search_stats *stats, bool census, int32_t reach, int32_t symmetry,
-                int64_t *islands, uint64_t *fingerprint, gol_island_kind *kinds, int64_t kinds_cap, int64_t *n_kinds)
-{
-    const char *what = census ? "census" : "search";
-    if (!b || !found || first < 0 || total < 0 || horizon < 0 || first > ((int64_t)1 << 40) || total > ((int64_t)1 << 26) ||
-        first + total > ((int64_t)1 << 40))
-        return gol_set_error(GOL_EINVAL, "bad batch %s (soups [%lld, +%lld) in 0..2^40, at most 2^26, horizon %lld, or NULL)", what,
-                             (long long)first, (long long)total, (long long)horizon);
-    if (census && !tally_args_ok(reach, symmetry, kinds, kinds_cap, n_kinds))
-        return gol_set_error(GOL_EINVAL, "bad batch census (reach %d in 1..2, symmetry %d in 0..1, kinds_cap %lld in 0..2^23, or NULL)",
-                             reach, symmetry, (long long)kinds_cap);
-    if (!b->rules.empty()) return gol_set_error(GOL_ESTATE, "batch %s: the boards of the batch have different rules", what);
-    OnDevice dev(b->device);
-    HIPCHK(dev.err);
-    const int64_t m = std::min(b->n, total);
-    // every launch makes L turns (no longer than the horizon), so ages are multiples of L
-    const int64_t L = std::max<int64_t>(1, std::min<int64_t>(b->auto_tpl ? auto_turns(std::max<int64_t>(m, 1), b->H, b->W) : b->tpl,
-                                                             horizon));
-    gol_batch_search_stats st{};
-    st.slots = m;
-    st.launch_turns = L;
-    Tally tally;
-    int tallied = GOL_OK;  // (a full table: the per-soup outputs stand, the call ends as after a search, and then says so)
-    if (total > 0 && horizon > 0) {
-        int rc = census ? tally_begin(b, reach, symmetry, kinds_cap, &tally) : GOL_OK;
-        if (!rc) rc = search(b, seed, first, total, horizon, found, period, alive, hash, &st, census ? &tally : nullptr, islands, fingerprint);
-        if (rc) return rc;
-        if (census) tallied = tally_end(b, tally, what, kinds, kinds_cap, n_kinds);
-    } else {  // nothing to run
-        gol_batch_no_results(total, found, period, alive, hash);
-        for (int64_t g = 0; census && g < total; ++g) {
-            if (islands) islands[g] = 0;
-            if (fingerprint) fingerprint[g] = 0;
-        }
-        if (census) *n_kinds = 0;
-    }
-    HIPCHK(hipMemsetAsync(b->boards, 0, (size_t)(b->n * b->H * b->Ww) * sizeof(uint64_t), b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));
-    b->turn = 0;
-    if (stats) *stats = st;
-    return tallied;
 }
 
 // gol_batch_load_words (load) and gol_batch_store_words: boards [i0, i1) between the caller's rows, row_stride and
@@ -449,6 +262,50 @@ int copy_words(gol_batch *b, bool load, int64_t i0, int64_t i1, uint64_t *words,
 }
 
 }  // namespace
+
+// gol_batch_search (ask NULL) and gol_batch_census_sym (gol_batch_census.cpp).
+int gol_batch_search_call(gol_batch *b, uint64_t seed, int64_t first, int64_t total, int64_t horizon, const gol_batch_soup_out &out,
+                          const gol_batch_census_ask *ask, gol_batch_search_stats *stats)
+{
+    const char *what = ask ? "census" : "search";
+    if (!b || !out.found || first < 0 || total < 0 || horizon < 0 || first > ((int64_t)1 << 40) || total > ((int64_t)1 << 26) ||
+        first + total > ((int64_t)1 << 40))
+        return gol_set_error(GOL_EINVAL, "bad batch %s (soups [%lld, +%lld) in 0..2^40, at most 2^26, horizon %lld, or NULL)", what,
+                             (long long)first, (long long)total, (long long)horizon);
+    if (ask && !gol_batch_tally_args_ok(*ask))
+        return gol_set_error(GOL_EINVAL, "bad batch census (reach %d in 1..2, symmetry %d in 0..1, kinds_cap %lld in 0..2^23, or NULL)",
+                             ask->reach, ask->symmetry, (long long)ask->kinds_cap);
+    if (!b->rules.empty()) return gol_set_error(GOL_ESTATE, "batch %s: the boards of the batch have different rules", what);
+    OnDevice dev(b->device);
+    HIPCHK(dev.err);
+    const int64_t m = std::min(b->n, total);
+    // every launch makes L turns (no longer than the horizon), so ages are multiples of L
+    const int64_t L = std::max<int64_t>(1, std::min<int64_t>(b->auto_tpl ? auto_turns(std::max<int64_t>(m, 1), b->H, b->W) : b->tpl,
+                                                             horizon));
+    gol_batch_search_stats st{};
+    st.slots = m;
+    st.launch_turns = L;
+    gol_batch_tally tally;
+    int tallied = GOL_OK;  // (a full table: the per-soup outputs stand, the call ends as after a search, and then says so)
+    if (total > 0 && horizon > 0) {
+        int rc = ask ? gol_batch_tally_begin(b, *ask, &tally) : GOL_OK;
+        if (!rc) rc = search(b, seed, first, total, horizon, out, &st, ask ? &tally : nullptr);
+        if (rc) return rc;
+        if (ask) tallied = gol_batch_tally_end(b, tally, what, *ask);
+    } else {  // nothing to run
+        gol_batch_no_results(total, out.found, out.period, out.alive, out.hash);
+        for (int64_t g = 0; ask && g < total; ++g) {
+            if (out.islands) out.islands[g] = 0;
+            if (out.fingerprint) out.fingerprint[g] = 0;
+        }
+        if (ask) *ask->n_kinds = 0;
+    }
+    HIPCHK(hipMemsetAsync(b->boards, 0, (size_t)(b->n * b->H * b->Ww) * sizeof(uint64_t), b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    b->turn = 0;
+    if (stats) *stats = st;
+    return tallied;
+}
 
 extern "C" void gol_batch_destroy(gol_batch *b)
 {
@@ -623,26 +480,7 @@ extern "C" int gol_batch_load_soups(gol_batch *b, uint64_t seed, int64_t first)
 extern "C" int gol_batch_search(gol_batch *b, uint64_t seed, int64_t first, int64_t total, int64_t horizon, int64_t *found,
                                 int64_t *period, uint64_t *alive, uint64_t *hash, gol_batch_search_stats *stats)
 {
-    return search_call(b, seed, first, total, horizon, found, period, alive, hash, stats, false, 0, 0, nullptr, nullptr, nullptr, 0,
-                       nullptr);
-}
-
-extern "C" int gol_batch_census_sym(gol_batch *b, uint64_t seed, int64_t first, int64_t total, int64_t horizon, int32_t reach,
-                                    int32_t symmetry, int64_t *found, int64_t *period, uint64_t *alive, uint64_t *hash,
-                                    int64_t *islands, uint64_t *fingerprint, gol_island_kind *kinds, int64_t kinds_cap,
-                                    int64_t *n_kinds, gol_batch_search_stats *stats)
-{
-    return search_call(b, seed, first, total, horizon, found, period, alive, hash, stats, true, reach, symmetry, islands, fingerprint,
-                       kinds, kinds_cap, n_kinds);
-}
-
-extern "C" int gol_batch_census(gol_batch *b, uint64_t seed, int64_t first, int64_t total, int64_t horizon, int32_t reach,
-                                int64_t *found, int64_t *period, uint64_t *alive, uint64_t *hash, int64_t *islands,
-                                uint64_t *fingerprint, gol_island_kind *kinds, int64_t kinds_cap, int64_t *n_kinds,
-                                gol_batch_search_stats *stats)
-{
-    return gol_batch_census_sym(b, seed, first, total, horizon, reach, GOL_ISLAND_FIXED, found, period, alive, hash, islands,
-                                fingerprint, kinds, kinds_cap, n_kinds, stats);
+    return gol_batch_search_call(b, seed, first, total, horizon, {found, period, alive, hash, nullptr, nullptr}, nullptr, stats);
 }
 
 extern "C" int gol_batch_step(gol_batch *b, int64_t turns, int64_t *settled)
@@ -687,121 +525,6 @@ extern "C" int gol_batch_run_cycles(gol_batch *b, int64_t turns, int64_t *found,
         }
     }
     return GOL_OK;
-}
-
-// The census of boards [i0, i1) in chunks of at most `per` boards, one launch each: the chunk's counts and fingerprints
-// come back whole, of its records the first min(dcap, the chunk's largest count) of every board in one strided copy to
-// a host block, from which a board's own records go to the caller's.  No board holds more than H W islands, so the
-// device never keeps more records per board than that, whatever cap says.
-extern "C" int gol_batch_islands_sym(gol_batch *b, int64_t i0, int64_t i1, int32_t reach, int32_t symmetry, int64_t cap,
-                                     int64_t *count, gol_island *islands, uint64_t *fingerprint)
-{
-    if (!b || !count || i0 < 0 || i0 > i1 || i1 > b->n || reach < 1 || reach > GOL_ISLAND_MAX_REACH || !symmetry_ok(symmetry) ||
-        cap < 0 || (cap > 0 && !islands))
-        return gol_set_error(GOL_EINVAL,
-                             "bad batch islands (boards [%lld, %lld) of %lld, reach %d in 1..2, symmetry %d in 0..1, cap %lld, or NULL)",
-                             (long long)i0, (long long)i1, b ? (long long)b->n : 0LL, reach, symmetry, (long long)cap);
-    if (i0 == i1) return GOL_OK;
-    OnDevice dev(b->device);
-    HIPCHK(dev.err);
-    const int64_t dcap = std::min(cap, b->H * b->W), rec = (int64_t)sizeof(gol_island);
-    const int64_t each = 2 * (int64_t)sizeof(int64_t) + dcap * rec;  // bytes of a board's scratch
-    const int64_t per = std::min(i1 - i0, std::max<int64_t>(1, GOL_ISLAND_SCRATCH_BYTES / each));
-    if (b->isl_bytes < per * each) {
-        if (b->isl) HIPCHK(hipFree(b->isl));
-        b->isl = nullptr;
-        b->isl_bytes = 0;
-        HIPCHK(hipMalloc(&b->isl, (size_t)(per * each)));
-        b->isl_bytes = per * each;
-    }
-    int64_t *dcount = (int64_t *)b->isl;
-    uint64_t *dfp = (uint64_t *)(b->isl + per * 8);
-    gol_island *drec = (gol_island *)(b->isl + per * 16);
-    std::vector<gol_island> stage;
-    for (int64_t c0 = i0; c0 < i1; c0 += per) {
-        const int64_t m = std::min(per, i1 - c0);
-        const gol_island_launch l = {b->boards + c0 * b->H * b->Ww, m, b->H, b->W, reach, symmetry, dcap, dcount, dcap ? drec : nullptr,
-                                     dfp};
-        HIPCHK(golk_batch_islands(l, b->stream));
-        HIPCHK(hipMemcpyAsync(count + (c0 - i0), dcount, (size_t)m * sizeof(int64_t), hipMemcpyDeviceToHost, b->stream));
-        if (fingerprint)
-            HIPCHK(hipMemcpyAsync(fingerprint + (c0 - i0), dfp, (size_t)m * sizeof(uint64_t), hipMemcpyDeviceToHost, b->stream));
-        HIPCHK(hipStreamSynchronize(b->stream));
-        int64_t most = 0;
-        for (int64_t i = c0; i < c0 + m; ++i) {
-            if (count[i - i0] < 0) return gol_set_error(GOL_EHIP, "batch islands: board %lld reached the census's trip bound", (long long)i);
-            most = std::max(most, std::min(count[i - i0], dcap));
-        }
-        if (most == 0) continue;
-        try {
-            stage.resize((size_t)(m * most));
-        } catch (const std::exception &) {
-            return gol_set_error(GOL_ENOMEM, "batch islands: %lld records of %lld boards", (long long)most, (long long)m);
-        }
-        HIPCHK(hipMemcpy2DAsync(stage.data(), (size_t)(most * rec), drec, (size_t)(dcap * rec), (size_t)(most * rec), (size_t)m,
-                                hipMemcpyDeviceToHost, b->stream));
-        HIPCHK(hipStreamSynchronize(b->stream));
-        for (int64_t i = c0; i < c0 + m; ++i)
-            memcpy(islands + (i - i0) * cap, stage.data() + (i - c0) * most, (size_t)(std::min(count[i - i0], dcap) * rec));
-    }
-    return GOL_OK;
-}
-
-extern "C" int gol_batch_islands(gol_batch *b, int64_t i0, int64_t i1, int32_t reach, int64_t cap, int64_t *count,
-                                 gol_island *islands, uint64_t *fingerprint)
-{
-    return gol_batch_islands_sym(b, i0, i1, reach, GOL_ISLAND_FIXED, cap, count, islands, fingerprint);
-}
-
-// The tally of boards [i0, i1) as they stand: the chunks of gol_batch_islands (counts and fingerprints alone in the
-// scratch), each one dense TALLY launch with owner = the board's index, then the table's one read-back.
-extern "C" int gol_batch_islands_tally_sym(gol_batch *b, int64_t i0, int64_t i1, int32_t reach, int32_t symmetry, int64_t *count,
-                                           uint64_t *fingerprint, gol_island_kind *kinds, int64_t kinds_cap, int64_t *n_kinds)
-{
-    if (!b || !count || i0 < 0 || i0 > i1 || i1 > b->n || !tally_args_ok(reach, symmetry, kinds, kinds_cap, n_kinds))
-        return gol_set_error(GOL_EINVAL,
-                             "bad batch islands_tally (boards [%lld, %lld) of %lld, reach %d in 1..2, symmetry %d in 0..1, kinds_cap "
-                             "%lld in 0..2^23, or NULL)",
-                             (long long)i0, (long long)i1, b ? (long long)b->n : 0LL, reach, symmetry, (long long)kinds_cap);
-    if (i0 == i1) {
-        *n_kinds = 0;
-        return GOL_OK;
-    }
-    OnDevice dev(b->device);
-    HIPCHK(dev.err);
-    const int64_t each = 2 * (int64_t)sizeof(int64_t);  // bytes of a board's scratch
-    const int64_t per = std::min(i1 - i0, std::max<int64_t>(1, GOL_ISLAND_SCRATCH_BYTES / each));
-    if (b->isl_bytes < per * each) {
-        if (b->isl) HIPCHK(hipFree(b->isl));
-        b->isl = nullptr;
-        b->isl_bytes = 0;
-        HIPCHK(hipMalloc(&b->isl, (size_t)(per * each)));
-        b->isl_bytes = per * each;
-    }
-    int64_t *dcount = (int64_t *)b->isl;
-    uint64_t *dfp = (uint64_t *)(b->isl + per * 8);
-    Tally t;
-    const int rc = tally_begin(b, reach, symmetry, kinds_cap, &t);
-    if (rc) return rc;
-    for (int64_t c0 = i0; c0 < i1; c0 += per) {
-        const int64_t m = std::min(per, i1 - c0);
-        const gol_island_launch l = {b->boards + c0 * b->H * b->Ww, m, b->H, b->W, reach, symmetry, 0, dcount, nullptr, dfp, t.table,
-                                     t.log2, t.dropped, c0};
-        HIPCHK(golk_batch_islands(l, b->stream));
-        HIPCHK(hipMemcpyAsync(count + (c0 - i0), dcount, (size_t)m * sizeof(int64_t), hipMemcpyDeviceToHost, b->stream));
-        if (fingerprint)
-            HIPCHK(hipMemcpyAsync(fingerprint + (c0 - i0), dfp, (size_t)m * sizeof(uint64_t), hipMemcpyDeviceToHost, b->stream));
-        HIPCHK(hipStreamSynchronize(b->stream));
-        for (int64_t i = c0; i < c0 + m; ++i)
-            if (count[i - i0] < 0) return gol_set_error(GOL_EHIP, "batch islands_tally: board %lld reached the census's trip bound", (long long)i);
-    }
-    return tally_end(b, t, "islands_tally", kinds, kinds_cap, n_kinds);
-}
-
-extern "C" int gol_batch_islands_tally(gol_batch *b, int64_t i0, int64_t i1, int32_t reach, int64_t *count, uint64_t *fingerprint,
-                                       gol_island_kind *kinds, int64_t kinds_cap, int64_t *n_kinds)
-{
-    return gol_batch_islands_tally_sym(b, i0, i1, reach, GOL_ISLAND_FIXED, count, fingerprint, kinds, kinds_cap, n_kinds);
 }
 
 extern "C" int gol_batch_alive_counts(gol_batch *b, uint64_t *counts, int64_t cap) { return reduce(b, false, counts, cap); }

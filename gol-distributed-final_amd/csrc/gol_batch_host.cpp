@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "gol_batch.h"
+#include "gol_island.h"
 #include "golhip.h"
 
 int gol_set_error(int code, const char *fmt, ...);
@@ -272,8 +273,7 @@ extern "C" int gol_batch_census_sym_host(int64_t H, int64_t W, uint32_t birth, u
                                          int64_t *islands, uint64_t *fingerprint, gol_island_kind *kinds, int64_t kinds_cap,
                                          int64_t *n_kinds)
 {
-    if (reach < 1 || reach > 2 || (symmetry != GOL_ISLAND_FIXED && symmetry != GOL_ISLAND_FREE) || kinds_cap < 0 || !n_kinds ||
-        (kinds_cap > 0 && !kinds))
+    if (!gol_island_mode_ok(reach, symmetry) || kinds_cap < 0 || !n_kinds || (kinds_cap > 0 && !kinds))
         return gol_set_error(GOL_EINVAL, "bad host batch census (reach %d in 1..2, symmetry %d in 0..1, kinds_cap %lld, or NULL)", reach,
                              symmetry, (long long)kinds_cap);
     // every record of every found soup, then the tally; the outputs are written once nothing can fail

@@ -15,7 +15,8 @@
 //   - the hash of the cells of M in one row, and its FREE form: a code in the eight orientations of the square
 //     (gol_island_orient), the eight sums of a row and their minimum, the free hash;
 //   - the descriptor of one launch, plain or TALLY, with the one check of what makes it valid;
-//   - the kind table of a tally: the packed shape, the empty slot, the home slot and the probe step.
+//   - the kind table of a tally: the packed shape and its unpacking, the empty slot, the home slot and the probe step;
+//   - the check of a census's reach and symmetry (gol_island_mode_ok).
 #pragma once
 #include <stdint.h>
 
@@ -42,6 +43,11 @@ GOL_BATCH_HD uint64_t gol_island_shape_pack(int32_t cells, uint32_t rows, uint32
 {
     return (uint64_t)(uint32_t)cells << 32 | (uint64_t)(rows & 0xffffu) << 16 | (uint64_t)(cols & 0xffffu);
 }
+// A filled slot as the kind a caller reads: the shape unpacked.
+GOL_BATCH_HD gol_island_kind gol_island_slot_kind(const gol_island_slot &s)
+{
+    return {s.hash, (int64_t)s.count, (int64_t)s.first, (int32_t)(s.shape >> 32), (uint16_t)(s.shape >> 16), (uint16_t)s.shape};
+}
 // The tag a hash is tallied under: 0 is the empty slot's.
 GOL_BATCH_HD uint64_t gol_island_tally_tag(uint64_t hash) { return hash ? hash : 1u; }
 // The home slot of a tag in a table of 2^log2 slots, and the slot a probe visits after `slot`.
@@ -54,6 +60,12 @@ GOL_BATCH_HD bool gol_island_kind_before(const gol_island_kind &a, const gol_isl
 GOL_BATCH_HD uint64_t gol_island_tally_next(uint64_t slot, int32_t log2) { return (slot + 1u) & (((uint64_t)1 << log2) - 1u); }
 
 GOL_BATCH_HD uint64_t gol_island_term(uint64_t code, int32_t reach) { return gol_batch_splitmix64(code ^ ((uint64_t)reach << 32)); }
+
+// The reach and the symmetry of a census: the one place they are checked, for launches, entries and twins alike.
+GOL_BATCH_HD bool gol_island_mode_ok(int32_t reach, int32_t symmetry)
+{
+    return reach >= 1 && reach <= GOL_ISLAND_MAX_REACH && (symmetry == GOL_ISLAND_FIXED || symmetry == GOL_ISLAND_FREE);
+}
 
 // One launch of the census, as gol_dev_batch_islands (table NULL: plain, the fields after fingerprint 0) or
 // gol_dev_batch_islands_tally (table not NULL: TALLY, cap 0) takes it; the pointers are device memory.
@@ -81,8 +93,7 @@ struct gol_island_launch {
 GOL_BATCH_HD bool gol_island_launch_ok(const gol_island_launch &l)
 {
     if (!l.boards || !l.count || !gol_batch_shape_ok(l.n, l.H, l.W)) return false;
-    if (l.reach < 1 || l.reach > GOL_ISLAND_MAX_REACH || l.cap < 0) return false;
-    if (l.symmetry != GOL_ISLAND_FIXED && l.symmetry != GOL_ISLAND_FREE) return false;
+    if (!gol_island_mode_ok(l.reach, l.symmetry) || l.cap < 0) return false;
     if (!l.pairs && (l.pair_count || l.found || l.max_pairs != 0)) return false;
     if (!l.table)  // plain
         return (l.cap == 0 || l.islands != nullptr) && !l.dropped && !l.pairs && l.table_log2 == 0 && l.owner0 == 0;

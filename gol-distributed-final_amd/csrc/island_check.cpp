@@ -4,106 +4,18 @@
 // plain child process by tests/test_island_ref_cpu.py.  The board is a heap block of its exact size -- (H - 1) * stride
 // + ceil(W / 64) words, its padding bits and the words between its rows set -- and the records a heap block of exactly
 // `cap` records, so a read or write past either is a sanitizer report.  Every shape runs both reaches at three
-// densities and three caps against a flood fill written here, cell by cell, with its own splitmix64: the count, the
+// densities and three caps against the flood fill of check_common.h, cell by cell, with its own splitmix64: the count, the
 // first min(count, cap) records, the fingerprint, and the records past them untouched.  Then the refusals, which write
 // nothing.  Exit status 0: all equal; 1: a difference (printed).
-#include <stdarg.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <string.h>
-
-#include <algorithm>
-#include <vector>
-
-#include "golhip.h"
-
-static char g_msg[512];
-int gol_set_error(int code, const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_msg, sizeof g_msg, fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-static uint64_t g_state = 0x9E3779B97F4A7C15ULL;
-static uint64_t rnd()
-{
-    g_state ^= g_state << 13;
-    g_state ^= g_state >> 7;
-    g_state ^= g_state << 17;
-    return g_state;
-}
-
-static uint64_t mix(uint64_t x)  // splitmix64, written out here
-{
-    uint64_t z = x + 0x9E3779B97F4A7C15ULL;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-    return z ^ (z >> 31);
-}
-
-// the census of the H x W cells of `cell`, by the definition of golhip.h
-static void naive(int64_t H, int64_t W, int reach, const std::vector<uint8_t> &cell, std::vector<gol_island> &out, uint64_t *fp)
-{
-    std::vector<uint8_t> seen((size_t)(H * W), 0);
-    std::vector<int64_t> stack;
-    out.clear();
-    *fp = 0;
-    auto at = [&](int64_t y, int64_t x) { return (size_t)((((y % H) + H) % H) * W + (((x % W) + W) % W)); };
-    for (int64_t i = 0; i < H * W; ++i) {
-        if (!cell[(size_t)i] || seen[(size_t)i]) continue;
-        gol_island r = {(int32_t)(i / W), (int32_t)(i % W), 0, 0, 0, 0};
-        std::vector<uint8_t> rows((size_t)H, 0), cols((size_t)W, 0);
-        stack.assign(1, i);
-        seen[(size_t)i] = 1;
-        while (!stack.empty()) {
-            const int64_t c = stack.back(), y = c / W, x = c % W;
-            stack.pop_back();
-            uint64_t code = 0;
-            for (int dy = -reach; dy <= reach; ++dy)
-                for (int dx = -reach; dx <= reach; ++dx) {
-                    const size_t o = at(y + dy, x + dx);
-                    if (!cell[o]) continue;
-                    code += (uint64_t)1 << ((dy + reach) * (2 * reach + 1) + (dx + reach));
-                    if (!seen[o]) seen[o] = 1, stack.push_back((int64_t)o);
-                }
-            r.cells += 1;
-            r.rows += !rows[(size_t)y];
-            r.cols += !cols[(size_t)x];
-            rows[(size_t)y] = cols[(size_t)x] = 1;
-            r.hash += mix(code ^ ((uint64_t)reach << 32));
-        }
-        out.push_back(r);
-        *fp += r.hash;
-    }
-}
-
-static bool same(const gol_island &a, const gol_island &b)
-{
-    return a.y == b.y && a.x == b.x && a.cells == b.cells && a.rows == b.rows && a.cols == b.cols && a.hash == b.hash;
-}
+#include "check_common.h"
 
 static int check(int64_t H, int64_t W, int64_t pad, int reach, int density, int64_t cap)
 {
-    const int64_t Ww = (W + 63) / 64, stride = Ww + pad;
-    const size_t words = (size_t)((H - 1) * stride + Ww);
-    const uint64_t gap = 0xA5A5A5A5A5A5A5A5ULL, tail = W % 64 ? ((uint64_t)1 << (W % 64)) - 1 : ~(uint64_t)0;
-    uint64_t *b = new uint64_t[words];
-    std::vector<uint8_t> cell((size_t)(H * W), 0);
-    for (size_t i = 0; i < words; ++i) b[i] = gap;
-    for (int64_t y = 0; y < H; ++y) {
-        for (int64_t w = 0; w < Ww; ++w) {
-            uint64_t v = density == 0 ? rnd() & rnd() & rnd() & rnd() & rnd() : (density == 1 ? rnd() & rnd() & rnd() : rnd());
-            if (w == Ww - 1) v = (v & tail) | (gap & ~tail);  // padding bits set: never read
-            b[y * stride + w] = v;
-        }
-        for (int64_t x = 0; x < W; ++x) cell[(size_t)(y * W + x)] = (uint8_t)(b[y * stride + x / 64] >> (x % 64) & 1);
-    }
+    const int64_t stride = (W + 63) / 64 + pad;
+    uint64_t *b = random_board(H, W, stride, density);
     std::vector<gol_island> want;
     uint64_t want_fp;
-    naive(H, W, reach, cell, want, &want_fp);
+    flood(H, W, reach, GOL_ISLAND_FIXED, cells_of(b, H, W, stride), want, &want_fp);
     gol_island *got = new gol_island[(size_t)cap];
     memset(got, 0xA5, (size_t)cap * sizeof(gol_island));
     int64_t count = 77;

@@ -182,3 +182,71 @@ def test_named_patterns_are_found_again(G):
             names = {(int(r["cells"]), int(r["rows"]), int(r["cols"]), int(r["hash"])): k
                      for k, r in ((k, G.island(t, reach)) for k, t in pats.items())}
             assert sorted(names[k] for k in I.key(recs[0, :3])) == ["beehive", "blinker", "block"]
+
+
+# --------------------------------------------------------------------------------- more than one scratch chunk
+CHUNK_N, CHUNK_SIDE, CHUNK_FIRST = 44, 512, 1
+CHUNK_PATTERNS = ("x = 3, y = 3\nbo$2bo$3o!", "x = 2, y = 2\n2o$2o!", "x = 4, y = 3\nb2o$o2bo$b2o!", "x = 3, y = 3\n2o$obo$bo!",
+                  "x = 3, y = 3\nbo$2bo$3o!")  # glider, block, beehive, boat, glider
+
+
+def _chunk_boards(G):
+    """Board i: 1 + i % 5 objects, CHUNK_PATTERNS[k] at a place that depends on i.  Object 0, a glider, lies in rows
+    63 to 65 (the lanes of two waves); object 1, a block, in rows 511 and 0, for i % 3 == 0 in columns 511 and 0 too."""
+    side = CHUNK_SIDE
+    pats = [G.parse_rle(t)[0] for t in CHUNK_PATTERNS]
+    cells = np.zeros((CHUNK_N, side, side), dtype=np.uint8)
+    for i in range(CHUNK_N):
+        places = ((63, 5 + 11 * i), (side - 1, side - 1 if i % 3 == 0 else 40 + 7 * i), (150 + i, 300 - 5 * i),
+                  (260 + 2 * i, 17 + 9 * i), (400 - i, 100 + 3 * i))
+        for k in range(1 + i % 5):
+            for dy, dx in np.argwhere(pats[k]):
+                cells[i, (places[k][0] + dy) % side, (places[k][1] + dx) % side] = 1
+    return cells
+
+
+def _host_twin(G, words, reach, symmetry, cap=16):
+    """(count, records, fingerprint) of one board of CHUNK_SIDE from the host twin, symmetry 0 through the entry without _sym."""
+    count, fp = ctypes.c_int64(-7), ctypes.c_uint64(7)
+    recs = np.zeros(cap, dtype=I.DTYPE)
+    tail = (words.ctypes.data, words.shape[1], cap, ctypes.byref(count), recs.ctypes.data, ctypes.byref(fp))
+    if symmetry == 0:
+        rc = G.lib().gol_batch_islands_host(CHUNK_SIDE, CHUNK_SIDE, reach, *tail)
+    else:
+        rc = G.lib().gol_batch_islands_sym_host(CHUNK_SIDE, CHUNK_SIDE, reach, symmetry, *tail)
+    assert rc == 0 and 0 <= count.value <= cap, G.lib().gol_last_error()
+    return count.value, recs[:count.value], fp.value
+
+
+def test_batch_islands_across_scratch_chunks(G):
+    """gol_batch_islands over more boards than one chunk of its device scratch holds (GOL_ISLAND_SCRATCH_BYTES,
+    csrc/gol_batch_census.cpp): boards [1, 44) of 44 boards of 512 x 512 with cap = H W are a chunk of 42 boards and a
+    chunk of one, so the second trip of the chunk loop, its offsets into the caller's arrays and its own strided
+    copy of the records run.  Every board against the host twins (pinned to the Python references on the CPU), the
+    three boards at the chunk boundary against the Python references themselves."""
+    import island_sym_ref as Y
+    side, first, count = CHUNK_SIDE, CHUNK_FIRST, CHUNK_N - CHUNK_FIRST
+    cap = side * side
+    each = 16 + 24 * cap  # bytes of a board's scratch: its count, its fingerprint, cap records
+    per = (256 << 20) // each
+    assert (each, per) == (6291472, 42) and count > per, "the call must take more than one chunk"
+    cells = _chunk_boards(G)
+    words = G.Batch.pack(cells)
+    assert len({w.tobytes() for w in words}) == CHUNK_N
+    with G.Batch(CHUNK_N, side, side, device=0) as b:
+        b.load(cells)
+        for reach, symmetry, ref in ((1, G.ISLAND_FIXED, I), (2, G.ISLAND_FREE, Y)):
+            counts, recs, fps = b.islands(reach=reach, cap=cap, first=first, count=count, fingerprints=True, symmetry=symmetry)
+            assert recs.shape == (count, cap)
+            for j in range(count):  # (never the whole of recs: its pages past the records are untouched)
+                i = first + j
+                where = (reach, symmetry, i)
+                wcount, wrecs, wfp = _host_twin(G, words[i], reach, symmetry)
+                assert 1 <= wcount <= 1 + i % 5, where
+                assert int(counts[j]) == wcount and int(fps[j]) == wfp, (where, int(counts[j]), wcount)
+                assert np.array_equal(recs[j, :wcount], wrecs), (where, recs[j, :wcount], wrecs)
+                assert not recs[j, wcount:wcount + 8].tobytes().strip(b"\0"), (where, "a record past count was written")
+                if i >= first + per - 2:  # boards 41 and 42, the first chunk's last, and 43, the second chunk's only one
+                    prec, pfp = ref.census(cells[i], reach)
+                    assert wcount == len(prec) and wfp == pfp and np.array_equal(wrecs, prec), where
+        assert np.array_equal(b.store_words(), words)
