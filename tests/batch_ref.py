@@ -46,11 +46,13 @@ Every case carries check(): assertions on the model's results alone that the cas
 there for."""
 import dataclasses
 import functools
+import os
 
 import numpy as np
 
 import cycle_ref as C
 import rule_ref as R
+from oracle import oracle as O
 
 GAP = np.uint64(0xA5A5A5A5A5A5A5A5)
 FILL32, FILL64 = np.int32(-0x5A5A5A5B), np.int64(-0x5A5A5A5A5A5A5A5B)  # bytes 0xA5
@@ -549,3 +551,84 @@ def refusals(p):
     # (each family's base arguments are good)
     good = [dict(), dict(scan, scan=1), dict(cyc), dict(lst, left=p["left"]), dict(aged), dict(aged, have_prev=1, done=3)]
     return [dict(base, **kw) for kw in bad], [dict(base, **kw) for kw in good]
+
+
+# ---------------------------------------------------------------- what the tests of golhip.Batch and its host twins share
+
+BATCH_CHECK = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gol-distributed-final_amd", "build", "asan",
+                           "batch_check")  # the stand-alone program of the sanitizer build
+
+
+def to_words(cells):
+    """uint8[..., H, W] cells (non-zero = alive) as uint64[..., H, ceil(W / 64)]: bit c % 64 of word
+    c // 64 of a row is cell c, written out bit by bit (independent of the library's packing)."""
+    cells = np.asarray(cells) != 0
+    W = cells.shape[-1]
+    out = np.zeros(cells.shape[:-1] + ((W + 63) // 64,), dtype=np.uint64)
+    for c in range(W):
+        out[..., c // 64] |= cells[..., c].astype(np.uint64) << np.uint64(c % 64)
+    return out
+
+
+def from_words(words, W):
+    """The inverse: uint8[..., H, W] of 0 / 1."""
+    words = np.asarray(words, dtype=np.uint64)
+    out = np.zeros(words.shape[:-1] + (W,), dtype=np.uint8)
+    for c in range(W):
+        out[..., c] = (words[..., c // 64] >> np.uint64(c % 64)) & np.uint64(1)
+    return out
+
+
+def tail_mask(W):
+    return np.uint64((1 << (W % 64)) - 1 if W % 64 else 2 ** 64 - 1)
+
+
+# (board, turns, (found, period) as the reference must give them)
+PATTERNS = [
+    (C.place(5, 5, []), 10, (1, 1)),
+    (C.place(5, 5, C.BLOCK, 1, 1), 10, (1, 1)),
+    (C.place(5, 5, C.BLINKER, 2, 1), 10, (3, 2)),
+    (C.place(17, 17, C.PULSAR, 2, 2), 40, (6, 3)),
+    (C.place(129, 65, C.PULSAR, 57, 58), 40, (6, 3)),
+    (C.place(20, 20, C.ROW10, 10, 5), 100, (30, 15)),
+    (C.place(130, 33, C.ROW10, 0, 28), 100, (30, 15)),
+    (C.place(129, 65, C.ROW10, 63, 60), 100, (30, 15)),
+    (C.place(8, 8, C.GLIDER), 200, (63, 32)),
+    (C.place(16, 16, C.GLIDER), 400, (127, 64)),
+    (C.place(7, 9, C.GLIDER), 600, (507, 252)),
+    (C.place(16, 16, C.R_PENTOMINO, 6, 6), 300, (129, 2)),
+]
+
+
+def batch_n(G, H, W):
+    """Two full workgroups and one board in a third; at least 3."""
+    with G.Batch(1, H, W) as b:
+        info = b.info()
+    assert info["waves_per_board"] == (H + 63) // 64 and info["words_per_lane"] >= (W + 31) // 32
+    return max(3, 2 * info["boards_per_workgroup"] + 1)
+
+
+def random_boards(seed, n, H, W):
+    """n different boards of 0 / 1 at densities 0.2 .. 0.6."""
+    return np.stack([R.random_board(seed + i, H, W, 0.2 + 0.4 * i / max(n - 1, 1)) for i in range(n)])
+
+
+def check_queries(b, cells):
+    """store, store_words, alive_counts and hashes of the batch against the cells (0 / 1) it should hold."""
+    words = to_words(cells)
+    got = b.store_words()
+    assert got.shape == words.shape and np.array_equal(got, words)
+    assert np.array_equal(b.store(), cells * 255)
+    assert b.alive_counts().tolist() == [O.popcount_words(w) for w in words]
+    assert b.hashes().tolist() == [O.hash_words(w) for w in words]
+
+
+def ref_settle(board, rule, turns):
+    """(the first t in [2, turns] with state(t) == state(t - 2), else -1; state(turns))."""
+    states = [np.asarray(board, dtype=np.uint8)]
+    found = -1
+    for t in range(1, turns + 1):
+        states.append(R.step(states[-1], *rule))
+        if found < 0 and t >= 2 and np.array_equal(states[t], states[t - 2]):
+            found = t
+    return found, states[-1]

@@ -14,8 +14,8 @@ import numpy as np
 
 import cycle_ref as C
 import rule_ref as R
+from batch_ref import from_words, tail_mask, to_words
 from oracle import oracle as O
-from test_batch_cpu import from_words, tail_mask, to_words
 
 
 def soup_words(seed: int, g: int, H: int, W: int) -> np.ndarray:

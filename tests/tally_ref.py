@@ -18,6 +18,7 @@ import numpy as np
 import island_ref as I
 import rule_ref as R
 import search_ref as S
+from testlib import Guarded
 
 KIND_DTYPE = np.dtype([("hash", "<u8"), ("count", "<i8"), ("first", "<i8"), ("cells", "<i4"), ("rows", "<u2"), ("cols", "<u2")])
 # a slot of the device table: the last word is cells << 32 | rows << 16 | cols
@@ -132,3 +133,52 @@ def distinct_islands(n=1200):
             if p >> k & 1:
                 out[i, 4 if k < 6 else 6, 2 + k % 6] = 1
     return out
+
+
+# ------------------------------------------------- the arguments of the launch check (gol_batch_islands_tally_check_host)
+P = 0x1000  # a pointer that is never dereferenced
+ORDER = ("boards", "n", "H", "W", "reach", "pairs", "pair_count", "max_pairs", "found", "owner0", "count", "fingerprint", "table",
+         "table_log2", "dropped")
+DENSE = dict(boards=P, n=3, H=64, W=64, reach=1, pairs=None, pair_count=None, max_pairs=0, found=None, owner0=0, count=P,
+             fingerprint=P, table=P, table_log2=10, dropped=P)
+LISTED = dict(DENSE, pairs=P, pair_count=P, max_pairs=3, found=P)
+REFUSED = [(DENSE, bad) for bad in (
+    dict(boards=None), dict(count=None), dict(table=None), dict(dropped=None), dict(n=0), dict(n=(1 << 20) + 1), dict(H=0),
+    dict(H=513), dict(W=0), dict(W=513), dict(reach=0), dict(reach=3), dict(reach=-1), dict(table_log2=3), dict(table_log2=25),
+    dict(table_log2=0), dict(owner0=-1), dict(owner0=(1 << 40) + 1), dict(pair_count=P), dict(found=P), dict(max_pairs=1))]
+REFUSED += [(LISTED, bad) for bad in (dict(pair_count=None), dict(found=None), dict(max_pairs=0), dict(max_pairs=4),
+                                      dict(max_pairs=-1), dict(table=None), dict(dropped=None), dict(table_log2=25))]
+
+
+# ------------------------------------------------------------------------------ the buffers of a launch (GPU tests)
+FILL = 0xA5
+
+
+class Launch:
+    """The buffers of tally launches on one stack of boards: a table of 2^log2 slots (empty, made here), dropped,
+    and count / fingerprint of `outs` entries filled with the sentinel."""
+
+    def __init__(self, G, cells, log2, outs=None):
+        self.G, self.cells, self.log2 = G, cells, log2
+        self.n, self.H, self.W = cells.shape
+        self.boards = Guarded(G.Batch.pack(cells.astype(np.uint8)), name="boards")
+        outs = self.n if outs is None else outs
+        self.count = Guarded(np.full(outs * 8, FILL, dtype=np.uint8), name="count")
+        self.fp = Guarded(np.full(outs * 8, FILL, dtype=np.uint8), name="fingerprint")
+        self.table, self.dropped = Guarded(empty_table(log2), name="table"), Guarded(np.zeros(1, dtype=np.int64), name="dropped")
+
+    def run(self, reach, owner0=0, pairs=None, pair_count=None, max_pairs=0, found=None, n=None):
+        import torch
+        rc = self.G.lib().gol_dev_batch_islands_tally(
+            self.boards.ptr, self.n if n is None else n, self.H, self.W, reach, pairs.ptr if pairs else None,
+            pair_count.ptr if pair_count else None, max_pairs, found.ptr if found else None, owner0, self.count.ptr, self.fp.ptr,
+            self.table.ptr, self.log2, self.dropped.ptr, torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        return rc
+
+    def results(self):
+        """(count, fingerprint, kinds sorted, dropped) after checking the boards, every margin and the empty slots."""
+        assert self.boards.unchanged(), "the boards or their margins changed"
+        kinds, empties_ok = table(self.table.read(np.uint8).tobytes())
+        assert empties_ok, "a slot without a tag is not the empty pattern"
+        return self.count.read(np.int64), self.fp.read(np.uint64), kinds, int(self.dropped.read(np.int64)[0])

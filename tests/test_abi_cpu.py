@@ -15,16 +15,10 @@ import numpy as np
 import pytest
 
 from oracle import oracle as O
+from testlib import cpu_lib as G  # noqa: F401 (the fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "golhip.h")
-
-
-@pytest.fixture(scope="module")
-def G():
-    import golhip
-    golhip.lib()
-    return golhip
 
 
 def declared_functions():

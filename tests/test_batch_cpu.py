@@ -11,9 +11,8 @@ import numpy as np
 import pytest
 
 import rule_ref
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BATCH_CHECK = os.path.join(ROOT, "gol-distributed-final_amd", "build", "asan", "batch_check")
+from batch_ref import BATCH_CHECK, GAP, from_words, tail_mask, to_words
+from testlib import cpu_lib as G  # noqa: F401 (the fixture)
 
 # degenerate wraps, one to sixteen words per row, a last word partly and wholly used, more than 64 rows; five to
 # eight words (the 8-word row function) and an odd count of words below the 8 or 16 held
@@ -21,38 +20,6 @@ SHAPES = [(1, 1), (1, 2), (2, 1), (2, 2), (3, 3), (2, 5), (5, 2), (16, 16), (7, 
           (5, 65), (3, 96), (4, 511), (4, 512), (3, 481), (64, 1), (65, 31), (5, 129), (3, 150), (4, 256), (3, 270)]
 RULES = ["B3/S23", "B36/S23", "B3678/S34678", "B2/S", "B0/S8", "B012345678/S012345678"]
 TURNS = 4
-GAP = np.uint64(0xA5A5A5A5A5A5A5A5)
-
-
-@pytest.fixture(scope="module")
-def G():
-    import golhip
-    golhip.lib()
-    return golhip
-
-
-def to_words(cells):
-    """uint8[..., H, W] cells (non-zero = alive) as uint64[..., H, ceil(W / 64)]: bit c % 64 of word
-    c // 64 of a row is cell c, written out bit by bit (independent of the library's packing)."""
-    cells = np.asarray(cells) != 0
-    W = cells.shape[-1]
-    out = np.zeros(cells.shape[:-1] + ((W + 63) // 64,), dtype=np.uint64)
-    for c in range(W):
-        out[..., c // 64] |= cells[..., c].astype(np.uint64) << np.uint64(c % 64)
-    return out
-
-
-def from_words(words, W):
-    """The inverse: uint8[..., H, W] of 0 / 1."""
-    words = np.asarray(words, dtype=np.uint64)
-    out = np.zeros(words.shape[:-1] + (W,), dtype=np.uint8)
-    for c in range(W):
-        out[..., c] = (words[..., c // 64] >> np.uint64(c % 64)) & np.uint64(1)
-    return out
-
-
-def tail_mask(W):
-    return np.uint64((1 << (W % 64)) - 1 if W % 64 else 2 ** 64 - 1)
 
 
 def host_step(G, H, W, rule, buf_in, buf_out, stride):

@@ -12,14 +12,8 @@ import pytest
 import batch_ref as B
 import cycle_ref as C
 import rule_ref as R
-from test_batch_cpu import to_words
-
-
-@pytest.fixture(scope="module")
-def G():
-    import golhip
-    golhip.lib()
-    return golhip
+from batch_ref import BATCH_CHECK, to_words
+from testlib import GOL_EINVAL, cpu_lib as G  # noqa: F401 (the fixture)
 
 
 # ---------------------------------------------------------------- the table
@@ -104,8 +98,6 @@ def test_cases_are_valid_and_show_their_point(inst):
 
 # ---------------------------------------------------------------- the launch check, without a launch
 
-GOL_EINVAL = -1
-
 
 def fake_ptr(name):
     """A non-null address per buffer: the check reads no memory."""
@@ -137,7 +129,6 @@ def test_the_check_under_sanitizers(tmp_path):
     line per launch, the expected answer first, NULL as 0."""
     import os
     import subprocess
-    from test_batch_cpu import BATCH_CHECK
     assert os.path.exists(BATCH_CHECK), "build/asan/batch_check is missing: run __graft_entry__.build()"
     accept, refuse = check_sets()
     path = tmp_path / "launches.txt"

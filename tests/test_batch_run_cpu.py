@@ -14,15 +14,8 @@ import pytest
 
 import cycle_ref as C
 import rule_ref as R
-from test_batch_cpu import BATCH_CHECK, GAP, tail_mask, to_words
-from test_batch_survey_cpu import PATTERNS
-
-
-@pytest.fixture(scope="module")
-def G():
-    import golhip
-    golhip.lib()
-    return golhip
+from batch_ref import BATCH_CHECK, GAP, PATTERNS, tail_mask, to_words
+from testlib import cpu_lib as G  # noqa: F401 (the fixture)
 
 
 def made_ref(found, period, turns, launch, t0=0):

@@ -15,19 +15,12 @@ import pytest
 import rule_ref as R
 import search_ref as S
 from oracle import oracle as O
-from test_batch_cpu import BATCH_CHECK, GAP, tail_mask
+from batch_ref import BATCH_CHECK, GAP, tail_mask
+from testlib import GOL_EINVAL, cpu_lib as G  # noqa: F401 (the fixture)
 
-GOL_EINVAL = -1
 SEED = 1  # (picked: the conditions of test_main_case_is_not_empty hold for it)
 MAIN = dict(H=16, W=16, rule="B3/S23", total=40, horizon=300)
 FILL = np.int64(-0x5A5A5A5A5A5A5A5B)
-
-
-@pytest.fixture(scope="module")
-def G():
-    import golhip
-    golhip.lib()
-    return golhip
 
 
 def main_ref(first=0, total=MAIN["total"], horizon=MAIN["horizon"], rule=MAIN["rule"]):

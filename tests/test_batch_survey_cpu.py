@@ -14,30 +14,8 @@ import pytest
 
 import cycle_ref as C
 import rule_ref as R
-from test_batch_cpu import BATCH_CHECK, GAP, tail_mask, to_words
-
-# (board, turns, (found, period) as the reference must give them)
-PATTERNS = [
-    (C.place(5, 5, []), 10, (1, 1)),
-    (C.place(5, 5, C.BLOCK, 1, 1), 10, (1, 1)),
-    (C.place(5, 5, C.BLINKER, 2, 1), 10, (3, 2)),
-    (C.place(17, 17, C.PULSAR, 2, 2), 40, (6, 3)),
-    (C.place(129, 65, C.PULSAR, 57, 58), 40, (6, 3)),
-    (C.place(20, 20, C.ROW10, 10, 5), 100, (30, 15)),
-    (C.place(130, 33, C.ROW10, 0, 28), 100, (30, 15)),
-    (C.place(129, 65, C.ROW10, 63, 60), 100, (30, 15)),
-    (C.place(8, 8, C.GLIDER), 200, (63, 32)),
-    (C.place(16, 16, C.GLIDER), 400, (127, 64)),
-    (C.place(7, 9, C.GLIDER), 600, (507, 252)),
-    (C.place(16, 16, C.R_PENTOMINO, 6, 6), 300, (129, 2)),
-]
-
-
-@pytest.fixture(scope="module")
-def G():
-    import golhip
-    golhip.lib()
-    return golhip
+from batch_ref import BATCH_CHECK, GAP, PATTERNS, tail_mask, to_words
+from testlib import cpu_lib as G  # noqa: F401 (the fixture)
 
 
 def cycles_host(G, cells, rule, turns, pad=0, in_place=False, want_period=True):

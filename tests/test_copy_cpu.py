@@ -13,7 +13,8 @@ import numpy as np
 import pytest
 
 import region_ref as RR
-from test_edit_cpu import CASES as PASTE_SHAPES, EDGES, board_cells, to_layout
+from region_ref import CASES as PASTE_SHAPES, EDGES, board_cells, to_layout
+from testlib import cpu_lib as G  # noqa: F401 (the fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 COPY_CHECK = os.path.join(ROOT, "gol-distributed-final_amd", "build", "asan", "copy_check")
@@ -31,13 +32,6 @@ for _lay, _W, _x0, _w in [(2, 1024, 1000, 50), (2, 3072, 3000, 200), (2, 1024, 7
     EXTRA += [(_lay, _W, _x0, _w, "empty"), (_lay, _W, _x0, _w, "corners")]
 SHAPES = [(layout, W, x0, w, "random") for layout, W, x0, w in PASTE_SHAPES] + EXTRA
 BROWS, ROW, ROWS, PROW = 6, 1, 4, 2
-
-
-@pytest.fixture(scope="module")
-def G():
-    import golhip
-    golhip.lib()
-    return golhip
 
 
 def region(cells, x0, w):

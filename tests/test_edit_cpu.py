@@ -13,19 +13,13 @@ import numpy as np
 import pytest
 
 import region_ref as RR
-from oracle import oracle as O
+from region_ref import CASES, EDGES, board_cells, from_layout, to_layout
+from testlib import cpu_lib as G  # noqa: F401 (the fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RLE_CHECK = os.path.join(ROOT, "gol-distributed-final_amd", "build", "asan", "rle_check")
 OPS = ["copy", "or", "xor", "andnot"]
 GLIDER = np.array([[0, 1, 0], [0, 0, 1], [1, 1, 1]], bool)
-
-
-@pytest.fixture(scope="module")
-def G():
-    import golhip
-    golhip.lib()
-    return golhip
 
 
 # ------------------------------------------------------------------ RLE parse
@@ -144,36 +138,6 @@ def test_rle_format_is_compact_and_checks_its_buffer(G):
 
 
 # ------------------------------------------------------------------ gol_paste_host against numpy
-def board_cells(seed, rows, W):
-    """rows x W bool cells of the oracle's random board (a width that is no multiple of 64: cut)."""
-    return O.unpack(O.random_words(seed, 0, rows, (W + 63) // 64))[:, :W] != 0
-
-
-def to_layout(layout, cells, pitch, rng):
-    """The cells as a host buffer in `layout` with row pitch `pitch`; the pad units hold garbage."""
-    rows, W = cells.shape
-    if layout == 0:
-        buf = rng.integers(0, 256, (rows, pitch), dtype=np.uint8)
-        # alive cells as 255 or another non-zero byte: the untouched ones must keep it
-        buf[:, :W] = np.where(cells, np.where(rng.random((rows, W)) < 0.3, 7, 255), 0)
-        return buf
-    Wd = W // 32
-    buf = rng.integers(0, 2 ** 32, (rows, pitch), dtype=np.uint32)
-    grouped = cells.reshape(rows, Wd, 32) if layout == 1 else cells.reshape(rows, 32, Wd).transpose(0, 2, 1)
-    buf[:, :Wd] = np.packbits(grouped, axis=2, bitorder="little").view("<u4")[:, :, 0]
-    return buf
-
-
-def from_layout(layout, buf, W):
-    rows = buf.shape[0]
-    if layout == 0:
-        return buf[:, :W] != 0
-    Wd = W // 32
-    bits = np.unpackbits(np.ascontiguousarray(buf[:, :Wd]).view(np.uint8).reshape(rows, Wd, 4), axis=2,
-                         bitorder="little").reshape(rows, Wd, 32).astype(bool)
-    return bits.reshape(rows, W) if layout == 1 else bits.transpose(0, 2, 1).reshape(rows, W)
-
-
 def np_paste(cells, row, rows, x0, p, op):
     """The edited cells and the mask of written cells (numpy restatement of the header's rules)."""
     out = cells.copy()
@@ -196,28 +160,6 @@ def pattern_words(G, p, stride, rng):
     if w % 64:
         words[:, pw - 1] |= rng.integers(0, 2 ** 63, h, dtype=np.uint64) << np.uint64(w % 64)
     return words
-
-
-# (layout, W, [(x0, w)]): band w = 1, w < Wd, w = Wd, Wd < w < W, w = W, x0 in band 0 and band 31, wraps in x;
-# standard x0 % 32 in {0, 1, 31}, w = W at x0 % 32 != 0, w <= 32 inside one word; bytes W = 100, 128 (one byte
-# per lane, or with a pitch that is a multiple of 4 aligned 4-byte words: both, see paste_cases) and W = 50
-SHAPES = [
-    (2, 1024, [(0, 1), (5, 1), (1023, 1), (3, 20), (30, 32), (17, 32), (10, 100), (0, 1024), (700, 1024), (1000, 40),
-               (995, 29), (1023, 33), (31, 993)]),
-    (2, 2048, [(2047, 1), (60, 10), (1, 64), (63, 64), (2000, 100), (100, 1900), (1999, 2048), (0, 2048), (2040, 65)]),
-    (1, 192, [(0, 192), (1, 192), (31, 192), (37, 192), (0, 32), (1, 31), (33, 5), (31, 1), (31, 2), (64, 64),
-              (65, 100), (191, 3), (160, 33), (95, 97), (1, 191)]),
-    (0, 100, [(0, 100), (99, 1), (99, 100), (37, 64), (50, 70), (3, 5)]),
-    (0, 128, [(0, 128), (127, 2), (1, 127), (64, 65), (2, 128), (6, 3)]),
-    (0, 50, [(49, 50), (3, 5), (0, 50)]),
-]
-CASES = [(layout, W, x0, w) for layout, W, xs in SHAPES for x0, w in xs]
-# The smallest shapes at which the unit step the kernels share with the host (gol_edit_paste_unit, the
-# bounds' gol_copy_occ_unit) can go wrong, each at a dense pitch: standard rows of 2 words with the
-# full width from the middle of a word (wrap_c: lane 0 also takes the cells that wrapped); byte rows
-# of 2 aligned 4-byte words, the same wrap in the 4-byte form; byte rows of 7 bytes, one per lane;
-# band rows with the carry into the next band and the wrap from bit 31 to bit 0.
-EDGES = [(1, 64, 33, 64), (0, 8, 3, 8), (0, 7, 5, 7), (2, 1024, 1023, 34)]
 
 
 def paste_cases(G, cases=CASES, pad=None):

@@ -13,18 +13,12 @@ import pytest
 import engine_model as M
 import rule_ref as R
 from oracle import oracle as O
-from test_edit_cpu import from_layout
+from region_ref import from_layout
+from testlib import cpu_lib as G  # noqa: F401 (the fixture)
 
 IDS = list(M.CONFIGS)
 BIT_IDS = [i for i in IDS if M.Model.of(M.CONFIGS[i]).bit]
 SHARDED_IDS = [i for i in IDS if M.CONFIGS[i]["engine"].get("shards", 1) > 1]
-
-
-@pytest.fixture(scope="module")
-def G():
-    import golhip
-    golhip.lib()
-    return golhip
 
 
 @functools.lru_cache(maxsize=None)

@@ -9,8 +9,9 @@ import numpy as np
 import pytest
 
 import rule_ref as R
+from batch_ref import batch_n, check_queries, random_boards, ref_settle, tail_mask, to_words
 from oracle import oracle as O
-from test_batch_cpu import tail_mask, to_words
+from testlib import gpu_lib as G  # noqa: F401 (the fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -22,41 +23,8 @@ SHAPES = [(1, 1), (2, 5), (5, 2), (3, 3), (16, 16), (63, 33), (64, 32), (64, 64)
 GAP = np.uint64(0x5A5A5A5A5A5A5A5A)
 
 
-@pytest.fixture(scope="module")
-def G():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import golhip
-    golhip.lib()
-    return golhip
-
-
-def batch_n(G, H, W):
-    """Two full workgroups and one board in a third; at least 3."""
-    with G.Batch(1, H, W) as b:
-        info = b.info()
-    assert info["waves_per_board"] == (H + 63) // 64 and info["words_per_lane"] >= (W + 31) // 32
-    return max(3, 2 * info["boards_per_workgroup"] + 1)
-
-
-def random_boards(seed, n, H, W):
-    """n different boards of 0 / 1 at densities 0.2 .. 0.6."""
-    return np.stack([R.random_board(seed + i, H, W, 0.2 + 0.4 * i / max(n - 1, 1)) for i in range(n)])
-
-
 def ref_run(boards, rule, turns):
     return np.stack([R.run(b, rule, turns)[0] for b in boards])
-
-
-def check_queries(b, cells):
-    """store, store_words, alive_counts and hashes of the batch against the cells (0 / 1) it should hold."""
-    words = to_words(cells)
-    got = b.store_words()
-    assert got.shape == words.shape and np.array_equal(got, words)
-    assert np.array_equal(b.store(), cells * 255)
-    assert b.alive_counts().tolist() == [O.popcount_words(w) for w in words]
-    assert b.hashes().tolist() == [O.hash_words(w) for w in words]
 
 
 @pytest.mark.parametrize("H,W", SHAPES)
@@ -180,17 +148,6 @@ def test_load_random(G, H, W):
         want[..., -1] &= tail_mask(W)
         assert np.array_equal(b.store_words(), want)
         assert b.alive_counts().tolist() == [O.popcount_words(w) for w in want]
-
-
-def ref_settle(board, rule, turns):
-    """(the first t in [2, turns] with state(t) == state(t - 2), else -1; state(turns))."""
-    states = [np.asarray(board, dtype=np.uint8)]
-    found = -1
-    for t in range(1, turns + 1):
-        states.append(R.step(states[-1], *rule))
-        if found < 0 and t >= 2 and np.array_equal(states[t], states[t - 2]):
-            found = t
-    return found, states[-1]
 
 
 def test_settle_random_soups(G):

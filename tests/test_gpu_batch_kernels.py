@@ -7,68 +7,26 @@ only moving cells sit in one word or one wave.  Every buffer of a launch -- boar
 and the inputs born, list, count and rules -- lies between two margins of sentinel bytes and is compared
 whole, margins included, so a word written for a board that is not listed, past *count or out of place
 shows."""
-import ctypes
-
 import numpy as np
 import pytest
 
 import batch_ref as B
 import cycle_ref as C
 import rule_ref as R
+from testlib import GOL_EINVAL, Guarded, error_word, gpu_lib as G  # noqa: F401 (the fixture)
 
 pytestmark = pytest.mark.gpu
 
-GOL_EINVAL = -1
-MARGIN = 64  # elements before and after every buffer
 NAMES = ("boards", "prev", "settled", "left", "born", "list", "count", "rules")
 
 
-@pytest.fixture(scope="module")
-def G():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import golhip
-    golhip.lib()
-    torch.cuda.set_device(0)
-    return golhip
+def _buffers(host):
+    """The device buffers of a launch: name -> Guarded of the host array (a buffer the launch does not have: absent)."""
+    return {k: Guarded(v, name=k) for k, v in host.items() if v is not None}
 
 
-def _error_word(G):
-    flags = ctypes.c_uint32(0xFFFF)
-    rc = G.lib().gol_dev_error(-1, ctypes.byref(flags))
-    return rc, flags.value
-
-
-def _padded(a):
-    """a flat, with MARGIN elements of 0x5A bytes before and after."""
-    a = np.ascontiguousarray(a).ravel()
-    m = np.frombuffer(b"\x5a" * (MARGIN * a.itemsize), dtype=a.dtype)
-    return np.concatenate([m, a, m])
-
-
-class Buffers:
-    """The device buffers of a launch: name -> torch tensor of the padded host array."""
-
-    def __init__(self, host):
-        import torch
-        self.host = {k: _padded(v) for k, v in host.items() if v is not None}
-        signed = {8: np.int64, 4: np.int32}
-        self.dev = {k: torch.from_numpy(v.view(signed[v.itemsize]).copy()).cuda() for k, v in self.host.items()}
-
-    def ptr(self, name):
-        if name not in self.dev:
-            return None
-        t = self.dev[name]
-        return t.data_ptr() + MARGIN * t.element_size()
-
-    def read(self, name):
-        return self.dev[name].cpu().numpy().view(self.host[name].dtype)
-
-    def write(self, name, a):
-        import torch
-        flat = np.ascontiguousarray(a).ravel().view(np.int32 if a.itemsize == 4 else np.int64)
-        self.dev[name][MARGIN:MARGIN + a.size] = torch.from_numpy(flat).cuda()
+def _ptr(buf, name):
+    return buf[name].ptr if name in buf else None
 
 
 def _host_buffers(c):
@@ -82,32 +40,27 @@ def _call(G, buf, c, **over):
     a = dict(n=c.n, H=c.H, W=c.W, turns=c.turns, turn0=c.turn0, have_prev=int(c.have_prev), write_prev=int(c.write_prev),
              birth=c.rule[0], survive=c.rule[1], scan=c.scan, done=c.done, slots=c.slots)
     a.update(over)
-    return G.lib().gol_dev_batch_step(buf.ptr("boards"), buf.ptr("prev"), buf.ptr("settled"), a["n"], a["H"], a["W"], a["turns"],
-                                      a["turn0"], a["have_prev"], a["write_prev"], a["birth"], a["survive"], buf.ptr("rules"),
-                                      a["scan"], a["done"], buf.ptr("list"), buf.ptr("count"), a["slots"], buf.ptr("left"),
-                                      buf.ptr("born"), torch.cuda.current_stream().cuda_stream)
+    return G.lib().gol_dev_batch_step(_ptr(buf, "boards"), _ptr(buf, "prev"), _ptr(buf, "settled"), a["n"], a["H"], a["W"], a["turns"],
+                                      a["turn0"], a["have_prev"], a["write_prev"], a["birth"], a["survive"], _ptr(buf, "rules"),
+                                      a["scan"], a["done"], _ptr(buf, "list"), _ptr(buf, "count"), a["slots"], _ptr(buf, "left"),
+                                      _ptr(buf, "born"), torch.cuda.current_stream().cuda_stream)
 
 
-def _compare(buf, want, where):
-    """Every buffer whole (margins included) against `want` (name -> array; a name not in it: unchanged)."""
-    for name in buf.dev:
-        w = _padded(want[name]) if want.get(name) is not None else buf.host[name]
-        got = buf.read(name)
-        if not np.array_equal(got, w):
-            bad = np.flatnonzero(got != w)
-            at = (bad[:6] - MARGIN).tolist()
-            raise AssertionError(f"{where}: {name} differs in {bad.size} of {w.size} elements, first at {at} "
-                                 f"(got {got[bad[:3]].tolist()}, want {w[bad[:3]].tolist()})")
+def _compare(buf, host, want, where):
+    """Every buffer whole (margins included) against `want` (name -> array; a name not in it: unchanged, as in `host`)."""
+    for name, g in buf.items():
+        g.expect(host[name] if want.get(name) is None else want[name], where)
 
 
 def _run_case(G, c):
     import torch
-    buf = Buffers(_host_buffers(c))
+    host = _host_buffers(c)
+    buf = _buffers(host)
     rc = _call(G, buf, c)
     assert rc == 0, (c.id, G.lib().gol_last_error())
     torch.cuda.synchronize()
     w = c.want
-    _compare(buf, {"boards": w["boards"], "prev": w["prev"], "settled": w["settled"], "left": w["left"]}, c.id)
+    _compare(buf, host, {"boards": w["boards"], "prev": w["prev"], "settled": w["settled"], "left": w["left"]}, c.id)
 
 
 @pytest.mark.parametrize("inst", B.INSTANTIATIONS, ids=B.inst_id)
@@ -116,7 +69,7 @@ def test_instantiation(G, inst):
     assert cases
     for c in cases:
         _run_case(G, c)
-    assert _error_word(G) == (0, 0)
+    assert error_word(G) == (0, 0)
 
 
 # ---------------------------------------------------------------- three launches, prev / done / turn0 threaded through
@@ -160,20 +113,20 @@ def test_chained_launches(G, inst):
     if aged:  # board 6 (a blinker) comes into its slot before the second launch
         host["born"] = np.full(n, B.FILL64, np.int64)
         host["born"][order] = [0, 0, 0, 0, 0, 0, CHAIN[0]]
-    buf = Buffers(host)
+    buf = _buffers(host)
     state = {k: (None if v is None else v.copy()) for k, v in host.items()}
     done = 0
     for i, turns in enumerate(CHAIN):
         count = None if not lst else len(order) if not aged or i > 0 else len(order) - 1
         if aged:
-            buf.write("count", np.array([count], np.int32))
+            buf["count"].write(np.array([count], np.int32))
         hp = scan != B.SCAN_NONE and i > 0
         wp = scan != B.SCAN_NONE and (aged or i < 2)
         a = dict(turns=turns, turn0=0 if aged else t0 + done, have_prev=int(hp), write_prev=int(wp), birth=rule[0], survive=rule[1],
                  scan=scan, done=done if scan == B.SCAN_CYCLES else 0, slots=len(order) if lst else 0, n=n, H=H, W=W)
-        rc = G.lib().gol_dev_batch_step(buf.ptr("boards"), buf.ptr("prev"), buf.ptr("settled"), n, H, W, turns, a["turn0"], a["have_prev"],
-                                        a["write_prev"], rule[0], rule[1], buf.ptr("rules"), scan, a["done"], buf.ptr("list"),
-                                        buf.ptr("count"), a["slots"], buf.ptr("left"), buf.ptr("born"),
+        rc = G.lib().gol_dev_batch_step(_ptr(buf, "boards"), _ptr(buf, "prev"), _ptr(buf, "settled"), n, H, W, turns, a["turn0"], a["have_prev"],
+                                        a["write_prev"], rule[0], rule[1], _ptr(buf, "rules"), scan, a["done"], _ptr(buf, "list"),
+                                        _ptr(buf, "count"), a["slots"], _ptr(buf, "left"), _ptr(buf, "born"),
                                         torch.cuda.current_stream().cuda_stream)
         assert rc == 0, G.lib().gol_last_error()
         w = B.launch_model(state["boards"], state["prev"], state["settled"], state["left"], H=H, W=W, turns=turns, turn0=a["turn0"],
@@ -184,7 +137,7 @@ def test_chained_launches(G, inst):
     torch.cuda.synchronize()
     if aged:
         state["count"] = np.array([len(order)], np.int32)
-    _compare(buf, state, B.inst_id(inst))
+    _compare(buf, host, state, B.inst_id(inst))
     # the whole call, from the references that know nothing of launches
     run = list(range(n)) if not lst else order
     rl = [rule if rules is None else tuple(int(v) for v in rules[b]) for b in range(n)]
@@ -211,7 +164,7 @@ def test_chained_launches(G, inst):
         assert all(state["settled"][b] == -1 for b in range(n) if b not in run)
         got = {found[b] - t0 for b in run}
         assert {-1 - t0, 1, 3, 6} <= got  # never, a still life, period 2, period 3 past the first launch
-    assert _error_word(G) == (0, 0)
+    assert error_word(G) == (0, 0)
 
 
 # ---------------------------------------------------------------- refusals
@@ -224,9 +177,9 @@ def test_refusals(G):
     host = dict(boards=boards, prev=np.full_like(boards, B.GAP), settled=np.full(n, -1, np.int64), left=np.full(n, 2, np.int64),
                 born=np.zeros(n, np.int64), list=np.arange(n, dtype=np.int32), count=np.array([n], np.int32),
                 rules=np.array([R.CONWAY] * n, np.uint32))
-    buf = Buffers(host)
+    buf = _buffers(host)
     L = G.lib()
-    p = {k: buf.ptr(k) for k in NAMES}
+    p = {k: _ptr(buf, k) for k in NAMES}
     st = torch.cuda.current_stream().cuda_stream
 
     def call(a):
@@ -237,10 +190,10 @@ def test_refusals(G):
         assert call(a) == GOL_EINVAL, a
         assert L.gol_last_error()
     torch.cuda.synchronize()
-    _compare(buf, {}, "refusals")
+    _compare(buf, host, {}, "refusals")
     # (each family's base arguments are good: one launch of each, on the same buffers)
     assert len(good) == 6
     for a in good:
         assert call(a) == 0, (a, L.gol_last_error())
     torch.cuda.synchronize()
-    assert _error_word(G) == (0, 0)
+    assert error_word(G) == (0, 0)

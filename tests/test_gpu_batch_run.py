@@ -10,21 +10,10 @@ import pytest
 import cycle_ref as C
 import rule_ref as R
 from cycle_ref import RULES
-from test_gpu_batch import batch_n, check_queries, random_boards, ref_settle
+from batch_ref import batch_n, check_queries, random_boards, ref_settle
+from testlib import GOL_EINVAL, gpu_lib as G  # noqa: F401 (the fixture)
 
 pytestmark = pytest.mark.gpu
-
-GOL_EINVAL = -1
-
-
-@pytest.fixture(scope="module")
-def G():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import golhip
-    golhip.lib()
-    return golhip
 
 
 def made_ref(found, period, turns, launch, t0=0):

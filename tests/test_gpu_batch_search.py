@@ -13,23 +13,13 @@ import cycle_ref as C
 import rule_ref as R
 import search_ref as S
 from oracle import oracle as O
-from test_batch_cpu import tail_mask
+from batch_ref import tail_mask
+from testlib import GOL_EINVAL, GOL_ESTATE, gpu_lib as G  # noqa: F401 (the fixture)
 
 pytestmark = pytest.mark.gpu
 
-GOL_EINVAL, GOL_ESTATE = -1, -6
 SEED = 1
 FILL32, FILL64 = np.int32(-0x5A5A5A5B), np.int64(-0x5A5A5A5A5A5A5A5B)  # bytes 0xA5
-
-
-@pytest.fixture(scope="module")
-def G():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import golhip
-    golhip.lib()
-    return golhip
 
 
 def assert_equal(got, want, where=None):

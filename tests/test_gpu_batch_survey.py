@@ -10,23 +10,12 @@ import pytest
 import cycle_ref as C
 import rule_ref as R
 from cycle_ref import RULES
-from test_batch_cpu import tail_mask
-from test_gpu_batch import batch_n, check_queries, random_boards, ref_settle
+from batch_ref import batch_n, check_queries, random_boards, ref_settle, tail_mask
+from testlib import GOL_EINVAL, GOL_ESTATE, gpu_lib as G  # noqa: F401 (the fixture)
 
 pytestmark = pytest.mark.gpu
 
-GOL_EINVAL, GOL_ESTATE = -1, -6
 MASKS = np.array([R.masks(r) for r in RULES], np.uint32)
-
-
-@pytest.fixture(scope="module")
-def G():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import golhip
-    golhip.lib()
-    return golhip
 
 
 def ref_each(cells, rules, turns):

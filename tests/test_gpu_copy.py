@@ -16,51 +16,14 @@ import pytest
 
 import rule_ref as R
 from oracle import oracle as O
-from test_gpu_edit import BYTE_EDITS, SEED, np_paste, random_cells, words_of
+from region_ref import BYTE_EDITS, SEED, apply_cuts, check_reads, np_box, np_paste, np_region, random_cells, words_of
+from testlib import gpu_lib as G  # noqa: F401 (the fixture)
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 WORKER = os.path.join(ROOT, "tests", "_copy_rank_worker.py")
 GUN = ("x = 36, y = 9, rule = B3/S23\n24bo$22bobo$12b2o6b2o12b2o$11bo3bo4b2o12b2o$2o8bo5bo3b2o$2o8bo3bob2o4bobo$"
        "10bo5bo7bo$11bo3bo$12b2o!\n")  # Gosper's glider gun
-
-
-@pytest.fixture(scope="module")
-def G():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import golhip
-    golhip.lib()
-    return golhip
-
-
-def np_region(cells, x0, y0, w, h):
-    """Rectangle cell (c, r) = board cell ((x0 + c) mod W, (y0 + r) mod H)."""
-    H, W = cells.shape
-    return cells[np.ix_((y0 + np.arange(h)) % H, (x0 + np.arange(w)) % W)]
-
-
-def np_box(sub):
-    """(bx, by, bw, bh, alive) of a bool array: the header's box, all zero without an alive cell."""
-    ys, xs = np.nonzero(sub)
-    if len(ys) == 0:
-        return 0, 0, 0, 0, 0
-    return int(xs.min()), int(ys.min()), int(xs.max() - xs.min() + 1), int(ys.max() - ys.min() + 1), len(ys)
-
-
-def check_reads(e, cells, rects, layout):
-    """copy, copy_words and bounds of every rectangle against numpy."""
-    for x0, y0, w, h in rects:
-        want = np_region(cells, x0, y0, w, h)
-        got, lay = e.copy(x0, y0, w, h, return_layout=True)
-        assert lay == layout and got.shape == (h, w) and got.dtype == bool, (x0, y0, w, h)
-        assert np.array_equal(got, want), (x0, y0, w, h)
-        words, alive = e.copy_words(x0, y0, w, h)
-        assert alive == np.count_nonzero(want) and words.shape == (h, (w + 63) // 64), (x0, y0, w, h)
-        bits = np.unpackbits(words.view(np.uint8), axis=1, bitorder="little")
-        assert np.array_equal(bits[:, :w] != 0, want) and not bits[:, w:].any(), (x0, y0, w, h)
-        assert e.bounds(x0, y0, w, h) == np_box(want), (x0, y0, w, h)
 
 
 # ---------------------------------------------------------------- band, in place
@@ -183,16 +146,6 @@ def test_exact_first_turn_pending(G):
 
 
 # ---------------------------------------------------------------- cut
-def apply_cuts(e, cells, rects, layout):
-    for x0, y0, w, h in rects:
-        want = np_region(cells, x0, y0, w, h)
-        words, alive, lay = e.copy_words(x0, y0, w, h, cut=True, return_layout=True)
-        assert np.array_equal(np.unpackbits(words.view(np.uint8), axis=1, bitorder="little")[:, :w] != 0, want), (x0, y0, w, h)
-        cells, cleared, _ = np_paste(cells, x0, y0, np.ones((h, w), bool), "andnot")
-        assert (alive, lay) == (cleared, layout) and cleared == np.count_nonzero(want), (x0, y0, w, h)
-    return cells
-
-
 def test_band_cut(G):
     H, W = 96, 1024
     cells = random_cells(H, W, 24)

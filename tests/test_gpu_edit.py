@@ -15,67 +15,12 @@ import pytest
 
 import rule_ref as R
 from oracle import oracle as O
+from region_ref import BYTE_EDITS, SEED, apply_edits, np_paste, random_cells, words_of
+from testlib import gpu_lib as G  # noqa: F401 (the fixture)
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 WORKER = os.path.join(ROOT, "tests", "_edit_rank_worker.py")
-SEED = 11
-
-
-@pytest.fixture(scope="module")
-def G():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import golhip
-    golhip.lib()
-    return golhip
-
-
-_boards = {}
-
-
-def random_cells(H, W, turns, seed=SEED):
-    """The oracle's board of load_random(seed) after `turns` turns as bool cells (computed once)."""
-    key = (H, W, turns, seed)
-    if key not in _boards:
-        cells = O.unpack(O.bits_run(O.random_words(seed, 0, H, W // 64), turns)) != 0
-        cells.setflags(write=False)
-        _boards[key] = cells
-    return _boards[key]
-
-
-def words_of(cells):
-    return O.pack(cells.astype(np.uint8) * 255)
-
-
-def np_paste(cells, x0, y0, p, op):
-    """(edited cells, cells changed, mask of written cells): pattern cell (c, r) lands on
-    ((x0 + c) mod W, (y0 + r) mod H)."""
-    H, W = cells.shape
-    p = np.asarray(p) != 0
-    ix = np.ix_((y0 + np.arange(p.shape[0])) % H, (x0 + np.arange(p.shape[1])) % W)
-    old = cells[ix]
-    new = {"copy": p, "or": old | p, "xor": old ^ p, "andnot": old & ~p}[op]
-    out = cells.copy()
-    out[ix] = new
-    written = np.zeros_like(cells)
-    written[ix] = True if op == "copy" else p
-    return out, int(np.count_nonzero(new != old)), written
-
-
-def apply_edits(e, cells, edits, layout, turn):
-    """Each edit (x0, y0, w, h, op, pattern seed or None = fill) on engine and numpy board alike."""
-    for x0, y0, w, h, op, seed in edits:
-        if seed is None:
-            p = np.ones((h, w), bool)
-            n, lay = e.fill(x0, y0, w, h, op, return_layout=True)
-        else:
-            p = np.random.default_rng(seed).random((h, w)) < 0.5
-            n, lay = e.paste(p, x0, y0, op, return_layout=True)
-        cells, want, _ = np_paste(cells, x0, y0, p, op)
-        assert (n, lay, e.turn) == (want, layout, turn), (x0, y0, w, h, op)
-    return cells
 
 
 # ---------------------------------------------------------------- band, in place
@@ -123,10 +68,6 @@ def test_standard_paste(G):
 
 
 # ---------------------------------------------------------------- byte rows
-BYTE_EDITS = [(90, 45, 30, 10, "copy", 1), (0, 0, 100, 3, "xor", 2), (99, 49, 2, 2, "or", 3), (13, 20, 64, 7, "andnot", 4),
-              (50, 10, 70, 5, "xor", None)]
-
-
 @pytest.mark.parametrize("H,W", [(50, 100), (50, 50)])  # aligned 4-byte words (W % 4 == 0); one byte per lane
 def test_bytes_paste_odd_width(G, H, W):
     rng = np.random.default_rng(5)

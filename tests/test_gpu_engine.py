@@ -14,21 +14,12 @@ import numpy as np
 import pytest
 
 from oracle import oracle as O
+from testlib import gpu_lib as golhip  # noqa: F401 (the fixture)
 
 pytestmark = pytest.mark.gpu
 
 SIZES = [16, 64, 512]
 TURNS = [0, 1, 100]
-
-
-@pytest.fixture(scope="module")
-def golhip():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import golhip as G
-    G.lib()
-    return G
 
 
 def _golden_board(golden_dir, size):

@@ -11,32 +11,11 @@ import numpy as np
 import pytest
 
 import island_ref as I
+from testlib import GOL_EINVAL, Guarded, gpu_lib as G  # noqa: F401 (the fixture)
 
 pytestmark = pytest.mark.gpu
 
-GOL_EINVAL = -1
-MARGIN = 64  # int64 words before and after every buffer
 FILL = 0xA5
-
-
-@pytest.fixture(scope="module")
-def G():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import golhip
-    golhip.lib()
-    torch.cuda.set_device(0)
-    return golhip
-
-
-def _device(host_bytes, fill=0x5A):
-    """A device buffer holding host_bytes (uint8) between two margins of `fill` bytes: (tensor, pointer, padded host)."""
-    import torch
-    m = np.full(MARGIN * 8, fill, dtype=np.uint8)
-    padded = np.concatenate([m, host_bytes, m])
-    t = torch.from_numpy(padded.copy()).cuda()
-    return t, t.data_ptr() + MARGIN * 8, padded
 
 
 def _launch(G, cells, reach, cap, with_fp=True):
@@ -45,22 +24,15 @@ def _launch(G, cells, reach, cap, with_fp=True):
     import torch
     n, H, W = cells.shape
     words = G.Batch.pack(cells.astype(np.uint8))
-    tb, pb, hb = _device(words.view(np.uint8).ravel())
-    tc, pc, hc = _device(np.full(n * 8, FILL, dtype=np.uint8))
-    tr, pr, hr = _device(np.full(n * cap * 24, FILL, dtype=np.uint8), fill=FILL)
-    tf, pf, hf = _device(np.full(n * 8, FILL, dtype=np.uint8))
-    rc = G.lib().gol_dev_batch_islands(pb, n, H, W, reach, cap, pc, pr if cap else None, pf if with_fp else None,
-                                       torch.cuda.current_stream().cuda_stream)
+    boards = Guarded(words, name="boards")
+    count = Guarded(np.full(n * 8, FILL, dtype=np.uint8), name="count")
+    recs = Guarded(np.full(n * cap * 24, FILL, dtype=np.uint8), fill=FILL, name="islands")
+    fp = Guarded(np.full(n * 8, FILL, dtype=np.uint8), name="fingerprint")
+    rc = G.lib().gol_dev_batch_islands(boards.ptr, n, H, W, reach, cap, count.ptr, recs.ptr if cap else None,
+                                       fp.ptr if with_fp else None, torch.cuda.current_stream().cuda_stream)
     torch.cuda.synchronize()
-    got = [t.cpu().numpy() for t in (tb, tc, tr, tf)]
-    assert np.array_equal(got[0], hb), "the boards or their margins changed"
-    lo, hi = MARGIN * 8, -MARGIN * 8
-    for g, h, name in ((got[1], hc, "count"), (got[2], hr, "islands"), (got[3], hf, "fingerprint")):
-        assert np.array_equal(g[:lo], h[:lo]) and np.array_equal(g[hi:], h[hi:]), f"a margin of {name} changed"
-    count = got[1][lo:hi].view(np.int64)
-    recs = got[2][lo:hi].view(I.DTYPE).reshape(n, cap)
-    fp = got[3][lo:hi].view(np.uint64)
-    return rc, count, recs, fp
+    assert boards.unchanged(), "the boards or their margins changed"
+    return rc, count.read(np.int64), recs.read(I.DTYPE, (n, cap)), fp.read(np.uint64)
 
 
 def _check_case(G, c, reach):
@@ -95,9 +67,9 @@ def test_refusals_launch_nothing(G):
     c = next(c for c in I.CASES if c.id == "five-cap3")
     n, H, W = c.cells.shape
     words = G.Batch.pack(c.cells.astype(np.uint8))
-    tb, pb, _ = _device(words.view(np.uint8).ravel())
-    tc, pc, hc = _device(np.full(n * 8, FILL, dtype=np.uint8))
-    tr, pr, hr = _device(np.full(n * 3 * 24, FILL, dtype=np.uint8))
+    boards, count = Guarded(words, name="boards"), Guarded(np.full(n * 8, FILL, dtype=np.uint8), name="count")
+    recs = Guarded(np.full(n * 3 * 24, FILL, dtype=np.uint8), name="islands")
+    pb, pc, pr = boards.ptr, count.ptr, recs.ptr
     s = torch.cuda.current_stream().cuda_stream
     f = G.lib().gol_dev_batch_islands
     bad = [f(None, n, H, W, 1, 3, pc, pr, None, s), f(pb, n, H, W, 1, 3, None, pr, None, s), f(pb, n, H, W, 1, 3, pc, None, None, s),
@@ -105,7 +77,7 @@ def test_refusals_launch_nothing(G):
            f(pb, n, H, W, 0, 3, pc, pr, None, s), f(pb, n, H, W, 3, 3, pc, pr, None, s), f(pb, n, H, W, 1, -1, pc, pr, None, s)]
     torch.cuda.synchronize()
     assert bad == [GOL_EINVAL] * len(bad)
-    assert np.array_equal(tc.cpu().numpy(), hc) and np.array_equal(tr.cpu().numpy(), hr)
+    assert count.unchanged() and recs.unchanged()
 
 
 # ------------------------------------------------------------------------------------------------ through Batch

@@ -2,7 +2,7 @@
 FREE> (csrc/gol_island.hip) on caller memory through gol_dev_batch_islands_sym and gol_dev_batch_islands_tally_sym,
 against the reference of tests/island_sym_ref.py (which turns and mirrors the board with numpy and never a window
 code), every compared field bit for bit.  The harness is that of tests/test_gpu_islands.py and
-tests/test_gpu_tally.py: every buffer of a launch lies between two margins of sentinel bytes, the records are
+tests/test_gpu_tally.py (testlib.Guarded, tally_ref.Launch): every buffer of a launch lies between two margins of sentinel bytes, the records are
 filled with 0xA5 before the launch, and the boards are compared byte for byte after the call.  Then the same
 through golhip.Batch: the census of a soup search, the eight images of a batch of boards, a batch against its
 transpose, and named patterns."""
@@ -14,25 +14,19 @@ import pytest
 import island_ref as I
 import island_sym_ref as F
 import tally_ref as T
-from test_gpu_islands import FILL, MARGIN, _device
-from test_gpu_tally import Buf, Launch
+from tally_ref import Launch
+from testlib import GOL_EINVAL, Guarded, gpu_lib
 
 pytestmark = pytest.mark.gpu
 
-GOL_EINVAL = -1
+FILL = 0xA5
 FIXED, FREE = F.FIXED, F.FREE
 
 
 @pytest.fixture(scope="module")
-def G():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import golhip
-    golhip.lib()
-    torch.cuda.set_device(0)
-    assert (golhip.ISLAND_FIXED, golhip.ISLAND_FREE) == (FIXED, FREE)
-    return golhip
+def G(gpu_lib):
+    assert (gpu_lib.ISLAND_FIXED, gpu_lib.ISLAND_FREE) == (FIXED, FREE)
+    return gpu_lib
 
 
 def _launch(G, cells, reach, symmetry, cap, with_fp=True, sym_entry=True):
@@ -41,25 +35,18 @@ def _launch(G, cells, reach, symmetry, cap, with_fp=True, sym_entry=True):
     import torch
     n, H, W = cells.shape
     words = G.Batch.pack(cells.astype(np.uint8))
-    tb, pb, hb = _device(words.view(np.uint8).ravel())
-    tc, pc, hc = _device(np.full(n * 8, FILL, dtype=np.uint8))
-    tr, pr, hr = _device(np.full(n * cap * 24, FILL, dtype=np.uint8), fill=FILL)
-    tf, pf, hf = _device(np.full(n * 8, FILL, dtype=np.uint8))
-    tail = (cap, pc, pr if cap else None, pf if with_fp else None, torch.cuda.current_stream().cuda_stream)
+    boards = Guarded(words, name="boards")
+    count = Guarded(np.full(n * 8, FILL, dtype=np.uint8), name="count")
+    recs = Guarded(np.full(n * cap * 24, FILL, dtype=np.uint8), fill=FILL, name="islands")
+    fp = Guarded(np.full(n * 8, FILL, dtype=np.uint8), name="fingerprint")
+    tail = (cap, count.ptr, recs.ptr if cap else None, fp.ptr if with_fp else None, torch.cuda.current_stream().cuda_stream)
     if sym_entry:
-        rc = G.lib().gol_dev_batch_islands_sym(pb, n, H, W, reach, symmetry, *tail)
+        rc = G.lib().gol_dev_batch_islands_sym(boards.ptr, n, H, W, reach, symmetry, *tail)
     else:
-        rc = G.lib().gol_dev_batch_islands(pb, n, H, W, reach, *tail)
+        rc = G.lib().gol_dev_batch_islands(boards.ptr, n, H, W, reach, *tail)
     torch.cuda.synchronize()
-    got = [t.cpu().numpy() for t in (tb, tc, tr, tf)]
-    assert np.array_equal(got[0], hb), "the boards or their margins changed"
-    lo, hi = MARGIN * 8, -MARGIN * 8
-    for g, h, name in ((got[1], hc, "count"), (got[2], hr, "islands"), (got[3], hf, "fingerprint")):
-        assert np.array_equal(g[:lo], h[:lo]) and np.array_equal(g[hi:], h[hi:]), f"a margin of {name} changed"
-    count = got[1][lo:hi].view(np.int64)
-    recs = got[2][lo:hi].view(I.DTYPE).reshape(n, cap)
-    fp = got[3][lo:hi].view(np.uint64)
-    return rc, count, recs, fp
+    assert boards.unchanged(), "the boards or their margins changed"
+    return rc, count.read(np.int64), recs.read(I.DTYPE, (n, cap)), fp.read(np.uint64)
 
 
 @pytest.mark.parametrize("c", I.CASES, ids=lambda c: c.id)
@@ -243,9 +230,9 @@ def test_refusals_launch_nothing(G):
     c = next(c for c in I.CASES if c.id == "five-cap3")
     n, H, W = c.cells.shape
     words = G.Batch.pack(c.cells.astype(np.uint8))
-    tb, pb, _ = _device(words.view(np.uint8).ravel())
-    tc, pc, hc = _device(np.full(n * 8, FILL, dtype=np.uint8))
-    tr, pr, hr = _device(np.full(n * 3 * 24, FILL, dtype=np.uint8))
+    boards, count = Guarded(words, name="boards"), Guarded(np.full(n * 8, FILL, dtype=np.uint8), name="count")
+    recs = Guarded(np.full(n * 3 * 24, FILL, dtype=np.uint8), name="islands")
+    pb, pc, pr = boards.ptr, count.ptr, recs.ptr
     s = torch.cuda.current_stream().cuda_stream
     f = G.lib().gol_dev_batch_islands_sym
     bad = [f(pb, n, H, W, 1, 2, 3, pc, pr, None, s), f(pb, n, H, W, 1, -1, 3, pc, pr, None, s), f(pb, n, H, W, 2, 8, 3, pc, pr, None, s),
@@ -257,7 +244,7 @@ def test_refusals_launch_nothing(G):
     bad += [L.run(1, 2), L.run(1, -1), L.run(0, FREE), L.run(3, FREE), L.run(1, FREE, owner0=-1)]
     torch.cuda.synchronize()
     assert bad == [GOL_EINVAL] * len(bad)
-    assert np.array_equal(tc.cpu().numpy(), hc) and np.array_equal(tr.cpu().numpy(), hr)
+    assert count.unchanged() and recs.unchanged()
     for buf in (L.count, L.fp, L.table, L.dropped, L.boards):
         assert buf.unchanged()
     # and through Batch, before any GPU work

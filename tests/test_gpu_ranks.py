@@ -18,21 +18,12 @@ import numpy as np
 import pytest
 
 from oracle import oracle as O
+from testlib import gpu_lib as G  # noqa: F401 (the fixture)
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 WORKER = os.path.join(ROOT, "tests", "_rank_worker.py")
 SPIN_LIB = os.path.join(ROOT, "gol-distributed-final_amd", "golhip", "libgolhip_spintest.so")
-
-
-@pytest.fixture(scope="module")
-def G():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import golhip
-    golhip.lib()
-    return golhip
 
 
 def run_ranks(G, nranks, H, W, scenario, per_rank=None, timeout=150, ipc_timeout_ms=30000, transport="ipc", **kw):

@@ -11,6 +11,7 @@ import pytest
 
 import rule_ref as R
 from oracle import oracle as O
+from testlib import gpu_lib as golhip  # noqa: F401 (the fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -32,16 +33,6 @@ SHAPES = [
     ("band", 24, 9216),
 ]
 SINGLE_BIT = [(1 << n, 0) for n in range(9)] + [(0, 1 << n) for n in range(9)]
-
-
-@pytest.fixture(scope="module")
-def golhip():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import golhip as G
-    G.lib()
-    return G
 
 
 def _seed(H, W, density):

@@ -2,26 +2,15 @@
 shard for the views, one for the paste, one for the reads): each query small, then past the scratch's
 first capacity of 4096 words, then small again, a cut that has the read and the edit scratch live on
 one stream, and a step of the board they leave.  Every comparison is exact, against the numpy
-references of test_gpu_view, test_gpu_edit and test_gpu_copy."""
+references of tests/region_ref.py."""
 import numpy as np
 import pytest
 
 from oracle import oracle as O
-from test_gpu_copy import apply_cuts, check_reads
-from test_gpu_edit import apply_edits, random_cells, words_of
-from test_gpu_view import check_view
+from region_ref import apply_cuts, apply_edits, check_reads, check_view, random_cells, words_of
+from testlib import gpu_lib as G  # noqa: F401 (the fixture)
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def G():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import golhip
-    golhip.lib()
-    return golhip
 
 
 def grow_and_shrink(e, cells, layout, small, turn):

@@ -12,31 +12,13 @@ data -- pitch padding, guard rows around every allocation, all of dst -- holds a
 read or a write one word out of place shows: the rule with birth on 0 neighbours turns anything
 read in place of a dead cell into live cells.
 """
-import ctypes
-
 import numpy as np
 import pytest
 
 import step_ref as S
+from testlib import error_word, gpu_lib as G  # noqa: F401 (the fixture)
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def G():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import golhip
-    golhip.lib()
-    torch.cuda.set_device(0)
-    return golhip
-
-
-def _error_word(G):
-    flags = ctypes.c_uint32(0xFFFF)
-    rc = G.lib().gol_dev_error(-1, ctypes.byref(flags))
-    return rc, flags.value
 
 
 def _dev(words):
@@ -85,7 +67,7 @@ def _launch(G, c, count=True):
                slots.data_ptr() if count else None, st)
     assert rc == 0, (c.id, G.lib().gol_last_error())
     torch.cuda.synchronize()
-    assert _error_word(G) == (0, 0), c.id
+    assert error_word(G) == (0, 0), c.id
     return before, {n: _host(t) for n, t in dev.items()}, slots
 
 
@@ -150,7 +132,7 @@ def test_chained_launches_see_each_other(G, kind, k, dw):
     assert _call(G, kind, k, dw, ptrs(a, b), R, Wd, pitch, r1, n1, 3, rule, None, st) == 0
     assert _call(G, kind, k, dw, ptrs(b, a), R, Wd, pitch, r2, n2, 4, rule, slots.data_ptr(), st) == 0
     torch.cuda.synchronize()
-    assert _error_word(G) == (0, 0)
+    assert error_word(G) == (0, 0)
     t1, t2 = S.stepped(seed, R, Wd, rule, k), S.expected(t0, 0, R, 2 * k, rule)
     want_b = np.full_like(a_host, S.SENT)
     want_b[g + r1:g + r1 + n1, :Wd] = pack(t1[r1:r1 + n1])
@@ -190,12 +172,12 @@ def test_refusals_launch_nothing(G, kind):
         rc = _call_entry(G, kind, ptr, S.refusal_args(kind, b), slots.data_ptr(), st)
         assert rc == G._lib.GOL_EINVAL, (kind, b)
     torch.cuda.synchronize()
-    assert _error_word(G) == (0, 0)
+    assert error_word(G) == (0, 0)
     assert bool((_host(dst) == S.SENT).all()) and int(slots.sum().item()) == S.COUNT_SEED[1]
     # and the call they were derived from is a good one
     assert _call_entry(G, kind, ptr, good, slots.data_ptr(), st) == 0
     torch.cuda.synchronize()
-    assert _error_word(G) == (0, 0)
+    assert error_word(G) == (0, 0)
     out = _host(dst)
     assert bool((out[g:g + R, :Wd] == 0).all()) and bool((out[:, Wd:] == S.SENT).all())
     assert int(slots.sum().item()) == S.COUNT_SEED[1]

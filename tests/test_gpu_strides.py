@@ -10,8 +10,6 @@ path exists): one and several shards, band, standard and byte rows.
 GOLHIP_SEQUENCE_LIBRARY names another build of the library to run the same cases on.
 """
 import ctypes
-import os
-import types
 
 import numpy as np
 import pytest
@@ -19,23 +17,13 @@ import pytest
 import engine_model as M
 import io_ref as IO
 from oracle import oracle as O
+from testlib import env  # noqa: F401 (the fixture)
 
 pytestmark = pytest.mark.gpu
 
 CIDS = list(M.CONFIGS)
 BIT_CIDS = [cid for cid in CIDS if M.Model.of(M.CONFIGS[cid]).bit]
 assert CIDS == ["band1", "band3", "std2", "bytes", "w32", "odd"] and BIT_CIDS == ["band1", "band3", "std2"]
-
-
-@pytest.fixture(scope="module")
-def env():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import golhip as G
-    path = os.environ.get("GOLHIP_SEQUENCE_LIBRARY")
-    L = G._lib.load(path) if path else G.lib()
-    return types.SimpleNamespace(G=G, L=L, torch=torch, EINVAL=G._lib.GOL_EINVAL, ESTATE=G._lib.GOL_ESTATE)
 
 
 def engine(env, c):

@@ -18,28 +18,16 @@ error word afterwards.
 Band `plain` (many rounds, no tail) needs >= 512 resident workgroups and a board of several GB
 and is left to the CPU test.
 """
-import ctypes
-
 import numpy as np
 import pytest
 
 from oracle import oracle as O
+from testlib import error_word, gpu_lib as G  # noqa: F401 (the fixture)
 
 pytestmark = pytest.mark.gpu
 
 SENT = 0x5A  # every byte of the sentinel
 KERNELS = {"band": 12, "bytes": 32}
-
-
-@pytest.fixture(scope="module")
-def G():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import golhip
-    golhip.lib()
-    torch.cuda.set_device(0)
-    return golhip
 
 
 def _units(kernel, W, pad):
@@ -55,12 +43,6 @@ def first_rows(G, kernel, mode, W, cus, slots, lo, hi, step=1, pad=0, row0=0, st
         if info["mode"] == mode and also(info):
             return rows
     raise AssertionError(f"no {kernel} launch of [{lo}, {hi}) rows x {W} has mode {mode} on {cus} CUs / {slots} slots")
-
-
-def _error_word(G):
-    flags = ctypes.c_uint32(0xFFFF)
-    rc = G.lib().gol_dev_error(-1, ctypes.byref(flags))
-    return rc, flags.value
 
 
 def run_case(G, kernel, mode, W, cus, slots, rows, *, row0=0, below=0, pad=0, separate=False, count=False, strip=0,
@@ -105,7 +87,7 @@ def run_case(G, kernel, mode, W, cus, slots, rows, *, row0=0, below=0, pad=0, se
         L.check(lib.gol_dev_bytes_step_k_on(top.data_ptr(), mid.data_ptr(), bot.data_ptr(), dst.data_ptr(), R, width,
                                             pitch, row0, rows, k, strip, cptr, st, *as_dev))
     torch.cuda.synchronize()
-    assert _error_word(G) == (0, 0)
+    assert error_word(G) == (0, 0)
     # the written rows, bit for bit
     out = dst[row0:row0 + rows]
     if kernel == "band":
@@ -275,7 +257,7 @@ def test_plain_entry_is_the_on_entry_with_this_device(G, kernel, k, count):
         name = ("gol_dev_band_step" if kernel == "band" else "gol_dev_bytes_step_k") + ("_on" if on else "")
         L.check(getattr(lib, name)(*args))
         torch.cuda.synchronize()
-        assert _error_word(G) == (0, 0)
+        assert error_word(G) == (0, 0)
         outs.append((dst, int(slots_t.sum().item()) if count else None))
     (plain, plain_n), (on, on_n) = outs
     assert bool((plain != SENT).any()), "nothing was written"
@@ -318,7 +300,7 @@ def test_counter_hand_over(G, kernel):
             else:
                 L.check(lib.gol_dev_bytes_step_k_on(*args, 0, None, s.cuda_stream, cus, slots))
     s.synchronize()
-    assert _error_word(G) == (0, 0)
+    assert error_word(G) == (0, 0)
 
     def cells(t, r0, rows):
         t = t[r0:r0 + rows]
@@ -363,4 +345,4 @@ def test_pretended_device_arguments(G, kernel):
     assert bool((dst == SENT).all()), "a refused call launched"
     assert launch(8, 8) == L.GOL_OK and launch(0, 0) == L.GOL_OK and launch(0, 0, 8) == L.GOL_OK
     torch.cuda.synchronize()
-    assert _error_word(G) == (0, 0)
+    assert error_word(G) == (0, 0)

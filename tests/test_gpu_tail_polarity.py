@@ -14,21 +14,12 @@ import numpy as np
 import pytest
 
 from oracle import oracle as O
+from testlib import gpu_lib as golhip  # noqa: F401 (the fixture)
 
 pytestmark = [pytest.mark.gpu, pytest.mark.timeout(120)]
 
 INPUTS = ("dead", "alive", "soup50", "soup5", "gliders")
 GLIDER = ((0, 1), (1, 2), (2, 0), (2, 1), (2, 2))  # heads down and to the right, one cell per 4 turns
-
-
-@pytest.fixture(scope="module")
-def golhip():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import golhip as G
-    G.lib()
-    return G
 
 
 @functools.lru_cache(maxsize=None)

@@ -11,77 +11,13 @@ import pytest
 
 import island_ref as I
 import tally_ref as T
+from tally_ref import ORDER, REFUSED, Launch
+from testlib import GOL_EINVAL, GOL_ENOMEM, GOL_ESTATE, Guarded, gpu_lib as G  # noqa: F401 (the fixture)
 
 pytestmark = pytest.mark.gpu
 
-GOL_EINVAL, GOL_ENOMEM, GOL_ESTATE = -1, -3, -6
-MARGIN = 64  # int64 words before and after every buffer
-FILL = 0xA5
+FILL = T.FILL
 SENTINEL = int.from_bytes(bytes([FILL]) * 8, "little")
-
-
-@pytest.fixture(scope="module")
-def G():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import golhip
-    golhip.lib()
-    torch.cuda.set_device(0)
-    from golhip import _lib
-    assert (_lib.GOL_EINVAL, _lib.GOL_ENOMEM, _lib.GOL_ESTATE) == (GOL_EINVAL, GOL_ENOMEM, GOL_ESTATE)
-    return golhip
-
-
-class Buf:
-    """A device buffer holding `host` (any array, as bytes) between two margins of `fill` bytes."""
-
-    def __init__(self, host, fill=0x5A):
-        import torch
-        m = np.full(MARGIN * 8, fill, dtype=np.uint8)
-        self.before = np.concatenate([m, np.ascontiguousarray(host).view(np.uint8).ravel(), m])
-        self.t = torch.from_numpy(self.before.copy()).cuda()
-        self.ptr = self.t.data_ptr() + MARGIN * 8
-
-    def read(self, dtype, name):
-        """The contents after checking the margins."""
-        got = self.t.cpu().numpy()
-        lo, hi = MARGIN * 8, len(got) - MARGIN * 8
-        assert np.array_equal(got[:lo], self.before[:lo]) and np.array_equal(got[hi:], self.before[hi:]), f"a margin of {name} changed"
-        return got[lo:hi].view(dtype)
-
-    def unchanged(self):
-        return np.array_equal(self.t.cpu().numpy(), self.before)
-
-
-class Launch:
-    """The buffers of tally launches on one stack of boards: a table of 2^log2 slots (empty, made here), dropped,
-    and count / fingerprint of `outs` entries filled with the sentinel."""
-
-    def __init__(self, G, cells, log2, outs=None):
-        self.G, self.cells, self.log2 = G, cells, log2
-        self.n, self.H, self.W = cells.shape
-        self.boards = Buf(G.Batch.pack(cells.astype(np.uint8)))
-        outs = self.n if outs is None else outs
-        self.count, self.fp = Buf(np.full(outs * 8, FILL, dtype=np.uint8)), Buf(np.full(outs * 8, FILL, dtype=np.uint8))
-        self.table, self.dropped = Buf(T.empty_table(log2)), Buf(np.zeros(1, dtype=np.int64))
-
-    def run(self, reach, owner0=0, pairs=None, pair_count=None, max_pairs=0, found=None, n=None):
-        import torch
-        rc = self.G.lib().gol_dev_batch_islands_tally(
-            self.boards.ptr, self.n if n is None else n, self.H, self.W, reach, pairs.ptr if pairs else None,
-            pair_count.ptr if pair_count else None, max_pairs, found.ptr if found else None, owner0, self.count.ptr, self.fp.ptr,
-            self.table.ptr, self.log2, self.dropped.ptr, torch.cuda.current_stream().cuda_stream)
-        torch.cuda.synchronize()
-        return rc
-
-    def results(self):
-        """(count, fingerprint, kinds sorted, dropped) after checking the boards, every margin and the empty slots."""
-        assert self.boards.unchanged(), "the boards or their margins changed"
-        kinds, empties_ok = T.table(self.table.read(np.uint8, "table").tobytes())
-        assert empties_ok, "a slot without a tag is not the empty pattern"
-        return (self.count.read(np.int64, "count"), self.fp.read(np.uint64, "fingerprint"), kinds,
-                int(self.dropped.read(np.int64, "dropped")[0]))
 
 
 def want_of_case(c, reach, owner0=0):
@@ -184,9 +120,9 @@ def _listed(G, cells, reach, k, max_pairs, owner0=0, expired=True):
         found[soups[dead]] = -1
         cells[slots[dead]] = 1  # a full board: one huge island, were it read
     L = Launch(G, cells, 10, outs=100)
-    pairs = Buf(np.stack([slots, soups], axis=1).astype(np.int32))
-    rc = L.run(reach, owner0=owner0, pairs=pairs, pair_count=Buf(np.array([k, 0], dtype=np.int32)), max_pairs=max_pairs,
-               found=Buf(found))
+    pairs = Guarded(np.stack([slots, soups], axis=1).astype(np.int32), name="pairs")
+    rc = L.run(reach, owner0=owner0, pairs=pairs, pair_count=Guarded(np.array([k, 0], dtype=np.int32), name="pair_count"),
+               max_pairs=max_pairs, found=Guarded(found, name="found"))
     assert pairs.unchanged()
     return L, rc, [(int(s), int(g)) for s, g in zip(slots[:k], soups[:k])], dead
 
@@ -214,8 +150,9 @@ def test_listed_passes_over_bad_pairs(G, boards):
     """A slot outside the boards or a negative soup (the restock pass writes -1 for a soup it cannot place) is passed over."""
     cells, _ = boards
     L = Launch(G, cells[:4], 10, outs=8)
-    pairs = Buf(np.array([[0, 2], [4, 1], [-1, 3], [1, -1], [3, 5]], dtype=np.int32))
-    rc = L.run(1, pairs=pairs, pair_count=Buf(np.array([5, 0], dtype=np.int32)), max_pairs=4, found=Buf(np.zeros(8, dtype=np.int64)), n=4)
+    pairs = Guarded(np.array([[0, 2], [4, 1], [-1, 3], [1, -1], [3, 5]], dtype=np.int32), name="pairs")
+    rc = L.run(1, pairs=pairs, pair_count=Guarded(np.array([5, 0], dtype=np.int32), name="pair_count"), max_pairs=4,
+               found=Guarded(np.zeros(8, dtype=np.int64), name="found"), n=4)
     assert rc == 0
     count, _, kinds, _ = L.results()
     # (max_pairs 4: the fifth pair is not run)
@@ -225,10 +162,9 @@ def test_listed_passes_over_bad_pairs(G, boards):
 
 # --------------------------------------------------------------------------------------- the raw entry, refusals
 def test_refusals_launch_nothing(G, boards):
-    from test_tally_ref_cpu import ORDER, REFUSED
     cells, _ = boards
     L = Launch(G, cells[:3], 10)
-    pairs, pc, found = Buf(np.zeros((3, 2), dtype=np.int32)), Buf(np.array([3, 0], dtype=np.int32)), Buf(np.zeros(3, dtype=np.int64))
+    pairs, pc, found = Guarded(np.zeros((3, 2), dtype=np.int32)), Guarded(np.array([3, 0], dtype=np.int32)), Guarded(np.zeros(3, dtype=np.int64))
     real = dict(boards=L.boards.ptr, count=L.count.ptr, fingerprint=L.fp.ptr, table=L.table.ptr, dropped=L.dropped.ptr,
                 pairs=pairs.ptr, pair_count=pc.ptr, found=found.ptr)
     check, launch = G.lib().gol_batch_islands_tally_check_host, G.lib().gol_dev_batch_islands_tally
@@ -247,12 +183,12 @@ def test_refusals_launch_nothing(G, boards):
 
 def test_table_clear(G):
     import torch
-    t = Buf(np.full(64 * 32, 0x77, dtype=np.uint8))
-    d = Buf(np.full(8, 0x77, dtype=np.uint8))
+    t = Guarded(np.full(64 * 32, 0x77, dtype=np.uint8), name="table")
+    d = Guarded(np.full(8, 0x77, dtype=np.uint8), name="dropped")
     s = torch.cuda.current_stream().cuda_stream
     assert G.lib().gol_dev_island_table_clear(t.ptr, 6, d.ptr, s) == 0
     torch.cuda.synchronize()
-    assert np.array_equal(t.read(T.SLOT_DTYPE, "table"), T.empty_table(6)) and d.read(np.int64, "dropped")[0] == 0
+    assert np.array_equal(t.read(T.SLOT_DTYPE), T.empty_table(6)) and d.read(np.int64)[0] == 0
     assert G.lib().gol_dev_island_table_clear(t.ptr, 3, d.ptr, s) == GOL_EINVAL
     assert G.lib().gol_dev_island_table_clear(None, 6, d.ptr, s) == GOL_EINVAL
 

@@ -13,14 +13,13 @@ from which the one shape per kernel is made that sends some threads round the gr
 GOLHIP_SEQUENCE_LIBRARY names another build of the library to run the same cases on.
 """
 import ctypes
-import os
-import types
 
 import numpy as np
 import pytest
 
 import io_ref as IO
 from oracle import oracle as O
+from testlib import Guarded, env  # noqa: F401 (the fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -32,39 +31,9 @@ SECOND_TRIP = {"random_fill": 256 * 64 * 256, "popcount": 256 * 16 * 256, "hash"
 GROW0 = [0, 7, 1 << 33]
 
 
-@pytest.fixture(scope="module")
-def env():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import golhip as G
-    path = os.environ.get("GOLHIP_SEQUENCE_LIBRARY")
-    L = G._lib.load(path) if path else G.lib()
-    torch.cuda.set_device(0)
-    return types.SimpleNamespace(G=G, L=L, torch=torch, EINVAL=G._lib.GOL_EINVAL)
-
-
-class Dev:
-    """A numpy array in device memory (a torch byte tensor), `off` bytes past a 16-byte boundary,
-    with 16 poisoned bytes before and after it that get() finds untouched."""
-    SLACK = 16
-
-    def __init__(self, env, arr, off=0):
-        assert 0 <= off < 16
-        self.env, self.shape, self.dtype, self.off = env, arr.shape, arr.dtype, self.SLACK + off
-        raw = np.ascontiguousarray(arr).view(np.uint8).reshape(-1)
-        self.n = raw.size
-        host = np.full(self.n + 3 * self.SLACK, IO.OUT_POISON, dtype=np.uint8)
-        host[self.off:self.off + self.n] = raw
-        self.t = env.torch.from_numpy(host).cuda()
-        assert self.t.data_ptr() % 16 == 0
-        self.ptr = self.t.data_ptr() + self.off
-
-    def get(self):
-        self.env.torch.cuda.synchronize()
-        raw = self.t.cpu().numpy()
-        assert (raw[:self.off] == IO.OUT_POISON).all() and (raw[self.off + self.n:] == IO.OUT_POISON).all()
-        return raw[self.off:self.off + self.n].copy().view(self.dtype).reshape(self.shape)
+def dev(arr, off=0):
+    """A numpy array in device memory, `off` bytes past a 16-byte boundary, between poisoned margins that read() finds untouched."""
+    return Guarded(arr, fill=IO.OUT_POISON, off=off)
 
 
 def ok(env, rc):
@@ -72,11 +41,11 @@ def ok(env, rc):
 
 
 def slots_sum(slots):
-    return int(slots.get().sum(dtype=np.uint64))
+    return int(slots.read().sum(dtype=np.uint64))
 
 
 def new_slots(env):
-    return Dev(env, np.zeros(SLOT_WORDS, dtype=np.uint64))
+    return dev(np.zeros(SLOT_WORDS, dtype=np.uint64))
 
 
 def rng_of(*key):
@@ -95,9 +64,9 @@ def fill(env, out, row0, rows, grow0, W, pitch, seed):
 @pytest.mark.parametrize("rows,W", FILL_SHAPES)
 def test_random_fill_is_the_oracles_board(env, rows, W, grow0):
     Wd, pitch, seed = W // 32, W // 32 + 2, 0x9E3779B97F4A7C15 ^ rows
-    out = Dev(env, IO.poisoned(rows + 2, pitch, np.uint32))
+    out = dev(IO.poisoned(rows + 2, pitch, np.uint32))
     fill(env, out, 1, rows, grow0, W, pitch, seed)
-    got, clean = IO.split_written(out.get(), 1, rows, Wd)
+    got, clean = IO.split_written(out.read(), 1, rows, Wd)
     assert clean
     assert np.array_equal(np.ascontiguousarray(got).view("<u8"), O.random_words(seed, grow0, rows, W // 64))
 
@@ -107,14 +76,14 @@ def test_random_fill_in_two_calls_and_of_no_rows(env, grow0):
     H, W, seed = 5, 192, 77
     Wd, pitch = W // 32, W // 32 + 4
     for a in range(H + 1):  # a = 0 and a = H: one of the calls has no rows
-        out = Dev(env, IO.poisoned(H + 2, pitch, np.uint32))
+        out = dev(IO.poisoned(H + 2, pitch, np.uint32))
         fill(env, out, 1, a, grow0, W, pitch, seed)
         fill(env, out, 1 + a, H - a, grow0 + a, W, pitch, seed)
-        got, clean = IO.split_written(out.get(), 1, H, Wd)
+        got, clean = IO.split_written(out.read(), 1, H, Wd)
         assert clean and np.array_equal(np.ascontiguousarray(got).view("<u8"), O.random_words(seed, grow0, H, W // 64)), a
-    out = Dev(env, IO.poisoned(2, pitch, np.uint32))
+    out = dev(IO.poisoned(2, pitch, np.uint32))
     fill(env, out, 1, 0, grow0, W, pitch, seed)
-    assert IO.split_written(out.get(), 0, 0, 0)[1]
+    assert IO.split_written(out.read(), 0, 0, 0)[1]
 
 
 # ------------------------------------------------------------------ gol_dev_popcount
@@ -126,7 +95,7 @@ def test_popcount_counts_the_words_and_not_the_padding(env, rows, Wd):
     L, pitch = env.L, Wd + 3
     words = rng_of(1, rows, Wd).integers(0, 1 << 32, (rows, Wd), dtype=np.uint32)
     want = int(np.unpackbits(words.view(np.uint8)).sum(dtype=np.int64))
-    src = Dev(env, IO.pitched(words, pitch, ONES32, 1, 1))
+    src = dev(IO.pitched(words, pitch, ONES32, 1, 1))
     slots = new_slots(env)
     ok(env, L.gol_dev_popcount(src.ptr + 4 * pitch, rows, Wd, pitch, slots.ptr, None))
     assert slots_sum(slots) == want
@@ -146,7 +115,7 @@ HASH_SHAPES = [(7, 6), (5, 2), (IO.second_trip_rows(SECOND_TRIP["hash"], 2100), 
 def dev_hash(env, words, grow0, pad=ONES32, slots=None, pitch=None):
     rows, Wd = words.shape
     pitch = pitch or Wd + 2
-    src = Dev(env, IO.pitched(words, pitch, pad, 1, 1))
+    src = dev(IO.pitched(words, pitch, pad, 1, 1))
     slots = slots or new_slots(env)
     ok(env, env.L.gol_dev_hash(src.ptr + 4 * pitch, rows, grow0, Wd, pitch, slots.ptr, None))
     return slots_sum(slots)
@@ -186,12 +155,12 @@ def test_hash_adds_over_splits_and_sees_rows_bits_and_no_padding(env, grow0):
 def dev_pack(env, board, stride, pitch, flag=True):
     """(bits written, output padding and outer rows untouched, *nonbinary or None)"""
     rows, W = board.shape
-    src = Dev(env, IO.pitched(board, stride, IO.PAD_BYTE, 1, 1))
-    bits = Dev(env, IO.poisoned(rows + 2, pitch, np.uint32))
-    f = Dev(env, np.zeros(1, dtype=np.uint32)) if flag else None
+    src = dev(IO.pitched(board, stride, IO.PAD_BYTE, 1, 1))
+    bits = dev(IO.poisoned(rows + 2, pitch, np.uint32))
+    f = dev(np.zeros(1, dtype=np.uint32)) if flag else None
     ok(env, env.L.gol_dev_pack(src.ptr + stride, rows, W, stride, bits.ptr + 4 * pitch, pitch, f.ptr if f else None, None))
-    got, clean = IO.split_written(bits.get(), 1, rows, W // 32)
-    return got, clean, int(f.get()[0]) if f else None
+    got, clean = IO.split_written(bits.read(), 1, rows, W // 32)
+    return got, clean, int(f.read()[0]) if f else None
 
 
 @pytest.mark.parametrize("W", [32, 96, 2112])
@@ -233,10 +202,10 @@ def test_pack_on_the_second_trip(env):
 def dev_unpack(env, words, stride, off=0):
     rows, Wd = words.shape
     pitch = Wd + 1
-    src = Dev(env, IO.pitched(words, pitch, ONES32, 1, 1))
-    out = Dev(env, IO.poisoned(rows + 2, stride, np.uint8), off=off)
+    src = dev(IO.pitched(words, pitch, ONES32, 1, 1))
+    out = dev(IO.poisoned(rows + 2, stride, np.uint8), off=off)
     ok(env, env.L.gol_dev_unpack(src.ptr + 4 * pitch, rows, 32 * Wd, pitch, out.ptr + stride, stride, None))
-    got, clean = IO.split_written(out.get(), 1, rows, 32 * Wd)
+    got, clean = IO.split_written(out.read(), 1, rows, 32 * Wd)
     return got, clean, [(out.ptr + (1 + y) * stride) % 16 == 0 for y in range(rows)]
 
 
@@ -277,9 +246,9 @@ def test_unpack_on_the_second_trip(env):
 # ------------------------------------------------------------------ gol_dev_bytes_step
 def dev_bytes_step(env, src, board, stride, y0, y1, out_stride, out_off):
     H, W = board.shape
-    out = Dev(env, IO.poisoned(y1 - y0 + 2, out_stride, np.uint8), off=out_off)
+    out = dev(IO.poisoned(y1 - y0 + 2, out_stride, np.uint8), off=out_off)
     ok(env, env.L.gol_dev_bytes_step(src.ptr, H, W, stride, y0, y1, out.ptr + out_stride, out_stride, None))
-    return IO.split_written(out.get(), 1, y1 - y0, W)
+    return IO.split_written(out.read(), 1, y1 - y0, W)
 
 
 @pytest.mark.parametrize("H", [1, 2, 3, 40])
@@ -294,7 +263,7 @@ def test_bytes_step_vector_and_scalar_kernel_on_one_board(env, W, H):
                 ("output + 1", a16 + 16, a16 + 32, 0, 1), ("strides", W + 5, W + 9, 0, 0)]
     slabs = sorted({(0, H), (0, 1), (H - 1, H), (H // 3, H // 3 + max(1, H // 2))})
     for name, stride, out_stride, in_off, out_off in variants:
-        src = Dev(env, IO.pitched(board, stride, 255), off=in_off)
+        src = dev(IO.pitched(board, stride, 255), off=in_off)
         for y0, y1 in slabs:
             got, clean = dev_bytes_step(env, src, board, stride, y0, y1, out_stride, out_off)
             assert clean and np.array_equal(got, O.next_state_slab(board, y0, y1)), (name, y0, y1)
@@ -304,7 +273,7 @@ def test_bytes_step_scalar_kernel_on_the_second_trip(env):
     W = 1050
     H = IO.second_trip_rows(SECOND_TRIP["bytes_step_scalar"], W)
     board = IO.random_bytes(rng_of(10), H, W)
-    src = Dev(env, IO.pitched(board, W + 5, 255))
+    src = dev(IO.pitched(board, W + 5, 255))
     got, clean = dev_bytes_step(env, src, board, W + 5, 0, H, W + 9, 0)
     assert clean and np.array_equal(got, O.next_state_slab(board, 0, H))
 
@@ -312,8 +281,8 @@ def test_bytes_step_scalar_kernel_on_the_second_trip(env):
 # ------------------------------------------------------------------ refusals
 def test_bad_arguments_are_refused_before_any_launch(env):
     L = env.L
-    src, dst = Dev(env, IO.poisoned(64, 1024, np.uint8)), Dev(env, IO.poisoned(64, 1024, np.uint8))
-    slots, flag = Dev(env, IO.poisoned(1, SLOT_WORDS, np.uint64)), Dev(env, IO.poisoned(1, 1, np.uint32))
+    src, dst = dev(IO.poisoned(64, 1024, np.uint8)), dev(IO.poisoned(64, 1024, np.uint8))
+    slots, flag = dev(IO.poisoned(1, SLOT_WORDS, np.uint64)), dev(IO.poisoned(1, 1, np.uint32))
     s, d, sl = src.ptr, dst.ptr, slots.ptr
     tables = [  # launcher, arguments it accepts, single changes it must refuse
         (L.gol_dev_random_fill, dict(dst=d, rows=2, grow0=0, W=128, pitch=6, seed=1, stream=None),
@@ -339,9 +308,9 @@ def test_bad_arguments_are_refused_before_any_launch(env):
             assert fn(*{**good, **change}.values()) == env.EINVAL, (fn.__name__, change)
             assert L.gol_last_error()
     for buf in (src, dst, slots, flag):  # nothing ran
-        assert (buf.get().view(np.uint8) == IO.OUT_POISON).all()
-    src2 = Dev(env, np.zeros((64, 1024), dtype=np.uint8))
-    zero = Dev(env, np.zeros(SLOT_WORDS, dtype=np.uint64))
+        assert (buf.read().view(np.uint8) == IO.OUT_POISON).all()
+    src2 = dev(np.zeros((64, 1024), dtype=np.uint8))
+    zero = dev(np.zeros(SLOT_WORDS, dtype=np.uint64))
     for fn, good, _ in tables:  # and what the tables change is accepted
         good = {k: {s: src2.ptr, sl: zero.ptr}.get(v, v) if isinstance(v, int) else v for k, v in good.items()}
         ok(env, fn(*good.values()))

@@ -14,48 +14,13 @@ import numpy as np
 import pytest
 
 from oracle import oracle as O
+from region_ref import check_view, ref_counts, ref_pixels
+from testlib import gpu_lib as G  # noqa: F401 (the fixture)
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 WORKER = os.path.join(ROOT, "tests", "_view_rank_worker.py")
 SEED = 11
-
-
-@pytest.fixture(scope="module")
-def G():
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    import golhip
-    golhip.lib()
-    return golhip
-
-
-def ref_counts(board, x0, y0, scale, out_w, out_h):
-    """n(i, j) of the issue's definition on a byte board (alive = byte != 0)."""
-    rows = np.take(board, y0 + np.arange(out_h * scale), axis=0, mode="wrap")
-    box = np.take(rows, x0 + np.arange(out_w * scale), axis=1, mode="wrap") != 0
-    return box.reshape(out_h, scale, out_w, scale).sum(axis=(1, 3)).astype(np.uint32)
-
-
-def ref_pixels(counts, scale):
-    s2 = scale * scale
-    return ((255 * counts.astype(np.int64) + s2 - 1) // s2).astype(np.uint8)
-
-
-def check_view(e, board, view, layout=None):
-    """Counts and pixels of `view` on engine e against the numpy reference on `board`."""
-    want = ref_counts(board, *view)
-    got, lay = e.view_counts(*view, return_layout=True)
-    assert got.dtype == np.uint32 and got.shape == (view[4], view[3])
-    bad = np.argwhere(got != want)
-    assert bad.size == 0, f"view {view}: {len(bad)} counts differ, first (j, i) = {bad[0]}: {got[tuple(bad[0])]} != {want[tuple(bad[0])]}"
-    pix, lay2 = e.view(*view, return_layout=True)
-    assert pix.dtype == np.uint8 and np.array_equal(pix, ref_pixels(want, view[2])), f"view {view}: pixels differ"
-    assert lay == lay2
-    if layout is not None:
-        assert lay == layout
-    return got, pix
 
 
 _boards = {}

@@ -13,17 +13,10 @@ import numpy as np
 import pytest
 
 import island_ref as I
+from testlib import GOL_EINVAL, cpu_lib as G  # noqa: F401 (the fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ISLAND_CHECK = os.path.join(ROOT, "gol-distributed-final_amd", "build", "asan", "island_check")
-GOL_EINVAL = -1
-
-
-@pytest.fixture(scope="module")
-def G():
-    import golhip
-    golhip.lib()
-    return golhip
 
 
 def host_census(G, cells, reach, cap=None, stride_pad=0):

@@ -18,19 +18,18 @@ import island_ref as I
 import island_sym_ref as F
 import rule_ref as R
 import tally_ref as T
+from tally_ref import DENSE, LISTED, ORDER, REFUSED
+from testlib import GOL_EINVAL, cpu_lib  # noqa: F401 (the fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYM_CHECK = os.path.join(ROOT, "gol-distributed-final_amd", "build", "asan", "island_sym_check")
-GOL_EINVAL = -1
 FIXED, FREE = F.FIXED, F.FREE
 
 
 @pytest.fixture(scope="module")
-def G():
-    import golhip
-    golhip.lib()
-    assert (golhip.ISLAND_FIXED, golhip.ISLAND_FREE) == (FIXED, FREE)
-    return golhip
+def G(cpu_lib):
+    assert (cpu_lib.ISLAND_FIXED, cpu_lib.ISLAND_FREE) == (FIXED, FREE)
+    return cpu_lib
 
 
 # ------------------------------------------------------------------------------------------------------ orient
@@ -312,7 +311,6 @@ def test_refusals_write_nothing(G):
 def test_launch_checks_take_the_symmetry(G):
     """gol_island_launch_ok's new field, through the two exports: 0 and 1 pass, everything else is refused, and the
     other refusals are those of the entries without _sym."""
-    from test_tally_ref_cpu import DENSE, LISTED, ORDER, REFUSED
     L = G.lib()
     P = 0x1000
     good = dict(boards=P, n=3, H=64, W=64, reach=1, symmetry=FREE, cap=8, count=P, islands=P, fingerprint=P)

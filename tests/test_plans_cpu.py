@@ -12,13 +12,7 @@ once and flag exactly the launches that read ghost rows.
 """
 import numpy as np
 import pytest
-
-
-@pytest.fixture(scope="module")
-def G():
-    import golhip
-    golhip.lib()
-    return golhip
+from testlib import cpu_lib as G  # noqa: F401 (the fixture)
 
 
 def _run_plans(G, H, n, k):

@@ -11,6 +11,7 @@ import pytest
 
 import rule_ref as R
 from oracle import oracle as O
+from testlib import cpu_lib as G  # noqa: F401 (the fixture)
 
 CANONICAL = {
     "B3/S23": (0x008, 0x00C),
@@ -28,13 +29,6 @@ MALFORMED = [
 ]
 SINGLE_BIT = [(1 << n, 0) for n in range(9)] + [(0, 1 << n) for n in range(9)]
 CIRCUIT_RULES = SINGLE_BIT + [R.masks(t) for t in ("B3/S23", "B36/S23", "B3678/S34678", "B0123478/S01234678")]
-
-
-@pytest.fixture(scope="module")
-def G():
-    import golhip
-    golhip.lib()
-    return golhip
 
 
 @pytest.mark.parametrize("text", sorted(CANONICAL))

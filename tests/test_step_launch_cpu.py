@@ -11,18 +11,11 @@ import subprocess
 import pytest
 
 import step_ref as S
+from testlib import GOL_EINVAL, cpu_lib as G  # noqa: F401 (the fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 STEP_CHECK = os.path.join(ROOT, "gol-distributed-final_amd", "build", "asan", "step_check")
-GOL_EINVAL = -1
 ALLOCS = ("src", "top", "mid", "bot", "dst")
-
-
-@pytest.fixture(scope="module")
-def G():
-    import golhip
-    golhip.lib()
-    return golhip
 
 
 def fake_ptr(alloc):

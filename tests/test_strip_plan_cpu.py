@@ -20,6 +20,7 @@ K, RPB and NS come from the library (gol_strip_info).
 """
 import numpy as np
 import pytest
+from testlib import cpu_lib as G  # noqa: F401 (the fixture)
 
 BAND_U = 232  # words per column group of the band pipeline: (64 - 2 * 3 halo lanes) * 4
 BYTES_U = 62 * 32  # cells per column group of the byte pipeline
@@ -28,13 +29,6 @@ BYTES_MODES = BAND_MODES - {"small", "tail"}
 CUS = (8, 64, 256, 304, 100)  # 100: not a multiple of 8, never ranked
 # BASELINE.json's boards: (kernel, H, W)
 BOARDS = (("bytes", 16384, 16384), ("band", 65536, 65536), ("band", 262144, 262144), ("band", 1 << 20, 1 << 20))
-
-
-@pytest.fixture(scope="module")
-def G():
-    import golhip
-    golhip.lib()
-    return golhip
 
 
 def _width(kernel, ngroups):

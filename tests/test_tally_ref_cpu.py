@@ -15,17 +15,11 @@ import pytest
 import island_ref as I
 import rule_ref as R
 import tally_ref as T
+from tally_ref import DENSE, LISTED, ORDER, P, REFUSED
+from testlib import GOL_EINVAL, cpu_lib as G  # noqa: F401 (the fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TALLY_CHECK = os.path.join(ROOT, "gol-distributed-final_amd", "build", "asan", "tally_check")
-GOL_EINVAL = -1
-
-
-@pytest.fixture(scope="module")
-def G():
-    import golhip
-    golhip.lib()
-    return golhip
 
 
 def host_tally(G, pairs, cap=None):
@@ -115,20 +109,6 @@ def test_tally_check_under_sanitizers():
     r = subprocess.run([TALLY_CHECK], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     assert "0 bad" in r.stdout
-
-
-P = 0x1000  # a pointer that is never dereferenced
-ORDER = ("boards", "n", "H", "W", "reach", "pairs", "pair_count", "max_pairs", "found", "owner0", "count", "fingerprint", "table",
-         "table_log2", "dropped")
-DENSE = dict(boards=P, n=3, H=64, W=64, reach=1, pairs=None, pair_count=None, max_pairs=0, found=None, owner0=0, count=P,
-             fingerprint=P, table=P, table_log2=10, dropped=P)
-LISTED = dict(DENSE, pairs=P, pair_count=P, max_pairs=3, found=P)
-REFUSED = [(DENSE, bad) for bad in (
-    dict(boards=None), dict(count=None), dict(table=None), dict(dropped=None), dict(n=0), dict(n=(1 << 20) + 1), dict(H=0),
-    dict(H=513), dict(W=0), dict(W=513), dict(reach=0), dict(reach=3), dict(reach=-1), dict(table_log2=3), dict(table_log2=25),
-    dict(table_log2=0), dict(owner0=-1), dict(owner0=(1 << 40) + 1), dict(pair_count=P), dict(found=P), dict(max_pairs=1))]
-REFUSED += [(LISTED, bad) for bad in (dict(pair_count=None), dict(found=None), dict(max_pairs=0), dict(max_pairs=4),
-                                      dict(max_pairs=-1), dict(table=None), dict(dropped=None), dict(table_log2=25))]
 
 
 def test_launch_check_refusals(G):

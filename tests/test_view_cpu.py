@@ -8,17 +8,11 @@ import re
 import pytest
 
 from oracle import oracle as O
+from testlib import cpu_lib as G  # noqa: F401 (the fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "golhip.h")
 NEW = ["gol_engine_view", "gol_engine_view_counts", "gol_view_plan", "gol_broker_view"]
-
-
-@pytest.fixture(scope="module")
-def G():
-    import golhip
-    golhip.lib()
-    return golhip
 
 
 def brute(H, nranks, rank, y0, vrows):
