@@ -293,6 +293,24 @@ extern "C" int gol_dev_batch_step(uint64_t *boards, uint64_t *prev, int64_t *set
     return GOL_OK;
 }
 
+extern "C" int gol_dev_batch_step_map(uint64_t *boards, uint64_t *prev, int64_t *settled, int64_t n, int64_t H, int64_t W,
+                                      int32_t turns, int64_t turn0, int32_t have_prev, int32_t write_prev, const uint32_t *maps,
+                                      int32_t map_each, int32_t scan, int64_t done, const int32_t *list, const int32_t *count,
+                                      int64_t slots, int64_t *left, const int64_t *born, void *stream)
+{
+    const gol_batch_launch l = {boards, prev, settled, n, H, W, turns, turn0, have_prev != 0, write_prev != 0, 0, 0,
+                                nullptr, scan, done, list, count, slots, left, born, maps, map_each != 0};
+    // (without maps it would be the launch of gol_dev_batch_step under B/S, which is not this entry's)
+    const hipError_t e = maps ? golk_batch_step(l, (hipStream_t)stream) : hipErrorInvalidValue;
+    if (e == hipErrorInvalidValue)  // gol_batch_launch_ok said no: nothing was launched
+        return gol_set_error(GOL_EINVAL,
+                             "bad batch_step_map arguments (n %lld, %lld x %lld, %d turns, scan %d, done %lld, slots %lld, map_each %d, or a "
+                             "pointer)",
+                             (long long)n, (long long)H, (long long)W, turns, scan, (long long)done, (long long)slots, map_each);
+    if (e != hipSuccess) return gol_set_error(GOL_EHIP, "batch_step_map: %s", hipGetErrorString(e));
+    return GOL_OK;
+}
+
 extern "C" int gol_dev_batch_islands_sym(const uint64_t *boards, int64_t n, int64_t H, int64_t W, int32_t reach, int32_t symmetry,
                                          int64_t cap, int64_t *count, gol_island *islands, uint64_t *fingerprint, void *stream)
 {

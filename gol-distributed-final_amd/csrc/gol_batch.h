@@ -134,6 +134,9 @@ struct gol_batch_launch {
     int64_t slots;                // with a list: the grid's board slots, >= *count; else 0 (the grid is sized by n)
     int64_t *left;                // the finish
     const int64_t *born;          // the aged search
+    // MAP rules (gol_map.h), or NULL: 16 words for every board, or map_each: n times 16, board b under maps + 16 b
+    const uint32_t *maps;
+    bool map_each;
 };
 
 // What makes a launch valid, per mode; everything else is refused and nothing is launched.
@@ -141,6 +144,8 @@ GOL_BATCH_HD bool gol_batch_launch_ok(const gol_batch_launch &l)
 {
     if (!l.boards || !gol_batch_shape_ok(l.n, l.H, l.W) || l.turns < 1 || l.birth >= 512 || l.survive >= 512 || l.done < 0)
         return false;
+    // maps take the place of the masks and of the rules per board; the aged search has one map; no maps, no flag
+    if (l.maps ? l.rules || l.birth || l.survive || (l.born && l.map_each) : l.map_each) return false;
     // a scan has its result and its second buffer; without one there is no scan mode and neither prev flag
     const bool scans = l.settled != nullptr;
     if (scans ? !l.prev || (l.scan != GOL_BATCH_SCAN_SETTLE && l.scan != GOL_BATCH_SCAN_CYCLES)

@@ -256,6 +256,7 @@ void golk_batch_shape(int64_t H, int64_t W, int *waves_per_board, int *boards_pe
 hipError_t golk_batch_step(const gol_batch_launch &l, hipStream_t s)
 {
     if (!gol_batch_launch_ok(l)) return hipErrorInvalidValue;
+    if (l.maps) return golk_batch_map_step(l, s);  // MAP rules: the kernel unit of their own (gol_batch_map.hip)
     int wpb, bpw, nw;
     golk_batch_shape(l.H, l.W, &wpb, &bpw, &nw);
     const BatchArgs a = {l.boards, l.prev, l.settled, l.n, l.turn0, gol_batch_row_init(l.W), (int32_t)l.H, (int32_t)((l.W + 63) / 64),

@@ -1,5 +1,5 @@
 // gol_batch_engine.cpp -- batches of small boards (include/golhip.h): the handle, the argument
-// checks, the rules per board, the split of a stepping call into launches (one gol_batch_launch per call,
+// checks, the rules per board and the MAP rules (gol_map.h), the split of a stepping call into launches (one gol_batch_launch per call,
 // gol_batch.h), the retiring call's lists and readbacks, the soup search's driver (with the census launch that
 // gol_batch_census adds to its harvest) and the strided copies.  The handle itself is gol_batch_int.h's; the island
 // census, the tally's kind table and their entries are gol_batch_census.cpp.
@@ -54,6 +54,24 @@ int reduce(gol_batch *b, bool hash, uint64_t *out, int64_t cap)
     return GOL_OK;
 }
 
+// A batch under MAP rules: the descriptor's two map fields from the device copy of the maps, brought up to date, and no
+// masks.  This is all a driver knows of maps.
+int use_maps(gol_batch *b, gol_batch_launch *l)
+{
+    if (b->maps.empty()) return GOL_OK;
+    if (b->maps_dirty || !b->dmaps) {
+        const int rc = need(b->dmaps, GOL_MAP_WORDS * b->n);
+        if (rc) return rc;
+        HIPCHK(hipMemcpyAsync(b->dmaps, b->maps.data(), b->maps.size() * sizeof(uint32_t), hipMemcpyHostToDevice, b->stream));
+        HIPCHK(hipStreamSynchronize(b->stream));  // (the host copy may change after the call)
+        b->maps_dirty = false;
+    }
+    l->birth = l->survive = 0;
+    l->maps = b->dmaps;
+    l->map_each = b->maps.size() > GOL_MAP_WORDS;
+    return GOL_OK;
+}
+
 // The start of a stepping call: the launch descriptor with what every launch of the call shares (the boards, the shape,
 // the rule, or the device copy of the rules per board brought up to date), and for a scan (scan != GOL_BATCH_SCAN_NONE)
 // its result per board (aux) at -1 and its second buffer.  The drivers set per launch the fields that differ.
@@ -68,7 +86,9 @@ int begin_call(gol_batch *b, int scan, int64_t turns, gol_batch_launch *l)
         l->settled = (int64_t *)b->aux;
         HIPCHK(hipMemsetAsync(l->settled, 0xff, (size_t)b->n * sizeof(int64_t), b->stream));
     }
-    if (b->rules.empty() || turns == 0) return GOL_OK;
+    if (turns == 0) return GOL_OK;
+    if (!b->maps.empty()) return use_maps(b, l);
+    if (b->rules.empty()) return GOL_OK;
     if (b->rules_dirty || !b->drules) {
         const int rc = need(b->drules, (int64_t)b->rules.size());
         if (rc) return rc;
@@ -189,6 +209,8 @@ int search(gol_batch *b, uint64_t seed, int64_t first, int64_t total, int64_t ho
     // the aged launch: the cycle scan of the listed slots in their own ages from turn 0, the snapshot always written
     gol_batch_launch l = {b->boards, b->prev, age, n, b->H, b->W, L, 0, false, true, b->birth, b->survive, nullptr,
                           GOL_BATCH_SCAN_CYCLES, 0, active, counts, 0, nullptr, born};
+    rc = use_maps(b, &l);
+    if (rc) return rc;
     int32_t *host = b->scounts;
     host[0] = (int32_t)m;
     for (int64_t done = 0; host[0] > 0;) {
@@ -276,6 +298,7 @@ int gol_batch_search_call(gol_batch *b, uint64_t seed, int64_t first, int64_t to
         return gol_set_error(GOL_EINVAL, "bad batch census (reach %d in 1..2, symmetry %d in 0..1, kinds_cap %lld in 0..2^23, or NULL)",
                              ask->reach, ask->symmetry, (long long)ask->kinds_cap);
     if (!b->rules.empty()) return gol_set_error(GOL_ESTATE, "batch %s: the boards of the batch have different rules", what);
+    if (b->maps.size() > GOL_MAP_WORDS) return gol_set_error(GOL_ESTATE, "batch %s: the boards of the batch have different maps", what);
     OnDevice dev(b->device);
     HIPCHK(dev.err);
     const int64_t m = std::min(b->n, total);
@@ -313,7 +336,7 @@ extern "C" void gol_batch_destroy(gol_batch *b)
     {
         OnDevice dev(b->device);
         if (b->stream) (void)hipStreamSynchronize(b->stream);
-        void *const device[] = {b->boards, b->prev, b->aux, b->drules, b->lists, b->left, b->slists, b->sages, b->tab, b->isl, b->kind};
+        void *const device[] = {b->boards, b->prev, b->aux, b->drules, b->dmaps, b->lists, b->left, b->slists, b->sages, b->tab, b->isl, b->kind};
         for (void *p : device)
             if (p) (void)hipFree(p);
         for (void *p : {(void *)b->hcounts, (void *)b->scounts})
@@ -382,12 +405,14 @@ extern "C" int gol_batch_set_rule(gol_batch *b, uint32_t birth, uint32_t survive
     b->birth = birth;
     b->survive = survive;
     b->rules.clear();
+    b->maps.clear();
     return GOL_OK;
 }
 
 extern "C" int gol_batch_rule(gol_batch *b, uint32_t *birth, uint32_t *survive)
 {
     if (!b) return gol_set_error(GOL_EINVAL, "batch is NULL");
+    if (!b->maps.empty()) return gol_set_error(GOL_ESTATE, "the batch runs under MAP rules (gol_batch_maps)");
     if (!b->rules.empty()) return gol_set_error(GOL_ESTATE, "the boards of the batch have different rules (gol_batch_rules)");
     if (birth) *birth = b->birth;
     if (survive) *survive = b->survive;
@@ -404,6 +429,7 @@ extern "C" int gol_batch_set_rules(gol_batch *b, int64_t i0, int64_t i1, const u
             return gol_set_error(GOL_EINVAL, "bad batch rule of board %lld (B 0x%x, S 0x%x: masks are 9 bits)", (long long)i,
                                  birth[i - i0], survive[i - i0]);
     if (i0 == i1) return GOL_OK;
+    b->maps.clear();  // (the boards outside [i0, i1) are under birth / survive again)
     if (b->rules.empty()) {  // one rule so far
         bool same = true;
         for (int64_t i = i0; i < i1 && same; ++i) same = birth[i - i0] == b->birth && survive[i - i0] == b->survive;
@@ -432,10 +458,66 @@ extern "C" int gol_batch_rules(gol_batch *b, int64_t i0, int64_t i1, uint32_t *b
     if (!b || !birth || !survive || i0 < 0 || i0 > i1 || i1 > b->n)
         return gol_set_error(GOL_EINVAL, "bad batch rules (boards [%lld, %lld) of %lld, or NULL)", (long long)i0, (long long)i1,
                              b ? (long long)b->n : 0LL);
+    if (!b->maps.empty()) return gol_set_error(GOL_ESTATE, "the batch runs under MAP rules (gol_batch_maps)");
     for (int64_t i = i0; i < i1; ++i) {
         birth[i - i0] = b->rules.empty() ? b->birth : b->rules[2 * i];
         survive[i - i0] = b->rules.empty() ? b->survive : b->rules[2 * i + 1];
     }
+    return GOL_OK;
+}
+
+// MAP rules (gol_map.h).  One map for the batch: the rules per board go, the masks stay unused until a rule is set again.
+extern "C" int gol_batch_set_map(gol_batch *b, const uint32_t *map)
+{
+    if (!b || !map) return gol_set_error(GOL_EINVAL, "bad batch set_map arguments (NULL)");
+    try {
+        b->maps.assign(map, map + GOL_MAP_WORDS);
+    } catch (const std::bad_alloc &) {
+        return gol_set_error(GOL_ENOMEM, "the map of the batch");
+    }
+    b->rules.clear();
+    b->maps_dirty = true;
+    return GOL_OK;
+}
+
+// The board's map as the batch stands: its own, the batch's one map, or its life-like rule as a map.
+static void map_of(const gol_batch *b, int64_t i, uint32_t *out)
+{
+    if (b->maps.size() > GOL_MAP_WORDS) memcpy(out, b->maps.data() + GOL_MAP_WORDS * i, GOL_MAP_WORDS * sizeof(uint32_t));
+    else if (!b->maps.empty()) memcpy(out, b->maps.data(), GOL_MAP_WORDS * sizeof(uint32_t));
+    else if (b->rules.empty()) gol_map_from_rule(b->birth, b->survive, out);
+    else gol_map_from_rule(b->rules[2 * i], b->rules[2 * i + 1], out);
+}
+
+extern "C" int gol_batch_set_maps(gol_batch *b, int64_t i0, int64_t i1, const uint32_t *maps)
+{
+    if (!b || !maps || i0 < 0 || i0 > i1 || i1 > b->n)
+        return gol_set_error(GOL_EINVAL, "bad batch set_maps (boards [%lld, %lld) of %lld, or NULL)", (long long)i0, (long long)i1,
+                             b ? (long long)b->n : 0LL);
+    if (i0 == i1) return GOL_OK;
+    std::vector<uint32_t> all;  // every board's map: the other boards keep theirs, a life-like rule as its map
+    try {
+        all.resize((size_t)(GOL_MAP_WORDS * b->n));
+    } catch (const std::bad_alloc &) {
+        return gol_set_error(GOL_ENOMEM, "maps of %lld boards", (long long)b->n);
+    }
+    for (int64_t i = 0; i < b->n; ++i) map_of(b, i, all.data() + GOL_MAP_WORDS * i);
+    memcpy(all.data() + GOL_MAP_WORDS * i0, maps, (size_t)(GOL_MAP_WORDS * (i1 - i0)) * sizeof(uint32_t));
+    bool same = true;
+    for (int64_t i = 1; i < b->n && same; ++i) same = !memcmp(all.data(), all.data() + GOL_MAP_WORDS * i, GOL_MAP_WORDS * sizeof(uint32_t));
+    if (same) all.resize(GOL_MAP_WORDS);  // one map: the launches of gol_batch_set_map
+    b->maps.swap(all);
+    b->rules.clear();
+    b->maps_dirty = true;
+    return GOL_OK;
+}
+
+extern "C" int gol_batch_maps(gol_batch *b, int64_t i0, int64_t i1, uint32_t *maps)
+{
+    if (!b || !maps || i0 < 0 || i0 > i1 || i1 > b->n)
+        return gol_set_error(GOL_EINVAL, "bad batch maps (boards [%lld, %lld) of %lld, or NULL)", (long long)i0, (long long)i1,
+                             b ? (long long)b->n : 0LL);
+    for (int64_t i = i0; i < i1; ++i) map_of(b, i, maps + GOL_MAP_WORDS * (i - i0));
     return GOL_OK;
 }
 

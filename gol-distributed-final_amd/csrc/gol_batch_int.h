@@ -8,6 +8,7 @@
 #include "gol_batch.h"
 #include "gol_engine_int.h"
 #include "gol_island.h"
+#include "gol_map.h"
 
 struct gol_batch {
     int64_t n = 0, H = 0, W = 0, Ww = 0;
@@ -20,6 +21,11 @@ struct gol_batch {
     std::vector<uint32_t> rules;
     uint32_t *drules = nullptr;  // the device copy of `rules` (on demand), stale while rules_dirty
     bool rules_dirty = false;
+    // MAP rules (gol_map.h).  empty: the batch runs under birth / survive or `rules`; 16 words: every board under this
+    // map; 16 n words, not all boards equal: a map per board.  Set: `rules` is empty and the masks are not used.
+    std::vector<uint32_t> maps;
+    uint32_t *dmaps = nullptr;  // the device copy of `maps` (16 n words, on demand), stale while maps_dirty
+    bool maps_dirty = false;
     int64_t turn = 0;
     hipStream_t stream = nullptr;
     uint64_t *boards = nullptr;

@@ -119,6 +119,8 @@ hipError_t golk_bounds_cols(const gol_region &r, const uint32_t *occ, uint64_t *
 struct gol_batch_launch;
 void golk_batch_shape(int64_t H, int64_t W, int *waves_per_board, int *boards_per_wg, int *words_per_lane);
 hipError_t golk_batch_step(const gol_batch_launch &launch, hipStream_t s);
+// The step kernel of MAP rules (gol_batch_map.hip): a launch whose descriptor has maps, which golk_batch_step hands over.
+hipError_t golk_batch_map_step(const gol_batch_launch &launch, hipStream_t s);
 // The island census (gol_island.hip): one launch of what the descriptor says (gol_island.h; every field is that of
 // gol_dev_batch_islands, include/golhip.h).  hipErrorInvalidValue, nothing launched, unless gol_island_launch_ok accepts it.
 struct gol_island_launch;

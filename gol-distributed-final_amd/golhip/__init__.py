@@ -14,13 +14,14 @@
 * ``Batch.islands`` / ``island`` / ``ISLAND_DTYPE``  the island census of every board of a batch, labelled on the GPU: per island a translation-invariant record (gol_batch_islands), and the record of a lone pattern to name it by
 * ``symmetry=ISLAND_FREE`` (``ISLAND_FIXED`` the default) on ``Batch.islands``, ``Batch.islands_tally``, ``Batch.census`` and ``island``  the free hash: the smallest of an island's hashes in the eight orientations of the square, computed in the kernel, so a tally holds one line per object however it is turned or mirrored (the _sym entries)
 * ``Batch.census`` / ``Batch.islands_tally`` / ``ISLAND_KIND_DTYPE``  the tally of island kinds (kind -> occurrences, with an example soup) of a streamed soup search or of the boards as they stand, built on the GPU inside the search's harvest (gol_batch_census, gol_batch_islands_tally)
+* ``Batch(rule="MAP...")`` / ``Batch.set_map`` / ``Batch.set_maps`` / ``Batch.maps`` / ``parse_map`` / ``format_map`` / ``map_from_rule``  MAP rules: any two-state rule of the 3x3 block as a 512-bit table, one for the batch or one per board, under every stepping call of a batch (gol_batch_set_map, gol_batch_set_maps)
 * ``distributor``          controller mirror (gol/gol.go + gol/distributor.go) over the broker API
 * ``next_state_slab`` / ``partition_rows``  worker.go:15-70 / broker.go:135-206
 
 Everything runs through libgolhip.so (hipcc, gfx950); there is no CPU fallback.
 """
-from ._lib import (GolError, device_count, format_rle, format_rule, halo_plan, lib, parse_rle, parse_rule,  # noqa: F401
-                   step_plan, strip_plan, view_plan)
+from ._lib import (GolError, device_count, format_map, format_rle, format_rule, halo_plan, lib, map_from_rule,  # noqa: F401
+                   parse_map, parse_rle, parse_rule, step_plan, strip_plan, view_plan)
 from .batch import ISLAND_DTYPE, ISLAND_FIXED, ISLAND_FREE, ISLAND_KIND_DTYPE, Batch, island  # noqa: F401
 from .broker import Operations  # noqa: F401
 from .engine import Engine, next_state_slab, partition_rows  # noqa: F401

@@ -198,6 +198,17 @@ SIGNATURES = [
     ("gol_batch_verdict_host", ctypes.c_int, [_i64, _i64, _i64]),
     ("gol_batch_step_check_host", ctypes.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i32, _i64, _i32, _i32, ctypes.c_uint32,
                                                  ctypes.c_uint32, _vp, _i32, _i64, _vp, _vp, _i64, _vp, _vp]),
+    # MAP rules of a batch (probed by symbol: a library without them still binds with strict=False)
+    ("gol_map_parse", ctypes.c_int, [ctypes.c_char_p, _vp]),
+    ("gol_map_format", ctypes.c_int, [_vp, ctypes.c_char_p, _i64]),
+    ("gol_map_from_rule_host", ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint32, _vp]),
+    ("gol_map_eval_host", ctypes.c_int, [_vp, _vp, _P(ctypes.c_uint32)]),
+    ("gol_batch_step_map_host", ctypes.c_int, [_i64, _i64, _vp, _vp, _vp, _i64, _i64]),
+    ("gol_batch_set_map", ctypes.c_int, [_vp, _vp]),
+    ("gol_batch_set_maps", ctypes.c_int, [_vp, _i64, _i64, _vp]),
+    ("gol_batch_maps", ctypes.c_int, [_vp, _i64, _i64, _vp]),
+    ("gol_batch_step_map_check_host", ctypes.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i32, _i64, _i32, _i32, _vp, _i32, _i32, _i64,
+                                                     _vp, _vp, _i64, _vp, _vp]),
     ("gol_batch_islands", ctypes.c_int, [_vp, _i64, _i64, _i32, _i64, _vp, _vp, _vp]),
     ("gol_batch_islands_host", ctypes.c_int, [_i64, _i64, _i32, _vp, _i64, _i64, _vp, _vp, _vp]),
     ("gol_batch_islands_check_host", ctypes.c_int, [_vp, _i64, _i64, _i64, _i32, _i64, _vp, _vp, _vp]),
@@ -254,6 +265,8 @@ SIGNATURES = [
     ("gol_dev_batch_restock", ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
     ("gol_dev_batch_step", ctypes.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i32, _i64, _i32, _i32, ctypes.c_uint32,
                                           ctypes.c_uint32, _vp, _i32, _i64, _vp, _vp, _i64, _vp, _vp, _vp]),
+    ("gol_dev_batch_step_map", ctypes.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i32, _i64, _i32, _i32, _vp, _i32, _i32, _i64, _vp,
+                                              _vp, _i64, _vp, _vp, _vp]),
     ("gol_dev_batch_islands", ctypes.c_int, [_vp, _i64, _i64, _i64, _i32, _i64, _vp, _vp, _vp, _vp]),
     ("gol_dev_batch_islands_tally", ctypes.c_int, [_vp, _i64, _i64, _i64, _i32, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i32, _vp,
                                                    _vp]),
@@ -405,6 +418,46 @@ def format_rule(birth: int, survive: int, library=None) -> str:
     buf = ctypes.create_string_buffer(24)
     _lib_check(L, L.gol_rule_format(birth, survive, buf, len(buf)))
     return buf.value.decode()
+
+
+def _as_map(table) -> "np.ndarray":
+    import numpy as np
+    a = np.asarray(table)
+    if a.shape != (16,) or a.dtype.kind not in "ui" or np.any(a < 0) or np.any(a.astype(np.uint64) >= 1 << 32):
+        raise GolError(GOL_EINVAL, f"a map is 16 uint32 words (512 bits), got {a.dtype} {a.shape}")
+    return np.ascontiguousarray(a, dtype=np.uint32)
+
+
+def parse_map(text: str, library=None) -> "np.ndarray":
+    """gol_map_parse: "MAP" and 86 base64 characters (with or without "=="), or "B36/S23", -> uint32[16], the
+    512-bit table whose bit i = 256 NW + 128 N + 64 NE + 32 W + 16 C + 8 E + 4 SW + 2 S + SE says whether the cell is
+    alive next turn.  Host code: no GPU needed."""
+    import numpy as np
+    L = library or lib()
+    m = np.zeros(16, dtype=np.uint32)
+    _lib_check(L, L.gol_map_parse(str(text).encode(), m.ctypes.data))
+    return m
+
+
+def format_map(table, library=None) -> str:
+    """gol_map_format: the text of a map, "MAP" and 86 base64 characters."""
+    L = library or lib()
+    m = _as_map(table)
+    buf = ctypes.create_string_buffer(90)
+    _lib_check(L, L.gol_map_format(m.ctypes.data, buf, len(buf)))
+    return buf.value.decode()
+
+
+def map_from_rule(rule, library=None) -> "np.ndarray":
+    """gol_map_from_rule_host: a life-like rule ("B36/S23" or a (birth, survive) pair of 9-bit masks) as a map."""
+    import numpy as np
+    L = library or lib()
+    birth, survive = parse_rule(rule, L) if isinstance(rule, str) else (int(rule[0]), int(rule[1]))
+    if not (0 <= birth < 1 << 32 and 0 <= survive < 1 << 32):
+        raise GolError(GOL_EINVAL, f"rule masks out of range ({birth}, {survive})")
+    m = np.zeros(16, dtype=np.uint32)
+    _lib_check(L, L.gol_map_from_rule_host(birth, survive, m.ctypes.data))
+    return m
 
 
 def pack_pattern(cells) -> "np.ndarray":

@@ -14,7 +14,7 @@ import ctypes
 
 import numpy as np
 
-from ._lib import GOL_EINVAL, GOL_ENOMEM, GolError, format_rule, lib, parse_rle, parse_rule
+from ._lib import GOL_EINVAL, GOL_ENOMEM, GolError, _as_map, format_rule, lib, parse_map, parse_rle, parse_rule
 
 # gol_island (include/golhip.h): the record of an island, 24 bytes
 ISLAND_DTYPE = np.dtype([("y", "<i4"), ("x", "<i4"), ("cells", "<i4"), ("rows", "<u2"), ("cols", "<u2"), ("hash", "<u8")])
@@ -222,8 +222,10 @@ class Batch:
 
     # -- the rule
     def set_rule(self, rule) -> None:
-        """The rule of every later turn: "B36/S23" or a (birth, survive) pair of 9-bit masks.  The
-        boards and the turn counter stay."""
+        """The rule of every later turn: "B36/S23" or a (birth, survive) pair of 9-bit masks, or "MAP..." (set_map).
+        The boards and the turn counter stay."""
+        if isinstance(rule, str) and rule.startswith("MAP"):
+            return self.set_map(rule)
         birth, survive = parse_rule(rule, self._L) if isinstance(rule, str) else (int(rule[0]), int(rule[1]))
         if not (0 <= birth < 1 << 32 and 0 <= survive < 1 << 32):
             raise GolError(GOL_EINVAL, f"rule masks out of range ({birth}, {survive})")
@@ -231,7 +233,8 @@ class Batch:
 
     @property
     def rule(self) -> str:
-        """The rule all boards share; GolError(GOL_ESTATE) when their rules differ (see rules())."""
+        """The rule all boards share; GolError(GOL_ESTATE) when their rules differ (see rules()) and under MAP rules
+        (see maps())."""
         b, s = ctypes.c_uint32(), ctypes.c_uint32()
         self._check(self._L.gol_batch_rule(self._h, ctypes.byref(b), ctypes.byref(s)))
         return format_rule(b.value, s.value, self._L)
@@ -259,6 +262,31 @@ class Batch:
         birth, survive = (np.zeros(max(count, 0), dtype=np.uint32) for _ in range(2))
         self._check(self._L.gol_batch_rules(self._h, first, first + count, birth.ctypes.data, survive.ctypes.data))
         return np.stack([birth, survive], axis=1)
+
+    # -- MAP rules: any two-state rule of the 3x3 block as a table of 512 bits (gol_batch_set_map in golhip.h)
+    def set_map(self, table) -> None:
+        """Every board under one map from now on: "MAP..." text (or "B36/S23", as its map) or uint32[16], bit
+        i = 256 NW + 128 N + 64 NE + 32 W + 16 C + 8 E + 4 SW + 2 S + SE of the table = the cell is alive next turn.
+        Clears the rules; set_rule / set_rules clear the maps.  The boards and the turn counter stay."""
+        m = parse_map(table, self._L) if isinstance(table, str) else _as_map(table)
+        self._check(self._L.gol_batch_set_map(self._h, m.ctypes.data))
+
+    def set_maps(self, maps, first: int = 0) -> None:
+        """The maps of boards [first, first + k) from uint32[k, 16]; the other boards keep what they run under (a
+        life-like rule as its map)."""
+        a = np.asarray(maps)
+        if a.ndim != 2 or a.shape[1] != 16 or a.dtype != np.uint32:
+            raise GolError(GOL_EINVAL, f"maps are a uint32 array of shape (k, 16), got {a.dtype} {a.shape}")
+        a = np.ascontiguousarray(a)
+        self._check(self._L.gol_batch_set_maps(self._h, first, first + a.shape[0], a.ctypes.data))
+
+    def maps(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        """uint32[count, 16]: the maps of boards [first, first + count) (default: all from `first`) as the batch
+        stands; a board under a life-like rule has that rule's map."""
+        count = self.n - first if count is None else count
+        out = np.zeros((max(count, 0), 16), dtype=np.uint32)
+        self._check(self._L.gol_batch_maps(self._h, first, first + count, out.ctypes.data))
+        return out
 
     # -- stepping and queries
     def step(self, turns: int, settled: bool = False):

@@ -733,6 +733,70 @@ int gol_batch_step_check_host(const uint64_t *boards, const uint64_t *prev, cons
                               int64_t W, int32_t turns, int64_t turn0, int32_t have_prev, int32_t write_prev, uint32_t birth,
                               uint32_t survive, const uint32_t *rules, int32_t scan, int64_t done, const int32_t *list,
                               const int32_t *count, int64_t slots, const int64_t *left, const int64_t *born);
+/* MAP rules of a batch: any two-state rule of the 3x3 block, the isotropic
+ * non-totalistic and the anisotropic ones included, as a table of 512 bits (no
+ * version bump: probe by symbol).  The kernel is csrc/gol_batch_map.hip, the
+ * circuit it shares with the host functions csrc/gol_map.h.
+ *
+ * A map is uint32_t map[16].  Its bit i is (map[i >> 5] >> (i & 31)) & 1, for i
+ * in 0..511.  For cell (y, x) of an H x W torus:
+ *   i = 256 NW + 128 N + 64 NE + 32 W + 16 C + 8 E + 4 SW + 2 S + SE
+ * where N is the cell at row (y - 1) mod H and S the one at row (y + 1) mod H, W
+ * is at column (x - 1) mod W and E at column (x + 1) mod W, and C is the cell
+ * itself.  The formula holds as written on every torus: on W = 1 the three
+ * columns are the same cell, on H = 2 the row above is the row below.  The cell
+ * is alive next turn iff bit i is set, i = 0 included: a map may give birth on
+ * empty ground, as B0 rules do, and the padding of a row's last word still
+ * stays clear.
+ * Text: "MAP" followed by the base64 (standard alphabet) of the 64 bytes whose
+ * bit i is bit 7 - (i & 7) of byte i >> 3, MSB first: 86 characters, which
+ * gol_map_parse accepts with or without a trailing "==" (and whose last four
+ * bits must be zero); gol_map_format writes the 86.  This is the form Golly and
+ * LifeViewer write.  Hensel notation ("B2-a/S12") is not parsed: a caller
+ * builds such a rule as a table.
+ *  - gol_map_parse: "MAP..." as above, or a life-like rule "B.../S..." through
+ *    gol_rule_parse, into map[16].  GOL_EINVAL: NULL, a wrong length, a character
+ *    that is not base64, bits after the 512th; map is then untouched.
+ *  - gol_map_format: the text of a map into buf, 90 bytes with the final 0;
+ *    GOL_EINVAL: NULL, len < 90.
+ *  - gol_map_from_rule_host: the life-like rule (9-bit masks) as a map: bit i is
+ *    the survive (C set) or birth mask's bit at the count of the other eight.
+ *  - gol_map_eval_host: the circuit on nine planes of 32 cells, x[k] the plane of
+ *    weight 2^(8 - k) in i, that is x = {NW, N, NE, W, C, E, SW, S, SE}: bit j of
+ *    *next = the map's bit at the index formed from bit j of every plane.
+ *  - gol_batch_step_map_host: `turns` >= 0 turns of one H x W torus on host
+ *    memory under a map, with the row function the kernel runs; in, out and
+ *    row_stride as for gol_batch_step_host (they may be the same buffer).
+ *    GOL_EINVAL: H or W outside 1..512, row_stride < Ww, turns < 0, NULL.
+ *  - gol_batch_set_map: every board under one map.  gol_batch_set_maps: boards
+ *    [i0, i1) under maps + 16 (i - i0); the other boards keep what they run
+ *    under, a life-like rule as its map; a batch whose maps are all equal runs
+ *    as after set_map.  gol_batch_maps: the maps of boards [i0, i1) as the batch
+ *    stands (a life-like rule as its map).  The boards and the turn stay.
+ *    gol_batch_set_rule and set_rules clear the maps (after set_rules the boards
+ *    outside its range run under the rule set_rule gave last, default B3/S23),
+ *    and set_map / set_maps clear the rules.  While maps are set gol_batch_rule
+ *    and gol_batch_rules return GOL_ESTATE, their outputs untouched.
+ *  - Under maps step (with and without settled), step_cycles and run_cycles
+ *    work as described above, with one map or a map per board; search, census
+ *    and census_sym work under one map and return GOL_ESTATE under differing
+ *    maps, as for differing rules.  The island calls, alive_counts, hashes,
+ *    loads and stores do not depend on the rule.
+ *  - gol_batch_step_map_check_host: the argument check of gol_dev_batch_step_map
+ *    (below), its arguments without the stream; as gol_batch_step_check_host. */
+int gol_map_parse(const char *text, uint32_t *map);
+int gol_map_format(const uint32_t *map, char *buf, int64_t len);
+int gol_map_from_rule_host(uint32_t birth, uint32_t survive, uint32_t *map);
+int gol_map_eval_host(const uint32_t *map, const uint32_t x[9], uint32_t *next);
+int gol_batch_step_map_host(int64_t H, int64_t W, const uint32_t *map, const uint64_t *in, uint64_t *out, int64_t row_stride,
+                            int64_t turns);
+int gol_batch_set_map(gol_batch *b, const uint32_t *map);
+int gol_batch_set_maps(gol_batch *b, int64_t i0, int64_t i1, const uint32_t *maps);
+int gol_batch_maps(gol_batch *b, int64_t i0, int64_t i1, uint32_t *maps);
+int gol_batch_step_map_check_host(const uint64_t *boards, const uint64_t *prev, const int64_t *settled, int64_t n, int64_t H,
+                                  int64_t W, int32_t turns, int64_t turn0, int32_t have_prev, int32_t write_prev,
+                                  const uint32_t *maps, int32_t map_each, int32_t scan, int64_t done, const int32_t *list,
+                                  const int32_t *count, int64_t slots, const int64_t *left, const int64_t *born);
 /* The island census of a batch: per board its islands, the connected groups of
  * alive cells, each with a fingerprint that no torus translation changes,
  * labelled on the GPU in one launch on the boards where they lie (the kernel
@@ -1306,6 +1370,17 @@ int gol_dev_batch_step(uint64_t *boards, uint64_t *prev, int64_t *settled, int64
                        int64_t turn0, int32_t have_prev, int32_t write_prev, uint32_t birth, uint32_t survive,
                        const uint32_t *rules, int32_t scan, int64_t done, const int32_t *list, const int32_t *count,
                        int64_t slots, int64_t *left, const int64_t *born, void *stream);
+/* The same launch under MAP rules ("MAP rules of a batch", above; no version
+ * bump: probe by symbol): gol_dev_batch_step's arguments with maps and map_each
+ * in place of birth, survive and rules.  map_each == 0: maps is uint32_t[16], the
+ * map of every board; else uint32_t[16 n], board b under maps + 16 b.  Every mode
+ * above is taken with the same meaning; the aged mode requires map_each == 0.
+ * maps is only read.  GOL_EINVAL, nothing launched: as gol_dev_batch_step, and a
+ * NULL maps. */
+int gol_dev_batch_step_map(uint64_t *boards, uint64_t *prev, int64_t *settled, int64_t n, int64_t H, int64_t W, int32_t turns,
+                           int64_t turn0, int32_t have_prev, int32_t write_prev, const uint32_t *maps, int32_t map_each,
+                           int32_t scan, int64_t done, const int32_t *list, const int32_t *count, int64_t slots, int64_t *left,
+                           const int64_t *born, void *stream);
 /* One launch of the island census (gol_batch_islands, above, where islands,
  * records and fingerprints are defined) on caller device memory: boards as for
  * gol_dev_batch_step, only read; count int64_t[n]; islands n cap records (may be
