@@ -15,7 +15,8 @@
 // kernels (golk::rule), any other rule gol_rule_sum3 + gol_rule_eval (gol_rule.h).  The padding of the
 // result is cleared afterwards (a cell of the padding has neighbours, and B0 rules give birth there).
 // Also here, for the same reason: the step kernel's modes and the marks of its cycle scan, the soup words and the
-// census, and the descriptor of one launch with the one check of what makes it valid (no HIP header is needed).
+// census, the descriptor of one launch with the one check of what makes it valid, and the host twins' unpacking of a
+// uint64 row into a lane's words and back (no HIP header is needed).
 #pragma once
 #include <stdint.h>
 
@@ -183,6 +184,22 @@ GOL_BATCH_HD gol_batch_row gol_batch_row_init(int64_t W)  // 1 <= W <= GOL_BATCH
 GOL_BATCH_HD bool gol_batch_conway(uint32_t birth, uint32_t survive)
 {
     return birth == GOL_RULE_BIRTH_CONWAY && survive == GOL_RULE_SURVIVE_CONWAY;
+}
+
+// A host row of ceil(W / 64) uint64 words as the g.nw words a lane holds (the padding of the input masked off), and back
+// (an odd nwr: the upper half of the last uint64 word is padding).
+GOL_BATCH_HD void gol_batch_unpack_row(const gol_batch_row &g, const uint64_t *row, uint32_t *c)
+{
+    for (int j = 0; j < g.nw; ++j) {
+        c[j] = j < g.nwr ? (uint32_t)(row[j / 2] >> (32 * (j & 1))) : 0u;
+        if (j == g.nwr - 1) c[j] &= g.tail;
+    }
+}
+
+GOL_BATCH_HD void gol_batch_pack_row(const gol_batch_row &g, const uint32_t *c, uint64_t *row)
+{
+    for (int w = 0; w < (g.nwr + 1) / 2; ++w)
+        row[w] = (uint64_t)c[2 * w] | (uint64_t)(2 * w + 1 < g.nw ? c[2 * w + 1] : 0u) << 32;
 }
 
 // The horizontal sums of a row (padding zero).  nwr and tb are wave-uniform in a kernel.

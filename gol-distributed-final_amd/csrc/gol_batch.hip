@@ -41,54 +41,31 @@
 //
 // This unit holds the step kernel, the dispatch over its 85 instantiations and its one entry, golk_batch_step, which
 // launches what a gol_batch_launch describes once gol_batch_launch_ok (gol_batch.h) accepts it.  The small kernels round
-// it (fills, census, the passes between the launches of a call) are gol_batch_pass.hip.
+// it (fills, census, the passes between the launches of a call) are gol_batch_pass.hip.  What the kernel shares with the
+// MAP kernel (gol_batch_map.hip) outside its body -- the arguments, a lane's row load and store, the launch code -- is
+// gol_batch_args.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <algorithm>
+#include <cstddef>
 
-#include "gol_device.h"
 #define GOL_BATCH_CONWAY golk::rule  // B3/S23 on the step kernels' 7 gates
-#include "gol_batch.h"
+#include "gol_batch_args.h"
 
 namespace {
 
-struct BatchArgs {
-    uint64_t *boards;  // n boards of H rows of Ww uint64 words, dense; stepped in place
-    uint64_t *prev;    // SCAN: state(start - 1) in (have_prev), state(end - 1) out (write_prev); same shape
-    int64_t *settled;  // SCAN: n turns, -1 = not settled yet
-    int64_t n, turn0;  // boards; the turn of the loaded state
-    gol_batch_row g;
-    int32_t H, Ww, wpb, bpw;  // rows, uint64 words per row, waves per board, boards per workgroup
-    int32_t turns;            // >= 1
-    int32_t have_prev, write_prev;
-    uint32_t birth, survive;
+using golk::load_row;
+using golk::store_row;
+
+// (aligned to 4 bytes, so that the masks stand right after write_prev as they always did; pad puts the pointer at a
+// multiple of 8 in the arguments)
+struct __attribute__((packed, aligned(4))) RuleParams {
+    uint32_t birth, survive, pad;
     const uint32_t *rules;  // GOL_BATCH_RULE_EACH: n pairs (birth, survive)
-    int64_t done;           // GOL_BATCH_SCAN_CYCLES: the turns of the call before this launch
-    // LIST: the board of slot i of the grid is list[i], i < *count (a slot past the count has no board)
-    const int32_t *list, *count;
-    int64_t *left;  // LIST without a scan (the finish): per board the turns it still has to make, taken off here
-    // AGED (gol_batch_search): per board the call's turn count `done` of the launch before which it was filled
-    const int64_t *born;
 };
-
-template <int NW>
-__device__ __forceinline__ void load_row(const uint64_t *row, int32_t Ww, bool on, uint32_t (&c)[NW])
-{
-    const uint32_t *p = (const uint32_t *)row;
-#pragma unroll
-    for (int j = 0; j < NW; ++j) c[j] = on && j < 2 * Ww ? p[j] : 0u;
-}
-
-// (a row is 2 Ww words in memory; with NW = 1 the second one is padding)
-template <int NW>
-__device__ __forceinline__ void store_row(uint64_t *row, int32_t Ww, const uint32_t (&c)[NW])
-{
-    uint32_t *p = (uint32_t *)row;
-#pragma unroll
-    for (int j = 0; j < (NW < 2 ? 2 : NW); ++j)
-        if (j < 2 * Ww) p[j] = j < NW ? c[j < NW ? j : 0] : 0u;
-}
+using BatchArgs = golk::BatchArgs<RuleParams>;
+static_assert((offsetof(BatchArgs, rule) + offsetof(RuleParams, rules)) % 8 == 0, "rules is aligned in the kernel's arguments");
 
 template <int NW, int RULE, int SCAN, bool LIST, bool AGED>
 __global__ __launch_bounds__(512) void batch_step_kernel(const BatchArgs a)
@@ -129,11 +106,11 @@ __global__ __launch_bounds__(512) void batch_step_kernel(const BatchArgs a)
     const gol_batch_row g = a.g;
     // the board's own rule: the board's index is wave-uniform, and made scalar it turns the read into a scalar
     // load (a wave past the batch's end reads the last board's rule, and computes on zeros)
-    uint32_t birth = a.birth, survive = a.survive;
+    uint32_t birth = a.rule.birth, survive = a.rule.survive;
     if (RULE == GOL_BATCH_RULE_EACH) {
         const uint32_t i = __builtin_amdgcn_readfirstlane((uint32_t)(board < a.n ? board : a.n - 1));
-        birth = __builtin_amdgcn_readfirstlane(a.rules[2 * (size_t)i]);
-        survive = __builtin_amdgcn_readfirstlane(a.rules[2 * (size_t)i + 1]);
+        birth = __builtin_amdgcn_readfirstlane(a.rule.rules[2 * (size_t)i]);
+        survive = __builtin_amdgcn_readfirstlane(a.rule.rules[2 * (size_t)i + 1]);
     }
     gol_rule_tab tab;
     gol_rule_expand(birth, survive, tab);
@@ -252,26 +229,17 @@ void golk_batch_shape(int64_t H, int64_t W, int *waves_per_board, int *boards_pe
     *words_per_lane = gol_batch_row_init(W).nw;
 }
 
-
 hipError_t golk_batch_step(const gol_batch_launch &l, hipStream_t s)
 {
     if (!gol_batch_launch_ok(l)) return hipErrorInvalidValue;
     if (l.maps) return golk_batch_map_step(l, s);  // MAP rules: the kernel unit of their own (gol_batch_map.hip)
-    int wpb, bpw, nw;
-    golk_batch_shape(l.H, l.W, &wpb, &bpw, &nw);
-    const BatchArgs a = {l.boards, l.prev, l.settled, l.n, l.turn0, gol_batch_row_init(l.W), (int32_t)l.H, (int32_t)((l.W + 63) / 64),
-                         wpb, bpw, l.turns, l.have_prev, l.write_prev, l.birth, l.survive, l.rules, l.done, l.list, l.count,
-                         l.left, l.born};
-    const int64_t slots = l.list ? l.slots : l.n;  // without a list every board has its slot
-    const dim3 grid((unsigned)((slots + a.bpw - 1) / a.bpw)), block((unsigned)(a.bpw * a.wpb * 64));
+    const BatchArgs a = golk::batch_args(l, RuleParams{l.birth, l.survive, 0, l.rules});
+    dim3 grid, block;
+    golk::batch_grid(l, a.wpb, a.bpw, &grid, &block);
     const int rule = l.rules                               ? GOL_BATCH_RULE_EACH
                      : gol_batch_conway(l.birth, l.survive) ? GOL_BATCH_RULE_CONWAY
                                                             : GOL_BATCH_RULE_TABLE;
-    switch (nw) {
-    case 1: return launch<1>(rule, l.scan, l.list != nullptr, l.born != nullptr, a, grid, block, s);
-    case 2: return launch<2>(rule, l.scan, l.list != nullptr, l.born != nullptr, a, grid, block, s);
-    case 4: return launch<4>(rule, l.scan, l.list != nullptr, l.born != nullptr, a, grid, block, s);
-    case 8: return launch<8>(rule, l.scan, l.list != nullptr, l.born != nullptr, a, grid, block, s);
-    default: return launch<16>(rule, l.scan, l.list != nullptr, l.born != nullptr, a, grid, block, s);
-    }
+    return golk::with_nw(a.g.nw, [&](auto nw) {
+        return launch<decltype(nw)::value>(rule, l.scan, l.list != nullptr, l.born != nullptr, a, grid, block, s);
+    });
 }

@@ -54,18 +54,26 @@ int reduce(gol_batch *b, bool hash, uint64_t *out, int64_t cap)
     return GOL_OK;
 }
 
+// The device copy of a host vector of the batch (the rules per board, the maps) brought up to date: `count` words
+// allocated at its first use, the vector copied while the copy is stale.
+int upload(gol_batch *b, const std::vector<uint32_t> &host, uint32_t *&dev, int64_t count, bool &dirty)
+{
+    if (!dirty && dev) return GOL_OK;
+    const int rc = need(dev, count);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(dev, host.data(), host.size() * sizeof(uint32_t), hipMemcpyHostToDevice, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));  // (the host copy may change after the call)
+    dirty = false;
+    return GOL_OK;
+}
+
 // A batch under MAP rules: the descriptor's two map fields from the device copy of the maps, brought up to date, and no
 // masks.  This is all a driver knows of maps.
 int use_maps(gol_batch *b, gol_batch_launch *l)
 {
     if (b->maps.empty()) return GOL_OK;
-    if (b->maps_dirty || !b->dmaps) {
-        const int rc = need(b->dmaps, GOL_MAP_WORDS * b->n);
-        if (rc) return rc;
-        HIPCHK(hipMemcpyAsync(b->dmaps, b->maps.data(), b->maps.size() * sizeof(uint32_t), hipMemcpyHostToDevice, b->stream));
-        HIPCHK(hipStreamSynchronize(b->stream));  // (the host copy may change after the call)
-        b->maps_dirty = false;
-    }
+    const int rc = upload(b, b->maps, b->dmaps, GOL_MAP_WORDS * b->n, b->maps_dirty);
+    if (rc) return rc;
     l->birth = l->survive = 0;
     l->maps = b->dmaps;
     l->map_each = b->maps.size() > GOL_MAP_WORDS;
@@ -89,13 +97,8 @@ int begin_call(gol_batch *b, int scan, int64_t turns, gol_batch_launch *l)
     if (turns == 0) return GOL_OK;
     if (!b->maps.empty()) return use_maps(b, l);
     if (b->rules.empty()) return GOL_OK;
-    if (b->rules_dirty || !b->drules) {
-        const int rc = need(b->drules, (int64_t)b->rules.size());
-        if (rc) return rc;
-        HIPCHK(hipMemcpyAsync(b->drules, b->rules.data(), b->rules.size() * sizeof(uint32_t), hipMemcpyHostToDevice, b->stream));
-        HIPCHK(hipStreamSynchronize(b->stream));  // (the host copy may change after the call)
-        b->rules_dirty = false;
-    }
+    const int rc = upload(b, b->rules, b->drules, (int64_t)b->rules.size(), b->rules_dirty);
+    if (rc) return rc;
     l->rules = b->drules;
     return GOL_OK;
 }

@@ -24,17 +24,13 @@ template <int NW>
 void step_host(int64_t H, const gol_batch_row &g, uint32_t birth, uint32_t survive, const uint64_t *in, uint64_t *out,
                int64_t stride)
 {
-    const int64_t Ww = (g.nwr + 1) / 2;
     gol_rule_tab tab;
     gol_rule_expand(birth, survive, tab);
     // every row's cells (the padding of the input masked off) and sums first: out may be in
     std::vector<uint32_t> cells((size_t)H * NW), s0((size_t)H * NW), s1((size_t)H * NW);
     for (int64_t y = 0; y < H; ++y) {
         uint32_t c[NW], h0[NW], h1[NW];
-        for (int j = 0; j < NW; ++j) {
-            c[j] = j < g.nwr ? (uint32_t)(in[y * stride + j / 2] >> (32 * (j & 1))) : 0u;
-            if (j == g.nwr - 1) c[j] &= g.tail;
-        }
+        gol_batch_unpack_row(g, in + y * stride, c);
         gol_batch_hsum<NW>(c, g.nwr, g.tb, h0, h1);
         for (int j = 0; j < NW; ++j) {
             cells[(size_t)y * NW + j] = c[j];
@@ -53,10 +49,7 @@ void step_host(int64_t H, const gol_batch_row &g, uint32_t birth, uint32_t survi
         }
         if (gol_batch_conway(birth, survive)) gol_batch_next<NW, false>(tab, g, a0, a1, b0, b1, d0, d1, c, ~0u, next);
         else gol_batch_next<NW, true>(tab, g, a0, a1, b0, b1, d0, d1, c, ~0u, next);
-        for (int64_t w = 0; w < Ww; ++w) {  // (an odd nwr: the upper half of the last word is padding)
-            const uint32_t lo = next[2 * w], hi = 2 * w + 1 < NW ? next[2 * w + 1 < NW ? 2 * w + 1 : 0] : 0u;
-            out[y * stride + w] = (uint64_t)lo | (uint64_t)hi << 32;
-        }
+        gol_batch_pack_row(g, next, out + y * stride);
     }
 }
 

@@ -10,7 +10,10 @@
 // 2 NW sums) and forms their left and right planes itself; a wave's first and last row cross a wave, or wrap round the
 // torus, through LDS ([2][waves][2][NW], double-buffered), so a turn has one __syncthreads(), which also carries the
 // scan's "differs" bits.  The scans (settle, cycles with the Brent marks), the list, the finish with left[] and the
-// aged mode are batch_step_kernel's, statement by statement.
+// aged mode are batch_step_kernel's, statement by statement: a change to one is a change to both.  (One body under a
+// rule policy was built and left out: as a function inlined into two kernels of these names it did not compile to the
+// instructions of either)  The arguments, a lane's row load and store and the launch code are shared:
+// gol_batch_args.h.
 // The board's map is read once per launch by scalar loads, 16 dwords from maps + (map_each ? 16 board : 0), the board's
 // number made uniform as for the per-board rule read, so the table bits that select the circuit's leaves are
 // wave-uniform.
@@ -24,48 +27,19 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <algorithm>
-
-#include "gol_device.h"
-#include "gol_kernels.h"
+#include "gol_batch_args.h"
 #include "gol_map.h"
 
 namespace {
 
-struct MapArgs {
-    uint64_t *boards;  // n boards of H rows of Ww uint64 words, dense; stepped in place
-    uint64_t *prev;    // SCAN: state(start - 1) or the snapshot in (have_prev) and out (write_prev); same shape
-    int64_t *settled;  // SCAN: n turns, -1 = not found yet
-    int64_t n, turn0;  // boards; the turn of the loaded state
-    gol_batch_row g;
-    int32_t H, Ww, wpb, bpw;  // rows, uint64 words per row, waves per board, boards per workgroup
-    int32_t turns;            // >= 1
-    int32_t have_prev, write_prev;
+using golk::load_row;
+using golk::store_row;
+
+struct MapParams {
     const uint32_t *maps;  // 16 words, or map_each: n times 16
     int32_t map_each;
-    int64_t done;  // GOL_BATCH_SCAN_CYCLES: the turns of the call before this launch
-    const int32_t *list, *count;
-    int64_t *left;
-    const int64_t *born;
 };
-
-template <int NW>
-__device__ __forceinline__ void load_row(const uint64_t *row, int32_t Ww, bool on, uint32_t (&c)[NW])
-{
-    const uint32_t *p = (const uint32_t *)row;
-#pragma unroll
-    for (int j = 0; j < NW; ++j) c[j] = on && j < 2 * Ww ? p[j] : 0u;
-}
-
-// (a row is 2 Ww words in memory; with NW = 1 the second one is padding)
-template <int NW>
-__device__ __forceinline__ void store_row(uint64_t *row, int32_t Ww, const uint32_t (&c)[NW])
-{
-    uint32_t *p = (uint32_t *)row;
-#pragma unroll
-    for (int j = 0; j < (NW < 2 ? 2 : NW); ++j)
-        if (j < 2 * Ww) p[j] = j < NW ? c[j < NW ? j : 0] : 0u;
-}
+using MapArgs = golk::BatchArgs<MapParams>;
 
 template <int NW, int SCAN, bool LIST, bool AGED>
 __global__ __launch_bounds__(512) void batch_map_kernel(const MapArgs a)
@@ -106,8 +80,8 @@ __global__ __launch_bounds__(512) void batch_map_kernel(const MapArgs a)
     // (a wave past the batch's end, or without a board, reads a map that exists and computes on zeros)
     uint32_t map[GOL_MAP_WORDS];
     {
-        const uint32_t i = __builtin_amdgcn_readfirstlane((uint32_t)(a.map_each ? (has && board < a.n ? board : 0) : 0));
-        const uint32_t *mp = a.maps + GOL_MAP_WORDS * (size_t)i;
+        const uint32_t i = __builtin_amdgcn_readfirstlane((uint32_t)(a.rule.map_each ? (has && board < a.n ? board : 0) : 0));
+        const uint32_t *mp = a.rule.maps + GOL_MAP_WORDS * (size_t)i;
 #pragma unroll
         for (int j = 0; j < GOL_MAP_WORDS; ++j) map[j] = __builtin_amdgcn_readfirstlane(mp[j]);
     }
@@ -214,17 +188,10 @@ hipError_t launch(int scan, bool list, bool aged, const MapArgs &a, dim3 grid, d
 hipError_t golk_batch_map_step(const gol_batch_launch &l, hipStream_t s)
 {
     if (!gol_batch_launch_ok(l) || !l.maps) return hipErrorInvalidValue;
-    int wpb, bpw, nw;
-    golk_batch_shape(l.H, l.W, &wpb, &bpw, &nw);
-    const MapArgs a = {l.boards, l.prev, l.settled, l.n, l.turn0, gol_batch_row_init(l.W), (int32_t)l.H, (int32_t)((l.W + 63) / 64),
-                       wpb, bpw, l.turns, l.have_prev, l.write_prev, l.maps, l.map_each, l.done, l.list, l.count, l.left, l.born};
-    const int64_t slots = l.list ? l.slots : l.n;  // without a list every board has its slot
-    const dim3 grid((unsigned)((slots + a.bpw - 1) / a.bpw)), block((unsigned)(a.bpw * a.wpb * 64));
-    switch (nw) {
-    case 1: return launch<1>(l.scan, l.list != nullptr, l.born != nullptr, a, grid, block, s);
-    case 2: return launch<2>(l.scan, l.list != nullptr, l.born != nullptr, a, grid, block, s);
-    case 4: return launch<4>(l.scan, l.list != nullptr, l.born != nullptr, a, grid, block, s);
-    case 8: return launch<8>(l.scan, l.list != nullptr, l.born != nullptr, a, grid, block, s);
-    default: return launch<16>(l.scan, l.list != nullptr, l.born != nullptr, a, grid, block, s);
-    }
+    const MapArgs a = golk::batch_args(l, MapParams{l.maps, l.map_each});
+    dim3 grid, block;
+    golk::batch_grid(l, a.wpb, a.bpw, &grid, &block);
+    return golk::with_nw(a.g.nw, [&](auto nw) {
+        return launch<decltype(nw)::value>(l.scan, l.list != nullptr, l.born != nullptr, a, grid, block, s);
+    });
 }

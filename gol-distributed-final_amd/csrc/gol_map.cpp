@@ -117,15 +117,9 @@ extern "C" int gol_batch_step_map_host(int64_t H, int64_t W, const uint32_t *map
                              (long long)W, (long long)row_stride, (long long)turns);
     const gol_batch_row g = gol_batch_row_init(W);
     const int NW = g.nw;
-    const int64_t Ww = (W + 63) / 64;
     // every row's cells first (the padding of the input masked off): out may be in
     std::vector<uint32_t> cells((size_t)H * NW), next((size_t)H * NW);
-    for (int64_t y = 0; y < H; ++y)
-        for (int j = 0; j < NW; ++j) {
-            uint32_t c = j < g.nwr ? (uint32_t)(in[y * row_stride + j / 2] >> (32 * (j & 1))) : 0u;
-            if (j == g.nwr - 1) c &= g.tail;
-            cells[(size_t)y * NW + j] = c;
-        }
+    for (int64_t y = 0; y < H; ++y) gol_batch_unpack_row(g, in + y * row_stride, &cells[(size_t)y * NW]);
     for (int64_t t = 0; t < turns; ++t) switch (NW) {
         case 1: step_host<1>(H, g, map, cells, next); break;
         case 2: step_host<2>(H, g, map, cells, next); break;
@@ -133,11 +127,7 @@ extern "C" int gol_batch_step_map_host(int64_t H, int64_t W, const uint32_t *map
         case 8: step_host<8>(H, g, map, cells, next); break;
         default: step_host<16>(H, g, map, cells, next); break;
         }
-    for (int64_t y = 0; y < H; ++y)
-        for (int64_t w = 0; w < Ww; ++w) {  // (an odd nwr: the upper half of the last word is padding)
-            const uint32_t lo = cells[(size_t)y * NW + 2 * w], hi = 2 * w + 1 < NW ? cells[(size_t)y * NW + 2 * w + 1] : 0u;
-            out[y * row_stride + w] = (uint64_t)lo | (uint64_t)hi << 32;
-        }
+    for (int64_t y = 0; y < H; ++y) gol_batch_pack_row(g, &cells[(size_t)y * NW], out + y * row_stride);
     return GOL_OK;
 }
 
