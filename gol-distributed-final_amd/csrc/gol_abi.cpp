@@ -10,9 +10,12 @@
 #include <vector>
 
 #include "gol_batch.h"
+#include "gol_batch_kernels.h"
 #include "gol_engine_int.h"
 #include "gol_island.h"
 #include "gol_rule.h"
+#include "gol_step_kernels.h"
+#include "gol_util_kernels.h"
 
 // ------------------------------------------------------------------ errors
 static thread_local std::string g_err;

@@ -4,6 +4,7 @@
 #include <type_traits>
 
 #include "gol_pipe.h"
+#include "gol_step_kernels.h"
 
 namespace golk {
 
@@ -22,7 +23,7 @@ namespace golk {
 // workgroups resident on a CU put one wave of every role on every SIMD.  (Roles by wave index +
 // a per-workgroup rotation put two waves of one role on a SIMD for 64-75 % of the waves,
 // tools/timeline.py, profiles/r03/r03h_tl_roles.jsonl.)  Vector atomics of lane 0.
-// (The knob's default, 1, is in gol_device.h: the launcher reads it too.)
+// (The knob's default, 1, is in gol_step_device.h: the launcher reads it too.)
 __device__ __forceinline__ uint32_t cu_slot_index()
 {
     const uint32_t hw = __builtin_amdgcn_s_getreg((31 << 11) | 4);  // HW_ID

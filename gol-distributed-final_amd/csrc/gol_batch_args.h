@@ -11,6 +11,7 @@
 
 #include "gol_device.h"
 #include "gol_batch.h"
+#include "gol_batch_kernels.h"
 
 namespace golk {
 

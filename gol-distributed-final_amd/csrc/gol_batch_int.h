@@ -6,7 +6,8 @@
 #include <vector>
 
 #include "gol_batch.h"
-#include "gol_engine_int.h"
+#include "gol_batch_kernels.h"
+#include "gol_error.h"
 #include "gol_island.h"
 #include "gol_map.h"
 

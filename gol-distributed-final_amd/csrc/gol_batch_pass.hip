@@ -10,6 +10,7 @@
 
 #include "gol_device.h"
 #include "gol_batch.h"
+#include "gol_batch_kernels.h"
 
 namespace {
 

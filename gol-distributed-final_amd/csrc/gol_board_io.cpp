@@ -6,6 +6,7 @@
 #include <functional>
 
 #include "gol_engine_int.h"
+#include "gol_util_kernels.h"
 
 // ------------------------------------------------------------------ load
 // After the bit rows of every shard were packed with s.flag set on bytes other than 0/255:

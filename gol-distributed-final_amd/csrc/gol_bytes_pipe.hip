@@ -4,6 +4,7 @@
 #include <type_traits>
 
 #include "gol_pipe.h"
+#include "gol_step_kernels.h"
 
 namespace golk {
 

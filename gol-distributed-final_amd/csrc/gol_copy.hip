@@ -16,7 +16,7 @@
 #include <stdint.h>
 
 #include "gol_copy.h"
-#include "gol_kernels.h"
+#include "gol_region_kernels.h"
 
 namespace {
 

@@ -189,7 +189,7 @@ GOL_EDIT_HD int gol_edit_flips4(uint32_t a, uint32_t b)
 }
 
 // ------------------------------------------------------------------ a region launch and its check
-// What every region kernel (view, paste, copy, bounds: gol_kernels.h) and every host twin
+// What every region kernel (view, paste, copy, bounds: gol_region_kernels.h) and every host twin
 // (gol_paste_host, gol_copy_host, gol_bounds_host) is given: a rectangle of a run of board rows.
 struct gol_region {
     int32_t layout;     // how the rows are stored: GOL_EDIT_BYTES / _STANDARD / _BAND

@@ -10,7 +10,7 @@
 #include <stdint.h>
 
 #include "gol_edit.h"
-#include "gol_kernels.h"
+#include "gol_region_kernels.h"
 
 namespace {
 

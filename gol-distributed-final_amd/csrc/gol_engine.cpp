@@ -13,6 +13,7 @@
 // timing gol_timing.cpp, byte / PGM / word I/O and the cell lists gol_board_io.cpp, the viewport
 // frames and the paste gol_frames.cpp, the P5 header gol_pgm.cpp (gol_engine_int.h).
 #include "gol_engine_int.h"
+#include "gol_step_kernels.h"
 
 // The IPC transport's send buffer (exchange_ipc): 2 exchange parities x 4 plan ops x the ghost rows.
 static size_t ipc_out_bytes(const gol_engine *e) { return (size_t)2 * 4 * GOL_GHOST_ROWS * e->pitch * sizeof(uint32_t); }

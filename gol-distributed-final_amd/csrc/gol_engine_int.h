@@ -11,15 +11,7 @@
 #include "golhip.h"
 #include "gol_comm.h"
 #include "gol_internal.h"
-#include "gol_kernels.h"
-
-#define HIPCHK(expr)                                                                              \
-    do {                                                                                          \
-        hipError_t e_ = (expr);                                                                   \
-        if (e_ != hipSuccess)                                                                     \
-            return gol_set_error(e_ == hipErrorOutOfMemory ? GOL_ENOMEM : GOL_EHIP, "%s failed: %s (%s:%d)", #expr, \
-                                 hipGetErrorString(e_), __FILE__, __LINE__);                      \
-    } while (0)
+#include "gol_launch.h"  // GOL_COUNT_SLOTS
 
 #define NCCLCHK(expr)                                                                             \
     do {                                                                                          \

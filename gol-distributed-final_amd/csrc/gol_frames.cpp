@@ -1,10 +1,12 @@
 // gol_frames.cpp -- reading and editing the board engine's (gol_engine.cpp) board between steps,
 // where it is and as it is: the viewport frames (gol_engine_view, _view_counts), their write-side
 // twin, the paste (gol_engine_paste), and the reads at cell precision (gol_engine_copy, _bounds).
-// All four run the region kernels (gol_kernels.h) on rows [0, R) of the current buffer -- never the
+// All four run the region kernels (gol_region_kernels.h) on rows [0, R) of the current buffer -- never the
 // ghost rows, which an exchange for the next step may be writing -- with no layout conversion and
 // no change to cur / band / mode / the turn, through one per-shard driver (query_shards).
+#include "gol_edit.h"
 #include "gol_engine_int.h"
+#include "gol_region_kernels.h"
 
 // A shard's runs of a query's rows (gol_view_plan); n == 0: it holds none and takes no part.
 struct shard_runs {

@@ -8,7 +8,8 @@
 #include <vector>
 
 #include "golhip.h"
-#include "gol_step_launch.h"
+#include "gol_error.h"        // gol_set_error, HIPCHK
+#include "gol_step_launch.h"  // GOL_DEFAULT_DW (gol_engine::dw)
 
 struct gol_comm;
 class gol_ipc;
@@ -145,7 +146,6 @@ struct gol_engine {
     int64_t x_n = 0;
 };
 
-int gol_set_error(int code, const char *fmt, ...);
 // gol_plan.cpp: the index in `theirs` (the plan of mine[j].peer) of the send that pairs with my
 // receive mine[j], or -1 with the error set.
 __attribute__((visibility("hidden"))) int gol_halo_match(const gol_halo_op *mine, int j, const gol_halo_op *theirs,

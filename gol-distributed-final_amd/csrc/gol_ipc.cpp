@@ -27,7 +27,7 @@
 
 #include "gol_comm.h"
 #include "gol_internal.h"
-#include "gol_kernels.h"
+#include "gol_util_kernels.h"
 
 // ------------------------------------------------------------------ RCCL
 namespace {

@@ -56,6 +56,7 @@
 #include <algorithm>
 
 #include "gol_device.h"
+#include "gol_batch_kernels.h"
 #include "gol_island.h"
 
 namespace {

@@ -21,22 +21,25 @@
 // conversion, the blocked and exact byte kernels, and their launchers: golk_step, the one launcher
 // of every step kernel, takes a descriptor (gol_step_launch.h: the kernel table, the check, the
 // geometry) and expands the table into its dispatch.  The two split pipelines are
-// units of their own (gol_band_pipe.hip, gol_bytes_pipe.hip; launched through gol_device.h), the
+// units of their own (gol_band_pipe.hip, gol_bytes_pipe.hip; launched through gol_step_device.h), the
 // board utilities gol_util.hip; the launch state (error word, CU slots, claim counters, the strips
 // of a pipelined launch) is host code, gol_launch.cpp.
-// gol_device.h holds what the units share, gol_pipe.h what only the pipelines share.
+// gol_device.h holds the lane helpers every kernel unit shares, gol_step_device.h the step kernels'
+// machinery, gol_pipe.h what only the pipelines share.
 #include <stdlib.h>
 
 #include <type_traits>
 
-#include "gol_device.h"
 #include "gol_launch.h"
 #include "gol_rule.h"
+#include "gol_step_device.h"
+#include "gol_step_kernels.h"
+#include "gol_step_launch.h"
 
 namespace golk {
 
-// Truth tables, lane helpers, rule(), Pipe, the band stage (hsum_band, bstage), BitsArgs,
-// BytesKArgs, pack32 / unpack32: gol_device.h
+// Truth tables, lane helpers, rule(): gol_device.h.  Pipe, the band stage (hsum_band, bstage), BitsArgs,
+// BytesKArgs, pack32 / unpack32: gol_step_device.h
 
 // Standard layout, shifted frame: the horizontal 3-sum is formed from the cell and its two
 // LEFT neighbours, S'[p] = c[p] + c[p-1] + c[p-2] = the 3-sum centred on p-1, so a stage

@@ -9,6 +9,8 @@
 #include <utility>
 
 #include "gol_launch.h"
+#include "gol_step_kernels.h"
+#include "gol_step_launch.h"
 
 using namespace golk;
 

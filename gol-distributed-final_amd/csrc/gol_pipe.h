@@ -3,7 +3,7 @@
 // the loaders' interior-block arithmetic and the pair step.  Device code: included by .hip
 // units only.
 #pragma once
-#include "gol_device.h"
+#include "gol_step_device.h"
 
 namespace golk {
 

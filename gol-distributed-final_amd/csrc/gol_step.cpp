@@ -2,6 +2,8 @@
 // step plan, the launches of one step and the exchange that follows it, the exact first turn, the
 // stepping calls with their batched count points, and the whole-board count and hash.
 #include "gol_engine_int.h"
+#include "gol_step_kernels.h"
+#include "gol_util_kernels.h"
 
 // Turns per launch: the largest k of (family, dw) in the kernel table (gol_step_launch.h; every
 // kernel, the engine-only one included) that is <= want, the remaining turns and the smallest shard.

@@ -3,6 +3,7 @@
 // each with its launcher.  gol_device.h: splitmix64, slot_add, the wave sums.
 #include "gol_device.h"
 #include "gol_launch.h"
+#include "gol_util_kernels.h"
 
 namespace golk {
 

@@ -27,7 +27,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "gol_kernels.h"
+#include "gol_edit.h"
+#include "gol_region_kernels.h"
 
 namespace {
 

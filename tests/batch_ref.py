@@ -46,7 +46,6 @@ Every case carries check(): assertions on the model's results alone that the cas
 there for."""
 import dataclasses
 import functools
-import os
 
 import numpy as np
 
@@ -554,9 +553,6 @@ def refusals(p):
 
 
 # ---------------------------------------------------------------- what the tests of golhip.Batch and its host twins share
-
-BATCH_CHECK = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gol-distributed-final_amd", "build", "asan",
-                           "batch_check")  # the stand-alone program of the sanitizer build
 
 
 def to_words(cells):

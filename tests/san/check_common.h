@@ -1,12 +1,11 @@
 // check_common.h -- what the sanitizer check programs of the batch and of the island census share (batch_check.cpp,
 // island_check.cpp, island_sym_check.cpp, tally_check.cpp; each a stand-alone program built by `make asan`, which
-// includes this file once): the error stub the HIP-free host sources link against, the random numbers (one seed, one
+// includes this file once): the error stub (check_stub.h), the random numbers (one seed, one
 // sequence: the programs' random cases are fixed by it), a splitmix64 written out here, the random board as a heap
 // block of its exact size, and the references the census programs compare with -- a flood fill cell by cell, a tally
 // by a map, and the check of a census of a search.  Nothing here calls the code under test but check_census, which is
 // the test of it.
 #pragma once
-#include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
@@ -15,17 +14,8 @@
 #include <map>
 #include <vector>
 
+#include "check_stub.h"
 #include "golhip.h"
-
-static char g_msg[512];
-int gol_set_error(int code, const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_msg, sizeof g_msg, fmt, ap);
-    va_end(ap);
-    return code;
-}
 
 static uint64_t g_state = 0x9E3779B97F4A7C15ULL;
 static inline uint64_t rnd()

@@ -12,22 +12,12 @@
 //                    of gol_paste_host(COPY) of that pattern at the same place, the buffer after it.
 // copy_check bounds  stdin: records of 8 int64 (layout, W, pitch, buffer rows, row, rows, x0, w),
 //                    then the buffer.  stdout (binary): per record int64 rc, cmin, cmax, rmin, rmax, alive.
-#include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
 
+#include "check_stub.h"
 #include "golhip.h"
-
-static char g_msg[512];
-int gol_set_error(int code, const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_msg, sizeof g_msg, fmt, ap);
-    va_end(ap);
-    return code;
-}
 
 static bool read_exact(void *p, size_t n) { return n == 0 || fread(p, 1, n, stdin) == n; }
 

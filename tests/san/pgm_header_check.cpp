@@ -6,26 +6,16 @@
 //
 // stdin: records of  int64 W, int64 H, uint32 n, n header bytes.
 // stdout: one line per record: "<rc> <offset>" (offset -1 on error).
-#include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
 
 #include <vector>
 
+#include "check_stub.h"
 #include "golhip.h"
 
 int gol_pgm_parse_header(const uint8_t *h, size_t n, int64_t W, int64_t H, int64_t *off);
-
-static char g_msg[512];
-int gol_set_error(int code, const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_msg, sizeof g_msg, fmt, ap);
-    va_end(ap);
-    return code;
-}
 
 int main()
 {

@@ -11,24 +11,14 @@
 // rle_check paste  stdin: records of 12 int64 (layout, W, pitch, buffer rows, row, rows, prow, x0, w,
 //                  stride, op, pattern words; pattern words 0 = no pattern), the buffer, the pattern.
 //                  stdout (binary): per record int64 rc, int64 changed, the buffer after the call.
-#include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
 
 #include <vector>
 
+#include "check_stub.h"
 #include "golhip.h"
-
-static char g_msg[512];
-int gol_set_error(int code, const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_msg, sizeof g_msg, fmt, ap);
-    va_end(ap);
-    return code;
-}
 
 static bool read_exact(void *p, size_t n) { return n == 0 || fread(p, 1, n, stdin) == n; }
 

@@ -27,7 +27,7 @@ import rule_ref as RR
 
 SENT = 0x5A5A5A5A  # every word that is not board data: pitch padding, guard rows, all of dst
 GUARD = 2          # sentinel rows above and below every allocation
-RULE_DW = 2        # GOLK_RULE_DW (csrc/gol_kernels.h): words per lane of the rule kernels
+RULE_DW = 2        # GOLK_RULE_DW (csrc/gol_step_launch.h): words per lane of the rule kernels
 COUNT_SEED = (5, 1000003)  # (slot, value) the count slots hold before a launch
 DENSITY = 0.4
 

@@ -4,15 +4,14 @@ shape and rule, the caller's buffer contract, the ABI edges, the same code in a 
 under AddressSanitizer + UndefinedBehaviorSanitizer (build/asan/batch_check, a plain child process;
 nothing loaded into Python is sanitized), and the Python class's byte <-> word packing.  All
 comparisons are exact; the reference is rule_ref (np.roll sums), never the library."""
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
 import rule_ref
-from batch_ref import BATCH_CHECK, GAP, from_words, tail_mask, to_words
-from testlib import cpu_lib as G  # noqa: F401 (the fixture)
+from batch_ref import GAP, from_words, tail_mask, to_words
+from testlib import check_program, cpu_lib as G  # noqa: F401 (the fixture)
 
 # degenerate wraps, one to sixteen words per row, a last word partly and wholly used, more than 64 rows; five to
 # eight words (the 8-word row function) and an odd count of words below the 8 or 16 held
@@ -77,8 +76,7 @@ def test_step_host_einval(G):
 def test_batch_check_under_sanitizers():
     """The same shapes and rules in the stand-alone program, every buffer a heap block of its exact
     size, against a cell-by-cell neighbour count."""
-    assert os.path.exists(BATCH_CHECK), "build/asan/batch_check is missing: run __graft_entry__.build()"
-    r = subprocess.run([BATCH_CHECK], capture_output=True, text=True, timeout=120)
+    r = subprocess.run([check_program("batch_check")], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     assert "0 bad" in r.stdout
 

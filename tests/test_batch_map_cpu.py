@@ -2,7 +2,6 @@
 turns of one torus (gol_batch_step_map_host) and the text codec, against tests/map_ref.py; the refusals; and the
 sanitizer build's stand-alone program."""
 import ctypes
-import os
 import subprocess
 
 import numpy as np
@@ -11,11 +10,8 @@ import pytest
 import map_ref as M
 import rule_ref as R
 from batch_ref import from_words, tail_mask, to_words
-from testlib import GOL_EINVAL, GOL_OK
+from testlib import GOL_EINVAL, GOL_OK, check_program
 from testlib import cpu_lib as G  # noqa: F401 (the fixture)
-
-MAP_CHECK = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gol-distributed-final_amd", "build", "asan",
-                         "map_check")
 
 
 def eval_host(L, m, x):
@@ -143,7 +139,5 @@ def test_refusals(G):
 def test_map_check_program():
     """build/asan/map_check: the host twin, the codec and the launch check under AddressSanitizer + UBSan, on heap
     blocks of exact size (a plain child process)."""
-    if not os.path.exists(MAP_CHECK):
-        pytest.fail("build/asan/map_check is missing: run __graft_entry__.build()")
-    r = subprocess.run([MAP_CHECK], capture_output=True, text=True)
+    r = subprocess.run([check_program("map_check")], capture_output=True, text=True)
     assert r.returncode == 0 and ", 0 bad" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]

@@ -12,8 +12,8 @@ import pytest
 import batch_ref as B
 import cycle_ref as C
 import rule_ref as R
-from batch_ref import BATCH_CHECK, to_words
-from testlib import GOL_EINVAL, cpu_lib as G  # noqa: F401 (the fixture)
+from batch_ref import to_words
+from testlib import GOL_EINVAL, check_program, cpu_lib as G  # noqa: F401 (the fixture)
 
 
 # ---------------------------------------------------------------- the table
@@ -127,14 +127,12 @@ def test_the_check_accepts_every_case_and_refuses_the_list(G):
 def test_the_check_under_sanitizers(tmp_path):
     """The same two sets through gol_batch_launch_ok in the stand-alone program (build/asan/batch_check launch): a
     line per launch, the expected answer first, NULL as 0."""
-    import os
     import subprocess
-    assert os.path.exists(BATCH_CHECK), "build/asan/batch_check is missing: run __graft_entry__.build()"
     accept, refuse = check_sets()
     path = tmp_path / "launches.txt"
     path.write_text("".join(" ".join(str(int(v or 0)) for v in [ok] + a) + "\n"
                             for ok, group in ((1, accept), (0, refuse)) for a in group))
-    r = subprocess.run([BATCH_CHECK, "launch", str(path)], capture_output=True, text=True, timeout=120)
+    r = subprocess.run([check_program("batch_check"), "launch", str(path)], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     assert f"batch_check launch: {len(accept)} accepted, {len(refuse)} refused, 0 bad" in r.stdout
 

@@ -6,7 +6,6 @@ program under AddressSanitizer + UndefinedBehaviorSanitizer (build/asan/batch_ch
 process; nothing loaded into Python is sanitized).  All comparisons are exact, every expectation is
 the reference's, and each test first asserts on the reference alone that its input exercises its case."""
 import ctypes
-import os
 import subprocess
 
 import numpy as np
@@ -14,8 +13,8 @@ import pytest
 
 import cycle_ref as C
 import rule_ref as R
-from batch_ref import BATCH_CHECK, GAP, PATTERNS, tail_mask, to_words
-from testlib import cpu_lib as G  # noqa: F401 (the fixture)
+from batch_ref import GAP, PATTERNS, tail_mask, to_words
+from testlib import check_program, cpu_lib as G  # noqa: F401 (the fixture)
 
 
 def made_ref(found, period, turns, launch, t0=0):
@@ -150,7 +149,6 @@ def test_run_host_einval(G):
 def test_batch_check_run_under_sanitizers():
     """gol_batch_run_cycles_host in the stand-alone program, every buffer a heap block of its exact size,
     against gol_batch_cycles_host over a grid of shapes, turns and launch lengths."""
-    assert os.path.exists(BATCH_CHECK), "build/asan/batch_check is missing: run __graft_entry__.build()"
-    r = subprocess.run([BATCH_CHECK, "run"], capture_output=True, text=True, timeout=120)
+    r = subprocess.run([check_program("batch_check"), "run"], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     assert "batch_check run:" in r.stdout and " 0 bad" in r.stdout

@@ -6,7 +6,6 @@ the same code in the stand-alone program under AddressSanitizer + UndefinedBehav
 comparisons are exact, every expectation is the reference's, and the main case first asserts on the
 reference alone that it cannot pass on an empty result."""
 import ctypes
-import os
 import subprocess
 
 import numpy as np
@@ -15,8 +14,8 @@ import pytest
 import rule_ref as R
 import search_ref as S
 from oracle import oracle as O
-from batch_ref import BATCH_CHECK, GAP, tail_mask
-from testlib import GOL_EINVAL, cpu_lib as G  # noqa: F401 (the fixture)
+from batch_ref import GAP, tail_mask
+from testlib import GOL_EINVAL, check_program, cpu_lib as G  # noqa: F401 (the fixture)
 
 SEED = 1  # (picked: the conditions of test_main_case_is_not_empty hold for it)
 MAIN = dict(H=16, W=16, rule="B3/S23", total=40, horizon=300)
@@ -198,7 +197,6 @@ def test_search_host_refusals(G):
 def test_batch_check_search_under_sanitizers():
     """gol_batch_soup_host and gol_batch_search_host in the stand-alone program, every buffer a heap block of its
     exact size, against a scan written in the driver, over shapes, rules, slot counts and launch lengths."""
-    assert os.path.exists(BATCH_CHECK), "build/asan/batch_check is missing: run __graft_entry__.build()"
-    r = subprocess.run([BATCH_CHECK, "search"], capture_output=True, text=True, timeout=120)
+    r = subprocess.run([check_program("batch_check"), "search"], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     assert "batch_check search:" in r.stdout and " 0 bad" in r.stdout

@@ -6,7 +6,6 @@ the refusals; and the same code in the stand-alone program under AddressSanitize
 UndefinedBehaviorSanitizer (build/asan/batch_check cycles, a plain child process; nothing loaded into
 Python is sanitized).  All comparisons are exact, and every expectation is the reference's."""
 import ctypes
-import os
 import subprocess
 
 import numpy as np
@@ -14,8 +13,8 @@ import pytest
 
 import cycle_ref as C
 import rule_ref as R
-from batch_ref import BATCH_CHECK, GAP, PATTERNS, tail_mask, to_words
-from testlib import cpu_lib as G  # noqa: F401 (the fixture)
+from batch_ref import GAP, PATTERNS, tail_mask, to_words
+from testlib import check_program, cpu_lib as G  # noqa: F401 (the fixture)
 
 
 def cycles_host(G, cells, rule, turns, pad=0, in_place=False, want_period=True):
@@ -134,9 +133,8 @@ def test_batch_check_cycles_under_sanitizers():
     """gol_batch_cycles_host in the stand-alone program, every buffer a heap block of its exact size,
     against a scan written in the program itself; without an argument the program runs what it ran
     before."""
-    assert os.path.exists(BATCH_CHECK), "build/asan/batch_check is missing: run __graft_entry__.build()"
-    r = subprocess.run([BATCH_CHECK, "cycles"], capture_output=True, text=True, timeout=120)
+    r = subprocess.run([check_program("batch_check"), "cycles"], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     assert "batch_check cycles:" in r.stdout and " 0 bad" in r.stdout
-    r = subprocess.run([BATCH_CHECK, "no-such-mode"], capture_output=True, text=True, timeout=120)
+    r = subprocess.run([check_program("batch_check"), "no-such-mode"], capture_output=True, text=True, timeout=120)
     assert r.returncode == 2

@@ -10,14 +10,12 @@ import struct
 import subprocess
 
 import numpy as np
-import pytest
 
 import region_ref as RR
 from region_ref import CASES as PASTE_SHAPES, EDGES, board_cells, to_layout
-from testlib import cpu_lib as G  # noqa: F401 (the fixture)
+from testlib import check_program, cpu_lib as G  # noqa: F401 (the fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-COPY_CHECK = os.path.join(ROOT, "gol-distributed-final_amd", "build", "asan", "copy_check")
 
 # (layout, W, x0, w, cells): the paste's shapes on the random board, then band rows with an odd number
 # of 32-cell groups per band (W = 3072: Wd = 96), w = 63, 64, 65 at x0 % 64 = 31, one cell in the last
@@ -211,19 +209,14 @@ def test_copy_abi_edges(G):
 
 
 # ------------------------------------------------------------------ the same code under the sanitizers
-needs_check = pytest.mark.skipif(not os.path.exists(COPY_CHECK), reason="sanitizer build missing (make -C "
-                                 "gol-distributed-final_amd/csrc asan)")
-
-
 def _run_check(mode, blob):
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:exitcode=23", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1:exitcode=24")
-    p = subprocess.run([COPY_CHECK, mode], input=blob, env=env, capture_output=True, timeout=300)
+    p = subprocess.run([check_program("copy_check"), mode], input=blob, env=env, capture_output=True, timeout=300)
     err = p.stderr.decode(errors="replace")
     assert p.returncode == 0 and "Sanitizer" not in err and "runtime error" not in err, err[-4000:]
     return p.stdout
 
 
-@needs_check
 def test_copy_host_under_asan_ubsan(G):
     """The shapes of test_copy_host_matches_numpy on exact-size heap buffers (the pattern block ends
     with the last word the call may write): no report, the cells and counts of numpy, and the
@@ -247,7 +240,6 @@ def test_copy_host_under_asan_ubsan(G):
     assert off == len(out)
 
 
-@needs_check
 def test_bounds_host_under_asan_ubsan(G):
     cs = list(cases())
     blob = b""

@@ -14,10 +14,9 @@ import pytest
 
 import region_ref as RR
 from region_ref import CASES, EDGES, board_cells, from_layout, to_layout
-from testlib import cpu_lib as G  # noqa: F401 (the fixture)
+from testlib import check_program, cpu_lib as G  # noqa: F401 (the fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-RLE_CHECK = os.path.join(ROOT, "gol-distributed-final_amd", "build", "asan", "rle_check")
 OPS = ["copy", "or", "xor", "andnot"]
 GLIDER = np.array([[0, 1, 0], [0, 0, 1], [1, 1, 1]], bool)
 
@@ -245,19 +244,14 @@ def test_paste_abi_edges(G):
 
 
 # ------------------------------------------------------------------ the same code under the sanitizers
-needs_check = pytest.mark.skipif(not os.path.exists(RLE_CHECK), reason="sanitizer build missing (make -C "
-                                 "gol-distributed-final_amd/csrc asan)")
-
-
 def _run_check(mode, blob):
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:exitcode=23", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1:exitcode=24")
-    p = subprocess.run([RLE_CHECK, mode], input=blob, env=env, capture_output=True, timeout=300)
+    p = subprocess.run([check_program("rle_check"), mode], input=blob, env=env, capture_output=True, timeout=300)
     err = p.stderr.decode(errors="replace")
     assert p.returncode == 0 and "Sanitizer" not in err and "runtime error" not in err, err[-4000:]
     return p.stdout
 
 
-@needs_check
 def test_rle_codec_under_asan_ubsan(G):
     """The malformed texts, every truncation of valid texts and seeded random patterns through the
     stand-alone driver: each verdict equals the library's, and valid texts survive format + parse."""
@@ -280,7 +274,6 @@ def test_rle_codec_under_asan_ubsan(G):
     assert all(int(ln.split()[0]) == 0 for ln in lines[:len(valid)])
 
 
-@needs_check
 def test_paste_host_under_asan_ubsan(G):
     """The paste shapes of test_paste_host_matches_numpy on exact-size heap buffers (the pattern cut
     after the last word the call may read): no report, and the same cells and counts as numpy."""

@@ -6,17 +6,13 @@ UndefinedBehaviorSanitizer (build/asan/island_check, a plain child process; noth
 sanitized), the refusals of the launch check, golhip.island, and the precondition of the GPU soup test.  All
 comparisons are exact."""
 import ctypes
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
 import island_ref as I
-from testlib import GOL_EINVAL, cpu_lib as G  # noqa: F401 (the fixture)
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ISLAND_CHECK = os.path.join(ROOT, "gol-distributed-final_amd", "build", "asan", "island_check")
+from testlib import GOL_EINVAL, check_program, cpu_lib as G  # noqa: F401 (the fixture)
 
 
 def host_census(G, cells, reach, cap=None, stride_pad=0):
@@ -199,8 +195,7 @@ def test_host_twin_cap(G):
 def test_island_check_under_sanitizers():
     """The host twin in the stand-alone program, the board and the records heap blocks of their exact sizes,
     against a cell-by-cell flood fill."""
-    assert os.path.exists(ISLAND_CHECK), "build/asan/island_check is missing: run __graft_entry__.build()"
-    r = subprocess.run([ISLAND_CHECK], capture_output=True, text=True, timeout=120)
+    r = subprocess.run([check_program("island_check")], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     assert "0 bad" in r.stdout
 

@@ -8,7 +8,6 @@ the stand-alone driver under AddressSanitizer + UndefinedBehaviorSanitizer (buil
 child process; nothing loaded into Python is sanitized).  All comparisons are exact."""
 import ctypes
 import itertools
-import os
 import subprocess
 
 import numpy as np
@@ -19,10 +18,8 @@ import island_sym_ref as F
 import rule_ref as R
 import tally_ref as T
 from tally_ref import DENSE, LISTED, ORDER, REFUSED
-from testlib import GOL_EINVAL, cpu_lib  # noqa: F401 (the fixture)
+from testlib import GOL_EINVAL, check_program, cpu_lib  # noqa: F401 (the fixture)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SYM_CHECK = os.path.join(ROOT, "gol-distributed-final_amd", "build", "asan", "island_sym_check")
 FIXED, FREE = F.FIXED, F.FREE
 
 
@@ -333,7 +330,6 @@ def test_launch_checks_take_the_symmetry(G):
 def test_island_sym_check_under_sanitizers():
     """The FREE twins in the stand-alone program, the board and the records heap blocks of their exact sizes,
     against a cell-by-cell flood fill that reads every orientation's code off the board."""
-    assert os.path.exists(SYM_CHECK), "build/asan/island_sym_check is missing: run __graft_entry__.build()"
-    r = subprocess.run([SYM_CHECK], capture_output=True, text=True, timeout=120)
+    r = subprocess.run([check_program("island_sym_check")], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     assert "0 bad" in r.stdout

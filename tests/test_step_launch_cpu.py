@@ -5,16 +5,13 @@ tests/test_abi_cpu.py run through the gol_dev_* entries), reports the geometry s
 has exactly step_ref's kernel table; the same two sets run through the stand-alone program under
 ASan/UBSan (build/asan/step_check launch)."""
 import ctypes
-import os
 import subprocess
 
 import pytest
 
 import step_ref as S
-from testlib import GOL_EINVAL, cpu_lib as G  # noqa: F401 (the fixture)
+from testlib import GOL_EINVAL, check_program, cpu_lib as G  # noqa: F401 (the fixture)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-STEP_CHECK = os.path.join(ROOT, "gol-distributed-final_amd", "build", "asan", "step_check")
 ALLOCS = ("src", "top", "mid", "bot", "dst")
 
 
@@ -114,11 +111,10 @@ def test_the_table_is_step_refs(G):
 def test_the_check_under_sanitizers(tmp_path):
     """The same two sets through gol_step_launch_ok and the export in the stand-alone program:
     a line per launch, the expected answer first, NULL as 0."""
-    assert os.path.exists(STEP_CHECK), "build/asan/step_check is missing: run __graft_entry__.build()"
     accept, refuse = check_sets()
     path = tmp_path / "launches.txt"
     path.write_text("".join(" ".join(str(int(v)) for v in [ok] + a) + "\n"
                             for ok, group in ((1, accept), (0, refuse)) for a in group))
-    r = subprocess.run([STEP_CHECK, "launch", str(path)], capture_output=True, text=True, timeout=120)
+    r = subprocess.run([check_program("step_check"), "launch", str(path)], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     assert f"step_check launch: {len(accept)} accepted, {len(refuse)} refused, 0 bad" in r.stdout

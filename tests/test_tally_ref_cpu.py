@@ -6,7 +6,6 @@ Python is sanitized), the refusals of the launch check argument by argument, the
 preconditions of the GPU tests (tests/test_gpu_tally.py), asserted on the reference alone.  All comparisons are
 exact."""
 import ctypes
-import os
 import subprocess
 
 import numpy as np
@@ -16,10 +15,7 @@ import island_ref as I
 import rule_ref as R
 import tally_ref as T
 from tally_ref import DENSE, LISTED, ORDER, P, REFUSED
-from testlib import GOL_EINVAL, cpu_lib as G  # noqa: F401 (the fixture)
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TALLY_CHECK = os.path.join(ROOT, "gol-distributed-final_amd", "build", "asan", "tally_check")
+from testlib import GOL_EINVAL, check_program, cpu_lib as G  # noqa: F401 (the fixture)
 
 
 def host_tally(G, pairs, cap=None):
@@ -105,8 +101,7 @@ def test_host_census_twin_and_soup_preconditions(G, c):
 
 def test_tally_check_under_sanitizers():
     """The two host twins in the stand-alone program, every block a heap block of its exact size."""
-    assert os.path.exists(TALLY_CHECK), "build/asan/tally_check is missing: run __graft_entry__.build()"
-    r = subprocess.run([TALLY_CHECK], capture_output=True, text=True, timeout=120)
+    r = subprocess.run([check_program("tally_check")], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     assert "0 bad" in r.stdout
 

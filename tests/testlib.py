@@ -21,6 +21,15 @@ GOL_EQUIT = -7
 GOL_ECOMM = -8
 
 
+def check_program(name):
+    """The path of the stand-alone sanitizer program build/asan/`name` (tests/san/`name`.cpp, made by build()); a
+    test that asks for one that is not there fails."""
+    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gol-distributed-final_amd", "build",
+                        "asan", name)
+    assert os.path.exists(path), f"build/asan/{name} is missing: run __graft_entry__.build()"
+    return path
+
+
 def _gpu_package():
     import torch
     if not torch.cuda.is_available():

@@ -11,9 +11,12 @@
 #   tools/variant.sh kernels REV NAME           current sources with the three kernel units of REV
 #                                               (gol_kernels.hip, gol_band_pipe.hip, gol_bytes_pipe.hip)
 #                                               and, where REV has them, its gol_util.hip, gol_launch.cpp,
-#                                               gol_launch.h, gol_device.h / gol_pipe.h: the kernels of
+#                                               gol_launch.h and the kernel headers: the kernels of
 #                                               REV behind today's engine and ABI (REV must have the
-#                                               launch state in gol_launch.cpp)
+#                                               launch state in gol_launch.cpp; a REV from before
+#                                               the launcher headers were split brings its gol_kernels.h,
+#                                               whose prototypes must still be today's: the units of
+#                                               today then see the same launchers declared twice)
 #   tools/variant.sh res ["-DFLAG ..."]         VGPRs / LDS / scratch / occupancy of the pipe kernels
 set -e
 R=$(cd "$(dirname "$0")/.." && pwd)
@@ -56,7 +59,7 @@ case ${1:-} in
   kernels)
     REV=$2; N=$3; D=$V/src_$N
     copy_current "$D"
-    for f in gol_kernels.hip gol_band_pipe.hip gol_bytes_pipe.hip gol_util.hip gol_launch.cpp gol_launch.h gol_device.h gol_pipe.h; do
+    for f in gol_kernels.hip gol_band_pipe.hip gol_bytes_pipe.hip gol_util.hip gol_launch.cpp gol_launch.h gol_device.h gol_step_device.h gol_pipe.h gol_step_kernels.h gol_util_kernels.h gol_kernels.h; do
       if git -C "$R" cat-file -e "$REV:gol-distributed-final_amd/csrc/$f" 2>/dev/null; then
         git -C "$R" show "$REV:gol-distributed-final_amd/csrc/$f" > "$D/$f"
       fi
